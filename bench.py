@@ -7,9 +7,15 @@ then match every frame against its predecessor (B problems of ~2000 x ~2000 desc
 value = ORB keypoints+descriptors produced per second, whole job (all ranks), with matches/s and Hamming distances/s next to
 it. Frames shard across ranks with no data-path collective (replicas) => "scaling": "weak".
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
        N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times K steps and prints the headline line (value, ms_per_step, the rates and the per-stage event
+times of the timed steps). --full adds the side measurements and checks: each-kernel-alone and popcount-form passes, the
+rooflines (with rocprofv3 child runs), local BA, the other BASELINE configs, the class-boundary latency, the CPU oracle's
+baseline and the parity check of the last timed step. --dump-outputs DIR writes what the last timed step computed (rank 0's
+frames) as float .npy files, see dump_outputs().
 """
 import argparse
 import ctypes as C
@@ -62,6 +68,60 @@ class collector_paused:
         return False
 
 
+def synth_video_threaded(rows, cols, n_frames, seed=0, frames_per_scene=8, step=(3, 2), threads=16):
+    """synth.synth_video's frames, byte for byte, generated one scene per task on a thread pool (numpy releases the interpreter lock in
+    the noise and the arithmetic): the two 256-frame 1080p input batches take ~40 s on one core, which a plain run cannot afford."""
+    from concurrent.futures import ThreadPoolExecutor
+    from openvslam_amd.synth import frame_from_scene, synth_scene
+    out = np.empty((n_frames, rows, cols), np.uint8)
+
+    def scene(first):
+        sc = synth_scene(rows, cols, seed * 1000 + first // frames_per_scene)
+        for i in range(first, min(first + frames_per_scene, n_frames)):
+            k = i - first
+            out[i] = frame_from_scene(sc, rows, cols, (step[0] * k, step[1] * k), noise_seed=seed * 100003 + i)
+
+    with ThreadPoolExecutor(max(1, min(threads, os.cpu_count() or 1))) as pool:
+        list(pool.map(scene, range(0, n_frames, frames_per_scene)))
+    return out
+
+
+def dump_outputs(path, last_out, Bc, budget_bytes=64 << 20):
+    """--dump-outputs: what the last timed step handed its caller (extract_batch_dev + brute_force_match_batch_dev), rank 0's frames
+    in frame order, the valid rows of each frame only (rows behind a frame's count are stale bytes of earlier steps):
+      frame_index.npy      (F,) float64     which frames of the step are in the files
+      keypoint_counts.npy  (F,) float64     keypoints per frame
+      keypoints.npy        (n, 7) float32   x, y, size, angle, response, octave, class_id (the 28-byte records; the two ints exact)
+      descriptors.npy      (n, 8) float64   the 256-bit descriptor as eight little-endian 32-bit words (exact)
+      match_counts.npy     (F,) float64     matches of frame b against its predecessor in the scene
+      match_pairs.npy      (m, 2) float32   (idx_1 in the predecessor, idx_2 in frame b) index pairs, exact below 2^24
+    When all frames could exceed budget_bytes at the keypoint capacity, a fixed seeded sample of frames is written (the choice does not
+    depend on the outputs, so two builds dump the same frames)."""
+    cap = last_out[0]["cap"]
+    n_frames = Bc * len(last_out)
+    per_frame = cap * (7 * 4 + 8 * 8 + 2 * 4) + 3 * 8
+    keep = min(n_frames, max(1, budget_bytes // per_frame))
+    frames = np.arange(n_frames) if keep == n_frames else np.sort(np.random.default_rng(20240).choice(n_frames, keep, replace=False))
+    kps, desc, kcnt, pairs, mcnt = [], [], [], [], []
+    for g in frames:
+        lo = last_out[g // Bc]
+        b = g % Bc
+        n, m = int(lo["cnt"][b]), int(lo["mcnt"][b])
+        rec = np.ascontiguousarray(lo["kps"][b, :n]).reshape(n, 28)
+        kps.append(np.concatenate([rec.view("<f4")[:, :5], rec.view("<i4")[:, 5:7].astype(np.float32)], 1))
+        desc.append(np.ascontiguousarray(lo["desc"][b, :n]).view("<u4").astype(np.float64))
+        pairs.append(lo["pairs"][b, :m].astype(np.float32))
+        kcnt.append(n)
+        mcnt.append(m)
+    os.makedirs(path, exist_ok=True)
+    arrays = {"frame_index": frames.astype(np.float64), "keypoint_counts": np.array(kcnt, np.float64),
+              "keypoints": np.concatenate(kps).reshape(-1, 7), "descriptors": np.concatenate(desc).reshape(-1, 8),
+              "match_counts": np.array(mcnt, np.float64), "match_pairs": np.concatenate(pairs).reshape(-1, 2)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return arrays
+
+
 def level_sizes(rows, cols, scale=1.2, levels=8):
     sf = np.float32(1.0)
     out = [(rows, cols)]
@@ -96,7 +156,7 @@ def live_pmc_traffic(stage_kernel_prefix, batch=128, timeout_s=150):
     exe = shutil.which("rocprofv3") or ("/opt/rocm/bin/rocprofv3" if os.path.exists("/opt/rocm/bin/rocprofv3") else None)
     if not exe:
         return None, "rocprofv3 not found"
-    child = [sys.executable, os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-ba", "--overlap", "0",
+    child = [sys.executable, os.path.abspath(__file__), "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-ba", "--overlap", "0",
              "--batch", str(batch), "--fast-split", "0", "--live-pmc", "0"]
     means = {}
     with tempfile.TemporaryDirectory(prefix="ovs_pmc_", dir="/tmp") as td:
@@ -142,7 +202,13 @@ def main():
     ap.add_argument("--live-pmc", type=int, default=1, help="1: roofline.traffic from rocprofv3 --pmc passes THIS run spawns (two short child runs of this "
                                                              "script under the profiler, FETCH_SIZE and WRITE_SIZE separately); falls back to the committed "
                                                              "profiles/pmc_traffic.json when rocprofv3 is missing, fails or times out; 0: the committed file only")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run every side measurement and check (rooflines, "
+                                                        "popcount form, local BA, other configs, class latency, CPU baseline + parity); "
+                                                        "--no-cpu-baseline, --cpu-budget-s, --no-ba and --live-pmc act on these only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs (rank 0) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import torch.distributed as dist
@@ -187,16 +253,16 @@ def main():
             dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
 
     from openvslam_amd import _lib, feature, match
-    from openvslam_amd.synth import synth_video
 
     B = args.batch
     L = _lib.lib()
     # ---- synthetic input, resident in HBM before the timed region (each rank gets its own frames)
     # TWO distinct batches, alternated step by step: 2 x 265 MB of input cannot sit in the 256 MiB Infinity Cache, so level-0 reads
     # of the timed region come from HBM (bench hygiene)
-    frames = synth_video(ROWS, COLS, B, seed=100 + rank)
+    # (the ranks of a node share its 16 host threads)
+    frames = synth_video_threaded(ROWS, COLS, B, seed=100 + rank, threads=max(1, 16 // world))
     d_frames = torch.from_numpy(frames).cuda()
-    frames_alt = synth_video(ROWS, COLS, B, seed=900 + rank)
+    frames_alt = synth_video_threaded(ROWS, COLS, B, seed=900 + rank, threads=max(1, 16 // world))
     d_frames_alt = torch.from_numpy(frames_alt).cuda()
     n_chain = max(1, args.chains)
     if B % (8 * n_chain):
@@ -286,8 +352,9 @@ def main():
     elapsed = t1 - t0
     # ---- the LAST timed step's outputs, copied to the host before anything else touches the buffers: what the parity check below compares
     # with the CPU oracle (so the checked bytes are the ones the timed schedule itself produced: level-0 split, overlap, second stream)
+    # (a plain run takes it only for --dump-outputs)
     last_out = None
-    if rank == 0:
+    if rank == 0 and (args.full or args.dump_outputs):
         last_out = []
         for ch in chains:
             k, which = ch.last
@@ -295,6 +362,8 @@ def main():
             last_out.append(dict(which=which, cap=ch.ex.max_keypoints,
                                  kps=b["kps"].cpu().numpy().view(np.uint8).reshape(Bc, -1, 28), desc=b["desc"].cpu().numpy(),
                                  cnt=b["cnt"].cpu().numpy(), pairs=b["pairs"].cpu().numpy(), mcnt=b["mcnt"].cpu().numpy()))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last_out, Bc)
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -321,6 +390,56 @@ def main():
             stage_ms[key] += v / calls
         stage_ms["match_near"] += st2[0] / calls
         stage_ms["match_resolve"] += st2[1] / calls
+
+    # units per step: with two output buffer sets each one is permanently paired with one of the two alternating input batches (step parity
+    # picks both), so the mean over the buffer sets is the exact per-step average of the timed region (K even; +-1 step's difference else)
+    kp_step = matches_step = pairs_step = 0
+    for ch in chains:
+        for b in ch.bufs:
+            cnt = b["cnt"].cpu().numpy().astype(np.int64)
+            kp_step += cnt.sum() / float(ch.n_buf)
+            matches_step += b["mcnt"].cpu().numpy().astype(np.int64).sum() / float(ch.n_buf)
+            pairs_step += (cnt * cnt[ch.prev.cpu().numpy()]).sum() / float(ch.n_buf)
+    totals = torch.tensor([kp_step, matches_step, pairs_step], dtype=torch.float64, device="cuda")
+    if world > 1:
+        dist.all_reduce(totals, op=dist.ReduceOp.SUM)
+    kp_all, matches_all, pairs_all = (float(x) for x in totals.cpu().numpy())
+
+    head = {
+        "metric": "ORB kpts+descriptors/sec and Hamming matches/sec @1920x1080, 8-level pyramid",
+        "value": round(kp_all * args.steps / elapsed, 1),
+        "unit": "keypoints+descriptors/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic",
+        "config": {"workload": "BASELINE configs[1]: 1920x1080 mono, 8 pyramid levels (x1.2), 2000 ORB features, extract + "
+                               "robust::brute_force_match (thr 50, ratio 0.9) against the previous frame",
+                   "frames_per_step_per_gpu": B, "distinct_input_batches": 2, "sharding": "frames across ranks, no collective",
+                   "schedule": ("%d independent chain(s) of %d frames; " % (n_chain, Bc))
+                               + ("matching of step k on a second stream under the extraction of step k+1 (double-buffered)"
+                                  if args.overlap else "extraction and matching serial on one stream")},
+        "frames_per_sec": round(B * world * args.steps / elapsed, 2),
+        "matches_per_sec": round(matches_all * args.steps / elapsed, 1),
+        "hamming_distances_per_sec": round(pairs_all * args.steps / elapsed, 1),
+        "keypoints_per_frame": round(kp_step / B, 2),
+        "matches_per_frame": round(matches_step / B, 2),
+        "stage_ms_per_step": {k: round(v, 5) for k, v in stage_ms.items()},
+        "fast_level0_ms_inside_pyramid_window": round(fast_l0_ms, 5),
+        **({"test_hook": "OVS_BENCH_ONE_DEVICE=1: all ranks on ONE device over gloo -- a code-path test, not a measurement"} if one_device else {}),
+    }
+    if not args.full:
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(head))
+        return
 
     # ---- the same stages with each kernel ALONE on the GPU (extract, sync, match, sync): what the per-kernel rooflines below are quoted
     # on, because under the two-stream schedule the matcher and the pyramid stretch each other
@@ -408,20 +527,6 @@ def main():
                         and np.array_equal(kp_[i, :cnt_[i]], lo_["kps"][i, :cnt_[i]]) and np.array_equal(pr[i, :mcnt_[i]], lo_["pairs"][i, :mcnt_[i]])
     for ch in chains:
         ch.mt.set_near_path("matrix")
-
-    # units per step: with two output buffer sets each one is permanently paired with one of the two alternating input batches (step parity
-    # picks both), so the mean over the buffer sets is the exact per-step average of the timed region (K even; +-1 step's difference else)
-    kp_step = matches_step = pairs_step = 0
-    for ch in chains:
-        for b in ch.bufs:
-            cnt = b["cnt"].cpu().numpy().astype(np.int64)
-            kp_step += cnt.sum() / float(ch.n_buf)
-            matches_step += b["mcnt"].cpu().numpy().astype(np.int64).sum() / float(ch.n_buf)
-            pairs_step += (cnt * cnt[ch.prev.cpu().numpy()]).sum() / float(ch.n_buf)
-    totals = torch.tensor([kp_step, matches_step, pairs_step], dtype=torch.float64, device="cuda")
-    if world > 1:
-        dist.all_reduce(totals, op=dist.ReduceOp.SUM)
-    kp_all, matches_all, pairs_all = (float(x) for x in totals.cpu().numpy())
 
     ba_res = None if args.no_ba else bench_local_ba(world, rank, dist, torch)
     # a local map ten times larger (a loop-closure sized window): the size at which sharding the linearisation over GPUs can pay, see
@@ -584,31 +689,7 @@ def main():
                 cpu = None
 
         out = {
-            "metric": "ORB kpts+descriptors/sec and Hamming matches/sec @1920x1080, 8-level pyramid",
-            "value": round(kp_all * args.steps / elapsed, 1),
-            "unit": "keypoints+descriptors/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": "synthetic",
-            "config": {"workload": "BASELINE configs[1]: 1920x1080 mono, 8 pyramid levels (x1.2), 2000 ORB features, extract + "
-                                   "robust::brute_force_match (thr 50, ratio 0.9) against the previous frame",
-                       "frames_per_step_per_gpu": B, "distinct_input_batches": 2, "sharding": "frames across ranks, no collective",
-                       "schedule": ("%d independent chain(s) of %d frames; " % (n_chain, Bc))
-                                   + ("matching of step k on a second stream under the extraction of step k+1 (double-buffered)"
-                                      if args.overlap else "extraction and matching serial on one stream")},
-            "frames_per_sec": round(B * world * args.steps / elapsed, 2),
-            "matches_per_sec": round(matches_all * args.steps / elapsed, 1),
-            "hamming_distances_per_sec": round(pairs_all * args.steps / elapsed, 1),
-            "keypoints_per_frame": round(kp_step / B, 2),
-            "matches_per_frame": round(matches_step / B, 2),
-            "stage_ms_per_step": {k: round(v, 5) for k, v in stage_ms.items()},
-            "fast_level0_ms_inside_pyramid_window": round(fast_l0_ms, 5),
+            **head,
             "stage_ms_per_step_each_kernel_alone": {k: round(v, 5) for k, v in iso_ms.items()},
             "extract_algorithmic_GBps": round(extract_gbs, 2),
             "extract_frac_of_hbm_peak": round(extract_gbs / HBM_PEAK_GBS, 5),
@@ -624,7 +705,6 @@ def main():
             "value_popcount_near_path": round(kp_all * args.steps / elapsed_popc, 1),
             "ms_per_step_popcount_near_path": round(elapsed_popc / args.steps * 1e3, 4),
             "popcount_near_path_same_outputs_as_value_run": popc_sched_same,
-            **({"test_hook": "OVS_BENCH_ONE_DEVICE=1: all ranks on ONE device over gloo -- a code-path test, not a measurement"} if one_device else {}),
         }
         if cpu:
             out["speedup_vs_cpu_baseline"] = round(out["value"] / cpu["value"], 1)

@@ -45,7 +45,7 @@ def probe(tag, iters=20):
 if __name__ == "__main__":
     probe("fresh process")
     import bench
-    sys.argv = ["bench.py", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--live-pmc", "0", "--no-ba"]
+    sys.argv = ["bench.py", "--full", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--live-pmc", "0", "--no-ba"]
     try:
         bench.main()
     except SystemExit as e:
