@@ -217,7 +217,7 @@ struct GraphDev {   // device views shared by the kernels
                                  // (a landmark with more than 256 edges is a workgroup of its own)
     const int32_t* chunk_kf;     // [n_chunks] keyframe of every chunk of kPoseChunk entries of pose_edges
     const int32_t* chunk_start;  // [n_pose + 1] first chunk of every keyframe
-    double* pose_part;           // [n_chunks x 27] the chunks' sums of the 21 + 6 pose-block terms
+    double* pose_part;           // [2 n_chunks x 27] the half chunks' sums of the 21 + 6 pose-block terms
     int n_lm_wg, n_chunks;
     ovs_ba_cam cam;        // model 1: {cols, rows, -, -}
     double bf;
@@ -230,7 +230,7 @@ struct GraphDev {   // device views shared by the kernels
 // order: a landmark's contributions are added in ascending edge index, mono before stereo, exactly as the sequential loop did (Hll, bl, chi2
 // partials: the same bits as rounds 2-5 and as the oracle); a keyframe's 27 terms are a fixed-shape tree per chunk of 512 edges, the chunks
 // added in ascending order by k_reduce_scalars (deterministic; not the tree of rounds 2-5: last-bit differences in Hpp / bp).
-constexpr int kPoseChunk = 512;     // entries of pose_edges per keyframe workgroup (two per thread)
+constexpr int kPoseChunk = 512;     // entries of pose_edges per chunk (k_linearize2: two keyframe workgroups, one entry per thread)
 constexpr int kLmSlots = 256;       // edges per landmark workgroup
 
 // sum of x over the wave in lane 63: row_shr 1 / 2 / 4 / 8 inside the 16-lane rows, then row_bcast 15 / 31 -- data-parallel moves in the
@@ -268,146 +268,17 @@ __device__ __forceinline__ void block_sum_256(double (&v)[NV], double (*s_part)[
     __syncthreads();
 }
 
-// chunk c of keyframe k by one 256-thread workgroup: thread t takes entries t and t + 256 of the chunk, one after the other
-template <int kModel, bool kStage>
-__device__ __forceinline__ void lin_pose_chunk(const GraphDev& g, const int chunk, const double* __restrict__ poses, const double* __restrict__ points,
-                                               double huber_mono, double huber_stereo, double* __restrict__ Hpl, double (*s_part)[27],
-                                               double2* __restrict__ s_h) {
-    const int k = g.chunk_kf[chunk];
-    double acc[27];
-#pragma unroll
-    for (int i = 0; i < 27; ++i) acc[i] = 0.0;
-    const int e1 = g.pose_start[k + 1];
-    const int i0 = g.pose_start[k] + (chunk - g.chunk_start[k]) * kPoseChunk + (int)threadIdx.x;
-    auto zero_hpl = [&](int e) {
-        double2* const h = reinterpret_cast<double2*>(Hpl + 18 * (size_t)e);
-#pragma unroll
-        for (int a = 0; a < 9; ++a) h[a] = double2{0.0, 0.0};
-    };
-    if (g.fixed[k]) {   // (workgroup-uniform) a fixed keyframe's block and its edges' Hpl are zero
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-            if (i0 + 256 * u < e1) zero_hpl(g.pose_edges[i0 + 256 * u]);
-    } else {
-        const double* P = poses + 7 * (size_t)k;
-        // both entries' gathers (index -> record -> landmark) are issued before either edge is worked on, one after the other
-        int ee[2];
-        GEdge edd[2];
-        double XX[2][3];
-        int pt[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const bool in = i0 + 256 * u < e1;
-            ee[u] = in ? g.pose_edges[i0 + 256 * u] : -1;
-            pt[u] = in ? g.pose_pt[i0 + 256 * u] : 0;   // the landmark without going through the edge record: one dependent load less
-        }
-        // (the records' 40-byte gathers were staged through LDS the same way as the stores below -- five coalesced loads per 64 consecutive
-        // records -- and that changed nothing: 0.110 against 0.108 ms at a million edges; the loads are not what the kernel waits for)
-#pragma unroll
-        for (int u = 0; u < 2; ++u) edd[u] = g.edges[max(ee[u], 0)];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const double* x = points + 3 * (size_t)pt[u];
-            XX[u][0] = x[0];
-            XX[u][1] = x[1];
-            XX[u][2] = x[2];
-        }
-#pragma unroll 1
-        for (int u = 0; u < 2; ++u) {
-            const int e = u ? ee[1] : ee[0];
-            if (!kStage) {
-                if (e < 0) break;
-                if (!g.active[e]) {   // exact zeros for an edge at g2o level 1
-                    zero_hpl(e);
-                    continue;
-                }
-            }
-            const bool live = kStage ? (e >= 0 && g.active[e]) : true;
-            double2 hv[9];
-            if (kStage) {
-#pragma unroll
-                for (int a = 0; a < 9; ++a) hv[a] = double2{0.0, 0.0};
-            }
-            if (live) {
-                const GEdge ed = u ? edd[1] : edd[0];
-                const double X[3] = {u ? XX[1][0] : XX[0][0], u ? XX[1][1] : XX[0][1], u ? XX[1][2] : XX[0][2]};
-                const bool stereo = e >= g.n_mono;
-                double Jl[3][6], Jp[3][6], r[3], W, c2, rho0;
-                if (kModel == 1) edge_lin_equirect(P, X, ed, g.cam, huber_mono, Jl, Jp, r, W, c2, rho0);
-                else edge_lin(P, X, ed, stereo, g.cam, g.bf, stereo ? huber_stereo : huber_mono, Jl, Jp, r, W, c2, rho0);
-                int t = 0;
-#pragma unroll
-                for (int a = 0; a < 6; ++a) {
-#pragma unroll
-                    for (int b = a; b < 6; ++b) acc[t++] += W * dot3(Jp, a, Jp, b, stereo);
-                    double gq = Jp[0][a] * r[0];
-                    gq = gq + Jp[1][a] * r[1];
-                    if (stereo) gq = gq + Jp[2][a] * r[2];
-                    acc[t++] += gq;
-                }
-                // W_e = W Jp^T Jl: this side walks the edges in ascending index, so a wave's 64 records are 9 KB of consecutive bytes
-                double2* const h = reinterpret_cast<double2*>(Hpl + 18 * (size_t)e);
-#pragma unroll
-                for (int a = 0; a < 6; a += 2) {   // rows a, a + 1: entries 3 a .. 3 a + 5
-                    const double h0 = W * dot3(Jp, a, Jl, 0, stereo), h1 = W * dot3(Jp, a, Jl, 1, stereo), h2 = W * dot3(Jp, a, Jl, 2, stereo);
-                    const double h3 = W * dot3(Jp, a + 1, Jl, 0, stereo), h4 = W * dot3(Jp, a + 1, Jl, 1, stereo), h5 = W * dot3(Jp, a + 1, Jl, 2, stereo);
-                    if (kStage) {
-                        hv[3 * (a >> 1)] = double2{h0, h1};
-                        hv[3 * (a >> 1) + 1] = double2{h2, h3};
-                        hv[3 * (a >> 1) + 2] = double2{h4, h5};
-                    } else {
-                        h[3 * (a >> 1)] = double2{h0, h1};
-                        h[3 * (a >> 1) + 1] = double2{h2, h3};
-                        h[3 * (a >> 1) + 2] = double2{h4, h5};
-                    }
-                }
-            }
-            if (kStage) {
-                // Round 6, late: a lane storing its own 144-byte record writes nine 16-byte pieces, each store instruction touching 64 different
-                // 128-byte lines (9 M partial-line write requests per million edges). When the wave's 64 edges are consecutive (the usual case:
-                // edge lists arrive keyframe by keyframe) the records pass through LDS and every store instruction writes 1 KB of consecutive bytes.
-                const int lane = (int)threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-                const int e_first = __shfl(e, 0);
-                const bool contig = __ballot(e >= 0 && e == e_first + lane) == ~0ull;   // (wave-uniform)
-                if (contig) {
-                    double2* const sh = s_h + (size_t)wv * (64 * 9);
-#pragma unroll
-                    for (int a = 0; a < 9; ++a) sh[lane * 9 + a] = hv[a];
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    double2* const h = reinterpret_cast<double2*>(Hpl + 18 * (size_t)e_first);
-#pragma unroll
-                    for (int a = 0; a < 9; ++a) h[a * 64 + lane] = sh[a * 64 + lane];
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();   // (the next entry's records overwrite the buffer)
-                } else if (e >= 0) {
-                    double2* const h = reinterpret_cast<double2*>(Hpl + 18 * (size_t)e);
-#pragma unroll
-                    for (int a = 0; a < 9; ++a) h[a] = hv[a];
-                }
-            }
-        }
-    }
-    block_sum_256<27>(acc, s_part);
-    if (threadIdx.x < 27) {
-        double v = acc[0];
-#pragma unroll
-        for (int i = 1; i < 27; ++i) v = (int)threadIdx.x == i ? acc[i] : v;
-        g.pose_part[27 * (size_t)chunk + threadIdx.x] = v;
-    }
-}
-
 // Round 6, late: HALF a chunk (256 entries of a keyframe's edge list) by a 256-thread workgroup, ONE entry per thread -- the keyframe side of
-// k_linearize2. Two entries per thread (lin_pose_chunk) keep 27 running sums alive across both edges' Jacobians: 218 VGPRs, a budget the landmark
-// side would have to share in a merged launch (round 5's merged k_linearize paid exactly that). With one entry a term goes from the Jacobians
-// straight into its wave sum: 78 VGPRs. By itself that bought nothing (1 M edges: 0.119 against 0.122 ms with six instead of two waves per SIMD --
+// k_linearize2. Two entries per thread (the keyframe launch of rounds 5-6) kept 27 running sums alive across both edges' Jacobians: 218 VGPRs,
+// a budget the landmark side would have to share in a merged launch (round 5's merged k_linearize paid exactly that). With one entry a term
+// goes from the Jacobians straight into its wave sum: 78 VGPRs. By itself that bought nothing (1 M edges: 0.119 against 0.122 ms with six instead of two waves per SIMD --
 // the kernel is bound by its 144 bytes of Hpl per edge, not by latency); what it allows is the merged launch. A half chunk's sum is its four
 // waves' sums in wave order; k_reduce_scalars adds the halves in ascending order (a fixed shape; it differs from the two-entry form's in the
 // last bits of Hpp / bp, like every change of the tree so far; Hpl is per edge and keeps its bits).
 template <int kModel>
 __device__ __forceinline__ void lin_pose_half(const GraphDev& g, const int half_chunk, const double* __restrict__ poses, const double* __restrict__ points,
                                               double huber_mono, double huber_stereo, double* __restrict__ Hpl, double (*s_part)[27],   // [4][27]
-                                              double2* __restrict__ s_h) {   // [4 waves][64 x 9]: the records on their way to coalesced stores (lin_pose_chunk)
+                                              double2* __restrict__ s_h) {   // [4 waves][64 x 9]: the records on their way to coalesced stores
     const int chunk = half_chunk >> 1;
     const int k = g.chunk_kf[chunk];
     const int lane = (int)threadIdx.x & 63, wv = (int)threadIdx.x >> 6;
@@ -443,7 +314,10 @@ __device__ __forceinline__ void lin_pose_half(const GraphDev& g, const int half_
             }
         }
     }
-    {   // the records leave through LDS when the wave's 64 edges are consecutive (see lin_pose_chunk)
+    {
+        // W_e = W Jp^T Jl. A lane storing its own 144-byte record writes nine 16-byte pieces, each store instruction touching 64 different
+        // 128-byte lines (9 M partial-line write requests per million edges). When the wave's 64 edges are consecutive (the usual case: edge
+        // lists arrive keyframe by keyframe) the records pass through LDS and every store instruction writes 1 KB of consecutive bytes.
         const int e_first = __shfl(e, 0);
         const bool contig = __ballot(e >= 0 && e == e_first + lane) == ~0ull;   // (wave-uniform)
         if (contig) {
@@ -616,46 +490,6 @@ __global__ __launch_bounds__(256) void k_dup_check(const GEdge* __restrict__ led
     if (dup) atomicMin(dup_word, ((unsigned long long)(uint32_t)j << 32) | (uint32_t)k);
 }
 
-// The two halves of a linearisation are independent (different outputs, the same inputs). Round 5 ran them side by side in ONE launch; as
-// two launches each gets its own register budget: the keyframe side needs ~200 VGPRs (27 running sums beside both Jacobians: two waves per
-// SIMD), the landmark side fewer than 128 (four waves per SIMD) -- merged, every workgroup paid the larger figure.
-template <int kModel, bool kStage>
-__global__ __launch_bounds__(256) void k_lin_pose(GraphDev g, const double* __restrict__ poses, const double* __restrict__ points, double huber_mono,
-                                                 double huber_stereo, double* __restrict__ Hpl) {
-    __shared__ double s_part[4][27];
-    __shared__ double2 s_h[kStage ? 4 * 64 * 9 : 1];   // the four waves' 64 records of 144 bytes on their way to coalesced stores
-    lin_pose_chunk<kModel, kStage>(g, (int)blockIdx.x, poses, points, huber_mono, huber_stereo, Hpl, s_part, s_h);
-}
-template <int kModel>
-__global__ __launch_bounds__(256) void k_lin_landmark(GraphDev g, const double* __restrict__ poses, const double* __restrict__ points, double huber_mono,
-                                                     double huber_stereo, double* __restrict__ Hpp, double* __restrict__ bp, double* __restrict__ Hll,
-                                                     double* __restrict__ bl, double* __restrict__ lm_chi) {
-    __shared__ double s_c[14][kLmSlots + 1];   // + 1: the fourteen terms of a slot in fourteen different banks
-    __shared__ double s_d[5][256];
-    // first, the keyframes' blocks (k_lin_pose, the launch before this one, has left a keyframe's 27 terms as one sum per chunk of its edges):
-    // the chunks are added in ascending order; Hpp symmetric, bp
-    for (int k = (int)blockIdx.x; k < g.n_pose; k += (int)gridDim.x)
-        if (threadIdx.x < 27) {
-            const int t = (int)threadIdx.x;
-            double v = 0.0;
-            for (int c = g.chunk_start[k]; c < g.chunk_start[k + 1]; ++c) v += g.pose_part[27 * (size_t)c + t];
-            // term t of the upper triangle's rows (a, a .. 5), each followed by the row's right-hand side entry
-            int a = 0, rem = t;
-            while (rem >= 7 - a) {
-                rem -= 7 - a;
-                ++a;
-            }
-            if (rem == 6 - a) {
-                bp[6 * (size_t)k + a] = v;
-            } else {
-                const int b = a + rem;
-                Hpp[36 * (size_t)k + 6 * a + b] = v;
-                Hpp[36 * (size_t)k + 6 * b + a] = v;
-            }
-        }
-    lin_landmark_wg<kModel>(g, (int)blockIdx.x, poses, points, huber_mono, huber_stereo, Hll, bl, lm_chi, s_c, s_d);
-}
-
 // Both halves in ONE launch again (round 6, late; round 5's merged k_linearize was split because the keyframe side's 218 VGPRs set the budget of
 // every workgroup -- lin_pose_half needs 78, the landmark side 70): 2 n_chunks keyframe workgroups (half a chunk each) and n_lm_wg landmark
 // workgroups, interleaved one by one while both kinds last so that the keyframe side's stream of Hpl stores (144 bytes per edge: it is bound by
@@ -725,19 +559,18 @@ __device__ __forceinline__ double tree_sum_1024(double* __restrict__ s, const do
 // chi2[0..1] = sum of the per-landmark partials; chi2[2] = max |diagonal| over free pose blocks and landmarks with edges (g2o's
 // computeLambdaInit); one workgroup, fixed order. With `lm_scale` (a Levenberg-Marquardt trial: the landmarks' terms of the gain ratio's
 // denominator, written by the back-substitution) their sum goes to scale_sum[0] -- the additions of the former k_sum_1024, in its order.
-__global__ __launch_bounds__(1024) void k_reduce_scalars(GraphDev g, const double* __restrict__ lm_chi, const double* Hpp,   // (Hpp may be Hpp_out: no restrict)
-                                                        const double* __restrict__ Hll, double* __restrict__ chi2, double* __restrict__ mirror,
-                                                        const double* __restrict__ lm_scale, double* __restrict__ scale_sum,
+__global__ __launch_bounds__(1024) void k_reduce_scalars(GraphDev g, const double* __restrict__ lm_chi, double* __restrict__ chi2,
+                                                        double* __restrict__ mirror, const double* __restrict__ lm_scale, double* __restrict__ scale_sum,
                                                         unsigned long long* __restrict__ host_ll, unsigned int seq, const int32_t* __restrict__ fail2,
-                                                        double* Hpp_out = nullptr, double* __restrict__ bp_out = nullptr) {
+                                                        double* __restrict__ Hpp, double* __restrict__ bp) {
     // host_ll (round 6, the device solver's LM trials): the trial's outcome -- the gain ratio's two parts, the chi2 triple, the two failure words --
     // also goes straight into a page-locked block as twelve 64-bit words {seq : 32 | half of a double : 32}; the host polls them instead of
     // enqueuing a 264-byte D2H copy and waiting for the stream (a copy kernel, its launch gap and the wait's wake-up per trial). A word whose
     // upper half is this trial's sequence number carries this trial's data: no fence (a system-scope release here would write back every dirty
     // line of the L2 -- the ~50 us per trial that sank "one kernel writes the values into the page-locked block" in round 4).
     __shared__ double s0[1024], s1[1024], s2[1024];
-    if (Hpp_out && blockIdx.x > 0) {
-        // behind k_linearize2, workgroups 1 ..: the keyframes' blocks from the half chunks' sums (halves in ascending order); Hpp symmetric, bp.
+    if (blockIdx.x > 0) {
+        // workgroups 1 ..: the keyframes' blocks from the half chunks' sums (halves in ascending order); Hpp symmetric, bp.
         // (One workgroup doing this as well was a serial tail of 27 n_pose sums of up to 40 dependent loads: 1 M edges 0.162 against 0.124 ms.)
         // The free keyframes' diagonal entries also go into chi2[2] = the largest |diagonal entry| (g2o's computeLambdaInit), as an atomic maximum
         // on the bit pattern (non-negative doubles order like integers; a maximum does not depend on the order of its operands): workgroup 0 used
@@ -753,11 +586,11 @@ __global__ __launch_bounds__(1024) void k_reduce_scalars(GraphDev g, const doubl
                 ++a;
             }
             if (rem == 6 - a) {
-                bp_out[6 * (size_t)k + a] = v;
+                bp[6 * (size_t)k + a] = v;
             } else {
                 const int b = a + rem;
-                Hpp_out[36 * (size_t)k + 6 * a + b] = v;
-                Hpp_out[36 * (size_t)k + 6 * b + a] = v;
+                Hpp[36 * (size_t)k + 6 * a + b] = v;
+                Hpp[36 * (size_t)k + 6 * b + a] = v;
                 if (rem == 0 && !g.fixed[k]) dmax = fmax(dmax, fabs(v));
             }
         }
@@ -781,7 +614,7 @@ __global__ __launch_bounds__(1024) void k_reduce_scalars(GraphDev g, const doubl
         __syncthreads();   // (s0 is reused below)
     }
     double a = 0, b = 0, m = 0;
-    // the landmark workgroups' shares (k_lin_landmark), a thread's in ascending order
+    // the landmark workgroups' shares (k_linearize2's landmark partition), a thread's in ascending order
     for (int w0 = threadIdx.x; w0 < g.n_lm_wg; w0 += 8 * 1024) {   // eight triples in flight (a million edges: 4000 workgroups' shares, four
         double ca[8], cb[8], cm[8];                                 // dependent round trips with one at a time), added in the plain loop's order
 #pragma unroll
@@ -800,12 +633,7 @@ __global__ __launch_bounds__(1024) void k_reduce_scalars(GraphDev g, const doubl
                 m = fmax(m, cm[u]);
             }
     }
-    if (Hpp_out) {   // (uniform) the keyframes' diagonal entries reach chi2[2] from the workgroups that add them up (above): the landmarks' part here
-    } else {
-        for (int k = threadIdx.x; k < g.n_pose; k += 1024)
-            if (!g.fixed[k])
-                for (int d = 0; d < 6; ++d) m = fmax(m, fabs(Hpp[36 * (size_t)k + 7 * d]));
-    }
+    // (the keyframes' diagonal entries reach chi2[2] from the workgroups that add them up, above: m is the landmarks' part)
     s1[threadIdx.x] = b;
     s2[threadIdx.x] = m;
     const double ta = tree_sum_1024(s0, a);   // (its barrier also covers s1 and s2)
@@ -838,15 +666,11 @@ __global__ __launch_bounds__(1024) void k_reduce_scalars(GraphDev g, const doubl
         s2[0] = tm;
         chi2[0] = ta;
         chi2[1] = tb;
-        if (Hpp_out) {
-            if (tm > 0.0) atomicMax(reinterpret_cast<unsigned long long*>(chi2 + 2), (unsigned long long)__double_as_longlong(tm));
-        } else {
-            chi2[2] = tm;
-        }
+        if (tm > 0.0) atomicMax(reinterpret_cast<unsigned long long*>(chi2 + 2), (unsigned long long)__double_as_longlong(tm));
         if (mirror) {   // a second copy next to the solver's scalars: ONE download brings a Levenberg-Marquardt trial's outcome back
             mirror[0] = ta;
             mirror[1] = tb;
-            mirror[2] = tm;   // (behind k_linearize2: the landmarks' part only -- no reader: an LM trial consumes [0], [1] and the gain ratio's parts)
+            mirror[2] = tm;   // (the landmarks' part only -- no reader: an LM trial consumes [0], [1] and the gain ratio's parts)
         }
     }
     __syncthreads();
@@ -1117,7 +941,6 @@ __global__ __launch_bounds__(1024) void k_scan_i32(const int32_t* __restrict__ c
 }
 
 // schur_pair on the lists
-template <bool kCoop>
 __device__ __forceinline__ void schur_pair_l(const int pr, const int32_t* __restrict__ pair_ab, const int32_t* __restrict__ slot_pose,
                                              const int32_t* __restrict__ off, const int2* __restrict__ ent, const double* __restrict__ Hpp,
                                              const double* __restrict__ Hpl, const double* __restrict__ Y, double lambda, int pitch,
@@ -1129,22 +952,13 @@ __device__ __forceinline__ void schur_pair_l(const int pr, const int32_t* __rest
 #pragma unroll
     for (int i = 0; i < 36; ++i) acc[i] = 0.0;
     const int s1 = off[4 * pr + wave + 1];
-    if (!kCoop) {
-        for (int idx = off[4 * pr + wave] + lane; idx < s1; idx += 64) {
-            const int2 en = ent[idx];
-            const double* y = Y + 18 * (size_t)en.x;
-            const double* W2 = Hpl + 18 * (size_t)en.y;
-#pragma unroll
-            for (int a = 0; a < 6; ++a)
-#pragma unroll
-                for (int b = 0; b < 6; ++b) acc[6 * a + b] += (y[3 * a] * W2[3 * b] + y[3 * a + 1] * W2[3 * b + 1]) + y[3 * a + 2] * W2[3 * b + 2];
-        }
-    } else {
+    {
         // A lane reading its own two 144-byte records issues 18 loads that each touch 64 different lines: the address unit of the CU takes a line
         // per clock, 2300 clocks per batch of 64 entries -- and a diagonal pair (a, a) has all of a's ~2000 edges, eight batches per wave on ONE
         // CU: the launch waited for those 48 workgroups. Here the wave fetches the batch's 2 x 64 records as 2 x 576 16-byte pieces, consecutive
         // lanes taking consecutive pieces of a record (seven records per instruction, ~14 lines), through LDS; every lane then reads its own
-        // records from there (stride 144 bytes: conflict-free for 16-byte reads). The products and their order are those of the loop above.
+        // records from there (stride 144 bytes: conflict-free for 16-byte reads). Lane l takes entries l, l + 64, ... of the wave's list and adds
+        // acc[6 a + b] += (y_a0 W_b0 + y_a1 W_b1) + y_a2 W_b2 in that order.
         double2* const buf = s_rec + (size_t)wave * (64 * 9);
         const double2* const Y2 = reinterpret_cast<const double2*>(Y);
         const double2* const H2 = reinterpret_cast<const double2*>(Hpl);
@@ -1214,7 +1028,6 @@ __device__ __forceinline__ void schur_pair_l(const int pr, const int32_t* __rest
 }
 
 // (212 VGPRs, two waves per SIMD; three forced by amdgpu_waves_per_eu: 172 bytes of scratch)
-template <bool kCoop>
 __global__ __launch_bounds__(256) void k_schur_l(GraphDev g, int n_free, const int32_t* __restrict__ pair_ab, const int32_t* __restrict__ slot_pose,
                                                 const int32_t* __restrict__ off, const int2* __restrict__ ent, const double* __restrict__ Hpp,
                                                 const double* __restrict__ bp, const double* __restrict__ bl, const double* __restrict__ Hpl,
@@ -1222,7 +1035,7 @@ __global__ __launch_bounds__(256) void k_schur_l(GraphDev g, int n_free, const i
                                                 double* __restrict__ rhs, const int32_t* __restrict__ wg_pair, int n_pair_wg) {
     __shared__ double s_part[4][36];
     __shared__ double s_part6[4][6];
-    __shared__ double2 s_rec[kCoop ? 4 * 64 * 9 : 1];   // a batch's 64 records per wave
+    __shared__ double2 s_rec[4 * 64 * 9];   // a batch's 64 records per wave
     // grid: n_pair_wg pair workgroups, then n_free right-hand-side workgroups. wg_pair (graph_create) names the pair of every workgroup, -1 = none:
     // consecutive workgroups go to different XCDs (eight L2 caches), and the table gives every XCD whole ROWS a of the pair table, dealt so that
     // the eight get equal work -- the workgroups running side by side on an XCD then gather the same keyframe's Y records (and W records that
@@ -1231,25 +1044,23 @@ __global__ __launch_bounds__(256) void k_schur_l(GraphDev g, int n_free, const i
     if (q >= n_pair_wg) {   // (workgroup-uniform)
         schur_rhs(g, q - n_pair_wg, slot_pose, bp, bl, Y, rhs, s_part6);
     } else {
-        const int pr = wg_pair ? wg_pair[q] : q;
-        if (pr >= 0) schur_pair_l<kCoop>(pr, pair_ab, slot_pose, off, ent, Hpp, Hpl, Y, lambda, pitch, S, s_part, s_rec);
+        const int pr = wg_pair[q];
+        if (pr >= 0) schur_pair_l(pr, pair_ab, slot_pose, off, ent, Hpp, Hpl, Y, lambda, pitch, S, s_part, s_rec);
     }
 }
 
 // dxl_j = Hll^-1 (bl_j - sum_e W_e^T dxp[pose(e)]); X_trial = X + dxl; lm_scale[j] = dxl . (lambda dxl + bl_j)
-// `dx`: the keyframes' increments, six per reduced block when `slot_of_pose` is given (the device solver's solution vector, read in place),
-// else six per keyframe (the host solver's upload)
+// `dx`: the keyframes' increments, six per keyframe (the host solver's upload)
 __device__ __forceinline__ void backsub_landmark(const GraphDev& g, const int j, const double* __restrict__ Hinv, const double* __restrict__ Hpl,
-                                                 const double* __restrict__ bl, const double* __restrict__ dx,
-                                                 const int32_t* __restrict__ slot_of_pose, double lambda, const double* __restrict__ X,
-                                                 double* __restrict__ Xn, double* __restrict__ lm_scale) {
+                                                 const double* __restrict__ bl, const double* __restrict__ dx, double lambda,
+                                                 const double* __restrict__ X, double* __restrict__ Xn, double* __restrict__ lm_scale) {
     double r[3] = {bl[3 * (size_t)j], bl[3 * (size_t)j + 1], bl[3 * (size_t)j + 2]};
     for (int i = g.lm_start[j]; i < g.lm_start[j + 1]; ++i) {
         const int e = g.lm_edges[i];
         const int k = g.edges[e].pose;
         if (g.fixed[k]) continue;
         const double* W = Hpl + 18 * (size_t)e;
-        const double* d = dx + 6 * (size_t)(slot_of_pose ? slot_of_pose[k] : k);   // (k is free here: its slot is >= 0)
+        const double* d = dx + 6 * (size_t)k;
 #pragma unroll
         for (int c = 0; c < 3; ++c)
             r[c] -= ((W[c] * d[0] + W[3 + c] * d[1]) + (W[6 + c] * d[2] + W[9 + c] * d[3])) + (W[12 + c] * d[4] + W[15 + c] * d[5]);
@@ -1269,7 +1080,7 @@ __global__ __launch_bounds__(128) void k_backsub(GraphDev g, const double* __res
                                                 const double* __restrict__ bl, const double* __restrict__ dxp, double lambda,
                                                 const double* __restrict__ X, double* __restrict__ Xn, double* __restrict__ lm_scale) {
     const int j = (int)blockIdx.x * 128 + (int)threadIdx.x;
-    if (j < g.n_pt) backsub_landmark(g, j, Hinv, Hpl, bl, dxp, nullptr, lambda, X, Xn, lm_scale);
+    if (j < g.n_pt) backsub_landmark(g, j, Hinv, Hpl, bl, dxp, lambda, X, Xn, lm_scale);
 }
 
 // ---- LM trial state of the keyframes ------------------------------------------------------------------------------------------------
@@ -1378,7 +1189,7 @@ __device__ __forceinline__ void pose_update(const double* __restrict__ T, const 
 }
 
 
-// Back-substitution, one lane per EDGE (round 6): the landmarks of workgroup `wg` of k_lin_landmark's partition (whole landmarks, at most kLmSlots
+// Back-substitution, one lane per EDGE (round 6): the landmarks of workgroup `wg` of k_linearize2's landmark partition (whole landmarks, at most kLmSlots
 // edges). A lane per landmark walking its edges (backsub_landmark) is a chain of four dependent loads per edge and 313 waves at config 5: 23 us
 // of latency per Levenberg-Marquardt trial. Here every lane computes ITS slot's W_e^T dx (two dependent loads), and the landmark's lane then
 // subtracts its slots' terms from bl_j in list order -- backsub_landmark's subtractions, in its order: the same bits (an edge of a fixed
@@ -1447,27 +1258,23 @@ __device__ __forceinline__ void backsub_wg(const GraphDev& g, const int wg, cons
 }
 
 // The trial state of a Levenberg-Marquardt step in ONE launch (round 5): workgroup 0 advances the keyframes, the others back-substitute the
-// landmarks (kByEdge: one workgroup of k_lin_landmark's partition each, one lane per edge -- round 6; else 128 or 256 landmarks each, one lane per
-// landmark). The landmarks read the keyframes' increments from the solver's solution vector (slot order) instead of the dxp array the
-// keyframe workgroup writes, so the two halves are independent; as two launches the single keyframe workgroup held the queue for 9.5 us.
-template <bool kByEdge>
+// landmarks (one workgroup of k_linearize2's landmark partition each, one lane per edge -- round 6). The landmarks read the keyframes'
+// increments from the solver's solution vector (slot order) instead of the dxp array the keyframe workgroup writes, so the two halves are
+// independent; as two launches the single keyframe workgroup held the queue for 9.5 us.
 __global__ __launch_bounds__(256) void k_trial_update(GraphDev g, const double* __restrict__ T, const int32_t* __restrict__ slot_of_pose,
                                                      const double* __restrict__ x, const double* __restrict__ bp, double lambda,
                                                      double* __restrict__ Tn, double* __restrict__ p7n, double* __restrict__ dxp,
                                                      double* __restrict__ scal_pose, const double* __restrict__ Hinv, const double* __restrict__ Hpl,
                                                      const double* __restrict__ bl, const double* __restrict__ X, double* __restrict__ Xn,
-                                                     double* __restrict__ lm_scale, int32_t* __restrict__ next_fail, int lm_per_wg) {
+                                                     double* __restrict__ lm_scale, int32_t* __restrict__ next_fail) {
     __shared__ double s_term[256][7];   // a keyframe's six products (and whether it is free): thread 0 adds them in keyframe order
     if (blockIdx.x == 0) {   // (workgroup-uniform)
         // the NEXT trial's failure word (the two words alternate): its last reader, the host, consumed it a trial ago -- a memset launch less per trial
         if (threadIdx.x == 0) *next_fail = 0;
         pose_update(T, slot_of_pose, g.n_pose, x, bp, lambda, Tn, p7n, dxp, scal_pose, s_term);
-    } else if (kByEdge) {
+    } else {
         backsub_wg(g, (int)blockIdx.x - 1, Hinv, Hpl, bl, x, slot_of_pose, lambda, X, Xn, lm_scale,
                    reinterpret_cast<double (*)[kLmSlots + 1]>(&s_term[0][0]));   // (3 x 257 of the 1792 doubles)
-    } else {
-        const int j = ((int)blockIdx.x - 1) * lm_per_wg + (int)threadIdx.x;   // (landmarks_per_workgroup, as in k_linearize)
-        if ((int)threadIdx.x < lm_per_wg && j < g.n_pt) backsub_landmark(g, j, Hinv, Hpl, bl, x, slot_of_pose, lambda, X, Xn, lm_scale);
     }
 }
 
@@ -1514,7 +1321,7 @@ __global__ __launch_bounds__(256) void k_edge_chi2(GraphDev g, const double* __r
 // local_bundle_adjuster's chi-square gates on the device (round 6; until then both per-edge arrays came down -- 0.9 MB twice per call --, the host
 // judged 100 k edges in two loops and sent the active mask back up). An edge is an outlier when thr < chi2 or its depth is not positive
 // (upstream: `chi_sq_2D < edge->chi2() || !edge->depth_is_positive()`), thr by edge kind; the same double comparisons, so the same flags.
-//   after round 1 (chi_r1 == nullptr):  out[e] from chi[e] / depth[e]; active[e] = !out[e] (level-1 edges are masked, ba_graph_set_active);
+//   after round 1 (chi_r1 == nullptr):  out[e] from chi[e] / depth[e]; active[e] = !out[e] (level-1 edges are masked);
 //                                        *n_active += the inliers (integer atomics: any order gives the same count);
 //   final (chi_r1 != nullptr):           an edge optimised in round 2 (`use_final` and not a round-1 outlier) is judged by chi[e], any other by its
 //                                        round-1 value chi_r1[e] (g2o does not recompute the error of an inactive edge); depth[e] is the final state's.
@@ -1620,63 +1427,25 @@ struct ovs_ba_graph {
 
 namespace {
 
-// landmarks per 256-thread workgroup of k_linearize / k_trial_update: 128 (the upper two waves leave at once) while the launch then still fits the
-// chip in one go -- a landmark is a chain of dependent loads, so twice the workgroups on twice the compute units finish sooner --, 256 for larger maps
-static int landmarks_per_workgroup(int n_pose, int n_pt) {
-    static const int forced = [] {
-        const char* e = std::getenv("OVS_BA_LM_PER_WG");   // A/B switch: 128 | 256
-        return e ? std::atoi(e) : 0;
-    }();
-    if (forced == 128 || forced == 256) return forced;
-    return n_pose + (n_pt + 127) / 128 <= 512 ? 128 : 256;
-}
-
 // `trial_scale`: the linearisation closes a Levenberg-Marquardt trial -- the landmarks' gain-ratio terms the back-substitution left in
 // d_lm_tmp[3 n_pt ..) are summed into d_scal[0] by the same launch that sums chi2
 ovs_status graph_linearize(ovs_ba_graph* g, const double* d_poses, const double* d_points, double huber_mono, double huber_stereo, double* d_Hpp,
                            double* d_bp, double* d_Hll, double* d_bl, double* d_Hpl, double* d_chi3, hipStream_t s, double* d_chi_mirror = nullptr,
                            bool trial_scale = false, unsigned long long* host_ll = nullptr, unsigned int seq = 0) {
     const GraphDev v = g->view();
-    // One launch for both halves (k_linearize2): config 5 0.0325 -> 0.0249 ms, a million edges 0.124 -> 0.1005 ms per linearisation (a launch and
-    // its gap less; the Hpl records leave through LDS as whole lines; the keyframe side's stores and the landmark side's LDS reductions overlap).
-    // Before the stores were coalesced the merged launch LOST at a million edges (0.131 against 0.125 ms): the partial-line write requests of
-    // the keyframe side were what both halves queued behind. OVS_BA_LIN_MERGED=0: k_lin_pose (two entries per thread) and k_lin_landmark as two
-    // launches (0.110 ms at a million edges with the staged stores, 0.124 without: OVS_BA_HPL_STAGE=0). The two forms differ in the last bits
-    // of Hpp / bp (another summation tree), not in anything per edge or per landmark.
-    static const bool merged = [] {
-        const char* e = std::getenv("OVS_BA_LIN_MERGED");
-        return !(e && e[0] == '0');
-    }();
-    if (merged) {
-        const unsigned n_wg = (unsigned)(2 * g->n_chunks + g->n_lm_wg);
-        if (g->model == 1)
-            hipLaunchKernelGGL(k_linearize2<1>, dim3(n_wg), dim3(256), 0, s, v, d_poses, d_points, huber_mono, huber_stereo, d_Hpl, d_Hll, d_bl, g->d_lm_tmp, d_chi3);
-        else
-            hipLaunchKernelGGL(k_linearize2<0>, dim3(n_wg), dim3(256), 0, s, v, d_poses, d_points, huber_mono, huber_stereo, d_Hpl, d_Hll, d_bl, g->d_lm_tmp, d_chi3);
-        OVS_LAUNCH_TRY("k_linearize2");
-    } else {
-        if (g->n_chunks > 0) {
-            static const bool stage = [] {   // OVS_BA_HPL_STAGE=0: every lane stores its own record (round 6's first form)
-                const char* e = std::getenv("OVS_BA_HPL_STAGE");
-                return !(e && e[0] == '0');
-            }();
-            if (stage) {
-                if (g->model == 1) hipLaunchKernelGGL((k_lin_pose<1, true>), dim3(g->n_chunks), dim3(256), 0, s, v, d_poses, d_points, huber_mono, huber_stereo, d_Hpl);
-                else hipLaunchKernelGGL((k_lin_pose<0, true>), dim3(g->n_chunks), dim3(256), 0, s, v, d_poses, d_points, huber_mono, huber_stereo, d_Hpl);
-            } else if (g->model == 1) hipLaunchKernelGGL((k_lin_pose<1, false>), dim3(g->n_chunks), dim3(256), 0, s, v, d_poses, d_points, huber_mono, huber_stereo, d_Hpl);
-            else hipLaunchKernelGGL((k_lin_pose<0, false>), dim3(g->n_chunks), dim3(256), 0, s, v, d_poses, d_points, huber_mono, huber_stereo, d_Hpl);
-            OVS_LAUNCH_TRY("k_lin_pose");
-        }
-        if (g->model == 1)
-            hipLaunchKernelGGL(k_lin_landmark<1>, dim3(g->n_lm_wg), dim3(256), 0, s, v, d_poses, d_points, huber_mono, huber_stereo, d_Hpp, d_bp, d_Hll, d_bl, g->d_lm_tmp);
-        else
-            hipLaunchKernelGGL(k_lin_landmark<0>, dim3(g->n_lm_wg), dim3(256), 0, s, v, d_poses, d_points, huber_mono, huber_stereo, d_Hpp, d_bp, d_Hll, d_bl, g->d_lm_tmp);
-        OVS_LAUNCH_TRY("k_lin_landmark");
-    }
-    hipLaunchKernelGGL(k_reduce_scalars, dim3(1 + (merged ? (27 * g->n_pose + 1023) / 1024 : 0)), dim3(1024), 0, s, v, g->d_lm_tmp, d_Hpp, d_Hll, d_chi3, d_chi_mirror,
+    // One launch for both halves (k_linearize2): config 5 0.0325 -> 0.0249 ms, a million edges 0.124 -> 0.1005 ms per linearisation against the
+    // two launches of rounds 5-6 (a launch and its gap less; the Hpl records leave through LDS as whole lines; the keyframe side's stores and the
+    // landmark side's LDS reductions overlap). Before the stores were coalesced the merged launch LOST at a million edges (0.131 against
+    // 0.125 ms): the partial-line write requests of the keyframe side were what both halves queued behind.
+    const unsigned n_wg = (unsigned)(2 * g->n_chunks + g->n_lm_wg);
+    if (g->model == 1)
+        hipLaunchKernelGGL(k_linearize2<1>, dim3(n_wg), dim3(256), 0, s, v, d_poses, d_points, huber_mono, huber_stereo, d_Hpl, d_Hll, d_bl, g->d_lm_tmp, d_chi3);
+    else
+        hipLaunchKernelGGL(k_linearize2<0>, dim3(n_wg), dim3(256), 0, s, v, d_poses, d_points, huber_mono, huber_stereo, d_Hpl, d_Hll, d_bl, g->d_lm_tmp, d_chi3);
+    OVS_LAUNCH_TRY("k_linearize2");
+    hipLaunchKernelGGL(k_reduce_scalars, dim3(1 + (27 * g->n_pose + 1023) / 1024), dim3(1024), 0, s, v, g->d_lm_tmp, d_chi3, d_chi_mirror,
                        trial_scale ? g->d_lm_tmp + 3 * (size_t)g->n_pt : (const double*)nullptr, trial_scale ? g->d_scal : (double*)nullptr,
-                       trial_scale ? host_ll : (unsigned long long*)nullptr, seq, (const int32_t*)g->d_fail, merged ? d_Hpp : (double*)nullptr,
-                       merged ? d_bp : (double*)nullptr);
+                       trial_scale ? host_ll : (unsigned long long*)nullptr, seq, (const int32_t*)g->d_fail, d_Hpp, d_bp);
     OVS_LAUNCH_TRY("k_reduce_scalars");
     return OVS_OK;
 }
@@ -1920,10 +1689,10 @@ static ovs_status graph_create(int model, int32_t device, int32_t n_pose, const 
         lm_edges[(size_t)sc.fl[pt]++] = e;
         const int32_t at = sc.fp[edge_pose[e]]++;
         pose_edges[(size_t)at] = e;
-        pose_pt[(size_t)at] = pt;   // the landmark of every entry of pose_edges: k_schur's pair blocks and k_lin_pose walk a keyframe's observations without the 48-byte records
+        pose_pt[(size_t)at] = pt;   // the landmark of every entry of pose_edges: k_schur's pair blocks and k_linearize2 walk a keyframe's observations without the 48-byte records
     }
     const double t_p2 = now();
-    // k_lin_landmark's work partition: runs of whole landmarks with at most kLmSlots edges (and 256 landmarks). (The landmark of every slot and
+    // k_linearize2's landmark partition: runs of whole landmarks with at most kLmSlots edges (and 256 landmarks). (The landmark of every slot and
     // the check that a keyframe observes a landmark at most once -- upstream: landmark::add_observation ignores a second observation by the same
     // keyframe; the reduced system relies on it: k_edge_table keeps ONE edge per (keyframe, landmark), two edges of one free keyframe to one
     // landmark would need cross terms while Hpp / Hll / rhs would still count both, so such an edge list is refused -- moved to the device in
@@ -1944,7 +1713,7 @@ static ovs_status graph_create(int model, int32_t device, int32_t n_pose, const 
         wg_first[n_wg] = n_pt;
         g->n_lm_wg = n_wg;
         g->pl_bound = pl_bound;
-        // k_lin_pose: chunks of kPoseChunk entries of a keyframe's edge list
+        // k_linearize2's keyframe side: chunks of kPoseChunk entries of a keyframe's edge list (two workgroups each)
         int32_t* const chunk_kf = reinterpret_cast<int32_t*>(img + o_chunk_kf);
         int32_t* const chunk_start = reinterpret_cast<int32_t*>(img + o_chunk_start);
         int n_ch = 0;
@@ -2165,29 +1934,12 @@ ovs_status ba_graph_schur(ovs_ba_graph* g, const double* d_Hpp, const double* d_
                        g->d_fail + fail_word);
     OVS_LAUNCH_TRY("k_lm_prepare");
     if (g->n_free > 0) {
-        static const bool lists = [] {   // OVS_BA_SCHUR_LISTS=0: every trial's launch scans for the pairs' common landmarks itself (rounds 4-6)
-            const char* e = std::getenv("OVS_BA_SCHUR_LISTS");
-            return !(e && e[0] == '0');
-        }();
-        static const bool coop = [] {   // OVS_BA_SCHUR_COOP=0: every lane gathers its own two records
-            const char* e = std::getenv("OVS_BA_SCHUR_COOP");
-            return !(e && e[0] == '0');
-        }();
-        static const bool xcd = [] {   // OVS_BA_SCHUR_XCD=0: pairs in launch order (a-major), whatever XCD a workgroup lands on
-            const char* e = std::getenv("OVS_BA_SCHUR_XCD");
-            return !(e && e[0] == '0');
-        }();
-        const int32_t* const wgp = xcd ? g->d_wg_pair : nullptr;
-        const int n_pwg = xcd ? g->n_pair_wg : g->n_pairs;
-        if (lists && g->pl_ready && coop)
-            hipLaunchKernelGGL(k_schur_l<true>, dim3(g->n_free + n_pwg), dim3(256), 0, s, v, g->n_free, g->d_pair_ab, g->d_slot_pose, g->d_pl_off, g->d_pl_ent,
-                               d_Hpp, d_bp, d_bl, d_Hpl, g->d_Y, lambda, g->s_pitch, g->d_S, g->d_rhs, wgp, n_pwg);
-        else if (lists && g->pl_ready)
-            hipLaunchKernelGGL(k_schur_l<false>, dim3(g->n_free + n_pwg), dim3(256), 0, s, v, g->n_free, g->d_pair_ab, g->d_slot_pose, g->d_pl_off, g->d_pl_ent,
-                               d_Hpp, d_bp, d_bl, d_Hpl, g->d_Y, lambda, g->s_pitch, g->d_S, g->d_rhs, wgp, n_pwg);
-        else
+        if (!tuning().ba_schur_lists || !g->pl_ready)
             hipLaunchKernelGGL(k_schur, dim3(g->n_free + g->n_pairs), dim3(256), 0, s, v, g->n_free, g->d_pose_pt, g->d_pair_ab, g->d_slot_pose,
                                g->d_edge_of, d_Hpp, d_bp, d_bl, d_Hpl, g->d_Y, lambda, g->s_pitch, g->d_S, g->d_rhs);
+        else
+            hipLaunchKernelGGL(k_schur_l, dim3(g->n_free + g->n_pair_wg), dim3(256), 0, s, v, g->n_free, g->d_pair_ab, g->d_slot_pose, g->d_pl_off,
+                               g->d_pl_ent, d_Hpp, d_bp, d_bl, d_Hpl, g->d_Y, lambda, g->s_pitch, g->d_S, g->d_rhs, g->d_wg_pair, g->n_pair_wg);
         OVS_LAUNCH_TRY("k_schur");
     }
     return OVS_OK;
@@ -2208,23 +1960,9 @@ ovs_status ba_graph_backsub(ovs_ba_graph* g, const double* d_Hpl, const double* 
 ovs_status ba_graph_trial_update(ovs_ba_graph* g, const double* d_T, const double* d_bp, const double* d_Hpl, const double* d_bl, double lambda,
                                  double* d_Tn, double* d_p7n, const double* d_X, double* d_Xn, hipStream_t s, int next_fail_word) {
     const GraphDev v = g->view();
-    const int lm_per_wg = landmarks_per_workgroup(g->n_pose, g->n_pt);
-    if (tuning().ba_backsub_edges)
-        hipLaunchKernelGGL(k_trial_update<true>, dim3(1 + g->n_lm_wg), dim3(256), 0, s, v, d_T, g->d_slot_of_pose, g->d_rhs, d_bp, lambda, d_Tn, d_p7n, g->d_dxp,
-                           g->d_scal + 1, g->d_Hinv, d_Hpl, d_bl, d_X, d_Xn, g->d_lm_tmp + 3 * (size_t)g->n_pt, g->d_fail + next_fail_word, lm_per_wg);
-    else
-        hipLaunchKernelGGL(k_trial_update<false>, dim3(1 + (g->n_pt + lm_per_wg - 1) / lm_per_wg), dim3(256), 0, s, v, d_T, g->d_slot_of_pose, g->d_rhs, d_bp, lambda, d_Tn,
-                           d_p7n, g->d_dxp, g->d_scal + 1, g->d_Hinv, d_Hpl, d_bl, d_X, d_Xn, g->d_lm_tmp + 3 * (size_t)g->n_pt, g->d_fail + next_fail_word,
-                           lm_per_wg);
+    hipLaunchKernelGGL(k_trial_update, dim3(1 + g->n_lm_wg), dim3(256), 0, s, v, d_T, g->d_slot_of_pose, g->d_rhs, d_bp, lambda, d_Tn, d_p7n, g->d_dxp,
+                       g->d_scal + 1, g->d_Hinv, d_Hpl, d_bl, d_X, d_Xn, g->d_lm_tmp + 3 * (size_t)g->n_pt, g->d_fail + next_fail_word);
     OVS_LAUNCH_TRY("k_trial_update");
-    return OVS_OK;
-}
-
-// level-1 edges (round-1 outliers) are masked instead of rebuilding the graph: an inactive edge contributes exact zeros
-ovs_status ba_graph_set_active(ovs_ba_graph* g, const uint8_t* host_mask, hipStream_t s) {
-    if (g->n_edge() == 0) return OVS_OK;
-    OVS_HIP_TRY(hipMemcpyAsync(g->d_active, host_mask, (size_t)g->n_edge(), hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipStreamSynchronize(s));
     return OVS_OK;
 }
 
@@ -2235,7 +1973,8 @@ ovs_status ba_graph_edge_chi2(ovs_ba_graph* g, const double* d_poses, const doub
     return OVS_OK;
 }
 
-// k_edge_gate; `write_active`: the verdicts also become the graph's active mask (what ba_graph_set_active uploads on the host-gate path)
+// k_edge_gate; `write_active`: the verdicts also become the graph's active mask (level-1 edges are masked instead of rebuilding the graph: an
+// inactive edge contributes exact zeros)
 ovs_status ba_graph_edge_gate(ovs_ba_graph* g, double thr_mono, double thr_stereo, const double* d_chi, const uint8_t* d_depth, const double* d_chi_r1,
                               const uint8_t* d_out1, bool use_final, uint8_t* d_out, bool write_active, int32_t* d_n_active, hipStream_t s) {
     if (g->n_edge() == 0) return OVS_OK;

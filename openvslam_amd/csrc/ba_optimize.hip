@@ -30,7 +30,6 @@ ovs_status ba_graph_ensure_solver(ovs_ba_graph* g, hipStream_t s);
 ovs_status ba_graph_schur(ovs_ba_graph* g, const double* d_Hpp, const double* d_bp, const double* d_Hll, const double* d_bl, const double* d_Hpl,
                           double lambda, hipStream_t s, int fail_word, bool clear_first);
 ovs_status ba_graph_backsub(ovs_ba_graph* g, const double* d_Hpl, const double* d_bl, double lambda, const double* d_X, double* d_Xn, hipStream_t s);
-ovs_status ba_graph_set_active(ovs_ba_graph* g, const uint8_t* host_mask, hipStream_t s);
 ovs_status ba_graph_edge_chi2(ovs_ba_graph* g, const double* d_poses, const double* d_points, double* d_chi, uint8_t* d_depth, hipStream_t s);
 ovs_status ba_graph_edge_gate(ovs_ba_graph* g, double thr_mono, double thr_stereo, const double* d_chi, const uint8_t* d_depth, const double* d_chi_r1,
                               const uint8_t* d_out1, bool use_final, uint8_t* d_out, bool write_active, int32_t* d_n_active, hipStream_t s);
@@ -89,8 +88,8 @@ struct LmScratch {
     size_t d_cap = 0;
     double* h_pin = nullptr;
     size_t pin_cap = 0;
-    unsigned char* h_edge = nullptr;   // pinned: two slots of [chi2 per edge (f64) | depth flag per edge (u8)], the results of edge_chi2 (round 1, final)
-    size_t edge_cap = 0;               // edges per slot
+    unsigned char* h_edge = nullptr;   // pinned: round 1's inlier count (4 bytes), then the final outlier flags (one byte per edge)
+    size_t edge_cap = 0;               // bytes (>= edges)
     double* h_pts = nullptr;           // pinned: the landmarks on their way up (start of the call) and down (its end)
     size_t pts_cap = 0;                // doubles
     ~LmScratch() { release(); }
@@ -199,7 +198,7 @@ struct Lm {
             sc.h_edge = nullptr;
             sc.edge_cap = 0;
             const size_t cap = (ne + 1023) & ~(size_t)1023;
-            OVS_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sc.h_edge), 2 * cap * 9, hipHostMallocDefault));
+            OVS_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sc.h_edge), cap, hipHostMallocDefault));
             sc.edge_cap = cap;
         }
         h_edge = sc.h_edge;
@@ -274,10 +273,8 @@ struct Lm {
         volatile unsigned long long* const h_ll = reinterpret_cast<volatile unsigned long long*>(h_pin + pin_doubles - 16);
         static thread_local unsigned int ll_seq = 0;   // sequence number of a trial's words: per thread, like the page-locked block they land in
         for (int i = 0; i < 16; ++i) h_ll[i] = 0ull;    // (the stream is idle here; whatever the block's last user left cannot pass for a word)
-        static const bool ll_notify = [] {   // OVS_BA_LL_NOTIFY=0: a trial's outcome through a D2H copy and a stream synchronisation (rounds 4-5)
-            const char* e = std::getenv("OVS_BA_LL_NOTIFY");
-            return !(e && e[0] == '0');
-        }();   // one download per trial: [0] landmarks' / [1] keyframes' gain-ratio parts, [2..4] chi2 triple, byte 256: fail flag
+        const bool ll_notify = ovs::tuning().ba_ll_notify;   // OVS_BA_LL_NOTIFY=0: a trial's outcome through a D2H copy and a stream synchronisation
+        // (rounds 4-5); one download per trial: [0] landmarks' / [1] keyframes' gain-ratio parts, [2..4] chi2 triple, byte 256: fail flag
         OVS_HIP_TRY(hipMemcpyAsync(h_chi, cur.chi, sizeof(double) * 3, hipMemcpyDeviceToHost, stream));
         OVS_HIP_TRY(hipStreamSynchronize(stream));
         double current_chi = h_chi[1];
@@ -355,7 +352,8 @@ struct Lm {
                             h_chi[5] = val(1);
                             h_chi[0] = val(2);
                             h_chi[1] = val(3);
-                            h_chi[2] = val(4);
+                            h_chi[2] = val(4);   // (the largest |diagonal| of the LANDMARKS only, not the full maximum of the
+                                                 //  start damping above: nothing reads it after a trial)
                             const uint32_t f2[2] = {(uint32_t)(w[10] & 0xffffffffull), (uint32_t)(w[11] & 0xffffffffull)};
                             *h_fail = (int32_t)f2[fw];
                             polled = true;
@@ -366,7 +364,7 @@ struct Lm {
                         OVS_HIP_TRY(hipStreamSynchronize(stream));   // (polling hipStreamQuery instead: the same 6.5-6.6 ms per call, round 5)
                         h_chi[0] = h_blk[2];
                         h_chi[1] = h_blk[3];
-                        h_chi[2] = h_blk[4];
+                        h_chi[2] = h_blk[4];   // (mirror[2]: the landmarks' largest |diagonal| only, as in host_ll word 4)
                         h_chi[4] = h_blk[0];
                         h_chi[5] = h_blk[1];
                         *h_fail = reinterpret_cast<const int32_t*>(reinterpret_cast<const unsigned char*>(h_blk) + 256)[fw];
@@ -494,31 +492,8 @@ struct Lm {
 
     // What upstream reads after optimizer.optimize(): edge->chi2() -- the error STORED by the last computeActiveErrors(), i.e. at the last
     // LM trial state when the round ended on a rejected step (g2o pops the estimate back but leaves the errors) -- and
-    // edge->depth_is_positive(), which is evaluated from the vertices' current, accepted estimates (T, d_X).
-    ovs_status edge_chi2(ovs_ba_graph* g, const std::vector<Pose>& T, size_t ne, int slot, const double*& chi, const uint8_t*& depth) {
-        ovs_status st = upload_poses(T, d_poses, nullptr);
-        if (st != OVS_OK) return st;
-        double* const h_chi = reinterpret_cast<double*>(h_edge + (size_t)slot * edge_cap * 9);
-        uint8_t* const h_depth = h_edge + (size_t)slot * edge_cap * 9 + edge_cap * 8;
-        chi = h_chi;
-        depth = h_depth;
-        if (err_at_trial) {
-            st = ovs::ba_graph_edge_chi2(g, d_poses_n, d_Xn, d_echi, d_edepth, stream);
-            if (st != OVS_OK) return st;
-            if (ne) OVS_HIP_TRY(hipMemcpyAsync(h_chi, d_echi, sizeof(double) * ne, hipMemcpyDeviceToHost, stream));
-        }
-        st = ovs::ba_graph_edge_chi2(g, d_poses, d_X, d_echi, d_edepth, stream);
-        if (st != OVS_OK) return st;
-        if (ne) {
-            if (!err_at_trial) OVS_HIP_TRY(hipMemcpyAsync(h_chi, d_echi, sizeof(double) * ne, hipMemcpyDeviceToHost, stream));
-            OVS_HIP_TRY(hipMemcpyAsync(h_depth, d_edepth, ne, hipMemcpyDeviceToHost, stream));
-        }
-        OVS_HIP_TRY(hipStreamSynchronize(stream));
-        return OVS_OK;
-    }
-
-    // edge_chi2's two evaluations without the downloads (round 6): the chi2 upstream would read goes to `d_chi_judged`, the depth flags of the
-    // accepted state to d_edepth. Nothing is waited for.
+    // edge->depth_is_positive(), which is evaluated from the vertices' current, accepted estimates (T, d_X). Evaluated on the device (round 6):
+    // the chi2 upstream would read goes to `d_chi_judged`, the depth flags of the accepted state to d_edepth. Nothing is waited for.
     ovs_status edge_chi2_dev(ovs_ba_graph* g, const std::vector<Pose>& T, double* d_chi_judged) {
         ovs_status st = upload_poses(T, d_poses, nullptr);
         if (st != OVS_OK) return st;
@@ -581,7 +556,6 @@ static ovs_status local_ba_optimize_impl(int model, int32_t device, double* pose
     OVS_HIP_TRY(hipSetDevice(device));
     // ---- the work space first (round 6): the landmarks' upload is on its way while the host indexes the edges
     const bool trace = ovs::tuning().ba_trace;
-    const bool dev_gate = ovs::tuning().ba_dev_outliers;
     const double t_begin = Lm::now();
     const size_t ne = (size_t)n_mono + n_stereo;
     Lm L;
@@ -608,65 +582,25 @@ static ovs_status local_ba_optimize_impl(int model, int32_t device, double* pose
     st = L.run_round(g1.g, T, num_first_iter, true, force_stop_flag, &info_l[0], &info_l[1], &it1);
     if (st != OVS_OK) return st;
     const double t_r1 = Lm::now();
-    double t_gate1 = t_r1, t_r2 = t_r1;
-    if (dev_gate) {
-        // ---- round 6: the chi-square gates on the device (k_edge_gate): the per-edge arrays stay in HBM, the active mask is written where
-        //      round 2 reads it, 4 bytes come down after round 1 and the flags (one byte per edge) at the end
-        size_t n_act = 0;
-        st = L.gate_round1(g1.g, T, ne, &n_act);
+    // ---- the chi-square gates on the device (k_edge_gate, round 6): the per-edge arrays stay in HBM, the active mask is written where
+    //      round 2 reads it, 4 bytes come down after round 1 and the flags (one byte per edge) at the end
+    size_t n_act = 0;
+    st = L.gate_round1(g1.g, T, ne, &n_act);
+    if (st != OVS_OK) return st;
+    const double t_gate1 = Lm::now();
+    const bool stopped = force_stop_flag && *force_stop_flag;
+    if (!stopped) {
+        // ---- round 2: inliers only (outliers go to level 1), no robust kernel. The graph is kept: level-1 edges are masked, they then
+        //      contribute exact zeros and the sums over the remaining edges keep their order -- the result a rebuilt graph would give
+        st = L.run_round(g1.g, T, n_act ? num_second_iter : 0, false, force_stop_flag, &info_l[2], &info_l[3], &it2);
         if (st != OVS_OK) return st;
-        t_gate1 = Lm::now();
-        const bool stopped = force_stop_flag && *force_stop_flag;
-        if (!stopped) {
-            st = L.run_round(g1.g, T, n_act ? num_second_iter : 0, false, force_stop_flag, &info_l[2], &info_l[3], &it2);
-            if (st != OVS_OK) return st;
-        }
-        t_r2 = Lm::now();
-        const uint8_t* flags = nullptr;
-        st = L.gate_final(g1.g, T, ne, !stopped, flags);
-        if (st != OVS_OK) return st;
-        if (n_mono > 0) std::memcpy(mono_outlier, flags, (size_t)n_mono);
-        if (n_stereo > 0) std::memcpy(stereo_outlier, flags + n_mono, (size_t)n_stereo);
-    } else {
-        const double *chi_r1 = nullptr, *chi = nullptr;   // (page-locked slots of the scratch: round 1's stays valid beside the final one)
-        const uint8_t* depth = nullptr;
-        st = L.edge_chi2(g1.g, T, ne, 0, chi_r1, depth);
-        if (st != OVS_OK) return st;
-        chi = chi_r1;
-        std::vector<uint8_t> out_r1(ne);
-        for (int i = 0; i < n_mono; ++i) out_r1[i] = (kChi2D < chi[i]) || !depth[i];
-        for (int i = 0; i < n_stereo; ++i) out_r1[(size_t)n_mono + i] = (kChi3D < chi[(size_t)n_mono + i]) || !depth[(size_t)n_mono + i];
-        t_gate1 = Lm::now();
-        const bool stopped = force_stop_flag && *force_stop_flag;
-        if (!stopped) {
-            // ---- round 2: inliers only (outliers go to level 1), no robust kernel. The graph is kept: level-1 edges are masked, they then
-            // contribute exact zeros and the sums over the remaining edges keep their order -- the result a rebuilt graph would give, without
-            // indexing 100 k edges a second time
-            std::vector<uint8_t> act(ne);
-            size_t n_act = 0;
-            for (size_t e = 0; e < ne; ++e) n_act += (act[e] = out_r1[e] ? 0 : 1);
-            st = ovs::ba_graph_set_active(g1.g, act.data(), L.stream);
-            if (st != OVS_OK) return st;
-            st = L.run_round(g1.g, T, n_act ? num_second_iter : 0, false, force_stop_flag, &info_l[2], &info_l[3], &it2);
-            if (st != OVS_OK) return st;
-        }
-        t_r2 = Lm::now();
-        // ---- final outlier flags: an edge optimised in round 2 is judged at the final state; a level-1 edge keeps its round-1 chi2
-        //      (g2o does not recompute the error of inactive edges) but its depth test sees the final state
-        st = L.edge_chi2(g1.g, T, ne, 1, chi, depth);
-        if (st != OVS_OK) return st;
-        for (int i = 0; i < n_mono; ++i) {
-            const double c = (!stopped && !out_r1[i]) ? chi[i] : chi_r1[i];
-            mono_outlier[i] = (kChi2D < c) || !depth[i];
-        }
-        for (int i = 0; i < n_stereo; ++i) {
-            const size_t e = (size_t)n_mono + i;
-            const double c = (!stopped && !out_r1[e]) ? chi[e] : chi_r1[e];
-            stereo_outlier[i] = (kChi3D < c) || !depth[e];
-        }
-        OVS_HIP_TRY(hipMemcpyAsync(L.h_pts, L.d_X, sizeof(double) * 3 * (size_t)n_pt, hipMemcpyDeviceToHost, L.stream));
-        OVS_HIP_TRY(hipStreamSynchronize(L.stream));
     }
+    const double t_r2 = Lm::now();
+    const uint8_t* flags = nullptr;
+    st = L.gate_final(g1.g, T, ne, !stopped, flags);
+    if (st != OVS_OK) return st;
+    if (n_mono > 0) std::memcpy(mono_outlier, flags, (size_t)n_mono);
+    if (n_stereo > 0) std::memcpy(stereo_outlier, flags + n_mono, (size_t)n_stereo);
     std::vector<double> p7;
     Lm::pack_poses(T, p7);
     for (int k = 0; k < n_pose; ++k)

@@ -389,46 +389,16 @@ constexpr int kResSlots = 18;      // accumulator slots per wave (144 registers:
 constexpr int kResMaxPad = 288;
 constexpr int kResMaxTiles = (kResMaxPad / 16) * (kResMaxPad / 16 - 1) / 2;   // 153
 
-template <int N>
-__device__ __forceinline__ double row_bcast_c(double v) {   // lane N of every 16-lane row -> all lanes of that row
-    union {
-        double d;
-        int i[2];
-    } u, w;
-    u.d = v;
-    w.i[0] = __builtin_amdgcn_update_dpp(0, u.i[0], 0x150 + N, 0xf, 0xf, false);   // row_newbcast:N
-    w.i[1] = __builtin_amdgcn_update_dpp(0, u.i[1], 0x150 + N, 0xf, 0xf, false);
-    return w.d;
-}
-__device__ __forceinline__ double row_bcast(double v, int n) {   // n is a constant after unrolling: the switch folds away
-    switch (n) {
-        case 0: return row_bcast_c<0>(v);
-        case 1: return row_bcast_c<1>(v);
-        case 2: return row_bcast_c<2>(v);
-        case 3: return row_bcast_c<3>(v);
-        case 4: return row_bcast_c<4>(v);
-        case 5: return row_bcast_c<5>(v);
-        case 6: return row_bcast_c<6>(v);
-        case 7: return row_bcast_c<7>(v);
-        case 8: return row_bcast_c<8>(v);
-        case 9: return row_bcast_c<9>(v);
-        case 10: return row_bcast_c<10>(v);
-        case 11: return row_bcast_c<11>(v);
-        case 12: return row_bcast_c<12>(v);
-        case 13: return row_bcast_c<13>(v);
-        case 14: return row_bcast_c<14>(v);
-        default: return row_bcast_c<15>(v);
-    }
-}
-
 // ---- round 6: the diagonal block's pivot chain, scheduled by hand ---------------------------------------------------------------------
-// factor_block_dpp below compiles to a strictly serial stream: per pivot, ten dependent operations of the reciprocal square root (nothing
-// between them), THEN the 15 - k column updates at five instructions per broadcast (two v_mov 0 for update_dpp's `old`, s_nop, two 32-bit DPP
+// wave 0: the diagonal block (P rows 0..15; lane r of every 16-lane row holds row r) and y = L_dd^-1 rhs_block (vec[j0 ..]); leaves L_dd in P,
+// 1 / L[c][c] in invd.
+// The plain form (rounds 4-5: a pivot loop of row broadcasts, rsqrt_newton and fma column updates) compiled to a strictly serial stream: per
+// pivot, ten dependent operations of the reciprocal square root (nothing between them), THEN the 15 - k column updates at five instructions per broadcast (two v_mov 0 for update_dpp's `old`, s_nop, two 32-bit DPP
 // moves) -- ~430 cycles per pivot, 52 us of a 169 us solve. Here every instruction of the block is its own `asm volatile` (the compiler keeps
 // their order, allocates the registers and sees none of the hazards, which are therefore padded inside the strings): a broadcast is ONE
 // v_mov_b64_dpp row_newbcast (the only DPP control 64-bit operations have), column k + 1 is updated first so that the NEXT pivot's chain starts
 // at once, and the remaining column updates and the right-hand side's forward-substitution step are issued BETWEEN the chain's dependent
-// operations. Same operations on the same values as factor_block_dpp (the same bits); lanes r < k carry junk in a[k] and s, as there, and
+// operations. Same operations on the same values as the plain form (the same bits); lanes r < k carry junk in a[k] and s, as there, and
 // nothing reads it. 1 / L[k][k] and y_k are uniform after their broadcasts: every lane stores them (same address, same value).
 #define OVS_BC64(N, NOP)                                                                                                                    \
     asm volatile(NOP "v_mov_b64_dpp %0, %1 row_newbcast:" #N " row_mask:0xf bank_mask:0xf" : "=v"(o) : "v"(v));                              \
@@ -534,42 +504,6 @@ __device__ __forceinline__ void factor_block_sched(double* __restrict__ P, doubl
 #pragma unroll
         for (int cc = 0; cc < kNb; ++cc)
             if (cc <= r) P[r * kPitch + cc] = a[cc];
-        if (bad) *s_bad = 1;   // (lanes of one wave: the same value, any order)
-    }
-}
-
-// wave 0: the diagonal block (P rows 0..15; lane r of every 16-lane row holds row r) and y = L_dd^-1 rhs_block (vec[j0 ..]); leaves L_dd in P,
-// 1 / L[c][c] in invd
-__device__ __forceinline__ void factor_block_dpp(double* __restrict__ P, double* __restrict__ invd, double* __restrict__ vec, int j0, int lane,
-                                                 int* s_bad) {
-    const int r = lane & 15;
-    double a[kNb];
-#pragma unroll
-    for (int c = 0; c < kNb; ++c) a[c] = P[r * kPitch + c];
-    double s = vec[j0 + r], my_inv = 0.0;
-    bool bad = false;
-#pragma unroll
-    for (int k = 0; k < kNb; ++k) {
-        const double piv = row_bcast(a[k], k);
-        bad |= !(piv > 0.0 && piv < __builtin_inf());
-        const double y = rsqrt_newton(piv);
-        a[k] = (r == k) ? piv * y : a[k] * y;
-        my_inv = (r == k) ? y : my_inv;
-#pragma unroll
-        for (int c = k + 1; c < kNb; ++c) a[c] = __builtin_fma(-a[k], row_bcast(a[k], c), a[c]);   // L[c][k] sits in lane c
-    }
-    // forward substitution of the block's right-hand side: lane r carries rhs_r - sum_{c < r} L[r][c] y_c
-#pragma unroll
-    for (int k = 0; k < kNb; ++k) {
-        const double yk = row_bcast(s * my_inv, k);
-        s = (r == k) ? yk : (r > k ? __builtin_fma(-a[k], yk, s) : s);
-    }
-    if (lane < kNb) {
-#pragma unroll
-        for (int c = 0; c < kNb; ++c)
-            if (c <= r) P[r * kPitch + c] = a[c];
-        invd[j0 + r] = my_inv;
-        vec[j0 + r] = s;   // y
         if (bad) *s_bad = 1;   // (lanes of one wave: the same value, any order)
     }
 }
@@ -703,8 +637,7 @@ __device__ __forceinline__ void backward_substitution_res(double* __restrict__ S
 // none -- the marks' branches and 64-bit atomics inside the panel loop cost the register allocator 100 registers' worth of spills.
 // A failed pivot does NOT leave the kernel early (a second exit from the panel loop had the same effect): the factorisation runs on with
 // NaNs and the flag is raised at the end.
-// kSched: the diagonal block by factor_block_sched (round 6, default) or by factor_block_dpp (OVS_CHOL_SCHED=0; same bits).
-template <bool kTimed, bool kSched>
+template <bool kTimed>
 __global__ __launch_bounds__(kSolveThreads) void k_chol_resident(double* __restrict__ S, int n_pad, int32_t* __restrict__ fail,
                                                                 unsigned long long* __restrict__ tstats) {
     extern __shared__ double lds[];
@@ -743,7 +676,7 @@ __global__ __launch_bounds__(kSolveThreads) void k_chol_resident(double* __restr
     //      columns, which leave after one or two updates) in LDS behind the panels, lane-major: value e of lane l of tile u at T[(u * 4 + e) * 64 + l]
     double* const T = invd + n_pad;
     const int n_lds = n_tiles > kWaves * kResSlots ? n_tiles - kWaves * kResSlots : 0;
-    double* const DD = T + (size_t)n_lds * 256;   // kSched: the diagonal blocks' L (NT x 16 x kPitch doubles) for the backward substitution
+    double* const DD = T + (size_t)n_lds * 256;   // the diagonal blocks' L (NT x 16 x kPitch doubles) for the backward substitution
     int sd[kResSlots];
     v4d acc[kResSlots];
     const int lane_off = kq * n_pad + rl;
@@ -773,12 +706,11 @@ __global__ __launch_bounds__(kSolveThreads) void k_chol_resident(double* __restr
     for (int j = 0; j < NT; ++j) {
         const int j0 = j * kNb, m = n_pad - j0;
         if (wave == 0) {
-            if (kSched) factor_block_sched(P, invd, vec, j0, lane, &s_bad);
-            else factor_block_dpp(P, invd, vec, j0, lane, &s_bad);
+            factor_block_sched(P, invd, vec, j0, lane, &s_bad);
         }
         lds_barrier();
         SOLVE_MARK(1)   // diagonal block + forward substitution of its rhs + barrier
-        if (kSched && tid >= kSolveThreads - kNb * kNb) {
+        if (tid >= kSolveThreads - kNb * kNb) {
             // the block's copy for the backward substitution (strictly lower triangle, zeros elsewhere), made by the upper half of the workgroup, which
             // owns few or no rows below a block (n_pad <= 288: rows 16 .. 287 go to threads 0 .. 271) -- off wave 0's critical path
             const int e = tid - (kSolveThreads - kNb * kNb), r = e >> 4, c = e & 15;
@@ -833,8 +765,7 @@ __global__ __launch_bounds__(kSolveThreads) void k_chol_resident(double* __restr
         Pn = t;
     }
     __syncthreads();   // the panels written back above are read by other threads below
-    if (kSched) backward_substitution_res(S, vec, invd, DD, n_pad, tid, lane, wave);
-    else backward_substitution(S, vec, invd, n_pad, tid, lane, wave);
+    backward_substitution_res(S, vec, invd, DD, n_pad, tid, lane, wave);
     SOLVE_MARK(6)   // backward substitution
 #undef SOLVE_MARK
     if (tid == 0 && s_bad) atomicOr(fail, 2);   // (s_bad was last written before the panel loop's barriers)
@@ -859,25 +790,16 @@ ovs_status launch_dense_solve(double* d_S, int n, int32_t* d_fail, hipStream_t s
     if (n_pad <= kResMaxPad && tuning().chol_resident) {   // the trailing matrix fits the register file: k_chol_resident
         const int nt = n_pad / kNb, n_tiles = nt * (nt - 1) / 2, n_lds = std::max(0, n_tiles - (kSolveThreads / 64) * kResSlots);
         const size_t lds = sizeof(double) * (2 * (size_t)n_pad * kPitch + 2 * (size_t)n_pad + (size_t)n_lds * 256 + (size_t)nt * kNb * kPitch);
-        static LdsAttrCache cache[4];
-        static const bool sched = [] {
-            const char* e = std::getenv("OVS_CHOL_SCHED");
-            return !(e && e[0] == '0');
-        }();
-        const int which = (d_tstats ? 2 : 0) + (sched ? 1 : 0);
-        const void* const fns[4] = {reinterpret_cast<const void*>(k_chol_resident<false, false>), reinterpret_cast<const void*>(k_chol_resident<false, true>),
-                                    reinterpret_cast<const void*>(k_chol_resident<true, false>), reinterpret_cast<const void*>(k_chol_resident<true, true>)};
-        hipError_t e = ensure_dynamic_lds(fns[which], lds, cache[which]);
+        static LdsAttrCache cache;
+        static LdsAttrCache cache_timed;
+        const void* const fn = d_tstats ? reinterpret_cast<const void*>(k_chol_resident<true>) : reinterpret_cast<const void*>(k_chol_resident<false>);
+        hipError_t e = ensure_dynamic_lds(fn, lds, d_tstats ? cache_timed : cache);
         if (e != hipSuccess) {
             set_last_error("hipFuncSetAttribute(k_chol_resident)", e);
             return OVS_ERR_HIP;
         }
-        switch (which) {
-            case 0: hipLaunchKernelGGL((k_chol_resident<false, false>), dim3(1), dim3(kSolveThreads), lds, s, d_S, n_pad, d_fail, d_tstats); break;
-            case 1: hipLaunchKernelGGL((k_chol_resident<false, true>), dim3(1), dim3(kSolveThreads), lds, s, d_S, n_pad, d_fail, d_tstats); break;
-            case 2: hipLaunchKernelGGL((k_chol_resident<true, false>), dim3(1), dim3(kSolveThreads), lds, s, d_S, n_pad, d_fail, d_tstats); break;
-            default: hipLaunchKernelGGL((k_chol_resident<true, true>), dim3(1), dim3(kSolveThreads), lds, s, d_S, n_pad, d_fail, d_tstats); break;
-        }
+        if (d_tstats) hipLaunchKernelGGL((k_chol_resident<true>), dim3(1), dim3(kSolveThreads), lds, s, d_S, n_pad, d_fail, d_tstats);
+        else hipLaunchKernelGGL((k_chol_resident<false>), dim3(1), dim3(kSolveThreads), lds, s, d_S, n_pad, d_fail, d_tstats);
         OVS_LAUNCH_TRY("k_chol_resident");
         return OVS_OK;
     }

@@ -27,23 +27,28 @@ const Tuning& tuning() {
             const char* e = std::getenv(name);
             return e && e[0] ? std::atoi(e) : dflt;
         };
+        auto zero = [](const char* name) {   // a "=0" switch: true only when the value starts with '0'
+            const char* e = std::getenv(name);
+            return e && e[0] == '0';
+        };
         Tuning v;
-        v.fast_impl = num("OVS_FAST_IMPL", 1);
-        v.fast_map = num("OVS_FAST_MAP", 1);
-        v.fast_pf = std::max(0, num("OVS_FAST_PF", 0));
+        const char* tree_grid = std::getenv("OVS_TREE_GRID");
+        v.tree_grid = tree_grid ? std::atoi(tree_grid) : -1;
+        v.chol_resident = num("OVS_CHOL_RESIDENT", 1) != 0;
+        v.ba_schur_lists = !zero("OVS_BA_SCHUR_LISTS");
+        const char* retries = std::getenv("OVS_POSE_BATCH_RETRIES");
+        v.pose_batch_retries = retries && retries[0] ? (std::atoi(retries) != 0 ? 1 : 0) : -1;
+        v.pose_obs_regs = !zero("OVS_POSE_OBS_REGS");
+        v.pose_zero_copy = !zero("OVS_POSE_ZERO_COPY");
+        v.ba_ll_notify = !zero("OVS_BA_LL_NOTIFY");
+        v.ba_trace = std::getenv("OVS_BA_TRACE") != nullptr;
+        v.fast_timing = std::getenv("OVS_FAST_TIMING") != nullptr;
         v.fast_cells = std::max(0, num("OVS_FAST_CELLS", 0));
         v.fast_pad_lds = std::max(0, num("OVS_FAST_PAD_LDS", 0));
-        v.fast_timing = std::getenv("OVS_FAST_TIMING") != nullptr;
-        v.describe_xcd = num("OVS_DESCRIBE_XCD", 1) != 0;
-        v.resolve_wide_from = num("OVS_RESOLVE_WIDE_FROM", 1024);
         v.pose_threads = num("OVS_POSE_THREADS", 0);
         v.pose_groups = std::max(0, num("OVS_POSE_GROUPS", 0));
-        v.ba_trace = std::getenv("OVS_BA_TRACE") != nullptr;
+        v.resolve_wide_from = num("OVS_RESOLVE_WIDE_FROM", 1024);
         v.pyr_chain = std::max(0, num("OVS_PYR_CHAIN", 2));
-        v.pyr_pair = num("OVS_PYR_PAIR", 1) != 0;
-        v.chol_resident = num("OVS_CHOL_RESIDENT", 1) != 0;
-        v.ba_backsub_edges = num("OVS_BA_BACKSUB_EDGES", 1) != 0;
-        v.ba_dev_outliers = num("OVS_BA_DEV_OUTLIERS", 1) != 0;
         return v;
     }();
     return t;
@@ -594,7 +599,7 @@ ovs_status run_chain(ovs_orb* h, StageProfiler<4>& prof, const uint8_t* d_images
         const size_t src_fs = (l == 1) ? frame_stride : d.pyr_frame_bytes;
         const int src_pitch = (l == 1) ? (int)stride : gp.pitch;
         // batches: levels l and l + 1 in one launch where the geometry has a plan for the pair (the middle level is written once, never re-read)
-        if (tuning().pyr_pair && l + 1 < L && h->pair_off[l + 1] >= 0 && resize_pair_launchable(src, src_fs, src_pitch, geo.lv[l + 1].rows, geo.lv[l + 1].cols, nb)) {
+        if (l + 1 < L && h->pair_off[l + 1] >= 0 && resize_pair_launchable(src, src_fs, src_pitch, geo.lv[l + 1].rows, geo.lv[l + 1].cols, nb)) {
             const LevelGeo& g2 = geo.lv[l + 1];
             OVS_HIP_TRY(launch_resize_pair(src, src_fs, src_pitch, d.pyr + g.plane_off, g.pitch, g.rows, g.cols, d.pyr + g2.plane_off, g2.pitch, g2.rows, g2.cols,
                                            d.pyr_frame_bytes, h->d_taps + g.ytab_off, h->d_taps + g2.ytab_off, h->d_htaps + h->htab_off[l], h->d_htaps + h->htab_off[l + 1],
@@ -1060,12 +1065,7 @@ ovs_status ovs_orb_extract_submit(ovs_orb* h, const uint8_t* image, int32_t rows
             h->mirror_out = nullptr;
         }
     } cleared_guard{h};
-    // OVS_ORB_ZERO_COPY_OUT=0: results through a D2H copy command after the kernels (rounds 1-5)
-    static const bool zero_copy_out = [] {
-        const char* e = std::getenv("OVS_ORB_ZERO_COPY_OUT");
-        return !(e && e[0] == '0');
-    }();
-    h->mirror_out = zero_copy_out ? sl.h_out : nullptr;
+    h->mirror_out = sl.h_out;   // the kernels write counts + keypoints + descriptors straight into the slot's pinned block: no D2H copy
     if (timed) OVS_HIP_TRY(hipEventRecord(sl.t[0], cs));
     st = upload_plane(h, image, stride, rows, cols, sl.h_in, sl.d_img);
     if (st != OVS_OK) return st;
@@ -1082,8 +1082,6 @@ ovs_status ovs_orb_extract_submit(ovs_orb* h, const uint8_t* image, int32_t rows
                      h->d_out_desc, h->d_out_counts, h->out_cap, s);
     if (st != OVS_OK) return st;
     if (timed) OVS_HIP_TRY(hipEventRecord(sl.t[2], s));
-    // ONE D2H for counts + keypoints + descriptors (120 KB at 2000 features: cheaper than a count round trip followed by two copies)
-    if (!h->mirror_out) OVS_HIP_TRY(hipMemcpyAsync(sl.h_out, h->d_out_counts, h->out_block_bytes, hipMemcpyDeviceToHost, s));
     sl.has_pyr = false;
     if (h->host_pyr && h->p.num_levels > 1) {
         if (!sl.h_pyr) OVS_HIP_TRY(hipHostMalloc(&sl.h_pyr, h->d.pyr_frame_bytes, hipHostMallocDefault));

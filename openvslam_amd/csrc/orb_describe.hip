@@ -138,7 +138,7 @@ __global__ __launch_bounds__(64) void k_describe(const FrameGeo* __restrict__ ge
                                                 size_t frame_stride0, const uint8_t* __restrict__ pyr, size_t pyr_frame_bytes,
                                                 const uint64_t* __restrict__ lvl_kps, const uint32_t* __restrict__ lvl_count,
                                                 ovs_keypoint* __restrict__ kps, uint8_t* __restrict__ desc,
-                                                int32_t* __restrict__ counts, int cap, int batch, int xcd_map, ovs_keypoint* __restrict__ kps_m,
+                                                int32_t* __restrict__ counts, int cap, int batch, ovs_keypoint* __restrict__ kps_m,
                                                 uint8_t* __restrict__ desc_m, int32_t* __restrict__ counts_m) {
     // kps_m / desc_m / counts_m (round 6, one-frame host calls): a second copy of every output, written straight into the caller-side pinned
     // block -- the frame's results then need no D2H copy command after the kernel (nullptr: batches, device-resident callers)
@@ -153,18 +153,12 @@ __global__ __launch_bounds__(64) void k_describe(const FrameGeo* __restrict__ ge
     // stays in that XCD's L2 while its keypoints are described: 5.7 MB per frame, 2.4x less (profiles/r03_describe_pmc.txt).
     // The kernel's TIME does not move with it: it is bound by the vector ALU (637 VALU instructions per keypoint-wave x 4 cycles x 253
     // waves per SIMD = the 0.33 ms per 128 frames), see DESIGN.md section 3.4 for what was tried against that.
-    int frame, kslot;
     const int total_cap = geo->total_kp_cap;
-    if (xcd_map) {
-        const uint32_t w = blockIdx.x, x = w & 7u, j = w >> 3;
-        const uint32_t grp = j / (uint32_t)total_cap;
-        kslot = (int)(j - grp * (uint32_t)total_cap);
-        frame = (int)(grp * 8u + x);
-        if (frame >= batch) return;
-    } else {
-        frame = blockIdx.x / (uint32_t)total_cap;
-        kslot = blockIdx.x - frame * total_cap;
-    }
+    const uint32_t xcd = blockIdx.x & 7u, idx = blockIdx.x >> 3;
+    const uint32_t grp = idx / (uint32_t)total_cap;
+    const int kslot = (int)(idx - grp * (uint32_t)total_cap);
+    const int frame = (int)(grp * 8u + xcd);
+    if (frame >= batch) return;
     const int L = geo->num_levels;
     int level = 0;
     for (int l = 1; l < L; ++l)
@@ -340,11 +334,10 @@ __global__ __launch_bounds__(64) void k_describe(const FrameGeo* __restrict__ ge
 hipError_t launch_describe(const FrameGeo& hgeo, const DevBuffers& d, const uint8_t* img0, size_t stride0, size_t frame_stride0,
                            ovs_keypoint* kps, uint8_t* desc, int32_t* counts, int cap, int batch, hipStream_t s, ovs_keypoint* kps_m, uint8_t* desc_m,
                            int32_t* counts_m) {
-    const int xcd_map = tuning().describe_xcd ? 1 : 0;   // 0: plain frame-major order (A/B of the XCD mapping)
-    const int frames = xcd_map ? ((batch + 7) & ~7) : batch;   // frame 8 g + x on XCD x: pad the last group
+    const int frames = (batch + 7) & ~7;   // frame 8 g + x on XCD x: pad the last group
     dim3 grid((unsigned)hgeo.total_kp_cap * (unsigned)frames);
     hipLaunchKernelGGL(k_describe, grid, dim3(64), 0, s, d.geo, img0, stride0, frame_stride0, d.pyr, d.pyr_frame_bytes, d.lvl_kps,
-                       d.lvl_count, kps, desc, counts, cap, batch, xcd_map, kps_m, desc_m, counts_m);
+                       d.lvl_count, kps, desc, counts, cap, batch, kps_m, desc_m, counts_m);
     return hipGetLastError();
 }
 

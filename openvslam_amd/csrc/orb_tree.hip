@@ -808,10 +808,7 @@ hipError_t launch_tree(const FrameGeo& hgeo, const DevBuffers& d, int batch, hip
     const bool few = (long long)n_levels * batch <= 64;
     // the count pyramid of the grid form (tree_grid_depth per level): whatever the launch's levels need, and what the 160 KB leave
     size_t grid_words = 0;
-    static const int forced = [] {
-        const char* e = std::getenv("OVS_TREE_GRID");   // A/B switch: 0 = the sweep form of rounds 1-5 only, d = the finest grid's depth
-        return e ? std::atoi(e) : -1;
-    }();
+    const int forced = tuning().tree_grid;   // test hook: 0 = the sweep form only, d > 0 = the grid form with the finest grid's depth d
     const int grid_depth = forced > 0 ? std::min(forced, 7) : 0;
     // A tracker's single frame keeps the sweep form: one workgroup has a CU to itself there and both forms take the same ~56 us (measured
     // 56.9 against 55.5: its passes over the candidates are replaced by tables, a cleared pyramid and a second pass of the same latency), while

@@ -150,25 +150,29 @@ hipError_t launch_describe(const FrameGeo& hgeo, const DevBuffers& d, const uint
                            ovs_keypoint* kps, uint8_t* desc, int32_t* counts, int cap, int batch, hipStream_t s, ovs_keypoint* kps_m = nullptr, uint8_t* desc_m = nullptr,
                            int32_t* counts_m = nullptr);
 
-// Tuning / A-B switches of the launchers. Read from the environment ONCE per process (first use; thread-safe static initialisation) -- the
-// launch paths never call getenv, which is not safe against a host application's concurrent setenv. All default to the production setting.
+// Environment switches of the launchers. Read from the environment ONCE per process, all in tuning() (first use; thread-safe static
+// initialisation) -- the launch paths never call getenv, which is not safe against a host application's concurrent setenv. Unset, every switch
+// is the production setting.
 constexpr int kMaxTuningDevices = 16;
 struct Tuning {
-    int fast_impl;         // OVS_FAST_IMPL: 1 / unset = k_fast_cells (one workgroup per cell), 2 = k_fast_wave (round 6 experiment: one wavefront per cell, no barriers; same outputs, same batch time, 3x the single-frame time)
-    int fast_map;          // OVS_FAST_MAP: 1 / unset = groups fastest inside an XCD's share (round 6), 0 = frames fastest (rounds 3-5)
-    int fast_pf;           // OVS_FAST_PF: k_fast_wave's L2 prefetch distance in groups (0 = none)
+    // -- test hooks: force, at a small size, a path that production selects from the input
+    int tree_grid;         // OVS_TREE_GRID: unset = by launch (grid form for batches, sweep form for one frame), 0 = the sweep form only, d > 0 = the
+                           //   grid form everywhere with its finest grid at depth min(d, 7) (small d: the in-launch overflow fallback)
+    bool chol_resident;    // OVS_CHOL_RESIDENT=0: systems up to 288 unknowns take k_chol_solve (tiles through memory; production above 288)
+    bool ba_schur_lists;   // OVS_BA_SCHUR_LISTS=0: every trial's k_schur scans for the pairs' common landmarks itself (production above the pair-list bound)
+    int pose_batch_retries;// OVS_POSE_BATCH_RETRIES: the retries 1 .. 9 of an iteration in one pass -- 1 always, 0 never, unset (-1): by work per thread
+    bool pose_obs_regs;    // OVS_POSE_OBS_REGS=0: observations re-read from memory in every pass (the form for frames too large for registers)
+    bool pose_zero_copy;   // OVS_POSE_ZERO_COPY=0: the pose optimiser's inputs and outputs through copies (the form for frames too large for registers)
+    // -- deployment
+    bool ba_ll_notify;     // OVS_BA_LL_NOTIFY=0: a local-BA trial's outcome through a D2H copy and a stream synchronisation, not polled from pinned words
+    // -- diagnostics and tuning probes
+    bool ba_trace;         // OVS_BA_TRACE: per-iteration trace of the LM loops on stderr
+    bool fast_timing;      // OVS_FAST_TIMING: per-phase cycle counts of k_fast_cells, printed per launch
     int fast_cells;        // OVS_FAST_CELLS: consecutive cells per FAST workgroup (0 = by launch size)
     int fast_pad_lds;      // OVS_FAST_PAD_LDS: extra dynamic LDS per k_fast_cells workgroup (occupancy probe)
-    bool fast_timing;      // OVS_FAST_TIMING: per-phase cycle counts of k_fast_cells, printed per launch
-    bool describe_xcd;     // OVS_DESCRIBE_XCD=0: plain frame-major order in k_describe
-    int resolve_wide_from; // OVS_RESOLVE_WIDE_FROM: queries from which a resolver round takes 512 of them
     int pose_threads;      // OVS_POSE_THREADS: 256 / 512 (0 = by problem size)
     int pose_groups;       // OVS_POSE_GROUPS: workgroups a single frame's pose optimisation is spread over (0 = by observation count, 1 = one)
-    bool ba_trace;         // OVS_BA_TRACE: per-iteration trace of the LM loops on stderr
-    bool ba_backsub_edges; // OVS_BA_BACKSUB_EDGES=0: k_trial_update back-substitutes one lane per LANDMARK walking its edges (rounds 4-5) instead of one lane per edge (round 6; same bits)
-    bool ba_dev_outliers;  // OVS_BA_DEV_OUTLIERS=0: ovs_local_ba_optimize downloads the per-edge chi2 / depth arrays and judges the edges on the host (rounds 1-5) instead of on the device (round 6; same flags)
-    bool chol_resident;    // OVS_CHOL_RESIDENT=0: systems up to 288 unknowns take k_chol_solve (tiles through memory) instead of k_chol_resident
-    bool pyr_pair;         // OVS_PYR_PAIR=0: batches build the pyramid level by level (k_resize_linear_u8 x7) instead of two levels per launch (k_resize_pair_u8, round 6)
+    int resolve_wide_from; // OVS_RESOLVE_WIDE_FROM: queries from which a resolver round takes 512 of them
     int pyr_chain;         // OVS_PYR_CHAIN: frames per launch up to which the pyramid is ONE k_pyramid_chain launch (default 2: measured 24 vs 37 us for one frame, 33.5 vs 35.7 for two, 73 vs 46 for eight; 0 = never)
 };
 const Tuning& tuning();

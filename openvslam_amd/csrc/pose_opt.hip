@@ -727,26 +727,6 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_optimize(const double* __
 
 using namespace ovs;
 
-// OVS_POSE_BATCH_RETRIES: the retries 1 .. 9 of an iteration in one pass -- 1 always, 0 never, unset (-1): by work per thread (see
-// pose_optimize_host). Read once per process, like the switches of ovs::tuning().
-static int pose_batch_retries_env() {
-    static const int v = [] {
-        const char* e = std::getenv("OVS_POSE_BATCH_RETRIES");
-        return e && e[0] ? (std::atoi(e) != 0 ? 1 : 0) : -1;
-    }();
-    return v;
-}
-
-// OVS_POSE_OBS_REGS=0: observations re-read from memory in every pass (the form of rounds 3-5; same bits, for A/B timing and the test that
-// compares the two forms)
-static bool tuning_pose_obs_regs() {
-    static const bool v = [] {
-        const char* e = std::getenv("OVS_POSE_OBS_REGS");
-        return !(e && e[0] == '0');
-    }();
-    return v;
-}
-
 // ovs_pose_set_variant(OVS_POSE_VARIANT_RESET_EACH_ROUND, 0 | 1): process-wide, read at every launch
 static std::atomic<int> g_pose_reset_each_round{0};
 
@@ -768,10 +748,10 @@ static ovs_status pose_optimize_batch_dev(int model, const double* d_poses_in, c
         OVS_HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(k_pose_optimize<MODEL, TT, KR>), sizeof(double) * 28 * (TT + 8), configured)); \
         hipLaunchKernelGGL((k_pose_optimize<MODEL, TT, KR>), dim3(batch, groups > 1 ? 8 * groups : 1), dim3(TT), lds, (hipStream_t)stream, d_poses_in, d_obs, d_obs_offsets, \
                            cam, BF, ST, d_poses_out, d_outlier, d_num_valid, g_pose_reset_each_round.load(std::memory_order_relaxed), groups, d_gpart, \
-                           epoch0, pose_batch_retries_env() < 0 ? batch_retries_auto : pose_batch_retries_env(), stereo_hint);      \
+                           epoch0, tuning().pose_batch_retries < 0 ? batch_retries_auto : tuning().pose_batch_retries, stereo_hint);      \
     } while (0)
     // obs_in_regs: the caller knows every frame of the launch has at most 2 * groups * 256 observations (KREG = 2, 256-thread workgroups only)
-    const bool kreg = obs_in_regs && T == 256 && tuning_pose_obs_regs();
+    const bool kreg = obs_in_regs && T == 256 && tuning().pose_obs_regs;
     if (model == 1) {
         if (T == 512) OVS_POSE_LAUNCH(1, 512, 0, 0.0, 0);
         else if (kreg) OVS_POSE_LAUNCH(1, 256, 2, 0.0, 0);
@@ -883,10 +863,6 @@ static ovs_status pose_optimize_host(int model, int32_t device, const double* po
     // Round 6, zero copy: when the kernel reads every record exactly once (KREG form), it reads them -- and the pose -- straight from the pinned block
     // and writes pose, count and flags straight into it: no H2D copy before the launch, no D2H copy after it (two runtime copy commands and their
     // dependencies, ~20 us of a ~0.25 ms call). The exchange words stay in device memory. OVS_POSE_ZERO_COPY=0: the copies of rounds 3-5.
-    static const bool zero_copy_env = [] {
-        const char* e = std::getenv("OVS_POSE_ZERO_COPY");
-        return !(e && e[0] == '0');
-    }();
     bool first = true;
     for (;;) {
         // retries 1 .. 9 of an iteration in ONE pass (k_pose_optimize): nine trial poses per observation pay where a thread holds few
@@ -895,8 +871,8 @@ static ovs_status pose_optimize_host(int model, int32_t device, const double* po
         // 2000: 0.478 / 0.439 (a sequence that accepts its second or third trial has then evaluated seven poses for nothing). Same bits.
         const int batch_retries = (groups > 1 || n_obs <= 512) ? 1 : 0;
         const int threads = groups > 1 ? 256 : ((model == 1 ? n_obs >= 1500 : n_obs >= 768) ? 512 : 256);
-        const bool in_regs = n_obs <= 2 * groups * 256 && threads == 256 && tuning_pose_obs_regs() && tuning().pose_threads != 512;
-        const bool zero_copy = in_regs && zero_copy_env && first;
+        const bool in_regs = n_obs <= 2 * groups * 256 && threads == 256 && tuning().pose_obs_regs && tuning().pose_threads != 512;
+        const bool zero_copy = in_regs && tuning().pose_zero_copy && first;
         unsigned char* const io = zero_copy ? h : d;   // where the kernel finds its inputs and leaves its outputs
         if (!zero_copy) OVS_HIP_TRY(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, scratch.stream));
         const ovs_status st = pose_optimize_batch_dev(model, reinterpret_cast<double*>(io), reinterpret_cast<ovs_pose_obs*>(io + off_obs),

@@ -450,10 +450,14 @@ def test_dense_solve_failure_then_success(n):
 
 
 @pytest.mark.gpu
-def test_landmark_workgroup_shapes_give_the_same_bits(tmp_path):
-    """k_trial_update gives a workgroup 128 landmarks while the launch fits the chip in one go and 256 beyond (maps of more than ~59 k
-    landmarks: no other test is that large). The shape must not change a bit: a child process with OVS_BA_LM_PER_WG=256 (read once per process)
-    against this process (128 at these sizes) on one linearisation and on a whole ovs_local_ba_optimize, stereo edges included."""
+def test_local_ba_alternative_paths_give_the_same_bits_and_match_the_oracle(tmp_path, oracle):
+    """Two process-wide switches (read once per process, so each runs in a child) select paths of ovs_local_ba_optimize that production
+    does not take at this size: a trial's outcome through a D2H copy and a stream wait instead of the flag-carrying words the host polls
+    (OVS_BA_LL_NOTIFY=0), and the pairs' common landmarks found by every trial's k_schur itself instead of once per graph by k_pair_lists
+    (OVS_BA_SCHUR_LISTS=0; production above the pair-list bound). Both must give the default's bits on one linearisation and on a whole
+    ovs_local_ba_optimize, stereo edges included (stereo 0.35, 3000 landmarks). The default is checked against the oracle on the same scene:
+    the linearisation at the tolerances of test_graph_linearize_is_deterministic_and_matches_oracle, the optimisation at those of
+    test_local_ba_optimize."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -474,41 +478,52 @@ res.update({"opt_" + k: np.asarray(v) for k, v in r.items()})
 np.savez(sys.argv[1], **res)
 """
     outs = {}
-    # round 6, the same for: a trial's outcome through a D2H copy + stream wait instead of the flag-carrying words the host polls
-    # (OVS_BA_LL_NOTIFY=0), and the compiler-scheduled diagonal blocks / round-5 backward substitution of the dense solver (OVS_CHOL_SCHED=0)
-    variants = (("auto", {}), ("w256", {"OVS_BA_LM_PER_WG": "256"}), ("w128", {"OVS_BA_LM_PER_WG": "128"}), ("copies", {"OVS_BA_LL_NOTIFY": "0"}),
-                ("chol_r5", {"OVS_CHOL_SCHED": "0"}),
-                # round 6: back-substitution by one lane per landmark (rounds 4-5) instead of one per edge; the chi-square gates on the host
-                # (both per-edge arrays downloaded, the active mask uploaded) instead of k_edge_gate
-                ("backsub_lm", {"OVS_BA_BACKSUB_EDGES": "0"}), ("host_gates", {"OVS_BA_DEV_OUTLIERS": "0"}),
-                # the linearisation as two launches (k_lin_pose with two entries per thread, k_lin_landmark) instead of k_linearize2: another
-                # summation tree for Hpp / bp (last bits), the same bits for everything per edge and per landmark
-                ("lin_two_launches", {"OVS_BA_LIN_MERGED": "0"}),
-                # the pairs' common landmarks found by every trial's k_schur itself (rounds 4-6) instead of once per graph (k_pair_lists)
-                ("schur_scan", {"OVS_BA_SCHUR_LISTS": "0"}))
+    variants = (("auto", {}), ("copies", {"OVS_BA_LL_NOTIFY": "0"}), ("schur_scan", {"OVS_BA_SCHUR_LISTS": "0"}))
     for tag, env in variants:
         out = tmp_path / ("%s.npz" % tag)
         r = subprocess.run([sys.executable, "-c", code % (root, os.path.join(root, "tests")), str(out)], env=dict(os.environ, **env),
                            capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         outs[tag] = dict(np.load(out))
-    assert len(outs["auto"]) >= 10 and outs["auto"]["opt_info"][4] >= 3
+    got = outs["auto"]
+    assert len(got) >= 10 and got["opt_info"][4] >= 3
     for tag, _ in variants[1:]:
-        for k, v in outs["auto"].items():
-            if tag == "lin_two_launches" and k not in ("lin_Hll", "lin_bl", "lin_Hpl"):
-                if k.startswith("lin_"):
-                    assert np.allclose(v, outs[tag][k], rtol=1e-11, atol=1e-11 * np.abs(v).max()), (tag, k)
-                elif k in ("opt_poses", "opt_points"):
-                    assert np.allclose(v, outs[tag][k], rtol=1e-8, atol=1e-9), (tag, k)
-                continue
+        for k, v in got.items():
             assert np.array_equal(v, outs[tag][k]), (tag, k)
+    # the default against the oracle on the same scene
+    from oracle import lba
+    from test_ba import _lba_scene
+    d, mono, st, bf, _, _ = _lba_scene(21, n_pose=12, n_pt=3000, obs_per_pose=700, stereo_frac=0.35)
+    hm, hs = lba.SQRT_CHI2_MONO, lba.SQRT_CHI2_STEREO
+    want = oracle.ba_linearize(d["poses"], d["pose_fixed"], d["points"], mono, d["cam"], hm)
+    s = oracle.ba_linearize_stereo(d["poses"], d["pose_fixed"], d["points"], st, d["cam"], bf, hs)
+    for k in ("Hpp", "bp", "Hll", "bl", "chi2"):
+        want[k] = want[k] + s[k]
+    want["Hpl"] = np.concatenate([want["Hpl"], s["Hpl"]])
+    for k in ("Hpl", "Hll", "bl"):
+        assert np.array_equal(got["lin_" + k], want[k]), k
+    for k in ("Hpp", "bp", "chi2"):
+        scale = np.abs(want[k]).max()
+        assert np.allclose(got["lin_" + k], want[k], rtol=1e-13, atol=1e-13 * scale), k
+    free = d["pose_fixed"] == 0
+    md = max(np.abs(np.einsum("kii->ki", want["Hpp"][free])).max(), np.abs(np.einsum("kii->ki", want["Hll"])).max())
+    assert np.isclose(got["lin_max_diag"][0], md, rtol=1e-13)
+    want = lba.local_ba_optimize(d["poses"], d["pose_fixed"], d["points"], mono, d["cam"], st, bf)
+    assert np.array_equal(got["opt_info"][4:], want["info"][4:]) and want["info"][4] >= 3
+    assert np.allclose(got["opt_info"][:4], want["info"][:4], rtol=1e-7)
+    assert np.allclose(got["opt_poses"], want["poses"], rtol=1e-7, atol=1e-8)
+    assert np.allclose(got["opt_points"], want["points"], rtol=1e-7, atol=1e-8)
+    for k in ("mono_outlier", "stereo_outlier"):
+        assert (got["opt_" + k] != want[k]).sum() <= max(1, len(want[k]) // 5000), k
+    fixed = d["pose_fixed"].astype(bool)
+    assert np.array_equal(got["opt_poses"][fixed], d["poses"][fixed])
 
 
 @pytest.mark.gpu
 def test_a_landmark_with_more_edges_than_a_workgroup_has_lanes(tmp_path, oracle):
-    """A landmark seen by 270 keyframes (168 free: the device solver's size) is a workgroup of its own in k_lin_landmark and in k_trial_update's
-    one-lane-per-edge back-substitution, its edges passing in pieces of 256. The linearisation against the oracle, and the whole optimisation
-    bit-equal to the one-lane-per-landmark back-substitution (OVS_BA_BACKSUB_EDGES=0, child processes) and to the host-side gates."""
+    """A landmark seen by 270 keyframes (168 free: the device solver's size) is a workgroup of its own in k_linearize2's landmark partition and
+    in k_trial_update's one-lane-per-edge back-substitution, its edges passing in pieces of 256. The whole optimisation against the oracle, and
+    bit-equal to the one with every trial's k_schur scanning for the pairs' common landmarks (OVS_BA_SCHUR_LISTS=0, a child process)."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -540,8 +555,7 @@ r = ba.local_ba_optimize(d["poses"], d["pose_fixed"], d["points"], edges, d["cam
 np.savez(sys.argv[1], edges=edges, **{"opt_" + k: np.asarray(v) for k, v in r.items()})
 """
     outs = {}
-    variants = (("auto", {}), ("backsub_lm", {"OVS_BA_BACKSUB_EDGES": "0"}), ("host_gates", {"OVS_BA_DEV_OUTLIERS": "0"}),
-                ("schur_scan", {"OVS_BA_SCHUR_LISTS": "0"}))
+    variants = (("auto", {}), ("schur_scan", {"OVS_BA_SCHUR_LISTS": "0"}))
     for tag, env in variants:
         out = tmp_path / ("%s.npz" % tag)
         r = subprocess.run([sys.executable, "-c", code % (root, os.path.join(root, "tests")), str(out)], env=dict(os.environ, **env),

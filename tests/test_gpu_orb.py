@@ -239,12 +239,10 @@ def test_large_batch_takes_the_many_problem_tree_kernel(hip, oracle):
 
 
 def test_alternative_kernel_forms_give_the_same_bytes(tmp_path):
-    """Round 6 left five process-wide switches between kernel forms (the fifth: OVS_PYR_PAIR=0, the pyramid level by level instead of two levels per launch;
-    the other four: (read once per process, so each runs in a child): the one-wavefront-per-cell
-    FAST (OVS_FAST_IMPL=2), the frames-fastest work order of rounds 3-5 (OVS_FAST_MAP=0), the quad-tree's sweep form only (OVS_TREE_GRID=0) and
-    its grid form at a forced depth (OVS_TREE_GRID=3: most levels overflow and fall back inside the launch; 7: the deepest grid). Every one must
-    reproduce the default's counts, keypoint records and descriptors byte for byte on a 70-frame batch (which the test above checks against
-    the oracle)."""
+    """The quad-tree distribution has two forms that production picks by launch (read once per process, so each runs in a child): the sweep
+    form only (OVS_TREE_GRID=0) and the grid form at a forced depth (OVS_TREE_GRID=3: most levels overflow and fall back inside the launch;
+    7: the deepest grid). Every one must reproduce the default's counts, keypoint records and descriptors byte for byte on a 70-frame batch
+    (which the test above checks against the oracle)."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -277,8 +275,7 @@ for split in (True, False):
 print("SHA", h.hexdigest(), int(cnt.sum()))
 """
     out = {}
-    for tag, env in (("default", {}), ("wave", {"OVS_FAST_IMPL": "2"}), ("frames_fastest", {"OVS_FAST_MAP": "0"}), ("sweeps", {"OVS_TREE_GRID": "0"}),
-                     ("grid3", {"OVS_TREE_GRID": "3"}), ("grid7", {"OVS_TREE_GRID": "7"}), ("pyramid_per_level", {"OVS_PYR_PAIR": "0"})):
+    for tag, env in (("default", {}), ("sweeps", {"OVS_TREE_GRID": "0"}), ("grid3", {"OVS_TREE_GRID": "3"}), ("grid7", {"OVS_TREE_GRID": "7"})):
         r = subprocess.run([sys.executable, "-c", code % root], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, (tag, r.stderr[-2000:])
         line = [l for l in r.stdout.splitlines() if l.startswith("SHA")][-1].split()
