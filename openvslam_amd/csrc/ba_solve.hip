@@ -454,13 +454,15 @@ __device__ __forceinline__ void factor_steps(double (&a)[kNb], double& s, double
     invd_j[K] = y;
     double yn = y, h = 0.0;
     if constexpr (K + 1 < kNb) {   // column K + 1 first: the next pivot is final, its chain starts
-        a[K + 1] = vfnma64(a[K], bc64<true>(a[K], K + 1), a[K + 1]);
-        const double piv = bc64<true>(a[K + 1], K + 1);
+        a[K + 1] = vfnma64(a[K], bc64<true>(a[K], K + 1), a[K + 1]);   // (VALU write -> DPP read: a[K] is two instructions old at most)
+        const double piv = bc64<true>(a[K + 1], K + 1);                // (VALU write -> DPP read: a[K + 1] was written just above)
         bad |= !(piv > 0.0 && piv < __builtin_inf());
         yn = vrsq64(piv);
         h = vmul64(piv, cmh);
     }
-    const double yk = bc64<false>(sy, K);
+    // VALU write -> DPP read, two wait states: on the last pivot nothing but the store of invd_j[K] lies between sy's v_mul_f64 and its
+    // broadcast (one state), so that one takes the padded form; on the others the column K + 1 statements above already separate the two
+    const double yk = bc64<(K + 1 >= kNb)>(sy, K);
     vec_j[K] = yk;
     s = vfnma64(a[K], yk, s);
     // the three Newton steps of the next pivot, a column update behind each of their dependent operations
@@ -554,7 +556,8 @@ __device__ __forceinline__ void solve_rows_res(double* __restrict__ P, const dou
 // 8 more registers per slot, or whole second copies of the accumulator file across a switch -- and spill a third of the tiles. Wait states
 // inside the string (nothing in it is padded by the compiler): the A operands were just written by the negating v_xor (s_nop before the first
 // matrix instruction); the chain of four accumulates needs none; the result is read by compiler code afterwards (ds_write of a finished
-// tile): a 16-pass f64 matrix instruction needs 18 states before a memory / LDS / VALU reader -- 24 are spent (s_nop 15 + s_nop 7 = 10 ns per tile).
+// tile): a 16-pass f64 matrix instruction needs 18 states before a memory / LDS reader and 19 before a VALU reader (what hipcc leaves behind the
+// builtin: tools/asm_hazards.py) -- 24 are spent (s_nop 15 + s_nop 7 = 10 ns per tile). VALU write -> MFMA operand: two states, s_nop 3 gives four.
 __device__ __forceinline__ int res_active_tiles(int jj) { return jj * (jj + 1) / 2; }
 __device__ __forceinline__ void tile_update_tied(v4d& c, double a0, double a1, double a2, double a3, double b0, double b1, double b2, double b3) {
     asm volatile(
@@ -604,7 +607,7 @@ __device__ __forceinline__ void backward_substitution_res(double* __restrict__ S
             const double iv = invd[jb + rl];
 #pragma unroll
             for (int k = kNb - 1; k >= 0; --k) {
-                const double xk = bc64<true>(vmul64(res, iv), k);
+                const double xk = bc64<true>(vmul64(res, iv), k);   // (VALU write -> DPP read: the product was written just before)
                 res = vfnma64(tt[k], xk, res);
             }
             if (lane < kNb) vec[jb + rl] = vmul64(res, iv);
