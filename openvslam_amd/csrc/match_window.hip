@@ -967,13 +967,11 @@ struct ovs_wmatcher {
     int max_t = 0, max_q = 0;
     uint32_t max_entries = 0;
     hipStream_t stream = nullptr;
-    // grid of the target frame
+    // grid of a target frame that is uploaded per call (a resident frame carries its own)
     int32_t* d_cell_of = nullptr;
     int32_t* d_cell_start = nullptr;
     int32_t* d_items = nullptr;
-    int grid_cells_cap = 0;
     GridP gp{};
-    int grid_n = -1;
     // candidate lists
     uint32_t* d_counts = nullptr;
     uint32_t* d_offsets = nullptr;
@@ -982,29 +980,10 @@ struct ovs_wmatcher {
     bool overflow_dirty = true;        // the overflow word may be non-zero (build_lists clears it then)
     int32_t* d_assigned = nullptr;      // max(max_q, max_t)
     int32_t* d_num = nullptr;
-    // host-API staging
-    ovs_keypoint* d_t_kps = nullptr;
-    uint8_t* d_t_desc = nullptr;
-    uint8_t* d_t_flag = nullptr;
-    float* d_t_f = nullptr;
-    ovs_keypoint* d_q_kps = nullptr;
-    uint8_t* d_q_desc = nullptr;
-    uint8_t* d_q_flag = nullptr;
-    float* d_q_xy = nullptr;
-    float* d_q_f = nullptr;
-    int32_t* d_q_i = nullptr;
-    float* d_q_r = nullptr;
-    int32_t* d_q_i2 = nullptr;
-    double* d_q_pos = nullptr;
-    float* d_sf = nullptr;
-    double* d_tri_b1 = nullptr;
-    double* d_tri_b2 = nullptr;
-    int32_t* d_csr = nullptr;           // bow feature vectors: 2 x (ids | start | items)
-    size_t csr_cap = 0;
-    // round 3: d_overflow | d_num[4] | pad | d_assigned are ONE block (a call's results come down with one copy), and the frame-handle
-    // entry points stage their per-call host arrays through one pinned buffer into one device arena (one copy up)
+    // d_overflow | d_num[4] | pad | d_assigned are ONE block: a call's results come down with one copy (fetch_results)
     uint32_t* d_res_block = nullptr;
     int32_t* h_res = nullptr;           // pinned mirror of the result block
+    // every per-call host array goes through one pinned buffer into one device arena with one copy up (Stager)
     unsigned char* h_stage = nullptr;   // pinned
     unsigned char* d_stage = nullptr;
     size_t stage_cap = 0;
@@ -1039,6 +1018,10 @@ GridP make_gridp(const ovs_grid_params& p) {
     g.cols = p.cols;
     g.rows = p.rows;
     return g;
+}
+
+bool grid_params_ok(const ovs_grid_params* gp) {
+    return gp && gp->cols >= 1 && gp->rows >= 1 && gp->cols * gp->rows <= kMaxGridCells && gp->max_x > gp->min_x && gp->max_y > gp->min_y;
 }
 
 size_t resolve_lds_bytes(int n_q, int n_t) {
@@ -1079,82 +1062,31 @@ ovs_status launch_resolve(const ResolveArgs& ra_in, hipStream_t s) {
     return OVS_OK;
 }
 
-ovs_status grid_assign(ovs_wmatcher* w, const ovs_grid_params* gp, const ovs_keypoint* d_kps, int n, hipStream_t s) {
-    if (!gp || gp->cols < 1 || gp->rows < 1 || gp->cols * gp->rows > kMaxGridCells || !(gp->max_x > gp->min_x) || !(gp->max_y > gp->min_y))
-        return OVS_ERR_INVALID;
-    if (n > w->max_t) return OVS_ERR_CAPACITY;
-    w->gp = make_gridp(*gp);
-    w->grid_n = n;
-    const int nc = gp->cols * gp->rows;
+// k_grid_assign over `n` device keypoints: one workgroup, the member lists in LDS when they fit
+hipError_t launch_grid_assign(const ovs_keypoint* d_kps, int n, const GridP& g, int32_t* cell_of, int32_t* cell_start, int32_t* items, hipStream_t s) {
+    const int nc = g.cols * g.rows;
     const int in_lds = (n <= kGridItemsLds && (size_t)(2 * nc + 1 + n) * sizeof(int32_t) <= 144 * 1024) ? 1 : 0;
     const size_t lds = (size_t)(2 * nc + 1 + (in_lds ? n : 0)) * sizeof(int32_t);
-    if (lds > 64 * 1024)
-        OVS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_grid_assign), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_grid_assign, dim3(1), dim3(1024), lds, s, d_kps, n, w->gp, w->d_cell_of, w->d_cell_start, w->d_items, in_lds);
-    OVS_HIP_TRY(hipGetLastError());
-    return OVS_OK;
-}
-
-// The TARGET side of a windowed call (the keypoints that are searched through the grid): either host arrays -- uploaded into the context's
-// buffers and indexed by k_grid_assign, per call -- or a frame / keyframe RESIDENT in HBM (ovs_frame_dev: uploaded and indexed once, when the
-// handle was created). Keyframes are the long-lived, immutable objects of the map: mapping_module matches every new keyframe against ~20
-// covisible ones (fuse::replace_duplication), loop closing against more; with the handle none of those calls moves keypoints or descriptors.
-struct TargetRef {
-    const ovs_keypoint* kps;
-    const uint8_t* desc;
-    const float* x_right;
-    const int32_t* cell_start;
-    const int32_t* items;
-    GridP gp;
-};
-ovs_status stage_target(ovs_wmatcher* w, const ovs_frame_dev* res, const ovs_grid_params* gp, const ovs_keypoint* kps, const uint8_t* desc,
-                        const float* x_right, int n, hipStream_t s, TargetRef* t) {
-    if (res) {
-        if (res->device != w->device || res->n != n) return OVS_ERR_INVALID;
-        *t = TargetRef{res->d_kps, res->d_desc, res->has_stereo ? res->d_x_right : nullptr, res->d_cell_start, res->d_items, res->gp};
-        return OVS_OK;
+    if (lds > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_grid_assign), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
     }
-    OVS_HIP_TRY(hipMemcpyAsync(w->d_t_kps, kps, sizeof(ovs_keypoint) * (size_t)n, hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipMemcpyAsync(w->d_t_desc, desc, (size_t)32 * n, hipMemcpyHostToDevice, s));
-    if (x_right) OVS_HIP_TRY(hipMemcpyAsync(w->d_t_f, x_right, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, s));
-    const ovs_status st = grid_assign(w, gp, w->d_t_kps, n, s);
-    if (st != OVS_OK) return st;
-    *t = TargetRef{w->d_t_kps, w->d_t_desc, x_right ? w->d_t_f : nullptr, w->d_cell_start, w->d_items, w->gp};
+    hipLaunchKernelGGL(k_grid_assign, dim3(1), dim3(1024), lds, s, d_kps, n, g, cell_of, cell_start, items, in_lds);
+    return hipGetLastError();
+}
+
+// the context's own grid over device keypoints
+ovs_status grid_assign(ovs_wmatcher* w, const ovs_grid_params* gp, const ovs_keypoint* d_kps, int n, hipStream_t s) {
+    if (!grid_params_ok(gp)) return OVS_ERR_INVALID;
+    if (n > w->max_t) return OVS_ERR_CAPACITY;
+    w->gp = make_gridp(*gp);
+    OVS_HIP_TRY(launch_grid_assign(d_kps, n, w->gp, w->d_cell_of, w->d_cell_start, w->d_items, s));
     return OVS_OK;
 }
-
-// WinArgs::dead_from for a rule that accepts iff best <= thr and (ratio rules) !(fl(second * ratio) < best): the smallest distance d > thr with
-// fl(d * ratio) >= thr -- from there on a candidate can neither be an accepted best nor make the ratio test fail (the float product is monotone
-// in d, and "no second at all" counts as distance 256, which then accepts too). 257: nothing is dead; 0 would switch the filter off.
-static uint32_t dead_from_ratio(uint32_t thr, float ratio) {
-    if (!(ratio > 0.0f)) return 257u;
-    for (uint32_t d = thr + 1u; d <= 256u; ++d)
-        if ((float)d * ratio >= (float)thr) return d;
-    return 257u;
-}
-static uint32_t dead_from_thr(uint32_t thr) { return thr + 1u; }   // rules without a ratio test: best <= thr or nothing
-
-template <typename ARGS, typename KCOUNT, typename KFILL>
-ovs_status build_lists(ovs_wmatcher* w, const ARGS& args, int n_q, KCOUNT kcount, KFILL kfill, hipStream_t s, int q_per_block = 4) {
-    if (n_q > w->max_q) return OVS_ERR_CAPACITY;
-    // the overflow word is zero between calls unless a call ended without having read it as zero (a failed call, an overflow): only then is it cleared
-    // here (round 6: the clearing was a fill kernel and a launch gap in front of every list build).
-    // (Also tried: the counting launch's last workgroup scanning the counts instead of the one-workgroup k_scan_counts launch -- the device-scope
-    // release every workgroup needs before it takes its ticket is an L2 write-back on this multi-XCD part: +20 us per call, dropped.)
-    if (w->overflow_dirty) OVS_HIP_TRY(hipMemsetAsync(w->d_overflow, 0, sizeof(uint32_t), s));
-    w->overflow_dirty = true;
-    const dim3 grid((n_q + q_per_block - 1) / q_per_block);
-    hipLaunchKernelGGL(kcount, grid, dim3(256), 0, s, args, w->d_counts, (const uint32_t*)w->d_offsets, w->d_keys, w->max_entries, w->d_overflow);
-    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, s, (const uint32_t*)w->d_counts, n_q, w->d_offsets);
-    hipLaunchKernelGGL(kfill, grid, dim3(256), 0, s, args, w->d_counts, (const uint32_t*)w->d_offsets, w->d_keys, w->max_entries, w->d_overflow);
-    OVS_HIP_TRY(hipGetLastError());
-    return OVS_OK;
-}
-
 
 size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 
-// per-call staging of host arrays: memcpy into the context's pinned buffer, ONE hipMemcpyAsync for all of them
+// per-call staging of host arrays: memcpy into the context's pinned buffer, ONE copy up for all of them
 struct Stager {
     ovs_wmatcher* w;
     size_t used = 0;
@@ -1182,10 +1114,12 @@ struct Stager {
         used = off + bytes;
         return reinterpret_cast<T*>(w->d_stage + off);
     }
-    hipError_t flush(hipStream_t s) {
+    ovs_status flush(hipStream_t s) {   // behind the call's last put / reserve
+        if (overflow) return OVS_ERR_CAPACITY;
         flushed_on = s;
         flushed = true;
-        return used ? hipMemcpyAsync(w->d_stage, w->h_stage, used, hipMemcpyHostToDevice, s) : hipSuccess;
+        if (used) OVS_HIP_TRY(hipMemcpyAsync(w->d_stage, w->h_stage, used, hipMemcpyHostToDevice, s));
+        return OVS_OK;
     }
     // A call returns with its stream idle, on EVERY path: the next call (or the shim's immediate retry) memcpy's into the same pinned buffer, and
     // a frame arena may go back to the pool -- neither may happen while a copy or a kernel of a failed call is still in flight. After a
@@ -1197,6 +1131,87 @@ struct Stager {
     }
 };
 
+// One SIDE of a call -- the keypoints that are searched through the grid (the target of a windowed matcher), or either side of a BoW matcher:
+// host arrays, staged per call, or a frame / keyframe RESIDENT in HBM (ovs_frame_dev: uploaded and indexed once, when the handle was
+// created). Keyframes are the long-lived, immutable objects of the map: mapping_module matches every new keyframe against ~20 covisible
+// ones (fuse::replace_duplication), loop closing against more; with the handle none of those calls moves keypoints or descriptors.
+struct TargetRef {
+    const ovs_keypoint* kps;
+    const uint8_t* desc;
+    const float* x_right;
+    const double* bearings;
+    const int32_t* cell_start;   // nullptr: staged, not indexed yet (index_target)
+    const int32_t* items;
+    GridP gp;
+};
+// the one place that decides resident or uploaded; issues no device work (a staged side travels with the Stager's flush)
+ovs_status stage_target(ovs_wmatcher* w, Stager& stg, const ovs_frame_dev* res, const ovs_keypoint* kps, const uint8_t* desc, const float* x_right,
+                        const double* bearings, int n, TargetRef* t) {
+    if (res) {
+        if (res->device != w->device || res->n != n) return OVS_ERR_INVALID;
+        // bearings: the handle's when it carries them (ovs_frame_dev_attach_bearings), else the caller's
+        *t = TargetRef{res->d_kps, res->d_desc, res->has_stereo ? res->d_x_right : nullptr, res->d_bearings ? res->d_bearings : stg.put(bearings, (size_t)3 * n),
+                       res->d_cell_start, res->d_items, res->gp};
+        return OVS_OK;
+    }
+    *t = TargetRef{};
+    t->kps = stg.put(kps, (size_t)n);
+    t->desc = stg.put(desc, (size_t)32 * n);
+    t->x_right = stg.put(x_right, (size_t)n);
+    t->bearings = stg.put(bearings, (size_t)3 * n);
+    return OVS_OK;
+}
+// behind the flush: the grid of a staged target (a resident one brings its own)
+ovs_status index_target(ovs_wmatcher* w, const ovs_grid_params* gp, int n, TargetRef* t, hipStream_t s) {
+    if (t->cell_start) return OVS_OK;
+    const ovs_status st = grid_assign(w, gp, t->kps, n, s);
+    if (st != OVS_OK) return st;
+    t->cell_start = w->d_cell_start;
+    t->items = w->d_items;
+    t->gp = w->gp;
+    return OVS_OK;
+}
+
+// WinArgs::dead_from for a rule that accepts iff best <= thr and (ratio rules) !(fl(second * ratio) < best): the smallest distance d > thr with
+// fl(d * ratio) >= thr -- from there on a candidate can neither be an accepted best nor make the ratio test fail (the float product is monotone
+// in d, and "no second at all" counts as distance 256, which then accepts too). 257: nothing is dead; 0 would switch the filter off.
+uint32_t dead_from_ratio(uint32_t thr, float ratio) {
+    if (!(ratio > 0.0f)) return 257u;
+    for (uint32_t d = thr + 1u; d <= 256u; ++d)
+        if ((float)d * ratio >= (float)thr) return d;
+    return 257u;
+}
+uint32_t dead_from_thr(uint32_t thr) { return thr + 1u; }   // rules without a ratio test: best <= thr or nothing
+
+template <typename ARGS, typename KCOUNT, typename KFILL>
+ovs_status build_lists(ovs_wmatcher* w, const ARGS& args, int n_q, KCOUNT kcount, KFILL kfill, hipStream_t s, int q_per_block = 4) {
+    if (n_q > w->max_q) return OVS_ERR_CAPACITY;
+    // the overflow word is zero between calls unless a call ended without having read it as zero (a failed call, an overflow): only then is it cleared
+    // here (round 6: the clearing was a fill kernel and a launch gap in front of every list build).
+    // (Also tried: the counting launch's last workgroup scanning the counts instead of the one-workgroup k_scan_counts launch -- the device-scope
+    // release every workgroup needs before it takes its ticket is an L2 write-back on this multi-XCD part: +20 us per call, dropped.)
+    if (w->overflow_dirty) OVS_HIP_TRY(hipMemsetAsync(w->d_overflow, 0, sizeof(uint32_t), s));
+    w->overflow_dirty = true;
+    const dim3 grid((n_q + q_per_block - 1) / q_per_block);
+    hipLaunchKernelGGL(kcount, grid, dim3(256), 0, s, args, w->d_counts, (const uint32_t*)w->d_offsets, w->d_keys, w->max_entries, w->d_overflow);
+    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, s, (const uint32_t*)w->d_counts, n_q, w->d_offsets);
+    hipLaunchKernelGGL(kfill, grid, dim3(256), 0, s, args, w->d_counts, (const uint32_t*)w->d_offsets, w->d_keys, w->max_entries, w->d_overflow);
+    OVS_HIP_TRY(hipGetLastError());
+    return OVS_OK;
+}
+
+// what every resolver launch reads from the context: the lists build_lists wrote, the result block as output
+ResolveArgs resolve_args(const ovs_wmatcher* w, int n_q, int n_t) {
+    ResolveArgs ra{};
+    ra.offsets = w->d_offsets;
+    ra.keys = w->d_keys;
+    ra.n_q = n_q;
+    ra.n_t = n_t;
+    ra.assigned = w->d_assigned;
+    ra.num_matches = w->d_num;
+    return ra;
+}
+
 // results: overflow flag, counts and `n_out` assignments in one copy
 ovs_status fetch_results(ovs_wmatcher* w, int n_out, int32_t* assigned, int32_t* num_matches, hipStream_t s, bool check_overflow = true) {
     OVS_HIP_TRY(hipMemcpyAsync(w->h_res, w->d_res_block, sizeof(int32_t) * (8 + (size_t)n_out), hipMemcpyDeviceToHost, s));
@@ -1204,764 +1219,9 @@ ovs_status fetch_results(ovs_wmatcher* w, int n_out, int32_t* assigned, int32_t*
     std::memcpy(assigned, w->h_res + 8, sizeof(int32_t) * (size_t)n_out);
     *num_matches = w->h_res[1];
     if (check_overflow && w->h_res[0] == 0) w->overflow_dirty = false;   // read as zero behind every kernel of the call: still zero for the next one
-    return (check_overflow && w->h_res[0]) ? OVS_ERR_CAPACITY : OVS_OK;   // (k_fuse_best writes no overflow flag: the word may be stale)
+    return (check_overflow && w->h_res[0]) ? OVS_ERR_CAPACITY : OVS_OK;   // (k_fuse_best and k_cross_check write no overflow flag: the word may be stale)
 }
 
-
-}   // namespace
-
-extern "C" {
-
-ovs_status ovs_wmatcher_create(int32_t max_targets, int32_t max_queries, int32_t max_entries, int32_t device, ovs_wmatcher** out) {
-    if (!out || max_targets < 1 || max_queries < 1 || max_entries < 1 || max_targets > 65534 || max_queries > 65534) return OVS_ERR_INVALID;
-    *out = nullptr;
-    if (ovs_device_count() <= device || device < 0) return OVS_ERR_NO_DEVICE;
-    if (resolve_lds_bytes(max_queries, max_targets) > 150 * 1024) return OVS_ERR_CAPACITY;
-    ovs_wmatcher* w = new (std::nothrow) ovs_wmatcher();
-    if (!w) return OVS_ERR_INVALID;
-    w->device = device;
-    w->max_t = max_targets;
-    w->max_q = max_queries;
-    w->max_entries = (uint32_t)max_entries;
-#define CREATE_TRY(expr)                       \
-    do {                                       \
-        hipError_t _e = (expr);                \
-        if (_e != hipSuccess) {                \
-            ovs::set_last_error(#expr, _e);    \
-            ovs_wmatcher_destroy(w);           \
-            return OVS_ERR_HIP;                \
-        }                                      \
-    } while (0)
-    CREATE_TRY(hipSetDevice(device));
-    CREATE_TRY(hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking));
-    const size_t T = (size_t)max_targets, Q = (size_t)max_queries, M = std::max(T, Q);
-    CREATE_TRY(hipMalloc(&w->d_cell_of, sizeof(int32_t) * T));
-    CREATE_TRY(hipMalloc(&w->d_cell_start, sizeof(int32_t) * (kMaxGridCells + 1)));
-    CREATE_TRY(hipMalloc(&w->d_items, sizeof(int32_t) * T));
-    CREATE_TRY(hipMalloc(&w->d_counts, sizeof(uint32_t) * (Q + 1)));
-    CREATE_TRY(hipMalloc(&w->d_offsets, sizeof(uint32_t) * (Q + 1)));
-    CREATE_TRY(hipMalloc(&w->d_keys, sizeof(uint32_t) * (size_t)max_entries));
-    // result block: [0] overflow flag, [1..4] counts ([1] result count, [2] per-direction scratch count), [8..] assigned
-    CREATE_TRY(hipMalloc(&w->d_res_block, sizeof(int32_t) * (8 + M)));
-    w->d_overflow = w->d_res_block;
-    w->d_num = reinterpret_cast<int32_t*>(w->d_res_block) + 1;
-    w->d_assigned = reinterpret_cast<int32_t*>(w->d_res_block) + 8;
-    CREATE_TRY(hipMemset(w->d_res_block, 0, sizeof(int32_t) * 8));
-    CREATE_TRY(hipHostMalloc(reinterpret_cast<void**>(&w->h_res), sizeof(int32_t) * (8 + M), hipHostMallocDefault));
-    // per-call query-side staging: keypoints 28 + descriptors 32 + positions 24 + xy 8 + four 4-byte arrays + flags, per query, and the
-    // target-side flags; 256-byte alignment slack per array
-    w->stage_cap = Q * (28 + 32 + 24 + 8 + 16 + 1) + T * 2 + 16 * 256 + 4096;
-    CREATE_TRY(hipHostMalloc(reinterpret_cast<void**>(&w->h_stage), w->stage_cap, hipHostMallocDefault));
-    CREATE_TRY(hipMalloc(&w->d_stage, w->stage_cap));
-    CREATE_TRY(hipMalloc(&w->d_t_kps, sizeof(ovs_keypoint) * T));
-    CREATE_TRY(hipMalloc(&w->d_t_desc, 32 * T));
-    CREATE_TRY(hipMalloc(&w->d_t_flag, T));
-    CREATE_TRY(hipMalloc(&w->d_t_f, sizeof(float) * T));
-    CREATE_TRY(hipMalloc(&w->d_q_kps, sizeof(ovs_keypoint) * Q));
-    CREATE_TRY(hipMalloc(&w->d_q_desc, 32 * Q));
-    CREATE_TRY(hipMalloc(&w->d_q_flag, Q));
-    CREATE_TRY(hipMalloc(&w->d_q_xy, sizeof(float) * 2 * Q));
-    CREATE_TRY(hipMalloc(&w->d_q_f, sizeof(float) * Q));
-    CREATE_TRY(hipMalloc(&w->d_q_i, sizeof(int32_t) * Q));
-    CREATE_TRY(hipMalloc(&w->d_q_r, sizeof(float) * Q));
-    CREATE_TRY(hipMalloc(&w->d_q_i2, sizeof(int32_t) * Q));
-    CREATE_TRY(hipMalloc(&w->d_q_pos, sizeof(double) * 3 * Q));
-    CREATE_TRY(hipMalloc(&w->d_sf, sizeof(float) * OVS_MAX_LEVELS));
-    CREATE_TRY(hipMalloc(&w->d_tri_b1, sizeof(double) * 3 * Q));
-    CREATE_TRY(hipMalloc(&w->d_tri_b2, sizeof(double) * 3 * T));
-    w->csr_cap = 4 * (T + Q) + 16;
-    CREATE_TRY(hipMalloc(&w->d_csr, sizeof(int32_t) * w->csr_cap));
-#undef CREATE_TRY
-    *out = w;
-    return OVS_OK;
-}
-
-ovs_status ovs_wmatcher_destroy(ovs_wmatcher* w) {
-    if (!w) return OVS_OK;
-    if (w->stream) hipStreamSynchronize(w->stream);
-    if (w->h_res) hipHostFree(w->h_res);
-    if (w->h_stage) hipHostFree(w->h_stage);
-    void* ptrs[] = {w->d_cell_of, w->d_cell_start, w->d_items, w->d_counts, w->d_offsets, w->d_keys, w->d_res_block, w->d_stage,
-                    w->d_t_kps,   w->d_t_desc,     w->d_t_flag, w->d_t_f,    w->d_q_kps,   w->d_q_desc, w->d_q_flag,  w->d_q_xy,    w->d_q_f,
-                    w->d_q_i,     w->d_csr,        w->d_q_r,    w->d_q_i2,   w->d_q_pos,   w->d_sf,
-                    w->d_tri_b1,  w->d_tri_b2};
-    for (void* p : ptrs) hipFree(p);
-    if (w->stream) hipStreamDestroy(w->stream);
-    delete w;
-    return OVS_OK;
-}
-
-ovs_status ovs_grid_assign_dev(ovs_wmatcher* w, const ovs_grid_params* gp, const ovs_keypoint* d_kps, int32_t n, void* stream) {
-    if (!w || !d_kps || n < 0) return OVS_ERR_INVALID;
-    OVS_HIP_TRY(hipSetDevice(w->device));
-    return grid_assign(w, gp, d_kps, n, (hipStream_t)stream);
-}
-
-ovs_status ovs_assign_keypoints_to_grid(ovs_wmatcher* w, const ovs_grid_params* gp, const ovs_keypoint* kps, int32_t n,
-                                        int32_t* cell_start, int32_t* items, int32_t* n_items) {
-    if (!w || !gp || (n > 0 && !kps) || n < 0 || !cell_start || !n_items) return OVS_ERR_INVALID;
-    if (n > w->max_t) return OVS_ERR_CAPACITY;
-    OVS_HIP_TRY(hipSetDevice(w->device));
-    hipStream_t s = w->stream;
-    if (n) OVS_HIP_TRY(hipMemcpyAsync(w->d_t_kps, kps, sizeof(ovs_keypoint) * n, hipMemcpyHostToDevice, s));
-    ovs_status st = grid_assign(w, gp, w->d_t_kps, n, s);
-    if (st != OVS_OK) return st;
-    const int nc = gp->cols * gp->rows;
-    OVS_HIP_TRY(hipMemcpyAsync(cell_start, w->d_cell_start, sizeof(int32_t) * (nc + 1), hipMemcpyDeviceToHost, s));
-    OVS_HIP_TRY(hipStreamSynchronize(s));
-    *n_items = cell_start[nc];
-    if (items && *n_items > 0) {
-        OVS_HIP_TRY(hipMemcpyAsync(items, w->d_items, sizeof(int32_t) * *n_items, hipMemcpyDeviceToHost, s));
-        OVS_HIP_TRY(hipStreamSynchronize(s));
-    }
-    return OVS_OK;
-}
-
-ovs_status ovs_projection_match_frame_and_landmarks_dev(ovs_wmatcher* w, const ovs_grid_params* gp, const ovs_keypoint* d_kps,
-                                                        const uint8_t* d_desc, const float* d_stereo_x_right, const uint8_t* d_occupied,
-                                                        int32_t n, const float* d_lm_xy, const float* d_lm_x_right,
-                                                        const int32_t* d_lm_level, const uint8_t* d_lm_desc, const uint8_t* d_lm_valid,
-                                                        int32_t m, const float* scale_factors, int32_t num_levels, float margin,
-                                                        float lowe_ratio, int32_t* d_assigned, int32_t* d_num_matches, void* stream) {
-    if (!w || !d_kps || !d_desc || n < 0 || m < 0 || !d_assigned || !d_num_matches || !scale_factors || num_levels < 1 ||
-        num_levels > OVS_MAX_LEVELS || (m > 0 && (!d_lm_xy || !d_lm_level || !d_lm_desc)) || (d_stereo_x_right && !d_lm_x_right))
-        return OVS_ERR_INVALID;
-    OVS_HIP_TRY(hipSetDevice(w->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (m == 0) {
-        OVS_HIP_TRY(hipMemsetAsync(d_num_matches, 0, sizeof(int32_t), s));
-        return OVS_OK;
-    }
-    ovs_status st = grid_assign(w, gp, d_kps, n, s);
-    if (st != OVS_OK) return st;
-    WinArgs a{};
-    a.t_kps = d_kps;
-    a.t_desc = d_desc;
-    a.t_occupied = d_occupied;
-    a.t_x_right = d_stereo_x_right;
-    a.cell_start = w->d_cell_start;
-    a.items = w->d_items;
-    a.gp = w->gp;
-    a.n_q = m;
-    a.q_xy = d_lm_xy;
-    a.q_x_right = d_lm_x_right;
-    a.q_level = d_lm_level;
-    a.q_valid = d_lm_valid;
-    a.q_desc = d_lm_desc;
-    a.margin = margin;
-    for (int l = 0; l < OVS_MAX_LEVELS; ++l) a.sf[l] = l < num_levels ? scale_factors[l] : 1.0f;
-    a.mode = kModeProjection;
-    a.dead_from = dead_from_ratio(OVS_HAMMING_DIST_THR_HIGH, lowe_ratio);
-    st = build_lists(w, a, m, k_window_lists<false>, k_window_lists<true>, s);
-    if (st != OVS_OK) return st;
-    ResolveArgs ra{};
-    ra.offsets = w->d_offsets;
-    ra.keys = w->d_keys;
-    ra.n_q = m;
-    ra.n_t = n;
-    ra.lowe_ratio = lowe_ratio;
-    ra.assigned = d_assigned;
-    ra.num_matches = d_num_matches;
-    return launch_resolve<kRuleProjection>(ra, s);
-}
-
-ovs_status ovs_projection_match_frame_and_landmarks(ovs_wmatcher* w, const ovs_grid_params* gp, const ovs_keypoint* kps,
-                                                    const uint8_t* desc, const float* stereo_x_right, const uint8_t* occupied, int32_t n,
-                                                    const float* lm_xy, const float* lm_x_right, const int32_t* lm_level,
-                                                    const uint8_t* lm_desc, const uint8_t* lm_valid, int32_t m,
-                                                    const float* scale_factors, int32_t num_levels, float margin, float lowe_ratio,
-                                                    int32_t* assigned, int32_t* num_matches) {
-    if (!w || !num_matches || n < 0 || m < 0) return OVS_ERR_INVALID;
-    *num_matches = 0;
-    if (m == 0) return OVS_OK;
-    if (!assigned) return OVS_ERR_INVALID;
-    if (n == 0) {
-        for (int i = 0; i < m; ++i) assigned[i] = -1;
-        return OVS_OK;
-    }
-    if (!kps || !desc || !lm_xy || !lm_level || !lm_desc) return OVS_ERR_INVALID;
-    if (n > w->max_t || m > w->max_q) return OVS_ERR_CAPACITY;
-    OVS_HIP_TRY(hipSetDevice(w->device));
-    hipStream_t s = w->stream;
-    OVS_HIP_TRY(hipMemcpyAsync(w->d_t_kps, kps, sizeof(ovs_keypoint) * n, hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipMemcpyAsync(w->d_t_desc, desc, (size_t)32 * n, hipMemcpyHostToDevice, s));
-    if (stereo_x_right) OVS_HIP_TRY(hipMemcpyAsync(w->d_t_f, stereo_x_right, sizeof(float) * n, hipMemcpyHostToDevice, s));
-    if (occupied) OVS_HIP_TRY(hipMemcpyAsync(w->d_t_flag, occupied, (size_t)n, hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipMemcpyAsync(w->d_q_xy, lm_xy, sizeof(float) * 2 * m, hipMemcpyHostToDevice, s));
-    if (lm_x_right) OVS_HIP_TRY(hipMemcpyAsync(w->d_q_f, lm_x_right, sizeof(float) * m, hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipMemcpyAsync(w->d_q_i, lm_level, sizeof(int32_t) * m, hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipMemcpyAsync(w->d_q_desc, lm_desc, (size_t)32 * m, hipMemcpyHostToDevice, s));
-    if (lm_valid) OVS_HIP_TRY(hipMemcpyAsync(w->d_q_flag, lm_valid, (size_t)m, hipMemcpyHostToDevice, s));
-    ovs_status st = ovs_projection_match_frame_and_landmarks_dev(
-        w, gp, w->d_t_kps, w->d_t_desc, stereo_x_right ? w->d_t_f : nullptr, occupied ? w->d_t_flag : nullptr, n, w->d_q_xy,
-        lm_x_right ? w->d_q_f : nullptr, w->d_q_i, w->d_q_desc, lm_valid ? w->d_q_flag : nullptr, m, scale_factors, num_levels, margin,
-        lowe_ratio, w->d_assigned, w->d_num, s);
-    if (st != OVS_OK) return st;
-    uint32_t overflow = 0;
-    OVS_HIP_TRY(hipMemcpyAsync(assigned, w->d_assigned, sizeof(int32_t) * m, hipMemcpyDeviceToHost, s));
-    OVS_HIP_TRY(hipMemcpyAsync(num_matches, w->d_num, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    OVS_HIP_TRY(hipMemcpyAsync(&overflow, w->d_overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    OVS_HIP_TRY(hipStreamSynchronize(s));
-    if (!overflow) w->overflow_dirty = false;
-    return overflow ? OVS_ERR_CAPACITY : OVS_OK;
-}
-
-ovs_status ovs_area_match_in_consistent_area_dev(ovs_wmatcher* w, const ovs_grid_params* gp, const ovs_keypoint* d_kps_1,
-                                                 const uint8_t* d_desc_1, int32_t n1, const ovs_keypoint* d_kps_2,
-                                                 const uint8_t* d_desc_2, int32_t n2, float* d_prev_matched_xy,
-                                                 int32_t* d_matched_2_in_1, int32_t margin, float lowe_ratio, int32_t check_orientation,
-                                                 int32_t* d_num_matches, void* stream) {
-    if (!w || n1 < 0 || n2 < 0 || !d_num_matches || (n1 > 0 && (!d_kps_1 || !d_desc_1 || !d_prev_matched_xy || !d_matched_2_in_1)) ||
-        (n2 > 0 && (!d_kps_2 || !d_desc_2)))
-        return OVS_ERR_INVALID;
-    OVS_HIP_TRY(hipSetDevice(w->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (n1 == 0) {
-        OVS_HIP_TRY(hipMemsetAsync(d_num_matches, 0, sizeof(int32_t), s));
-        return OVS_OK;
-    }
-    ovs_status st = grid_assign(w, gp, d_kps_2, n2, s);
-    if (st != OVS_OK) return st;
-    WinArgs a{};
-    a.t_kps = d_kps_2;
-    a.t_desc = d_desc_2;
-    a.cell_start = w->d_cell_start;
-    a.items = w->d_items;
-    a.gp = w->gp;
-    a.n_q = n1;
-    a.q_xy = d_prev_matched_xy;
-    a.q_kps = d_kps_1;
-    a.q_desc = d_desc_1;
-    a.margin = (float)margin;
-    a.mode = kModeArea;
-    a.dead_from = dead_from_ratio(OVS_HAMMING_DIST_THR_LOW, lowe_ratio);
-    st = build_lists(w, a, n1, k_window_lists<false>, k_window_lists<true>, s);
-    if (st != OVS_OK) return st;
-    ResolveArgs ra{};
-    ra.offsets = w->d_offsets;
-    ra.keys = w->d_keys;
-    ra.n_q = n1;
-    ra.n_t = n2;
-    ra.lowe_ratio = lowe_ratio;
-    ra.check_orientation = check_orientation;
-    ra.q_kps = d_kps_1;
-    ra.t_kps = d_kps_2;
-    ra.prev_matched_xy = d_prev_matched_xy;
-    ra.assigned = d_matched_2_in_1;
-    ra.num_matches = d_num_matches;
-    return launch_resolve<kRuleArea>(ra, s);
-}
-
-ovs_status ovs_area_match_in_consistent_area(ovs_wmatcher* w, const ovs_grid_params* gp, const ovs_keypoint* kps_1, const uint8_t* desc_1,
-                                             int32_t n1, const ovs_keypoint* kps_2, const uint8_t* desc_2, int32_t n2,
-                                             float* prev_matched_xy, int32_t* matched_2_in_1, int32_t margin, float lowe_ratio,
-                                             int32_t check_orientation, int32_t* num_matches) {
-    if (!w || !num_matches || n1 < 0 || n2 < 0) return OVS_ERR_INVALID;
-    *num_matches = 0;
-    if (n1 == 0) return OVS_OK;
-    if (!kps_1 || !desc_1 || !prev_matched_xy || !matched_2_in_1) return OVS_ERR_INVALID;
-    if (n2 == 0) {
-        for (int i = 0; i < n1; ++i) matched_2_in_1[i] = -1;
-        return OVS_OK;
-    }
-    if (!kps_2 || !desc_2) return OVS_ERR_INVALID;
-    if (n2 > w->max_t || n1 > w->max_q) return OVS_ERR_CAPACITY;
-    OVS_HIP_TRY(hipSetDevice(w->device));
-    hipStream_t s = w->stream;
-    OVS_HIP_TRY(hipMemcpyAsync(w->d_q_kps, kps_1, sizeof(ovs_keypoint) * n1, hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipMemcpyAsync(w->d_q_desc, desc_1, (size_t)32 * n1, hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipMemcpyAsync(w->d_q_xy, prev_matched_xy, sizeof(float) * 2 * n1, hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipMemcpyAsync(w->d_t_kps, kps_2, sizeof(ovs_keypoint) * n2, hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipMemcpyAsync(w->d_t_desc, desc_2, (size_t)32 * n2, hipMemcpyHostToDevice, s));
-    ovs_status st = ovs_area_match_in_consistent_area_dev(w, gp, w->d_q_kps, w->d_q_desc, n1, w->d_t_kps, w->d_t_desc, n2, w->d_q_xy,
-                                                          w->d_assigned, margin, lowe_ratio, check_orientation, w->d_num, s);
-    if (st != OVS_OK) return st;
-    uint32_t overflow = 0;
-    OVS_HIP_TRY(hipMemcpyAsync(matched_2_in_1, w->d_assigned, sizeof(int32_t) * n1, hipMemcpyDeviceToHost, s));
-    OVS_HIP_TRY(hipMemcpyAsync(prev_matched_xy, w->d_q_xy, sizeof(float) * 2 * n1, hipMemcpyDeviceToHost, s));
-    OVS_HIP_TRY(hipMemcpyAsync(num_matches, w->d_num, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    OVS_HIP_TRY(hipMemcpyAsync(&overflow, w->d_overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    OVS_HIP_TRY(hipStreamSynchronize(s));
-    if (!overflow) w->overflow_dirty = false;
-    return overflow ? OVS_ERR_CAPACITY : OVS_OK;
-}
-
-} // extern "C" (helper below has internal linkage)
-
-struct TriParams {   // robust::match_for_triangulation extras (host pointers)
-    const float* x_right_1;
-    const float* x_right_2;
-    const double* bearings_1;
-    const double* bearings_2;
-    const double* E_12;
-    const double* epipole_in_2;
-    const float* scale_factors;
-    int num_levels;
-};
-
-static ovs_status bow_match_impl(ovs_wmatcher* w, const ovs_frame_dev* res_kf, const ovs_frame_dev* res_frm, int by_query, const uint8_t* frm_valid, const TriParams* tri, const ovs_keypoint* kf_kps, const uint8_t* kf_desc, const uint8_t* kf_valid,
-                                            int32_t n_kf, const int32_t* kf_node_ids, const int32_t* kf_node_start,
-                                            const int32_t* kf_items, int32_t kf_nodes, const ovs_keypoint* frm_kps,
-                                            const uint8_t* frm_desc, int32_t n_frm, const int32_t* frm_node_ids,
-                                            const int32_t* frm_node_start, const int32_t* frm_items, int32_t frm_nodes, float lowe_ratio,
-                                            int32_t check_orientation, int32_t* matched_kf_in_frm, int32_t* num_matches) {
-    if (!w || !num_matches || n_kf < 0 || n_frm < 0 || kf_nodes < 0 || frm_nodes < 0) return OVS_ERR_INVALID;
-    *num_matches = 0;
-    const int n_out = by_query ? n_kf : n_frm;
-    if (n_out == 0) return OVS_OK;
-    if (!matched_kf_in_frm) return OVS_ERR_INVALID;
-    for (int i = 0; i < n_out; ++i) matched_kf_in_frm[i] = -1;
-    if (n_frm == 0) return OVS_OK;
-    if (n_kf == 0 || kf_nodes == 0 || frm_nodes == 0) return OVS_OK;
-    if ((!res_kf && (!kf_kps || !kf_desc)) || !kf_node_ids || !kf_node_start || !kf_items || (!res_frm && (!frm_kps || !frm_desc)) || !frm_node_ids ||
-        !frm_node_start || !frm_items)
-        return OVS_ERR_INVALID;
-    if ((res_kf && (res_kf->device != w->device || res_kf->n != n_kf)) || (res_frm && (res_frm->device != w->device || res_frm->n != n_frm))) return OVS_ERR_INVALID;
-    const int nq = kf_node_start[kf_nodes], nfi = frm_node_start[frm_nodes];
-    if (nq == 0 || nfi == 0) return OVS_OK;
-    if (n_frm > w->max_t || n_kf > w->max_q || nq > w->max_q || (by_query && n_kf > std::max(w->max_t, w->max_q))) return OVS_ERR_CAPACITY;
-    const size_t need = (size_t)2 * kf_nodes + 1 + nq + (size_t)2 * frm_nodes + 1 + nfi;
-    if (need > w->csr_cap) return OVS_ERR_CAPACITY;
-    OVS_HIP_TRY(hipSetDevice(w->device));
-    hipStream_t s = w->stream;
-    int32_t* p = w->d_csr;
-    int32_t* d_kf_ids = p;          p += kf_nodes;
-    int32_t* d_kf_start = p;        p += kf_nodes + 1;
-    int32_t* d_kf_items = p;        p += nq;
-    int32_t* d_f_ids = p;           p += frm_nodes;
-    int32_t* d_f_start = p;         p += frm_nodes + 1;
-    int32_t* d_f_items = p;
-    OVS_HIP_TRY(hipMemcpyAsync(d_kf_ids, kf_node_ids, sizeof(int32_t) * kf_nodes, hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipMemcpyAsync(d_kf_start, kf_node_start, sizeof(int32_t) * (kf_nodes + 1), hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipMemcpyAsync(d_kf_items, kf_items, sizeof(int32_t) * nq, hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipMemcpyAsync(d_f_ids, frm_node_ids, sizeof(int32_t) * frm_nodes, hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipMemcpyAsync(d_f_start, frm_node_start, sizeof(int32_t) * (frm_nodes + 1), hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipMemcpyAsync(d_f_items, frm_items, sizeof(int32_t) * nfi, hipMemcpyHostToDevice, s));
-    // keypoints (angle, octave) and descriptors of either side: resident (a frame / keyframe handle) or uploaded per call
-    const ovs_keypoint* d_kf_kps = w->d_q_kps;
-    const uint8_t* d_kf_desc = w->d_q_desc;
-    const ovs_keypoint* d_frm_kps = w->d_t_kps;
-    const uint8_t* d_frm_desc = w->d_t_desc;
-    if (res_kf) {
-        d_kf_kps = res_kf->d_kps;
-        d_kf_desc = res_kf->d_desc;
-    } else {
-        OVS_HIP_TRY(hipMemcpyAsync(w->d_q_kps, kf_kps, sizeof(ovs_keypoint) * n_kf, hipMemcpyHostToDevice, s));
-        OVS_HIP_TRY(hipMemcpyAsync(w->d_q_desc, kf_desc, (size_t)32 * n_kf, hipMemcpyHostToDevice, s));
-    }
-    if (kf_valid) OVS_HIP_TRY(hipMemcpyAsync(w->d_q_flag, kf_valid, (size_t)n_kf, hipMemcpyHostToDevice, s));
-    if (res_frm) {
-        d_frm_kps = res_frm->d_kps;
-        d_frm_desc = res_frm->d_desc;
-    } else {
-        OVS_HIP_TRY(hipMemcpyAsync(w->d_t_kps, frm_kps, sizeof(ovs_keypoint) * n_frm, hipMemcpyHostToDevice, s));
-        OVS_HIP_TRY(hipMemcpyAsync(w->d_t_desc, frm_desc, (size_t)32 * n_frm, hipMemcpyHostToDevice, s));
-    }
-    if (frm_valid) OVS_HIP_TRY(hipMemcpyAsync(w->d_t_flag, frm_valid, (size_t)n_frm, hipMemcpyHostToDevice, s));
-    BowArgs a{};
-    a.kf_desc = d_kf_desc;
-    a.kf_valid = kf_valid ? w->d_q_flag : nullptr;
-    a.kf_node_ids = d_kf_ids;
-    a.kf_node_start = d_kf_start;
-    a.kf_items = d_kf_items;
-    a.kf_nodes = kf_nodes;
-    a.n_q = nq;
-    a.frm_desc = d_frm_desc;
-    a.frm_valid = frm_valid ? w->d_t_flag : nullptr;
-    if (tri) {
-        a.tri = 1;
-        a.kf_kps = d_kf_kps;
-        // bearings and stereo_x_right: from the handle when it carries them (ovs_frame_dev_attach_bearings), else uploaded
-        if (res_kf && res_kf->d_bearings) {
-            a.kf_bearings = res_kf->d_bearings;
-        } else {
-            if (!tri->bearings_1) return OVS_ERR_INVALID;
-            OVS_HIP_TRY(hipMemcpyAsync(w->d_tri_b1, tri->bearings_1, sizeof(double) * 3 * n_kf, hipMemcpyHostToDevice, s));
-            a.kf_bearings = w->d_tri_b1;
-        }
-        if (res_frm && res_frm->d_bearings) {
-            a.frm_bearings = res_frm->d_bearings;
-        } else {
-            if (!tri->bearings_2) return OVS_ERR_INVALID;
-            OVS_HIP_TRY(hipMemcpyAsync(w->d_tri_b2, tri->bearings_2, sizeof(double) * 3 * n_frm, hipMemcpyHostToDevice, s));
-            a.frm_bearings = w->d_tri_b2;
-        }
-        if (res_kf) {
-            a.kf_x_right = res_kf->has_stereo ? res_kf->d_x_right : nullptr;
-        } else if (tri->x_right_1) {
-            OVS_HIP_TRY(hipMemcpyAsync(w->d_q_f, tri->x_right_1, sizeof(float) * n_kf, hipMemcpyHostToDevice, s));
-            a.kf_x_right = w->d_q_f;
-        }
-        if (res_frm) {
-            a.frm_x_right = res_frm->has_stereo ? res_frm->d_x_right : nullptr;
-        } else if (tri->x_right_2) {
-            OVS_HIP_TRY(hipMemcpyAsync(w->d_t_f, tri->x_right_2, sizeof(float) * n_frm, hipMemcpyHostToDevice, s));
-            a.frm_x_right = w->d_t_f;
-        }
-        std::memcpy(a.E, tri->E_12, sizeof(double) * 9);
-        std::memcpy(a.epipole, tri->epipole_in_2, sizeof(double) * 3);
-        for (int l = 0; l < OVS_MAX_LEVELS; ++l) a.sf[l] = l < tri->num_levels ? tri->scale_factors[l] : 1.0f;
-    }
-    a.frm_node_ids = d_f_ids;
-    a.frm_node_start = d_f_start;
-    a.frm_items = d_f_items;
-    a.frm_nodes = frm_nodes;
-    a.dead_from = tri ? 0u : dead_from_ratio(OVS_HAMMING_DIST_THR_LOW, lowe_ratio);
-    ovs_status st = build_lists(w, a, nq, k_bow_lists<false>, k_bow_lists<true>, s, 256);
-    if (st != OVS_OK) return st;
-    ResolveArgs ra{};
-    ra.offsets = w->d_offsets;
-    ra.keys = w->d_keys;
-    ra.n_q = nq;
-    ra.n_t = n_frm;
-    ra.lowe_ratio = lowe_ratio;
-    ra.check_orientation = check_orientation;
-    ra.q_kps = d_kf_kps;
-    ra.q_items = d_kf_items;
-    ra.t_kps = d_frm_kps;
-    ra.assigned = w->d_assigned;
-    ra.num_matches = w->d_num;
-    ra.bow_by_query = by_query;
-    ra.n_out_q = n_kf;
-    ra.best_only_thr = OVS_HAMMING_DIST_THR_LOW;
-    st = tri ? launch_resolve<kRuleTriang>(ra, s) : launch_resolve<kRuleBow>(ra, s);
-    if (st != OVS_OK) return st;
-    uint32_t overflow = 0;
-    OVS_HIP_TRY(hipMemcpyAsync(matched_kf_in_frm, w->d_assigned, sizeof(int32_t) * n_out, hipMemcpyDeviceToHost, s));
-    OVS_HIP_TRY(hipMemcpyAsync(num_matches, w->d_num, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    OVS_HIP_TRY(hipMemcpyAsync(&overflow, w->d_overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    OVS_HIP_TRY(hipStreamSynchronize(s));
-    if (!overflow) w->overflow_dirty = false;
-    return overflow ? OVS_ERR_CAPACITY : OVS_OK;
-}
-
-
-extern "C" {
-
-ovs_status ovs_bow_match_frame_and_keyframe(ovs_wmatcher* w, const ovs_keypoint* kf_kps, const uint8_t* kf_desc, const uint8_t* kf_valid,
-                                            int32_t n_kf, const int32_t* kf_node_ids, const int32_t* kf_node_start,
-                                            const int32_t* kf_items, int32_t kf_nodes, const ovs_keypoint* frm_kps,
-                                            const uint8_t* frm_desc, int32_t n_frm, const int32_t* frm_node_ids,
-                                            const int32_t* frm_node_start, const int32_t* frm_items, int32_t frm_nodes, float lowe_ratio,
-                                            int32_t check_orientation, int32_t* matched_kf_in_frm, int32_t* num_matches) {
-    return bow_match_impl(w, nullptr, nullptr, 0, nullptr, nullptr, kf_kps, kf_desc, kf_valid, n_kf, kf_node_ids, kf_node_start, kf_items, kf_nodes, frm_kps, frm_desc, n_frm,
-                          frm_node_ids, frm_node_start, frm_items, frm_nodes, lowe_ratio, check_orientation, matched_kf_in_frm, num_matches);
-}
-
-ovs_status ovs_bow_match_keyframes(ovs_wmatcher* w, const ovs_keypoint* kps_1, const uint8_t* desc_1, const uint8_t* valid_1, int32_t n1,
-                                   const int32_t* node_ids_1, const int32_t* node_start_1, const int32_t* items_1, int32_t nodes_1,
-                                   const ovs_keypoint* kps_2, const uint8_t* desc_2, const uint8_t* valid_2, int32_t n2,
-                                   const int32_t* node_ids_2, const int32_t* node_start_2, const int32_t* items_2, int32_t nodes_2,
-                                   float lowe_ratio, int32_t check_orientation, int32_t* matched_2_in_1, int32_t* num_matches) {
-    return bow_match_impl(w, nullptr, nullptr, 1, valid_2, nullptr, kps_1, desc_1, valid_1, n1, node_ids_1, node_start_1, items_1, nodes_1, kps_2, desc_2, n2, node_ids_2,
-                          node_start_2, items_2, nodes_2, lowe_ratio, check_orientation, matched_2_in_1, num_matches);
-}
-
-ovs_status ovs_robust_match_for_triangulation(ovs_wmatcher* w, const ovs_keypoint* kps_1, const uint8_t* desc_1, const uint8_t* has_lm_1,
-                                              const float* x_right_1, const double* bearings_1, int32_t n1, const int32_t* node_ids_1,
-                                              const int32_t* node_start_1, const int32_t* items_1, int32_t nodes_1,
-                                              const ovs_keypoint* kps_2, const uint8_t* desc_2, const uint8_t* has_lm_2,
-                                              const float* x_right_2, const double* bearings_2, int32_t n2, const int32_t* node_ids_2,
-                                              const int32_t* node_start_2, const int32_t* items_2, int32_t nodes_2, const double* E_12,
-                                              const double* epipole_in_2, const float* scale_factors, int32_t num_levels,
-                                              int32_t check_orientation, int32_t* matched_2_in_1, int32_t* num_matches) {
-    if (!bearings_1 || !bearings_2 || !E_12 || !epipole_in_2 || !scale_factors || num_levels < 1 || num_levels > OVS_MAX_LEVELS || n1 < 0 || n2 < 0)
-        return OVS_ERR_INVALID;
-    // "valid" for the bow kernels = the keypoint has NO landmark yet
-    std::vector<uint8_t> v1((size_t)std::max(n1, 1), 1), v2((size_t)std::max(n2, 1), 1);
-    if (has_lm_1)
-        for (int i = 0; i < n1; ++i) v1[i] = has_lm_1[i] ? 0 : 1;
-    if (has_lm_2)
-        for (int i = 0; i < n2; ++i) v2[i] = has_lm_2[i] ? 0 : 1;
-    TriParams tp{x_right_1, x_right_2, bearings_1, bearings_2, E_12, epipole_in_2, scale_factors, num_levels};
-    return bow_match_impl(w, nullptr, nullptr, 1, v2.data(), &tp, kps_1, desc_1, v1.data(), n1, node_ids_1, node_start_1, items_1, nodes_1, kps_2, desc_2, n2,
-                          node_ids_2, node_start_2, items_2, nodes_2, 0.0f, check_orientation, matched_2_in_1, num_matches);
-}
-
-ovs_status ovs_projection_match_current_and_last_frames(ovs_wmatcher* w, const ovs_camera* cam, const ovs_grid_params* gp,
-                                                        const ovs_keypoint* curr_kps, const uint8_t* curr_desc,
-                                                        const float* curr_stereo_x_right, const uint8_t* curr_occupied, int32_t n_curr,
-                                                        const double* pose_cw_curr, const ovs_keypoint* last_kps, const double* last_pos_w,
-                                                        const uint8_t* last_lm_desc, const uint8_t* last_valid, int32_t n_last,
-                                                        const double* pose_cw_last, const float* scale_factors, int32_t num_levels,
-                                                        float margin, int32_t check_orientation, int32_t* assigned, int32_t* num_matches) {
-    if (!w || !cam || !gp || !num_matches || n_curr < 0 || n_last < 0 || !pose_cw_curr || !pose_cw_last || !scale_factors || num_levels < 1 ||
-        num_levels > OVS_MAX_LEVELS || (cam->model != 0 && cam->model != 1))
-        return OVS_ERR_INVALID;
-    *num_matches = 0;
-    if (n_last == 0) return OVS_OK;
-    if (!assigned) return OVS_ERR_INVALID;
-    for (int i = 0; i < n_last; ++i) assigned[i] = -1;
-    if (n_curr == 0) return OVS_OK;
-    if (!curr_kps || !curr_desc || !last_kps || !last_pos_w || !last_lm_desc) return OVS_ERR_INVALID;
-    if (n_curr > w->max_t || n_last > w->max_q) return OVS_ERR_CAPACITY;
-    OVS_HIP_TRY(hipSetDevice(w->device));
-    hipStream_t s = w->stream;
-    // motion direction (host, double): trans_wc = -rot_cw^T trans_cw; trans_lc = rot_lw trans_wc + trans_lw
-    const double* Rc = pose_cw_curr;
-    const double* tc = pose_cw_curr + 9;
-    const double twc[3] = {-((Rc[0] * tc[0] + Rc[3] * tc[1]) + Rc[6] * tc[2]), -((Rc[1] * tc[0] + Rc[4] * tc[1]) + Rc[7] * tc[2]),
-                           -((Rc[2] * tc[0] + Rc[5] * tc[1]) + Rc[8] * tc[2])};
-    const double* Rl = pose_cw_last;
-    const double tlc_z = ((Rl[6] * twc[0] + Rl[7] * twc[1]) + Rl[8] * twc[2]) + pose_cw_last[11];
-    const int forward = cam->setup == 0 ? 0 : (tlc_z > cam->true_baseline);
-    const int backward = cam->setup == 0 ? 0 : (-tlc_z > cam->true_baseline);
-    CamP cp{};
-    cp.model = cam->model;
-    cp.setup = cam->setup;
-    cp.fx = cam->fx;
-    cp.fy = cam->fy;
-    cp.cx = cam->cx;
-    cp.cy = cam->cy;
-    cp.fxb = cam->focal_x_baseline;
-    cp.cols = cam->cols;
-    cp.rows = cam->rows;
-    cp.min_x = gp->min_x;
-    cp.min_y = gp->min_y;
-    cp.max_x = gp->max_x;
-    cp.max_y = gp->max_y;
-    std::memcpy(cp.P, pose_cw_curr, sizeof(double) * 12);
-    OVS_HIP_TRY(hipMemcpyAsync(w->d_t_kps, curr_kps, sizeof(ovs_keypoint) * n_curr, hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipMemcpyAsync(w->d_t_desc, curr_desc, (size_t)32 * n_curr, hipMemcpyHostToDevice, s));
-    if (curr_stereo_x_right) OVS_HIP_TRY(hipMemcpyAsync(w->d_t_f, curr_stereo_x_right, sizeof(float) * n_curr, hipMemcpyHostToDevice, s));
-    if (curr_occupied) OVS_HIP_TRY(hipMemcpyAsync(w->d_t_flag, curr_occupied, (size_t)n_curr, hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipMemcpyAsync(w->d_q_kps, last_kps, sizeof(ovs_keypoint) * n_last, hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipMemcpyAsync(w->d_q_pos, last_pos_w, sizeof(double) * 3 * n_last, hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipMemcpyAsync(w->d_q_desc, last_lm_desc, (size_t)32 * n_last, hipMemcpyHostToDevice, s));
-    uint8_t* d_last_valid = nullptr;
-    if (last_valid) {   // staged behind the query flags (the kernel writes q_valid in place: same index, read-then-write by one lane)
-        OVS_HIP_TRY(hipMemcpyAsync(w->d_q_flag, last_valid, (size_t)n_last, hipMemcpyHostToDevice, s));
-        d_last_valid = w->d_q_flag;
-    }
-    float sf16[OVS_MAX_LEVELS];
-    for (int l = 0; l < OVS_MAX_LEVELS; ++l) sf16[l] = l < num_levels ? scale_factors[l] : 1.0f;
-    OVS_HIP_TRY(hipMemcpyAsync(w->d_sf, sf16, sizeof(sf16), hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipStreamSynchronize(s));   // sf16 is a stack array
-    ovs_status st = grid_assign(w, gp, w->d_t_kps, n_curr, s);
-    if (st != OVS_OK) return st;
-    hipLaunchKernelGGL(k_reproject_queries, dim3((n_last + 255) / 256), dim3(256), 0, s, cp, (const ovs_keypoint*)w->d_q_kps,
-                       (const double*)w->d_q_pos, (const uint8_t*)d_last_valid, n_last, margin, (const float*)w->d_sf, num_levels, forward,
-                       backward, (const float*)nullptr, 0.0, 0.0, 0.0, 0.0f, w->d_q_xy, w->d_q_f, w->d_q_r, w->d_q_i, w->d_q_i2, w->d_q_flag);
-    OVS_HIP_TRY(hipGetLastError());
-    WinArgs a{};
-    a.t_kps = w->d_t_kps;
-    a.t_desc = w->d_t_desc;
-    a.t_occupied = curr_occupied ? w->d_t_flag : nullptr;
-    a.t_x_right = curr_stereo_x_right ? w->d_t_f : nullptr;
-    a.cell_start = w->d_cell_start;
-    a.items = w->d_items;
-    a.gp = w->gp;
-    a.n_q = n_last;
-    a.q_xy = w->d_q_xy;
-    a.q_x_right = w->d_q_f;
-    a.q_valid = w->d_q_flag;
-    a.q_radius = w->d_q_r;
-    a.q_minl = w->d_q_i;
-    a.q_maxl = w->d_q_i2;
-    a.q_desc = w->d_q_desc;
-    a.margin = margin;
-    a.mode = kModeGeneric;
-    a.dead_from = dead_from_thr(OVS_HAMMING_DIST_THR_HIGH);
-    st = build_lists(w, a, n_last, k_window_lists<false>, k_window_lists<true>, s);
-    if (st != OVS_OK) return st;
-    ResolveArgs ra{};
-    ra.offsets = w->d_offsets;
-    ra.keys = w->d_keys;
-    ra.n_q = n_last;
-    ra.n_t = n_curr;
-    ra.check_orientation = check_orientation;
-    ra.q_kps = w->d_q_kps;
-    ra.t_kps = w->d_t_kps;
-    ra.assigned = w->d_assigned;
-    ra.num_matches = w->d_num;
-    ra.best_only_thr = OVS_HAMMING_DIST_THR_HIGH;
-    st = launch_resolve<kRuleBestOnly>(ra, s);
-    if (st != OVS_OK) return st;
-    uint32_t overflow = 0;
-    OVS_HIP_TRY(hipMemcpyAsync(assigned, w->d_assigned, sizeof(int32_t) * n_last, hipMemcpyDeviceToHost, s));
-    OVS_HIP_TRY(hipMemcpyAsync(num_matches, w->d_num, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    OVS_HIP_TRY(hipMemcpyAsync(&overflow, w->d_overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    OVS_HIP_TRY(hipStreamSynchronize(s));
-    if (!overflow) w->overflow_dirty = false;
-    return overflow ? OVS_ERR_CAPACITY : OVS_OK;
-}
-
-static ovs_status fuse_replace_duplication_impl(ovs_wmatcher* w, const ovs_frame_dev* res, const ovs_camera* cam, const ovs_grid_params* gp, const ovs_keypoint* kps,
-                                        const uint8_t* desc, const float* stereo_x_right, int32_t n, const double* pose_cw,
-                                        const double* lm_pos_w, const float* lm_dist_min_max, const double* lm_normal,
-                                        const uint8_t* lm_desc, const uint8_t* lm_valid, int32_t m, const float* scale_factors,
-                                        const float* inv_level_sigma_sq, int32_t num_levels, float log_scale_factor, float margin,
-                                        int32_t* best_idx, int32_t* num_fused) {
-    if (!w || !cam || !gp || !num_fused || n < 0 || m < 0 || !pose_cw || !scale_factors || !inv_level_sigma_sq || num_levels < 1 ||
-        num_levels > OVS_MAX_LEVELS || (cam->model != 0 && cam->model != 1))
-        return OVS_ERR_INVALID;
-    *num_fused = 0;
-    if (m == 0) return OVS_OK;
-    if (!best_idx) return OVS_ERR_INVALID;
-    for (int i = 0; i < m; ++i) best_idx[i] = -1;
-    if (n == 0) return OVS_OK;
-    if ((!res && (!kps || !desc)) || !lm_pos_w || !lm_dist_min_max || !lm_normal || !lm_desc) return OVS_ERR_INVALID;
-    if (n > w->max_t || m > w->max_q) return OVS_ERR_CAPACITY;
-    OVS_HIP_TRY(hipSetDevice(w->device));
-    hipStream_t s = w->stream;
-    FuseArgs a{};
-    a.cam.model = cam->model;
-    a.cam.setup = cam->setup;
-    a.cam.fx = cam->fx;
-    a.cam.fy = cam->fy;
-    a.cam.cx = cam->cx;
-    a.cam.cy = cam->cy;
-    a.cam.fxb = cam->focal_x_baseline;
-    a.cam.cols = cam->cols;
-    a.cam.rows = cam->rows;
-    a.cam.min_x = gp->min_x;
-    a.cam.min_y = gp->min_y;
-    a.cam.max_x = gp->max_x;
-    a.cam.max_y = gp->max_y;
-    std::memcpy(a.cam.P, pose_cw, sizeof(double) * 12);
-    const double* R = pose_cw;
-    const double* t = pose_cw + 9;
-    a.cc[0] = -((R[0] * t[0] + R[3] * t[1]) + R[6] * t[2]);
-    a.cc[1] = -((R[1] * t[0] + R[4] * t[1]) + R[7] * t[2]);
-    a.cc[2] = -((R[2] * t[0] + R[5] * t[1]) + R[8] * t[2]);
-    for (int l = 0; l < OVS_MAX_LEVELS; ++l) {
-        a.sf[l] = l < num_levels ? scale_factors[l] : 1.0f;
-        a.ils[l] = l < num_levels ? inv_level_sigma_sq[l] : 1.0f;
-    }
-    a.num_levels = num_levels;
-    a.log_scale_factor = log_scale_factor;
-    a.margin = margin;
-    a.m = m;
-    // the landmark side: five host arrays through the context's pinned buffer, ONE copy up (five pageable hipMemcpyAsync cost more than the kernel)
-    Stager stg(w);
-    a.lm_pos_w = stg.put(lm_pos_w, (size_t)3 * m);
-    a.lm_normal = stg.put(lm_normal, (size_t)3 * m);
-    a.lm_dist = stg.put(lm_dist_min_max, (size_t)2 * m);
-    a.lm_desc = stg.put(lm_desc, (size_t)32 * m);
-    a.lm_valid = stg.put(lm_valid, (size_t)m);
-    if (stg.overflow) return OVS_ERR_CAPACITY;
-    OVS_HIP_TRY(stg.flush(s));
-    TargetRef tg;
-    ovs_status st = stage_target(w, res, gp, kps, desc, stereo_x_right, n, s, &tg);
-    if (st != OVS_OK) return st;
-    a.t_kps = tg.kps;
-    a.t_desc = tg.desc;
-    a.t_x_right = tg.x_right;
-    a.cell_start = tg.cell_start;
-    a.items = tg.items;
-    a.gp = tg.gp;
-    a.variant = kFuseReplace;
-    a.max_dist = OVS_HAMMING_DIST_THR_LOW;
-    OVS_HIP_TRY(hipMemsetAsync(w->d_num, 0, sizeof(int32_t), s));
-    hipLaunchKernelGGL(k_fuse_best, dim3((unsigned)(((size_t)m * kFuseLanes + 255) / 256)), dim3(256), 0, s, a, w->d_assigned, w->d_num);
-    OVS_HIP_TRY(hipGetLastError());
-    return fetch_results(w, m, best_idx, num_fused, s, false);   // one copy down through the pinned mirror
-}
-
-static ovs_status projection_match_frame_and_keyframe_impl(ovs_wmatcher* w, const ovs_frame_dev* res, const ovs_camera* cam, const ovs_grid_params* gp,
-                                                   const ovs_keypoint* curr_kps, const uint8_t* curr_desc, const uint8_t* curr_occupied,
-                                                   int32_t n_curr, const double* pose_cw_curr, const ovs_keypoint* kf_kps,
-                                                   const double* kf_pos_w, const float* kf_dist_min_max, const uint8_t* kf_lm_desc,
-                                                   const uint8_t* kf_valid, int32_t n_kf, const float* scale_factors, int32_t num_levels,
-                                                   float log_scale_factor, float margin, uint32_t hamm_dist_thr, int32_t check_orientation,
-                                                   int32_t* assigned, int32_t* num_matches) {
-    if (!w || !cam || !gp || !num_matches || n_curr < 0 || n_kf < 0 || !pose_cw_curr || !scale_factors || num_levels < 1 ||
-        num_levels > OVS_MAX_LEVELS || (cam->model != 0 && cam->model != 1))
-        return OVS_ERR_INVALID;
-    *num_matches = 0;
-    if (n_kf == 0) return OVS_OK;
-    if (!assigned) return OVS_ERR_INVALID;
-    for (int i = 0; i < n_kf; ++i) assigned[i] = -1;
-    if (n_curr == 0) return OVS_OK;
-    if ((!res && (!curr_kps || !curr_desc)) || !kf_kps || !kf_pos_w || !kf_dist_min_max || !kf_lm_desc) return OVS_ERR_INVALID;
-    if (n_curr > w->max_t || n_kf > w->max_q) return OVS_ERR_CAPACITY;
-    if ((size_t)n_kf * 2 * sizeof(float) > (size_t)w->max_entries * sizeof(uint32_t)) return OVS_ERR_CAPACITY;
-    OVS_HIP_TRY(hipSetDevice(w->device));
-    hipStream_t s = w->stream;
-    CamP cp{};
-    cp.model = cam->model;
-    cp.setup = cam->setup;
-    cp.fx = cam->fx;
-    cp.fy = cam->fy;
-    cp.cx = cam->cx;
-    cp.cy = cam->cy;
-    cp.fxb = cam->focal_x_baseline;
-    cp.cols = cam->cols;
-    cp.rows = cam->rows;
-    cp.min_x = gp->min_x;
-    cp.min_y = gp->min_y;
-    cp.max_x = gp->max_x;
-    cp.max_y = gp->max_y;
-    std::memcpy(cp.P, pose_cw_curr, sizeof(double) * 12);
-    const double* R = pose_cw_curr;
-    const double* t = pose_cw_curr + 9;
-    const double ccx = -((R[0] * t[0] + R[3] * t[1]) + R[6] * t[2]), ccy = -((R[1] * t[0] + R[4] * t[1]) + R[7] * t[2]),
-                 ccz = -((R[2] * t[0] + R[5] * t[1]) + R[8] * t[2]);
-    float* d_dist = reinterpret_cast<float*>(w->d_keys);   // consumed by k_reproject_queries before the key buffer is written
-    if (curr_occupied) OVS_HIP_TRY(hipMemcpyAsync(w->d_t_flag, curr_occupied, (size_t)n_curr, hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipMemcpyAsync(w->d_q_kps, kf_kps, sizeof(ovs_keypoint) * n_kf, hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipMemcpyAsync(w->d_q_pos, kf_pos_w, sizeof(double) * 3 * n_kf, hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipMemcpyAsync(d_dist, kf_dist_min_max, sizeof(float) * 2 * n_kf, hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipMemcpyAsync(w->d_q_desc, kf_lm_desc, (size_t)32 * n_kf, hipMemcpyHostToDevice, s));
-    uint8_t* d_valid = nullptr;
-    if (kf_valid) {
-        OVS_HIP_TRY(hipMemcpyAsync(w->d_q_flag, kf_valid, (size_t)n_kf, hipMemcpyHostToDevice, s));
-        d_valid = w->d_q_flag;
-    }
-    float sf16[OVS_MAX_LEVELS];
-    for (int l = 0; l < OVS_MAX_LEVELS; ++l) sf16[l] = l < num_levels ? scale_factors[l] : 1.0f;
-    OVS_HIP_TRY(hipMemcpyAsync(w->d_sf, sf16, sizeof(sf16), hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipStreamSynchronize(s));   // sf16 is a stack array
-    TargetRef tg;
-    ovs_status st = stage_target(w, res, gp, curr_kps, curr_desc, nullptr, n_curr, s, &tg);
-    if (st != OVS_OK) return st;
-    hipLaunchKernelGGL(k_reproject_queries, dim3((n_kf + 255) / 256), dim3(256), 0, s, cp, (const ovs_keypoint*)w->d_q_kps,
-                       (const double*)w->d_q_pos, (const uint8_t*)d_valid, n_kf, margin, (const float*)w->d_sf, num_levels, 0, 0,
-                       (const float*)d_dist, ccx, ccy, ccz, log_scale_factor, w->d_q_xy, w->d_q_f, w->d_q_r, w->d_q_i, w->d_q_i2, w->d_q_flag);
-    OVS_HIP_TRY(hipGetLastError());
-    WinArgs a{};
-    a.t_kps = tg.kps;
-    a.t_desc = tg.desc;
-    a.t_occupied = curr_occupied ? w->d_t_flag : nullptr;
-    a.cell_start = tg.cell_start;
-    a.items = tg.items;
-    a.gp = tg.gp;
-    a.n_q = n_kf;
-    a.q_xy = w->d_q_xy;
-    a.q_x_right = w->d_q_f;
-    a.q_valid = w->d_q_flag;
-    a.q_radius = w->d_q_r;
-    a.q_minl = w->d_q_i;
-    a.q_maxl = w->d_q_i2;
-    a.q_desc = w->d_q_desc;
-    a.margin = margin;
-    a.mode = kModeGeneric;
-    a.dead_from = dead_from_thr((uint32_t)hamm_dist_thr);
-    st = build_lists(w, a, n_kf, k_window_lists<false>, k_window_lists<true>, s);
-    if (st != OVS_OK) return st;
-    ResolveArgs ra{};
-    ra.offsets = w->d_offsets;
-    ra.keys = w->d_keys;
-    ra.n_q = n_kf;
-    ra.n_t = n_curr;
-    ra.check_orientation = check_orientation;
-    ra.q_kps = w->d_q_kps;
-    ra.t_kps = tg.kps;
-    ra.assigned = w->d_assigned;
-    ra.num_matches = w->d_num;
-    ra.best_only_thr = hamm_dist_thr;
-    st = launch_resolve<kRuleBestOnly>(ra, s);
-    if (st != OVS_OK) return st;
-    uint32_t overflow = 0;
-    OVS_HIP_TRY(hipMemcpyAsync(assigned, w->d_assigned, sizeof(int32_t) * n_kf, hipMemcpyDeviceToHost, s));
-    OVS_HIP_TRY(hipMemcpyAsync(num_matches, w->d_num, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    OVS_HIP_TRY(hipMemcpyAsync(&overflow, w->d_overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    OVS_HIP_TRY(hipStreamSynchronize(s));
-    if (!overflow) w->overflow_dirty = false;
-    return overflow ? OVS_ERR_CAPACITY : OVS_OK;
-}
-
-namespace {
 void fill_cam(CamP& cp, const ovs_camera* cam, const ovs_grid_params* gp, const double* P) {
     cp.model = cam->model;
     cp.setup = cam->setup;
@@ -1978,25 +1238,390 @@ void fill_cam(CamP& cp, const ovs_camera* cam, const ovs_grid_params* gp, const 
     cp.max_y = gp->max_y;
     std::memcpy(cp.P, P, sizeof(double) * 12);
 }
+// camera centre -R^T t of the pose P = [R | t] (9 + 3 doubles, row-major R)
+void camera_centre(const double* P, double* cc) {
+    cc[0] = -((P[0] * P[9] + P[3] * P[10]) + P[6] * P[11]);
+    cc[1] = -((P[1] * P[9] + P[4] * P[10]) + P[7] * P[11]);
+    cc[2] = -((P[2] * P[9] + P[5] * P[10]) + P[8] * P[11]);
+}
 // Sim3_cw = [s R | t'] -> scale s = |first row of sR|, rot_cw = sR / s, trans_cw = t' / s, camera centre -R^T t (upstream decomposes the
 // 4x4 the same way in fuse::detect_duplication / projection::match_by_Sim3_transform)
 void decompose_sim3(const double* S, double* P, double* cc) {
     const double sc = std::sqrt((S[0] * S[0] + S[1] * S[1]) + S[2] * S[2]);
     for (int i = 0; i < 9; ++i) P[i] = S[i] / sc;
     for (int i = 0; i < 3; ++i) P[9 + i] = S[9 + i] / sc;
-    cc[0] = -((P[0] * P[9] + P[3] * P[10]) + P[6] * P[11]);
-    cc[1] = -((P[1] * P[9] + P[4] * P[10]) + P[7] * P[11]);
-    cc[2] = -((P[2] * P[9] + P[5] * P[10]) + P[8] * P[11]);
+    camera_centre(P, cc);
 }
-}   // namespace
+// the per-level tables the kernels index up to OVS_MAX_LEVELS: `src` (nullptr: none) for the levels in use, `fill` beyond
+void pad_levels(float* dst, const float* src, int num_levels, float fill) {
+    for (int l = 0; l < OVS_MAX_LEVELS; ++l) dst[l] = (src && l < num_levels) ? src[l] : fill;
+}
+// match_current_and_last_frames (stereo / RGBD only): trans_wc = -rot_cw^T trans_cw; trans_lc = rot_lw trans_wc + trans_lw; its z against the baseline
+void motion_direction(const ovs_camera* cam, const double* pose_cw_curr, const double* pose_cw_last, int* forward, int* backward) {
+    double twc[3];
+    camera_centre(pose_cw_curr, twc);
+    const double* Rl = pose_cw_last;
+    const double tlc_z = ((Rl[6] * twc[0] + Rl[7] * twc[1]) + Rl[8] * twc[2]) + pose_cw_last[11];
+    *forward = cam->setup == 0 ? 0 : (tlc_z > cam->true_baseline);
+    *backward = cam->setup == 0 ? 0 : (-tlc_z > cam->true_baseline);
+}
+// robust::match_for_triangulation: "valid" for the bow kernels = the keypoint has NO landmark yet
+std::vector<uint8_t> no_landmark_mask(const uint8_t* has_lm, int n) {
+    std::vector<uint8_t> v((size_t)std::max(n, 1), 1);
+    if (has_lm)
+        for (int i = 0; i < n; ++i) v[i] = has_lm[i] ? 0 : 1;
+    return v;
+}
 
-static ovs_status fuse_detect_duplication_impl(ovs_wmatcher* w, const ovs_frame_dev* res, const ovs_camera* cam, const ovs_grid_params* gp, const ovs_keypoint* kps,
-                                       const uint8_t* desc, int32_t n, const double* sim3_cw, const double* lm_pos_w,
-                                       const float* lm_dist_min_max, const double* lm_normal, const uint8_t* lm_desc, const uint8_t* lm_valid,
-                                       int32_t m, const float* scale_factors, int32_t num_levels, float log_scale_factor, float margin,
-                                       int32_t* best_idx, int32_t* num_found) {
-    if (!w || !cam || !gp || !num_found || n < 0 || m < 0 || !sim3_cw || !scale_factors || num_levels < 1 || num_levels > OVS_MAX_LEVELS ||
+// what k_reproject_queries writes per query, in the staging arena
+struct QueryScratch {
+    const uint8_t* valid_in;   // the caller's flags (nullptr: every query), read ...
+    uint8_t* valid;            // ... and written in place: same index, read-then-write by one lane
+    float *xy, *x_right, *radius;
+    int32_t *minl, *maxl;
+};
+QueryScratch reserve_queries(Stager& stg, const uint8_t* valid, int n) {
+    QueryScratch q{};
+    q.valid = valid ? const_cast<uint8_t*>(stg.put(valid, (size_t)n)) : stg.reserve<uint8_t>((size_t)n);
+    q.valid_in = valid ? q.valid : nullptr;
+    q.xy = stg.reserve<float>((size_t)2 * n);
+    q.x_right = stg.reserve<float>((size_t)n);
+    q.radius = stg.reserve<float>((size_t)n);
+    q.minl = stg.reserve<int32_t>((size_t)n);
+    q.maxl = stg.reserve<int32_t>((size_t)n);
+    return q;
+}
+// kModeGeneric: reprojected queries with their own radius and level window against a target's grid
+WinArgs generic_window_args(const TargetRef& t, bool stereo, const uint8_t* d_occupied, const QueryScratch& q, const uint8_t* d_q_desc, int n_q, float margin,
+                            uint32_t dead_from) {
+    WinArgs a{};
+    a.t_kps = t.kps;
+    a.t_desc = t.desc;
+    a.t_occupied = d_occupied;
+    a.t_x_right = stereo ? t.x_right : nullptr;
+    a.cell_start = t.cell_start;
+    a.items = t.items;
+    a.gp = t.gp;
+    a.n_q = n_q;
+    a.q_xy = q.xy;
+    a.q_x_right = q.x_right;
+    a.q_valid = q.valid;
+    a.q_radius = q.radius;
+    a.q_minl = q.minl;
+    a.q_maxl = q.maxl;
+    a.q_desc = d_q_desc;
+    a.margin = margin;
+    a.mode = kModeGeneric;
+    a.dead_from = dead_from;
+    return a;
+}
+// lists and the best-only resolver over reprojected queries, results down: the tail of the three kModeGeneric matchers
+ovs_status generic_match(ovs_wmatcher* w, const WinArgs& a, int n_t, const ovs_keypoint* d_query_kps, int check_orientation, uint32_t thr, int32_t* assigned,
+                         int32_t* num_matches, hipStream_t s) {
+    ovs_status st = build_lists(w, a, a.n_q, k_window_lists<false>, k_window_lists<true>, s);
+    if (st != OVS_OK) return st;
+    ResolveArgs ra = resolve_args(w, a.n_q, n_t);
+    ra.check_orientation = check_orientation;
+    ra.q_kps = d_query_kps;
+    ra.t_kps = a.t_kps;
+    ra.best_only_thr = thr;
+    st = launch_resolve<kRuleBestOnly>(ra, s);
+    if (st != OVS_OK) return st;
+    return fetch_results(w, a.n_q, assigned, num_matches, s);
+}
+
+// projection::match_frame_and_landmarks on device arrays: lists and resolver into the given device outputs
+ovs_status frame_and_landmarks_on_device(ovs_wmatcher* w, const TargetRef& t, const uint8_t* d_occupied, int n, const float* d_lm_xy, const float* d_lm_x_right,
+                                         const int32_t* d_lm_level, const uint8_t* d_lm_desc, const uint8_t* d_lm_valid, int m, const float* scale_factors,
+                                         int num_levels, float margin, float lowe_ratio, int32_t* d_assigned, int32_t* d_num_matches, hipStream_t s) {
+    WinArgs a{};
+    a.t_kps = t.kps;
+    a.t_desc = t.desc;
+    a.t_occupied = d_occupied;
+    a.t_x_right = t.x_right;
+    a.cell_start = t.cell_start;
+    a.items = t.items;
+    a.gp = t.gp;
+    a.n_q = m;
+    a.q_xy = d_lm_xy;
+    a.q_x_right = d_lm_x_right;
+    a.q_level = d_lm_level;
+    a.q_valid = d_lm_valid;
+    a.q_desc = d_lm_desc;
+    a.margin = margin;
+    pad_levels(a.sf, scale_factors, num_levels, 1.0f);
+    a.mode = kModeProjection;
+    a.dead_from = dead_from_ratio(OVS_HAMMING_DIST_THR_HIGH, lowe_ratio);
+    const ovs_status st = build_lists(w, a, m, k_window_lists<false>, k_window_lists<true>, s);
+    if (st != OVS_OK) return st;
+    ResolveArgs ra = resolve_args(w, m, n);
+    ra.lowe_ratio = lowe_ratio;
+    ra.assigned = d_assigned;
+    ra.num_matches = d_num_matches;
+    return launch_resolve<kRuleProjection>(ra, s);
+}
+
+// area::match_in_consistent_area on device arrays; d_prev_matched_xy is read AND updated by the resolver
+ovs_status area_on_device(ovs_wmatcher* w, const ovs_keypoint* d_kps_1, const uint8_t* d_desc_1, int n1, const TargetRef& t2, int n2, float* d_prev_matched_xy,
+                          int32_t* d_matched_2_in_1, int margin, float lowe_ratio, int check_orientation, int32_t* d_num_matches, hipStream_t s) {
+    WinArgs a{};
+    a.t_kps = t2.kps;
+    a.t_desc = t2.desc;
+    a.cell_start = t2.cell_start;
+    a.items = t2.items;
+    a.gp = t2.gp;
+    a.n_q = n1;
+    a.q_xy = d_prev_matched_xy;
+    a.q_kps = d_kps_1;
+    a.q_desc = d_desc_1;
+    a.margin = (float)margin;
+    a.mode = kModeArea;
+    a.dead_from = dead_from_ratio(OVS_HAMMING_DIST_THR_LOW, lowe_ratio);
+    const ovs_status st = build_lists(w, a, n1, k_window_lists<false>, k_window_lists<true>, s);
+    if (st != OVS_OK) return st;
+    ResolveArgs ra = resolve_args(w, n1, n2);
+    ra.lowe_ratio = lowe_ratio;
+    ra.check_orientation = check_orientation;
+    ra.q_kps = d_kps_1;
+    ra.t_kps = t2.kps;
+    ra.prev_matched_xy = d_prev_matched_xy;
+    ra.assigned = d_matched_2_in_1;
+    ra.num_matches = d_num_matches;
+    return launch_resolve<kRuleArea>(ra, s);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// One implementation per matcher. Each serves the host-array entry point and its resident twin (_f): `res` is the frame / keyframe handle
+// of the twin (then the host arrays of that side are nullptr and gp is the handle's), or nullptr. A frame's matcher-side data --
+// undistorted keypoints, descriptors, stereo_x_right and the keypoint grid -- is uploaded and indexed ONCE per handle; what travels per call
+// is what changes per call: the landmark side and the flags, through the Stager (one copy up), and the result block (one copy down).
+// ---------------------------------------------------------------------------------------------------------------------------
+
+ovs_status projection_match_frame_and_landmarks_impl(ovs_wmatcher* w, const ovs_frame_dev* res, const ovs_grid_params* gp, const ovs_keypoint* kps,
+                                                     const uint8_t* desc, const float* stereo_x_right, const uint8_t* occupied, int32_t n, const float* lm_xy,
+                                                     const float* lm_x_right, const int32_t* lm_level, const uint8_t* lm_desc, const uint8_t* lm_valid, int32_t m,
+                                                     const float* scale_factors, int32_t num_levels, float margin, float lowe_ratio, int32_t* assigned,
+                                                     int32_t* num_matches) {
+    if (!w || !num_matches || n < 0 || m < 0 || !scale_factors || num_levels < 1 || num_levels > OVS_MAX_LEVELS) return OVS_ERR_INVALID;
+    *num_matches = 0;
+    if (m == 0) return OVS_OK;
+    if (!assigned) return OVS_ERR_INVALID;
+    if (n == 0) {
+        for (int i = 0; i < m; ++i) assigned[i] = -1;
+        return OVS_OK;
+    }
+    const bool stereo = res ? res->has_stereo : stereo_x_right != nullptr;
+    if ((!res && (!kps || !desc)) || !lm_xy || !lm_level || !lm_desc || (stereo && !lm_x_right)) return OVS_ERR_INVALID;
+    Stager stg(w);
+    TargetRef tg;
+    ovs_status st = stage_target(w, stg, res, kps, desc, stereo_x_right, nullptr, n, &tg);
+    if (st != OVS_OK) return st;
+    if (n > w->max_t || m > w->max_q) return OVS_ERR_CAPACITY;
+    OVS_HIP_TRY(hipSetDevice(w->device));
+    hipStream_t s = w->stream;
+    const uint8_t* d_occupied = stg.put(occupied, (size_t)n);
+    const float* d_lm_xy = stg.put(lm_xy, (size_t)2 * m);
+    const float* d_lm_x_right = stereo ? stg.put(lm_x_right, (size_t)m) : nullptr;
+    const int32_t* d_lm_level = stg.put(lm_level, (size_t)m);
+    const uint8_t* d_lm_valid = stg.put(lm_valid, (size_t)m);
+    const uint8_t* d_lm_desc = stg.put(lm_desc, (size_t)32 * m);
+    if ((st = stg.flush(s)) != OVS_OK || (st = index_target(w, gp, n, &tg, s)) != OVS_OK) return st;
+    st = frame_and_landmarks_on_device(w, tg, d_occupied, n, d_lm_xy, d_lm_x_right, d_lm_level, d_lm_desc, d_lm_valid, m, scale_factors, num_levels, margin,
+                                       lowe_ratio, w->d_assigned, w->d_num, s);
+    if (st != OVS_OK) return st;
+    return fetch_results(w, m, assigned, num_matches, s);
+}
+
+ovs_status area_match_in_consistent_area_impl(ovs_wmatcher* w, const ovs_frame_dev* res_1, const ovs_frame_dev* res_2, const ovs_grid_params* gp,
+                                              const ovs_keypoint* kps_1, const uint8_t* desc_1, int32_t n1, const ovs_keypoint* kps_2, const uint8_t* desc_2,
+                                              int32_t n2, float* prev_matched_xy, int32_t* matched_2_in_1, int32_t margin, float lowe_ratio,
+                                              int32_t check_orientation, int32_t* num_matches) {
+    if (!w || !num_matches || n1 < 0 || n2 < 0) return OVS_ERR_INVALID;
+    *num_matches = 0;
+    if (n1 == 0) return OVS_OK;
+    if ((!res_1 && (!kps_1 || !desc_1)) || !prev_matched_xy || !matched_2_in_1) return OVS_ERR_INVALID;
+    if (n2 == 0) {
+        for (int i = 0; i < n1; ++i) matched_2_in_1[i] = -1;
+        return OVS_OK;
+    }
+    if (!res_2 && (!kps_2 || !desc_2)) return OVS_ERR_INVALID;
+    Stager stg(w);
+    // prev_matched_pts are read AND updated by the resolver: they live in the staging arena (first: offset 0) and come back with their own copy
+    float* d_prev = const_cast<float*>(stg.put(prev_matched_xy, (size_t)2 * n1));
+    TargetRef f1, f2;
+    ovs_status st = stage_target(w, stg, res_1, kps_1, desc_1, nullptr, nullptr, n1, &f1);
+    if (st == OVS_OK) st = stage_target(w, stg, res_2, kps_2, desc_2, nullptr, nullptr, n2, &f2);
+    if (st != OVS_OK) return st;
+    if (n2 > w->max_t || n1 > w->max_q) return OVS_ERR_CAPACITY;
+    OVS_HIP_TRY(hipSetDevice(w->device));
+    hipStream_t s = w->stream;
+    if ((st = stg.flush(s)) != OVS_OK || (st = index_target(w, gp, n2, &f2, s)) != OVS_OK) return st;
+    st = area_on_device(w, f1.kps, f1.desc, n1, f2, n2, d_prev, w->d_assigned, margin, lowe_ratio, check_orientation, w->d_num, s);
+    if (st != OVS_OK) return st;
+    OVS_HIP_TRY(hipMemcpyAsync(w->h_stage, d_prev, sizeof(float) * 2 * (size_t)n1, hipMemcpyDeviceToHost, s));
+    st = fetch_results(w, n1, matched_2_in_1, num_matches, s);
+    if (st != OVS_ERR_HIP) std::memcpy(prev_matched_xy, w->h_stage, sizeof(float) * 2 * (size_t)n1);   // only behind fetch_results' synchronisation
+    return st;
+}
+
+ovs_status projection_match_current_and_last_frames_impl(ovs_wmatcher* w, const ovs_frame_dev* res, const ovs_camera* cam, const ovs_grid_params* gp,
+                                                         const ovs_keypoint* curr_kps, const uint8_t* curr_desc, const float* curr_stereo_x_right,
+                                                         const uint8_t* curr_occupied, int32_t n_curr, const double* pose_cw_curr, const ovs_keypoint* last_kps,
+                                                         const double* last_pos_w, const uint8_t* last_lm_desc, const uint8_t* last_valid, int32_t n_last,
+                                                         const double* pose_cw_last, const float* scale_factors, int32_t num_levels, float margin,
+                                                         int32_t check_orientation, int32_t* assigned, int32_t* num_matches) {
+    if (!w || !cam || !gp || !num_matches || n_curr < 0 || n_last < 0 || !pose_cw_curr || !pose_cw_last || !scale_factors || num_levels < 1 ||
+        num_levels > OVS_MAX_LEVELS || (cam->model != 0 && cam->model != 1))
+        return OVS_ERR_INVALID;
+    *num_matches = 0;
+    if (n_last == 0) return OVS_OK;
+    if (!assigned) return OVS_ERR_INVALID;
+    for (int i = 0; i < n_last; ++i) assigned[i] = -1;
+    if (n_curr == 0) return OVS_OK;
+    if ((!res && (!curr_kps || !curr_desc)) || !last_kps || !last_pos_w || !last_lm_desc) return OVS_ERR_INVALID;
+    Stager stg(w);
+    TargetRef tg;
+    ovs_status st = stage_target(w, stg, res, curr_kps, curr_desc, curr_stereo_x_right, nullptr, n_curr, &tg);
+    if (st != OVS_OK) return st;
+    if (n_curr > w->max_t || n_last > w->max_q) return OVS_ERR_CAPACITY;
+    OVS_HIP_TRY(hipSetDevice(w->device));
+    hipStream_t s = w->stream;
+    int forward, backward;
+    motion_direction(cam, pose_cw_curr, pose_cw_last, &forward, &backward);
+    CamP cp{};
+    fill_cam(cp, cam, gp, pose_cw_curr);
+    float sf16[OVS_MAX_LEVELS];
+    pad_levels(sf16, scale_factors, num_levels, 1.0f);
+    const uint8_t* d_occupied = stg.put(curr_occupied, (size_t)n_curr);
+    const ovs_keypoint* d_query_kps = stg.put(last_kps, (size_t)n_last);
+    const double* d_q_pos = stg.put(last_pos_w, (size_t)3 * n_last);
+    const uint8_t* d_q_desc = stg.put(last_lm_desc, (size_t)32 * n_last);
+    const float* d_scale = stg.put(sf16, (size_t)OVS_MAX_LEVELS);
+    const QueryScratch q = reserve_queries(stg, last_valid, n_last);
+    if ((st = stg.flush(s)) != OVS_OK || (st = index_target(w, gp, n_curr, &tg, s)) != OVS_OK) return st;
+    hipLaunchKernelGGL(k_reproject_queries, dim3((n_last + 255) / 256), dim3(256), 0, s, cp, d_query_kps, d_q_pos, q.valid_in, n_last, margin, d_scale, num_levels, forward,
+                       backward, (const float*)nullptr, 0.0, 0.0, 0.0, 0.0f, q.xy, q.x_right, q.radius, q.minl, q.maxl, q.valid);
+    OVS_HIP_TRY(hipGetLastError());
+    const WinArgs a = generic_window_args(tg, true, d_occupied, q, d_q_desc, n_last, margin, dead_from_thr(OVS_HAMMING_DIST_THR_HIGH));
+    return generic_match(w, a, n_curr, d_query_kps, check_orientation, OVS_HAMMING_DIST_THR_HIGH, assigned, num_matches, s);
+}
+
+ovs_status projection_match_frame_and_keyframe_impl(ovs_wmatcher* w, const ovs_frame_dev* res, const ovs_camera* cam, const ovs_grid_params* gp,
+                                                    const ovs_keypoint* curr_kps, const uint8_t* curr_desc, const uint8_t* curr_occupied, int32_t n_curr,
+                                                    const double* pose_cw_curr, const ovs_keypoint* kf_kps, const double* kf_pos_w, const float* kf_dist_min_max,
+                                                    const uint8_t* kf_lm_desc, const uint8_t* kf_valid, int32_t n_kf, const float* scale_factors,
+                                                    int32_t num_levels, float log_scale_factor, float margin, uint32_t hamm_dist_thr, int32_t check_orientation,
+                                                    int32_t* assigned, int32_t* num_matches) {
+    if (!w || !cam || !gp || !num_matches || n_curr < 0 || n_kf < 0 || !pose_cw_curr || !scale_factors || num_levels < 1 ||
+        num_levels > OVS_MAX_LEVELS || (cam->model != 0 && cam->model != 1))
+        return OVS_ERR_INVALID;
+    *num_matches = 0;
+    if (n_kf == 0) return OVS_OK;
+    if (!assigned) return OVS_ERR_INVALID;
+    for (int i = 0; i < n_kf; ++i) assigned[i] = -1;
+    if (n_curr == 0) return OVS_OK;
+    if ((!res && (!curr_kps || !curr_desc)) || !kf_kps || !kf_pos_w || !kf_dist_min_max || !kf_lm_desc) return OVS_ERR_INVALID;
+    if (n_curr > w->max_t || n_kf > w->max_q) return OVS_ERR_CAPACITY;
+    OVS_HIP_TRY(hipSetDevice(w->device));
+    hipStream_t s = w->stream;
+    CamP cp{};
+    fill_cam(cp, cam, gp, pose_cw_curr);
+    double cc[3];
+    camera_centre(pose_cw_curr, cc);
+    float sf16[OVS_MAX_LEVELS];
+    pad_levels(sf16, scale_factors, num_levels, 1.0f);
+    Stager stg(w);
+    const uint8_t* d_occupied = stg.put(curr_occupied, (size_t)n_curr);
+    const ovs_keypoint* d_query_kps = stg.put(kf_kps, (size_t)n_kf);
+    const double* d_q_pos = stg.put(kf_pos_w, (size_t)3 * n_kf);
+    const float* d_q_dist = stg.put(kf_dist_min_max, (size_t)2 * n_kf);
+    const uint8_t* d_q_desc = stg.put(kf_lm_desc, (size_t)32 * n_kf);
+    const float* d_scale = stg.put(sf16, (size_t)OVS_MAX_LEVELS);
+    const QueryScratch q = reserve_queries(stg, kf_valid, n_kf);
+    TargetRef tg;
+    ovs_status st = stage_target(w, stg, res, curr_kps, curr_desc, nullptr, nullptr, n_curr, &tg);
+    if (st != OVS_OK || (st = stg.flush(s)) != OVS_OK || (st = index_target(w, gp, n_curr, &tg, s)) != OVS_OK) return st;
+    hipLaunchKernelGGL(k_reproject_queries, dim3((n_kf + 255) / 256), dim3(256), 0, s, cp, d_query_kps, d_q_pos, q.valid_in, n_kf, margin, d_scale, num_levels, 0, 0,
+                       d_q_dist, cc[0], cc[1], cc[2], log_scale_factor, q.xy, q.x_right, q.radius, q.minl, q.maxl, q.valid);
+    OVS_HIP_TRY(hipGetLastError());
+    const WinArgs a = generic_window_args(tg, false, d_occupied, q, d_q_desc, n_kf, margin, dead_from_thr(hamm_dist_thr));
+    return generic_match(w, a, n_curr, d_query_kps, check_orientation, hamm_dist_thr, assigned, num_matches, s);
+}
+
+ovs_status projection_match_by_sim3_transform_impl(ovs_wmatcher* w, const ovs_frame_dev* res, const ovs_camera* cam, const ovs_grid_params* gp,
+                                                   const ovs_keypoint* kps, const uint8_t* desc, const uint8_t* occupied, int32_t n, const double* sim3_cw,
+                                                   const double* lm_pos_w, const float* lm_dist_min_max, const double* lm_normal, const uint8_t* lm_desc,
+                                                   const uint8_t* lm_valid, int32_t m, const float* scale_factors, int32_t num_levels, float log_scale_factor,
+                                                   float margin, int32_t* assigned, int32_t* num_matches) {
+    if (!w || !cam || !gp || !num_matches || n < 0 || m < 0 || !sim3_cw || !scale_factors || num_levels < 1 || num_levels > OVS_MAX_LEVELS ||
         (cam->model != 0 && cam->model != 1))
+        return OVS_ERR_INVALID;
+    *num_matches = 0;
+    if (m == 0) return OVS_OK;
+    if (!assigned) return OVS_ERR_INVALID;
+    for (int i = 0; i < m; ++i) assigned[i] = -1;
+    if (n == 0) return OVS_OK;
+    if ((!res && (!kps || !desc)) || !lm_pos_w || !lm_dist_min_max || !lm_normal || !lm_desc) return OVS_ERR_INVALID;
+    if (n > w->max_t || m > w->max_q) return OVS_ERR_CAPACITY;
+    OVS_HIP_TRY(hipSetDevice(w->device));
+    hipStream_t s = w->stream;
+    CamP cp{};
+    double P[12], cc[3];
+    decompose_sim3(sim3_cw, P, cc);
+    fill_cam(cp, cam, gp, P);
+    float sf16[OVS_MAX_LEVELS];
+    pad_levels(sf16, scale_factors, num_levels, 1.0f);
+    Stager stg(w);
+    const uint8_t* d_occupied = stg.put(occupied, (size_t)n);
+    const double* d_q_pos = stg.put(lm_pos_w, (size_t)3 * m);
+    const float* d_q_dist = stg.put(lm_dist_min_max, (size_t)2 * m);
+    const double* d_q_normal = stg.put(lm_normal, (size_t)3 * m);
+    const uint8_t* d_q_desc = stg.put(lm_desc, (size_t)32 * m);
+    const float* d_scale = stg.put(sf16, (size_t)OVS_MAX_LEVELS);
+    const QueryScratch q = reserve_queries(stg, lm_valid, m);
+    TargetRef tg;
+    ovs_status st = stage_target(w, stg, res, kps, desc, nullptr, nullptr, n, &tg);
+    if (st != OVS_OK || (st = stg.flush(s)) != OVS_OK || (st = index_target(w, gp, n, &tg, s)) != OVS_OK) return st;
+    hipLaunchKernelGGL(k_reproject_queries, dim3((m + 255) / 256), dim3(256), 0, s, cp, (const ovs_keypoint*)nullptr, d_q_pos, q.valid_in, m, margin, d_scale,
+                       num_levels, 0, 0, d_q_dist, cc[0], cc[1], cc[2], log_scale_factor, q.xy, q.x_right, q.radius, q.minl, q.maxl, q.valid, d_q_normal, 0);
+    OVS_HIP_TRY(hipGetLastError());
+    const WinArgs a = generic_window_args(tg, false, d_occupied, q, d_q_desc, m, margin, dead_from_thr(OVS_HAMMING_DIST_THR_LOW));
+    return generic_match(w, a, n, nullptr, 0, OVS_HAMMING_DIST_THR_LOW, assigned, num_matches, s);
+}
+
+// the landmark side of a k_fuse_best launch: host arrays through the Stager
+void stage_fuse_landmarks(Stager& stg, FuseArgs& a, const double* lm_pos_w, const double* lm_normal, const float* lm_dist_min_max, const uint8_t* lm_desc,
+                          const uint8_t* lm_valid, int m) {
+    a.m = m;
+    a.lm_pos_w = stg.put(lm_pos_w, (size_t)3 * m);
+    a.lm_normal = stg.put(lm_normal, (size_t)3 * m);
+    a.lm_dist = stg.put(lm_dist_min_max, (size_t)2 * m);
+    a.lm_desc = stg.put(lm_desc, (size_t)32 * m);
+    a.lm_valid = stg.put(lm_valid, (size_t)m);
+}
+// k_fuse_best of `a.m` landmarks against an indexed target
+ovs_status launch_fuse_best(FuseArgs& a, const TargetRef& t, bool stereo, int32_t* d_best, int32_t* d_num, hipStream_t s) {
+    a.t_kps = t.kps;
+    a.t_desc = t.desc;
+    a.t_x_right = stereo ? t.x_right : nullptr;
+    a.cell_start = t.cell_start;
+    a.items = t.items;
+    a.gp = t.gp;
+    hipLaunchKernelGGL(k_fuse_best, dim3((unsigned)(((size_t)a.m * kFuseLanes + 255) / 256)), dim3(256), 0, s, a, d_best, d_num);
+    OVS_HIP_TRY(hipGetLastError());
+    return OVS_OK;
+}
+
+// fuse::replace_duplication (kFuseReplace: pose_cw, chi-square gate with inv_level_sigma_sq, stereo) and fuse::detect_duplication (kFuseDetect: `pose` is
+// Sim3_cw, no inv_level_sigma_sq, monocular)
+ovs_status fuse_duplication_impl(ovs_wmatcher* w, const ovs_frame_dev* res, int variant, const ovs_camera* cam, const ovs_grid_params* gp, const ovs_keypoint* kps,
+                                 const uint8_t* desc, const float* stereo_x_right, int32_t n, const double* pose, const double* lm_pos_w,
+                                 const float* lm_dist_min_max, const double* lm_normal, const uint8_t* lm_desc, const uint8_t* lm_valid, int32_t m,
+                                 const float* scale_factors, const float* inv_level_sigma_sq, int32_t num_levels, float log_scale_factor, float margin,
+                                 int32_t* best_idx, int32_t* num_found) {
+    const bool replace = variant == kFuseReplace;
+    if (!w || !cam || !gp || !num_found || n < 0 || m < 0 || !pose || !scale_factors || (replace && !inv_level_sigma_sq) || num_levels < 1 ||
+        num_levels > OVS_MAX_LEVELS || (cam->model != 0 && cam->model != 1))
         return OVS_ERR_INVALID;
     *num_found = 0;
     if (m == 0) return OVS_OK;
@@ -2008,178 +1633,40 @@ static ovs_status fuse_detect_duplication_impl(ovs_wmatcher* w, const ovs_frame_
     OVS_HIP_TRY(hipSetDevice(w->device));
     hipStream_t s = w->stream;
     FuseArgs a{};
-    double P[12];
-    decompose_sim3(sim3_cw, P, a.cc);
-    fill_cam(a.cam, cam, gp, P);
-    for (int l = 0; l < OVS_MAX_LEVELS; ++l) {
-        a.sf[l] = l < num_levels ? scale_factors[l] : 1.0f;
-        a.ils[l] = 1.0f;
+    if (replace) {
+        fill_cam(a.cam, cam, gp, pose);
+        camera_centre(pose, a.cc);
+    } else {
+        double P[12];
+        decompose_sim3(pose, P, a.cc);
+        fill_cam(a.cam, cam, gp, P);
     }
+    pad_levels(a.sf, scale_factors, num_levels, 1.0f);
+    pad_levels(a.ils, replace ? inv_level_sigma_sq : nullptr, num_levels, 1.0f);
     a.num_levels = num_levels;
     a.log_scale_factor = log_scale_factor;
     a.margin = margin;
-    a.m = m;
-    a.variant = kFuseDetect;
+    a.variant = variant;
     a.max_dist = OVS_HAMMING_DIST_THR_LOW;
-    Stager stg(w);   // the landmark side through the pinned buffer: one copy up
-    a.lm_pos_w = stg.put(lm_pos_w, (size_t)3 * m);
-    a.lm_normal = stg.put(lm_normal, (size_t)3 * m);
-    a.lm_dist = stg.put(lm_dist_min_max, (size_t)2 * m);
-    a.lm_desc = stg.put(lm_desc, (size_t)32 * m);
-    a.lm_valid = stg.put(lm_valid, (size_t)m);
-    if (stg.overflow) return OVS_ERR_CAPACITY;
-    OVS_HIP_TRY(stg.flush(s));
+    Stager stg(w);
+    stage_fuse_landmarks(stg, a, lm_pos_w, lm_normal, lm_dist_min_max, lm_desc, lm_valid, m);
     TargetRef tg;
-    ovs_status st = stage_target(w, res, gp, kps, desc, nullptr, n, s, &tg);
-    if (st != OVS_OK) return st;
-    a.t_kps = tg.kps;
-    a.t_desc = tg.desc;
-    a.cell_start = tg.cell_start;
-    a.items = tg.items;
-    a.gp = tg.gp;
+    ovs_status st = stage_target(w, stg, res, kps, desc, stereo_x_right, nullptr, n, &tg);
+    if (st != OVS_OK || (st = stg.flush(s)) != OVS_OK || (st = index_target(w, gp, n, &tg, s)) != OVS_OK) return st;
     OVS_HIP_TRY(hipMemsetAsync(w->d_num, 0, sizeof(int32_t), s));
-    hipLaunchKernelGGL(k_fuse_best, dim3((unsigned)(((size_t)m * kFuseLanes + 255) / 256)), dim3(256), 0, s, a, w->d_assigned, w->d_num);
-    OVS_HIP_TRY(hipGetLastError());
+    st = launch_fuse_best(a, tg, replace, w->d_assigned, w->d_num, s);
+    if (st != OVS_OK) return st;
     return fetch_results(w, m, best_idx, num_found, s, false);
 }
 
-static ovs_status projection_match_by_sim3_transform_impl(ovs_wmatcher* w, const ovs_frame_dev* res, const ovs_camera* cam, const ovs_grid_params* gp, const ovs_keypoint* kps,
-                                                  const uint8_t* desc, const uint8_t* occupied, int32_t n, const double* sim3_cw,
-                                                  const double* lm_pos_w, const float* lm_dist_min_max, const double* lm_normal,
-                                                  const uint8_t* lm_desc, const uint8_t* lm_valid, int32_t m, const float* scale_factors,
-                                                  int32_t num_levels, float log_scale_factor, float margin, int32_t* assigned,
-                                                  int32_t* num_matches) {
-    if (!w || !cam || !gp || !num_matches || n < 0 || m < 0 || !sim3_cw || !scale_factors || num_levels < 1 || num_levels > OVS_MAX_LEVELS ||
-        (cam->model != 0 && cam->model != 1))
-        return OVS_ERR_INVALID;
-    *num_matches = 0;
-    if (m == 0) return OVS_OK;
-    if (!assigned) return OVS_ERR_INVALID;
-    for (int i = 0; i < m; ++i) assigned[i] = -1;
-    if (n == 0) return OVS_OK;
-    if ((!res && (!kps || !desc)) || !lm_pos_w || !lm_dist_min_max || !lm_normal || !lm_desc) return OVS_ERR_INVALID;
-    if (n > w->max_t || m > w->max_q) return OVS_ERR_CAPACITY;
-    // (min, max) distances then the normals ride in the key buffer; both are consumed before the lists are written
-    if ((size_t)m * (2 * sizeof(float) + 3 * sizeof(double)) > (size_t)w->max_entries * sizeof(uint32_t)) return OVS_ERR_CAPACITY;
-    OVS_HIP_TRY(hipSetDevice(w->device));
-    hipStream_t s = w->stream;
-    CamP cp{};
-    double P[12], cc[3];
-    decompose_sim3(sim3_cw, P, cc);
-    fill_cam(cp, cam, gp, P);
-    float* d_dist = reinterpret_cast<float*>(w->d_keys);
-    double* d_normal = reinterpret_cast<double*>(d_dist + 2 * (size_t)m);
-    if (occupied) OVS_HIP_TRY(hipMemcpyAsync(w->d_t_flag, occupied, (size_t)n, hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipMemcpyAsync(w->d_q_pos, lm_pos_w, sizeof(double) * 3 * m, hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipMemcpyAsync(d_dist, lm_dist_min_max, sizeof(float) * 2 * m, hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipMemcpyAsync(d_normal, lm_normal, sizeof(double) * 3 * m, hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipMemcpyAsync(w->d_q_desc, lm_desc, (size_t)32 * m, hipMemcpyHostToDevice, s));
-    uint8_t* d_valid = nullptr;
-    if (lm_valid) {
-        OVS_HIP_TRY(hipMemcpyAsync(w->d_q_flag, lm_valid, (size_t)m, hipMemcpyHostToDevice, s));
-        d_valid = w->d_q_flag;
-    }
-    float sf16[OVS_MAX_LEVELS];
-    for (int l = 0; l < OVS_MAX_LEVELS; ++l) sf16[l] = l < num_levels ? scale_factors[l] : 1.0f;
-    OVS_HIP_TRY(hipMemcpyAsync(w->d_sf, sf16, sizeof(sf16), hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipStreamSynchronize(s));   // sf16 is a stack array
-    TargetRef tg;
-    ovs_status st = stage_target(w, res, gp, kps, desc, nullptr, n, s, &tg);
-    if (st != OVS_OK) return st;
-    hipLaunchKernelGGL(k_reproject_queries, dim3((m + 255) / 256), dim3(256), 0, s, cp, (const ovs_keypoint*)nullptr, (const double*)w->d_q_pos,
-                       (const uint8_t*)d_valid, m, margin, (const float*)w->d_sf, num_levels, 0, 0, (const float*)d_dist, cc[0], cc[1], cc[2],
-                       log_scale_factor, w->d_q_xy, w->d_q_f, w->d_q_r, w->d_q_i, w->d_q_i2, w->d_q_flag, (const double*)d_normal, 0);
-    OVS_HIP_TRY(hipGetLastError());
-    WinArgs a{};
-    a.t_kps = tg.kps;
-    a.t_desc = tg.desc;
-    a.t_occupied = occupied ? w->d_t_flag : nullptr;
-    a.cell_start = tg.cell_start;
-    a.items = tg.items;
-    a.gp = tg.gp;
-    a.n_q = m;
-    a.q_xy = w->d_q_xy;
-    a.q_x_right = w->d_q_f;
-    a.q_valid = w->d_q_flag;
-    a.q_radius = w->d_q_r;
-    a.q_minl = w->d_q_i;
-    a.q_maxl = w->d_q_i2;
-    a.q_desc = w->d_q_desc;
-    a.margin = margin;
-    a.mode = kModeGeneric;
-    a.dead_from = dead_from_thr(OVS_HAMMING_DIST_THR_LOW);
-    st = build_lists(w, a, m, k_window_lists<false>, k_window_lists<true>, s);
-    if (st != OVS_OK) return st;
-    ResolveArgs ra{};
-    ra.offsets = w->d_offsets;
-    ra.keys = w->d_keys;
-    ra.n_q = m;
-    ra.n_t = n;
-    ra.check_orientation = 0;
-    ra.q_kps = nullptr;
-    ra.t_kps = tg.kps;
-    ra.assigned = w->d_assigned;
-    ra.num_matches = w->d_num;
-    ra.best_only_thr = OVS_HAMMING_DIST_THR_LOW;
-    st = launch_resolve<kRuleBestOnly>(ra, s);
-    if (st != OVS_OK) return st;
-    uint32_t overflow = 0;
-    OVS_HIP_TRY(hipMemcpyAsync(assigned, w->d_assigned, sizeof(int32_t) * m, hipMemcpyDeviceToHost, s));
-    OVS_HIP_TRY(hipMemcpyAsync(num_matches, w->d_num, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    OVS_HIP_TRY(hipMemcpyAsync(&overflow, w->d_overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    OVS_HIP_TRY(hipStreamSynchronize(s));
-    if (!overflow) w->overflow_dirty = false;
-    return overflow ? OVS_ERR_CAPACITY : OVS_OK;
-}
-
-// one direction of match_keyframes_mutually: the landmarks of keyframe A (pose P_a, world positions) against the keypoints of keyframe B
-static ovs_status mutual_pass(ovs_wmatcher* w, const ovs_frame_dev* res_b, const ovs_camera* cam_b, const ovs_grid_params* gp_b, const ovs_keypoint* kps_b,
-                              const uint8_t* desc_b, int n_b, const double* pose_cw_a, const double* sim_ba, const double* lm_pos_w_a,
-                              const float* lm_dist_a, const uint8_t* lm_desc_a, const uint8_t* lm_valid_a, int n_a, const float* scale_factors,
-                              int num_levels, float log_scale_factor, float margin, int32_t* d_out, hipStream_t s) {
-    FuseArgs a{};
-    fill_cam(a.cam, cam_b, gp_b, sim_ba);
-    std::memcpy(a.P1, pose_cw_a, sizeof(double) * 12);
-    for (int l = 0; l < OVS_MAX_LEVELS; ++l) {
-        a.sf[l] = l < num_levels ? scale_factors[l] : 1.0f;
-        a.ils[l] = 1.0f;
-    }
-    a.num_levels = num_levels;
-    a.log_scale_factor = log_scale_factor;
-    a.margin = margin;
-    a.m = n_a;
-    a.variant = kFuseMutual;
-    a.max_dist = OVS_HAMMING_DIST_THR_HIGH;
-    OVS_HIP_TRY(hipMemcpyAsync(w->d_q_pos, lm_pos_w_a, sizeof(double) * 3 * n_a, hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipMemcpyAsync(w->d_q_xy, lm_dist_a, sizeof(float) * 2 * n_a, hipMemcpyHostToDevice, s));
-    OVS_HIP_TRY(hipMemcpyAsync(w->d_q_desc, lm_desc_a, (size_t)32 * n_a, hipMemcpyHostToDevice, s));
-    if (lm_valid_a) OVS_HIP_TRY(hipMemcpyAsync(w->d_q_flag, lm_valid_a, (size_t)n_a, hipMemcpyHostToDevice, s));
-    TargetRef tg;
-    ovs_status st = stage_target(w, res_b, gp_b, kps_b, desc_b, nullptr, n_b, s, &tg);
-    if (st != OVS_OK) return st;
-    a.t_kps = tg.kps;
-    a.t_desc = tg.desc;
-    a.cell_start = tg.cell_start;
-    a.items = tg.items;
-    a.gp = tg.gp;
-    a.lm_pos_w = w->d_q_pos;
-    a.lm_dist = w->d_q_xy;
-    a.lm_desc = w->d_q_desc;
-    a.lm_valid = lm_valid_a ? w->d_q_flag : nullptr;
-    hipLaunchKernelGGL(k_fuse_best, dim3((unsigned)(((size_t)n_a * kFuseLanes + 255) / 256)), dim3(256), 0, s, a, d_out, w->d_num + 1);   // per-direction count: scratch
-    OVS_HIP_TRY(hipGetLastError());
-    return OVS_OK;
-}
-
-static ovs_status projection_match_keyframes_mutually_impl(ovs_wmatcher* w, const ovs_frame_dev* res_1, const ovs_frame_dev* res_2, const ovs_camera* cam_1, const ovs_grid_params* gp_1,
-                                                   const ovs_keypoint* kps_1, const uint8_t* desc_1, int32_t n1, const double* pose_cw_1,
-                                                   const double* lm_pos_w_1, const float* lm_dist_1, const uint8_t* lm_desc_1,
-                                                   const uint8_t* lm_valid_1, const ovs_camera* cam_2, const ovs_grid_params* gp_2,
-                                                   const ovs_keypoint* kps_2, const uint8_t* desc_2, int32_t n2, const double* pose_cw_2,
-                                                   const double* lm_pos_w_2, const float* lm_dist_2, const uint8_t* lm_desc_2,
-                                                   const uint8_t* lm_valid_2, double s_12, const double* rot_12, const double* trans_12,
-                                                   const float* scale_factors, int32_t num_levels, float log_scale_factor, float margin,
-                                                   int32_t* matched_2_in_1, int32_t* num_matches) {
+ovs_status projection_match_keyframes_mutually_impl(ovs_wmatcher* w, const ovs_frame_dev* res_1, const ovs_frame_dev* res_2, const ovs_camera* cam_1,
+                                                    const ovs_grid_params* gp_1, const ovs_keypoint* kps_1, const uint8_t* desc_1, int32_t n1,
+                                                    const double* pose_cw_1, const double* lm_pos_w_1, const float* lm_dist_1, const uint8_t* lm_desc_1,
+                                                    const uint8_t* lm_valid_1, const ovs_camera* cam_2, const ovs_grid_params* gp_2, const ovs_keypoint* kps_2,
+                                                    const uint8_t* desc_2, int32_t n2, const double* pose_cw_2, const double* lm_pos_w_2, const float* lm_dist_2,
+                                                    const uint8_t* lm_desc_2, const uint8_t* lm_valid_2, double s_12, const double* rot_12, const double* trans_12,
+                                                    const float* scale_factors, int32_t num_levels, float log_scale_factor, float margin, int32_t* matched_2_in_1,
+                                                    int32_t* num_matches) {
     if (!w || !cam_1 || !cam_2 || !gp_1 || !gp_2 || !num_matches || n1 < 0 || n2 < 0 || !pose_cw_1 || !pose_cw_2 || !rot_12 || !trans_12 ||
         !scale_factors || num_levels < 1 || num_levels > OVS_MAX_LEVELS || (cam_1->model != 0 && cam_1->model != 1) ||
         (cam_2->model != 0 && cam_2->model != 1) || !(s_12 > 0.0))
@@ -2193,7 +1680,6 @@ static ovs_status projection_match_keyframes_mutually_impl(ovs_wmatcher* w, cons
         return OVS_ERR_INVALID;
     const int nmax = std::max(n1, n2);
     if (nmax > w->max_t || nmax > w->max_q) return OVS_ERR_CAPACITY;
-    if ((size_t)(n1 + n2) > (size_t)w->max_entries) return OVS_ERR_CAPACITY;   // the two one-way results ride in the key buffer
     OVS_HIP_TRY(hipSetDevice(w->device));
     hipStream_t s = w->stream;
     // Sim3 in both directions: [s_12 R_12 | t_12] takes keyframe-2 coordinates to keyframe 1; [R_12^T / s_12 | -(R_12^T / s_12) t_12] back
@@ -2204,36 +1690,123 @@ static ovs_status projection_match_keyframes_mutually_impl(ovs_wmatcher* w, cons
     for (int r = 0; r < 3; ++r)
         for (int c = 0; c < 3; ++c) S21[3 * r + c] = inv_s * rot_12[3 * c + r];
     for (int r = 0; r < 3; ++r) S21[9 + r] = -((S21[3 * r] * trans_12[0] + S21[3 * r + 1] * trans_12[1]) + S21[3 * r + 2] * trans_12[2]);
-    int32_t* d_2_in_1 = reinterpret_cast<int32_t*>(w->d_keys);
-    int32_t* d_1_in_2 = d_2_in_1 + n1;
-    ovs_status st = mutual_pass(w, res_2, cam_2, gp_2, kps_2, desc_2, n2, pose_cw_1, S21, lm_pos_w_1, lm_dist_1, lm_desc_1, lm_valid_1, n1, scale_factors,
-                                num_levels, log_scale_factor, margin, d_2_in_1, s);
-    if (st != OVS_OK) return st;
-    st = mutual_pass(w, res_1, cam_1, gp_1, kps_1, desc_1, n1, pose_cw_2, S12, lm_pos_w_2, lm_dist_2, lm_desc_2, lm_valid_2, n2, scale_factors, num_levels,
-                     log_scale_factor, margin, d_1_in_2, s);
-    if (st != OVS_OK) return st;
+    // two one-way searches, then the cross check. a21: the landmarks of keyframe 1 (pose 1, then S21) against the keypoints of keyframe 2; a12: the reverse
+    FuseArgs a21{}, a12{};
+    fill_cam(a21.cam, cam_2, gp_2, S21);
+    fill_cam(a12.cam, cam_1, gp_1, S12);
+    std::memcpy(a21.P1, pose_cw_1, sizeof(double) * 12);
+    std::memcpy(a12.P1, pose_cw_2, sizeof(double) * 12);
+    for (FuseArgs* a : {&a21, &a12}) {
+        pad_levels(a->sf, scale_factors, num_levels, 1.0f);
+        pad_levels(a->ils, nullptr, num_levels, 1.0f);
+        a->num_levels = num_levels;
+        a->log_scale_factor = log_scale_factor;
+        a->margin = margin;
+        a->variant = kFuseMutual;
+        a->max_dist = OVS_HAMMING_DIST_THR_HIGH;
+    }
+    Stager stg(w);   // both directions in one arena: one copy up
+    stage_fuse_landmarks(stg, a21, lm_pos_w_1, nullptr, lm_dist_1, lm_desc_1, lm_valid_1, n1);
+    stage_fuse_landmarks(stg, a12, lm_pos_w_2, nullptr, lm_dist_2, lm_desc_2, lm_valid_2, n2);
+    int32_t* d_2_in_1 = stg.reserve<int32_t>((size_t)n1);
+    int32_t* d_1_in_2 = stg.reserve<int32_t>((size_t)n2);
+    TargetRef t1, t2;
+    ovs_status st = stage_target(w, stg, res_1, kps_1, desc_1, nullptr, nullptr, n1, &t1);
+    if (st == OVS_OK) st = stage_target(w, stg, res_2, kps_2, desc_2, nullptr, nullptr, n2, &t2);
+    if (st != OVS_OK || (st = stg.flush(s)) != OVS_OK) return st;
+    // staged targets share the context's one grid: the second is indexed behind the first direction's kernel, in stream order.
+    // d_num[1] takes the per-direction counts: scratch
+    if ((st = index_target(w, gp_2, n2, &t2, s)) != OVS_OK || (st = launch_fuse_best(a21, t2, false, d_2_in_1, w->d_num + 1, s)) != OVS_OK) return st;
+    if ((st = index_target(w, gp_1, n1, &t1, s)) != OVS_OK || (st = launch_fuse_best(a12, t1, false, d_1_in_2, w->d_num + 1, s)) != OVS_OK) return st;
     OVS_HIP_TRY(hipMemsetAsync(w->d_num, 0, sizeof(int32_t), s));
-    hipLaunchKernelGGL(k_cross_check, dim3((n1 + 255) / 256), dim3(256), 0, s, (const int32_t*)d_2_in_1, (const int32_t*)d_1_in_2, n1, n2,
-                       w->d_assigned, w->d_num);
+    hipLaunchKernelGGL(k_cross_check, dim3((n1 + 255) / 256), dim3(256), 0, s, (const int32_t*)d_2_in_1, (const int32_t*)d_1_in_2, n1, n2, w->d_assigned, w->d_num);
     OVS_HIP_TRY(hipGetLastError());
-    OVS_HIP_TRY(hipMemcpyAsync(matched_2_in_1, w->d_assigned, sizeof(int32_t) * n1, hipMemcpyDeviceToHost, s));
-    OVS_HIP_TRY(hipMemcpyAsync(num_matches, w->d_num, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    OVS_HIP_TRY(hipStreamSynchronize(s));
-    return OVS_OK;
+    return fetch_results(w, n1, matched_2_in_1, num_matches, s, false);
 }
 
-}   // extern "C"
+struct TriParams {   // robust::match_for_triangulation extras (host pointers)
+    const float* x_right_1;
+    const float* x_right_2;
+    const double* bearings_1;
+    const double* bearings_2;
+    const double* E_12;
+    const double* epipole_in_2;
+    const float* scale_factors;
+    int num_levels;
+};
 
-// ---------------------------------------------------------------------------------------------------------------------------
-// Frame residency behind the class boundary (round 3): a frame's matcher-side data -- undistorted keypoints,
-// descriptors, stereo_x_right and the keypoint grid data::assign_keypoints_to_grid builds in the frame's constructor -- is uploaded and
-// indexed ONCE per frame (ovs_frame_dev), and the matchers that tracking_module calls two to four times on the same frame take the handle.
-// What remains per call is what really changes per call: the landmark side, staged through ONE pinned buffer into ONE device arena (one
-// copy up), and the result block (one copy down).
-// ---------------------------------------------------------------------------------------------------------------------------
-
-namespace {
-
+// bow_tree::match_frame_and_keyframe (by_query 0), bow_tree::match_keyframes (1) and robust::match_for_triangulation (1, tri): either side host
+// arrays or a resident frame / keyframe; the flags and the BoW feature vectors (node CSRs) always travel
+ovs_status bow_match_impl(ovs_wmatcher* w, const ovs_frame_dev* res_kf, const ovs_frame_dev* res_frm, int by_query, const uint8_t* frm_valid, const TriParams* tri,
+                          const ovs_keypoint* kf_kps, const uint8_t* kf_desc, const uint8_t* kf_valid, int32_t n_kf, const int32_t* kf_node_ids,
+                          const int32_t* kf_node_start, const int32_t* kf_items, int32_t kf_nodes, const ovs_keypoint* frm_kps, const uint8_t* frm_desc,
+                          int32_t n_frm, const int32_t* frm_node_ids, const int32_t* frm_node_start, const int32_t* frm_items, int32_t frm_nodes, float lowe_ratio,
+                          int32_t check_orientation, int32_t* matched_kf_in_frm, int32_t* num_matches) {
+    if (!w || !num_matches || n_kf < 0 || n_frm < 0 || kf_nodes < 0 || frm_nodes < 0) return OVS_ERR_INVALID;
+    *num_matches = 0;
+    const int n_out = by_query ? n_kf : n_frm;
+    if (n_out == 0) return OVS_OK;
+    if (!matched_kf_in_frm) return OVS_ERR_INVALID;
+    for (int i = 0; i < n_out; ++i) matched_kf_in_frm[i] = -1;
+    if (n_frm == 0) return OVS_OK;
+    if (n_kf == 0 || kf_nodes == 0 || frm_nodes == 0) return OVS_OK;
+    if ((!res_kf && (!kf_kps || !kf_desc)) || !kf_node_ids || !kf_node_start || !kf_items || (!res_frm && (!frm_kps || !frm_desc)) || !frm_node_ids ||
+        !frm_node_start || !frm_items)
+        return OVS_ERR_INVALID;
+    // keypoints (angle, octave), descriptors and for the triangulation matcher stereo_x_right and bearings of either side
+    Stager stg(w);
+    TargetRef kf, frm;
+    ovs_status st = stage_target(w, stg, res_kf, kf_kps, kf_desc, tri ? tri->x_right_1 : nullptr, tri ? tri->bearings_1 : nullptr, n_kf, &kf);
+    if (st == OVS_OK) st = stage_target(w, stg, res_frm, frm_kps, frm_desc, tri ? tri->x_right_2 : nullptr, tri ? tri->bearings_2 : nullptr, n_frm, &frm);
+    if (st != OVS_OK) return st;
+    const int nq = kf_node_start[kf_nodes], nfi = frm_node_start[frm_nodes];
+    if (nq == 0 || nfi == 0) return OVS_OK;
+    if (n_frm > w->max_t || n_kf > w->max_q || nq > w->max_q || (by_query && n_kf > std::max(w->max_t, w->max_q))) return OVS_ERR_CAPACITY;
+    OVS_HIP_TRY(hipSetDevice(w->device));
+    hipStream_t s = w->stream;
+    BowArgs a{};
+    a.kf_desc = kf.desc;
+    a.kf_valid = stg.put(kf_valid, (size_t)n_kf);
+    a.kf_node_ids = stg.put(kf_node_ids, (size_t)kf_nodes);
+    a.kf_node_start = stg.put(kf_node_start, (size_t)kf_nodes + 1);
+    a.kf_items = stg.put(kf_items, (size_t)nq);
+    a.kf_nodes = kf_nodes;
+    a.n_q = nq;
+    a.frm_desc = frm.desc;
+    a.frm_valid = stg.put(frm_valid, (size_t)n_frm);
+    a.frm_node_ids = stg.put(frm_node_ids, (size_t)frm_nodes);
+    a.frm_node_start = stg.put(frm_node_start, (size_t)frm_nodes + 1);
+    a.frm_items = stg.put(frm_items, (size_t)nfi);
+    a.frm_nodes = frm_nodes;
+    if ((st = stg.flush(s)) != OVS_OK) return st;   // (a feature vector beyond the arena's CSR budget: OVS_ERR_CAPACITY)
+    if (tri) {
+        if (!kf.bearings || !frm.bearings) return OVS_ERR_INVALID;
+        a.tri = 1;
+        a.kf_kps = kf.kps;
+        a.kf_bearings = kf.bearings;
+        a.frm_bearings = frm.bearings;
+        a.kf_x_right = kf.x_right;
+        a.frm_x_right = frm.x_right;
+        std::memcpy(a.E, tri->E_12, sizeof(double) * 9);
+        std::memcpy(a.epipole, tri->epipole_in_2, sizeof(double) * 3);
+        pad_levels(a.sf, tri->scale_factors, tri->num_levels, 1.0f);
+    }
+    a.dead_from = tri ? 0u : dead_from_ratio(OVS_HAMMING_DIST_THR_LOW, lowe_ratio);
+    st = build_lists(w, a, nq, k_bow_lists<false>, k_bow_lists<true>, s, 256);
+    if (st != OVS_OK) return st;
+    ResolveArgs ra = resolve_args(w, nq, n_frm);
+    ra.lowe_ratio = lowe_ratio;
+    ra.check_orientation = check_orientation;
+    ra.q_kps = kf.kps;
+    ra.q_items = a.kf_items;
+    ra.t_kps = frm.kps;
+    ra.bow_by_query = by_query;
+    ra.n_out_q = n_kf;
+    ra.best_only_thr = OVS_HAMMING_DIST_THR_LOW;
+    st = tri ? launch_resolve<kRuleTriang>(ra, s) : launch_resolve<kRuleBow>(ra, s);
+    if (st != OVS_OK) return st;
+    return fetch_results(w, n_out, matched_kf_in_frm, num_matches, s);
+}
 
 // device arenas of destroyed frame handles, kept for the next frame (a tracker creates one handle per frame: a hipMalloc / hipFree pair
 // per frame would cost more than the upload). Bounded; keyed by device and size.
@@ -2285,6 +1858,174 @@ struct FrameStage {
 
 extern "C" {
 
+ovs_status ovs_wmatcher_create(int32_t max_targets, int32_t max_queries, int32_t max_entries, int32_t device, ovs_wmatcher** out) {
+    if (!out || max_targets < 1 || max_queries < 1 || max_entries < 1 || max_targets > 65534 || max_queries > 65534) return OVS_ERR_INVALID;
+    *out = nullptr;
+    if (ovs_device_count() <= device || device < 0) return OVS_ERR_NO_DEVICE;
+    if (resolve_lds_bytes(max_queries, max_targets) > 150 * 1024) return OVS_ERR_CAPACITY;
+    ovs_wmatcher* w = new (std::nothrow) ovs_wmatcher();
+    if (!w) return OVS_ERR_INVALID;
+    w->device = device;
+    w->max_t = max_targets;
+    w->max_q = max_queries;
+    w->max_entries = (uint32_t)max_entries;
+#define CREATE_TRY(expr)                       \
+    do {                                       \
+        hipError_t _e = (expr);                \
+        if (_e != hipSuccess) {                \
+            ovs::set_last_error(#expr, _e);    \
+            ovs_wmatcher_destroy(w);           \
+            return OVS_ERR_HIP;                \
+        }                                      \
+    } while (0)
+    CREATE_TRY(hipSetDevice(device));
+    CREATE_TRY(hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking));
+    const size_t T = (size_t)max_targets, Q = (size_t)max_queries, M = std::max(T, Q);
+    CREATE_TRY(hipMalloc(&w->d_cell_of, sizeof(int32_t) * T));
+    CREATE_TRY(hipMalloc(&w->d_cell_start, sizeof(int32_t) * (kMaxGridCells + 1)));
+    CREATE_TRY(hipMalloc(&w->d_items, sizeof(int32_t) * T));
+    CREATE_TRY(hipMalloc(&w->d_counts, sizeof(uint32_t) * (Q + 1)));
+    CREATE_TRY(hipMalloc(&w->d_offsets, sizeof(uint32_t) * (Q + 1)));
+    CREATE_TRY(hipMalloc(&w->d_keys, sizeof(uint32_t) * (size_t)max_entries));
+    // result block: [0] overflow flag, [1..4] counts ([1] result count, [2] per-direction scratch count), [8..] assigned
+    CREATE_TRY(hipMalloc(&w->d_res_block, sizeof(int32_t) * (8 + M)));
+    w->d_overflow = w->d_res_block;
+    w->d_num = reinterpret_cast<int32_t*>(w->d_res_block) + 1;
+    w->d_assigned = reinterpret_cast<int32_t*>(w->d_res_block) + 8;
+    CREATE_TRY(hipMemset(w->d_res_block, 0, sizeof(int32_t) * 8));
+    CREATE_TRY(hipHostMalloc(reinterpret_cast<void**>(&w->h_res), sizeof(int32_t) * (8 + M), hipHostMallocDefault));
+    // The staging arena holds every array of ONE call, each aligned to 256 bytes, so it is sized for the entry point that stages the most with
+    // n == max_targets and m == max_queries. Which one that is depends on T : Q, hence three sums (every other entry point stages a subset of
+    // the first): the host form of projection::match_frame_and_keyframe (with the stereo_x_right that match_current_and_last_frames adds),
+    // the host form of robust::match_for_triangulation, and the host form of projection::match_keyframes_mutually (n1, n2 <= min(T, Q)).
+    const size_t N = std::min(T, Q);
+    const size_t cap_window = T * (sizeof(ovs_keypoint)    // target keypoints
+                                   + 32                    // target descriptors
+                                   + sizeof(float)         // target stereo_x_right
+                                   + 1)                    // occupied flags
+                              + Q * (sizeof(ovs_keypoint)  // query keypoints
+                                     + 3 * sizeof(double)  // world positions
+                                     + 3 * sizeof(double)  // mean normals (match_by_Sim3_transform, fuse; those stage no query keypoints: slack)
+                                     + 2 * sizeof(float)   // valid distance range
+                                     + 32                  // landmark descriptors
+                                     + 1                   // valid flags
+                                     + 2 * sizeof(float)   // k_reproject_queries: reprojection
+                                     + sizeof(float)       //   x_right
+                                     + sizeof(float)       //   search radius
+                                     + 2 * sizeof(int32_t))   //   level window
+                              + sizeof(float) * OVS_MAX_LEVELS   // padded scale factors
+                              + 15 * 256;
+    const size_t cap_bow = (T + Q) * (sizeof(ovs_keypoint)    // keypoints of either side
+                                      + 32                    // descriptors
+                                      + 1                     // valid / has-no-landmark flags
+                                      + sizeof(float)         // stereo_x_right
+                                      + 3 * sizeof(double))   // bearings
+                           + sizeof(int32_t) * (4 * (T + Q) + 16)   // the two feature vectors: ids | start | items (<= 3 n + 1 each with no empty node)
+                           + 16 * 256;
+    const size_t cap_mutual = 2 * N * (sizeof(ovs_keypoint)    // keypoints of either keyframe
+                                       + 32                    // descriptors
+                                       + 3 * sizeof(double)    // landmark positions
+                                       + 2 * sizeof(float)     // valid distance range
+                                       + 32                    // landmark descriptors
+                                       + 1                     // valid flags
+                                       + sizeof(int32_t))      // the one-way result
+                              + 14 * 256;
+    w->stage_cap = std::max(cap_window, std::max(cap_bow, cap_mutual));
+    CREATE_TRY(hipHostMalloc(reinterpret_cast<void**>(&w->h_stage), w->stage_cap, hipHostMallocDefault));
+    CREATE_TRY(hipMalloc(&w->d_stage, w->stage_cap));
+#undef CREATE_TRY
+    *out = w;
+    return OVS_OK;
+}
+
+ovs_status ovs_wmatcher_destroy(ovs_wmatcher* w) {
+    if (!w) return OVS_OK;
+    if (w->stream) hipStreamSynchronize(w->stream);
+    if (w->h_res) hipHostFree(w->h_res);
+    if (w->h_stage) hipHostFree(w->h_stage);
+    void* ptrs[] = {w->d_cell_of, w->d_cell_start, w->d_items, w->d_counts, w->d_offsets, w->d_keys, w->d_res_block, w->d_stage};
+    for (void* p : ptrs) hipFree(p);
+    if (w->stream) hipStreamDestroy(w->stream);
+    delete w;
+    return OVS_OK;
+}
+
+// ---- device-array forms (_dev): inputs and outputs in HBM, the caller's stream, nothing staged and nothing synchronised ----
+
+ovs_status ovs_grid_assign_dev(ovs_wmatcher* w, const ovs_grid_params* gp, const ovs_keypoint* d_kps, int32_t n, void* stream) {
+    if (!w || !d_kps || n < 0) return OVS_ERR_INVALID;
+    OVS_HIP_TRY(hipSetDevice(w->device));
+    return grid_assign(w, gp, d_kps, n, (hipStream_t)stream);
+}
+
+ovs_status ovs_projection_match_frame_and_landmarks_dev(ovs_wmatcher* w, const ovs_grid_params* gp, const ovs_keypoint* d_kps,
+                                                        const uint8_t* d_desc, const float* d_stereo_x_right, const uint8_t* d_occupied,
+                                                        int32_t n, const float* d_lm_xy, const float* d_lm_x_right,
+                                                        const int32_t* d_lm_level, const uint8_t* d_lm_desc, const uint8_t* d_lm_valid,
+                                                        int32_t m, const float* scale_factors, int32_t num_levels, float margin,
+                                                        float lowe_ratio, int32_t* d_assigned, int32_t* d_num_matches, void* stream) {
+    if (!w || !d_kps || !d_desc || n < 0 || m < 0 || !d_assigned || !d_num_matches || !scale_factors || num_levels < 1 ||
+        num_levels > OVS_MAX_LEVELS || (m > 0 && (!d_lm_xy || !d_lm_level || !d_lm_desc)) || (d_stereo_x_right && !d_lm_x_right))
+        return OVS_ERR_INVALID;
+    OVS_HIP_TRY(hipSetDevice(w->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (m == 0) {
+        OVS_HIP_TRY(hipMemsetAsync(d_num_matches, 0, sizeof(int32_t), s));
+        return OVS_OK;
+    }
+    TargetRef tg{d_kps, d_desc, d_stereo_x_right, nullptr, nullptr, nullptr, GridP{}};
+    const ovs_status st = index_target(w, gp, n, &tg, s);
+    if (st != OVS_OK) return st;
+    return frame_and_landmarks_on_device(w, tg, d_occupied, n, d_lm_xy, d_lm_x_right, d_lm_level, d_lm_desc, d_lm_valid, m, scale_factors, num_levels, margin,
+                                         lowe_ratio, d_assigned, d_num_matches, s);
+}
+
+ovs_status ovs_area_match_in_consistent_area_dev(ovs_wmatcher* w, const ovs_grid_params* gp, const ovs_keypoint* d_kps_1,
+                                                 const uint8_t* d_desc_1, int32_t n1, const ovs_keypoint* d_kps_2,
+                                                 const uint8_t* d_desc_2, int32_t n2, float* d_prev_matched_xy,
+                                                 int32_t* d_matched_2_in_1, int32_t margin, float lowe_ratio, int32_t check_orientation,
+                                                 int32_t* d_num_matches, void* stream) {
+    if (!w || n1 < 0 || n2 < 0 || !d_num_matches || (n1 > 0 && (!d_kps_1 || !d_desc_1 || !d_prev_matched_xy || !d_matched_2_in_1)) ||
+        (n2 > 0 && (!d_kps_2 || !d_desc_2)))
+        return OVS_ERR_INVALID;
+    OVS_HIP_TRY(hipSetDevice(w->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (n1 == 0) {
+        OVS_HIP_TRY(hipMemsetAsync(d_num_matches, 0, sizeof(int32_t), s));
+        return OVS_OK;
+    }
+    TargetRef t2{d_kps_2, d_desc_2, nullptr, nullptr, nullptr, nullptr, GridP{}};
+    const ovs_status st = index_target(w, gp, n2, &t2, s);
+    if (st != OVS_OK) return st;
+    return area_on_device(w, d_kps_1, d_desc_1, n1, t2, n2, d_prev_matched_xy, d_matched_2_in_1, margin, lowe_ratio, check_orientation, d_num_matches, s);
+}
+
+// ---- data::assign_keypoints_to_grid on its own (the matchers below build or bring their grids themselves) ----
+
+ovs_status ovs_assign_keypoints_to_grid(ovs_wmatcher* w, const ovs_grid_params* gp, const ovs_keypoint* kps, int32_t n,
+                                        int32_t* cell_start, int32_t* items, int32_t* n_items) {
+    if (!w || !gp || (n > 0 && !kps) || n < 0 || !cell_start || !n_items) return OVS_ERR_INVALID;
+    if (n > w->max_t) return OVS_ERR_CAPACITY;
+    OVS_HIP_TRY(hipSetDevice(w->device));
+    hipStream_t s = w->stream;
+    Stager stg(w);
+    const ovs_keypoint* d_kps = stg.put(kps, (size_t)n);
+    ovs_status st = stg.flush(s);
+    if (st == OVS_OK) st = grid_assign(w, gp, d_kps, n, s);
+    if (st != OVS_OK) return st;
+    const int nc = gp->cols * gp->rows;
+    OVS_HIP_TRY(hipMemcpyAsync(cell_start, w->d_cell_start, sizeof(int32_t) * (nc + 1), hipMemcpyDeviceToHost, s));
+    OVS_HIP_TRY(hipStreamSynchronize(s));
+    *n_items = cell_start[nc];
+    if (items && *n_items > 0) {
+        OVS_HIP_TRY(hipMemcpyAsync(items, w->d_items, sizeof(int32_t) * *n_items, hipMemcpyDeviceToHost, s));
+        OVS_HIP_TRY(hipStreamSynchronize(s));
+    }
+    return OVS_OK;
+}
+
+// ---- frame / keyframe handles ----
+
 ovs_status ovs_frame_dev_destroy(ovs_frame_dev* f) {
     if (!f) return OVS_OK;
     if (f->arena) g_frame_pool.give(f->device, f->arena_bytes, f->arena);
@@ -2297,7 +2038,7 @@ ovs_status ovs_frame_dev_create(int32_t device, const ovs_grid_params* gp, const
                                 const float* stereo_x_right, int32_t n, ovs_frame_dev** out) {
     if (!out || !gp || n < 0 || n > 65534 || (n > 0 && (!undist_kps || !desc))) return OVS_ERR_INVALID;
     *out = nullptr;
-    if (gp->cols < 1 || gp->rows < 1 || gp->cols * gp->rows > kMaxGridCells || !(gp->max_x > gp->min_x) || !(gp->max_y > gp->min_y)) return OVS_ERR_INVALID;
+    if (!grid_params_ok(gp)) return OVS_ERR_INVALID;
     if (ovs_device_count() <= device || device < 0) return OVS_ERR_NO_DEVICE;
     OVS_HIP_TRY(hipSetDevice(device));
     ovs_frame_dev* f = new (std::nothrow) ovs_frame_dev();
@@ -2359,13 +2100,7 @@ ovs_status ovs_frame_dev_create(int32_t device, const ovs_grid_params* gp, const
             if (stereo_x_right) std::memcpy(st.h + o_xr, stereo_x_right, 4 * (size_t)n);
             F_TRY(hipMemcpyAsync(f->arena, st.h, up_bytes, hipMemcpyHostToDevice, st.stream));
         }
-        const int in_lds = (n <= kGridItemsLds && (size_t)(2 * f->n_cells + 1 + n) * sizeof(int32_t) <= 144 * 1024) ? 1 : 0;
-        const size_t lds = (size_t)(2 * f->n_cells + 1 + (in_lds ? n : 0)) * sizeof(int32_t);
-        if (lds > 64 * 1024)
-            F_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_grid_assign), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_grid_assign, dim3(1), dim3(1024), lds, st.stream, (const ovs_keypoint*)f->d_kps, n, f->gp, f->d_cell_of, f->d_cell_start,
-                           f->d_items, in_lds);
-        F_TRY(hipGetLastError());
+        F_TRY(launch_grid_assign(f->d_kps, n, f->gp, f->d_cell_of, f->d_cell_start, f->d_items, st.stream));
         F_TRY(hipStreamSynchronize(st.stream));   // the handle is used from other streams afterwards
         rc = OVS_OK;
 #undef F_TRY
@@ -2379,244 +2114,111 @@ ovs_status ovs_frame_dev_create(int32_t device, const ovs_grid_params* gp, const
 }
 
 int32_t ovs_frame_dev_num_keypoints(const ovs_frame_dev* f) { return f ? f->n : -1; }
+int32_t ovs_frame_dev_device(const ovs_frame_dev* f) { return f ? f->device : -1; }
 
+// 3 doubles per keypoint (data::keyframe::bearings_), uploaded once. Call it before the handle is shared between threads.
+ovs_status ovs_frame_dev_attach_bearings(ovs_frame_dev* f, const double* bearings) {
+    if (!f || (f->n > 0 && !bearings)) return OVS_ERR_INVALID;
+    if (f->n == 0) return OVS_OK;
+    OVS_HIP_TRY(hipSetDevice(f->device));
+    if (!f->d_bearings) OVS_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&f->d_bearings), sizeof(double) * 3 * (size_t)f->cap));
+    OVS_HIP_TRY(hipMemcpy(f->d_bearings, bearings, sizeof(double) * 3 * (size_t)f->n, hipMemcpyHostToDevice));
+    return OVS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The matchers: the host-array forms and their resident twins (_f). A twin takes an ovs_frame_dev handle wherever the host form takes
+// (grid parameters, keypoints, descriptors, stereo_x_right, n) of a frame / keyframe; everything else -- the landmark side, poses,
+// thresholds, outputs -- is unchanged, and so are the results (tests/test_gpu_window.py runs every matcher in both forms against the oracle).
+// ---------------------------------------------------------------------------------------------------------------------------
+
+ovs_status ovs_projection_match_frame_and_landmarks(ovs_wmatcher* w, const ovs_grid_params* gp, const ovs_keypoint* kps,
+                                                    const uint8_t* desc, const float* stereo_x_right, const uint8_t* occupied, int32_t n,
+                                                    const float* lm_xy, const float* lm_x_right, const int32_t* lm_level,
+                                                    const uint8_t* lm_desc, const uint8_t* lm_valid, int32_t m,
+                                                    const float* scale_factors, int32_t num_levels, float margin, float lowe_ratio,
+                                                    int32_t* assigned, int32_t* num_matches) {
+    return projection_match_frame_and_landmarks_impl(w, nullptr, gp, kps, desc, stereo_x_right, occupied, n, lm_xy, lm_x_right, lm_level, lm_desc, lm_valid, m,
+                                                     scale_factors, num_levels, margin, lowe_ratio, assigned, num_matches);
+}
 ovs_status ovs_projection_match_frame_and_landmarks_f(ovs_wmatcher* w, const ovs_frame_dev* frm, const uint8_t* occupied, const float* lm_xy,
                                                       const float* lm_x_right, const int32_t* lm_level, const uint8_t* lm_desc,
                                                       const uint8_t* lm_valid, int32_t m, const float* scale_factors, int32_t num_levels,
                                                       float margin, float lowe_ratio, int32_t* assigned, int32_t* num_matches) {
-    if (!w || !frm || !num_matches || m < 0 || !scale_factors || num_levels < 1 || num_levels > OVS_MAX_LEVELS) return OVS_ERR_INVALID;
-    *num_matches = 0;
-    if (m == 0) return OVS_OK;
-    if (!assigned) return OVS_ERR_INVALID;
-    const int n = frm->n;
-    if (n == 0) {
-        for (int i = 0; i < m; ++i) assigned[i] = -1;
-        return OVS_OK;
-    }
-    if (!lm_xy || !lm_level || !lm_desc || (frm->has_stereo && !lm_x_right)) return OVS_ERR_INVALID;
-    if (frm->device != w->device) return OVS_ERR_INVALID;
-    if (n > w->max_t || m > w->max_q) return OVS_ERR_CAPACITY;
-    OVS_HIP_TRY(hipSetDevice(w->device));
-    hipStream_t s = w->stream;
-    Stager stg(w);
-    WinArgs a{};
-    a.t_kps = frm->d_kps;
-    a.t_desc = frm->d_desc;
-    a.t_occupied = stg.put(occupied, (size_t)n);
-    a.t_x_right = frm->has_stereo ? frm->d_x_right : nullptr;
-    a.cell_start = frm->d_cell_start;
-    a.items = frm->d_items;
-    a.gp = frm->gp;
-    a.n_q = m;
-    a.q_xy = stg.put(lm_xy, (size_t)2 * m);
-    a.q_x_right = frm->has_stereo ? stg.put(lm_x_right, (size_t)m) : nullptr;
-    a.q_level = stg.put(lm_level, (size_t)m);
-    a.q_valid = stg.put(lm_valid, (size_t)m);
-    a.q_desc = stg.put(lm_desc, (size_t)32 * m);
-    a.margin = margin;
-    for (int l = 0; l < OVS_MAX_LEVELS; ++l) a.sf[l] = l < num_levels ? scale_factors[l] : 1.0f;
-    a.mode = kModeProjection;
-    a.dead_from = dead_from_ratio(OVS_HAMMING_DIST_THR_HIGH, lowe_ratio);
-    if (stg.overflow) return OVS_ERR_CAPACITY;
-    OVS_HIP_TRY(stg.flush(s));
-    ovs_status st = build_lists(w, a, m, k_window_lists<false>, k_window_lists<true>, s);
-    if (st != OVS_OK) return st;
-    ResolveArgs ra{};
-    ra.offsets = w->d_offsets;
-    ra.keys = w->d_keys;
-    ra.n_q = m;
-    ra.n_t = n;
-    ra.lowe_ratio = lowe_ratio;
-    ra.assigned = w->d_assigned;
-    ra.num_matches = w->d_num;
-    st = launch_resolve<kRuleProjection>(ra, s);
-    if (st != OVS_OK) return st;
-    return fetch_results(w, m, assigned, num_matches, s);
+    if (!frm) return OVS_ERR_INVALID;
+    return projection_match_frame_and_landmarks_impl(w, frm, &frm->gpp, nullptr, nullptr, nullptr, occupied, frm->n, lm_xy, lm_x_right, lm_level, lm_desc, lm_valid,
+                                                     m, scale_factors, num_levels, margin, lowe_ratio, assigned, num_matches);
 }
 
+ovs_status ovs_area_match_in_consistent_area(ovs_wmatcher* w, const ovs_grid_params* gp, const ovs_keypoint* kps_1, const uint8_t* desc_1,
+                                             int32_t n1, const ovs_keypoint* kps_2, const uint8_t* desc_2, int32_t n2,
+                                             float* prev_matched_xy, int32_t* matched_2_in_1, int32_t margin, float lowe_ratio,
+                                             int32_t check_orientation, int32_t* num_matches) {
+    return area_match_in_consistent_area_impl(w, nullptr, nullptr, gp, kps_1, desc_1, n1, kps_2, desc_2, n2, prev_matched_xy, matched_2_in_1, margin, lowe_ratio,
+                                              check_orientation, num_matches);
+}
 ovs_status ovs_area_match_in_consistent_area_f(ovs_wmatcher* w, const ovs_frame_dev* frm_1, const ovs_frame_dev* frm_2, float* prev_matched_xy,
                                                int32_t* matched_2_in_1, int32_t margin, float lowe_ratio, int32_t check_orientation,
                                                int32_t* num_matches) {
-    if (!w || !frm_1 || !frm_2 || !num_matches) return OVS_ERR_INVALID;
-    *num_matches = 0;
-    const int n1 = frm_1->n, n2 = frm_2->n;
-    if (n1 == 0) return OVS_OK;
-    if (!prev_matched_xy || !matched_2_in_1) return OVS_ERR_INVALID;
-    if (n2 == 0) {
-        for (int i = 0; i < n1; ++i) matched_2_in_1[i] = -1;
-        return OVS_OK;
-    }
-    if (frm_1->device != w->device || frm_2->device != w->device) return OVS_ERR_INVALID;
-    if (n2 > w->max_t || n1 > w->max_q) return OVS_ERR_CAPACITY;
-    OVS_HIP_TRY(hipSetDevice(w->device));
-    hipStream_t s = w->stream;
-    Stager stg(w);
-    // prev_matched_pts are read AND updated by the resolver: they live in the staging arena and come back with their own copy
-    const float* d_prev_c = stg.put(prev_matched_xy, (size_t)2 * n1);
-    if (stg.overflow) return OVS_ERR_CAPACITY;
-    float* d_prev = const_cast<float*>(d_prev_c);
-    OVS_HIP_TRY(stg.flush(s));
-    WinArgs a{};
-    a.t_kps = frm_2->d_kps;
-    a.t_desc = frm_2->d_desc;
-    a.cell_start = frm_2->d_cell_start;
-    a.items = frm_2->d_items;
-    a.gp = frm_2->gp;
-    a.n_q = n1;
-    a.q_xy = d_prev;
-    a.q_kps = frm_1->d_kps;
-    a.q_desc = frm_1->d_desc;
-    a.margin = (float)margin;
-    a.mode = kModeArea;
-    a.dead_from = dead_from_ratio(OVS_HAMMING_DIST_THR_LOW, lowe_ratio);
-    ovs_status st = build_lists(w, a, n1, k_window_lists<false>, k_window_lists<true>, s);
-    if (st != OVS_OK) return st;
-    ResolveArgs ra{};
-    ra.offsets = w->d_offsets;
-    ra.keys = w->d_keys;
-    ra.n_q = n1;
-    ra.n_t = n2;
-    ra.lowe_ratio = lowe_ratio;
-    ra.check_orientation = check_orientation;
-    ra.q_kps = frm_1->d_kps;
-    ra.t_kps = frm_2->d_kps;
-    ra.prev_matched_xy = d_prev;
-    ra.assigned = w->d_assigned;
-    ra.num_matches = w->d_num;
-    st = launch_resolve<kRuleArea>(ra, s);
-    if (st != OVS_OK) return st;
-    OVS_HIP_TRY(hipMemcpyAsync(w->h_stage, d_prev, sizeof(float) * 2 * (size_t)n1, hipMemcpyDeviceToHost, s));
-    st = fetch_results(w, n1, matched_2_in_1, num_matches, s);
-    if (st != OVS_ERR_HIP) std::memcpy(prev_matched_xy, w->h_stage, sizeof(float) * 2 * (size_t)n1);   // only behind fetch_results' synchronisation
-    return st;
+    if (!frm_1 || !frm_2) return OVS_ERR_INVALID;
+    return area_match_in_consistent_area_impl(w, frm_1, frm_2, &frm_2->gpp, nullptr, nullptr, frm_1->n, nullptr, nullptr, frm_2->n, prev_matched_xy, matched_2_in_1,
+                                              margin, lowe_ratio, check_orientation, num_matches);
 }
 
+ovs_status ovs_projection_match_current_and_last_frames(ovs_wmatcher* w, const ovs_camera* cam, const ovs_grid_params* gp,
+                                                        const ovs_keypoint* curr_kps, const uint8_t* curr_desc,
+                                                        const float* curr_stereo_x_right, const uint8_t* curr_occupied, int32_t n_curr,
+                                                        const double* pose_cw_curr, const ovs_keypoint* last_kps, const double* last_pos_w,
+                                                        const uint8_t* last_lm_desc, const uint8_t* last_valid, int32_t n_last,
+                                                        const double* pose_cw_last, const float* scale_factors, int32_t num_levels,
+                                                        float margin, int32_t check_orientation, int32_t* assigned, int32_t* num_matches) {
+    return projection_match_current_and_last_frames_impl(w, nullptr, cam, gp, curr_kps, curr_desc, curr_stereo_x_right, curr_occupied, n_curr, pose_cw_curr, last_kps,
+                                                         last_pos_w, last_lm_desc, last_valid, n_last, pose_cw_last, scale_factors, num_levels, margin,
+                                                         check_orientation, assigned, num_matches);
+}
 ovs_status ovs_projection_match_current_and_last_frames_f(ovs_wmatcher* w, const ovs_camera* cam, const ovs_frame_dev* curr,
                                                           const uint8_t* curr_occupied, const double* pose_cw_curr, const ovs_keypoint* last_kps,
                                                           const double* last_pos_w, const uint8_t* last_lm_desc, const uint8_t* last_valid,
                                                           int32_t n_last, const double* pose_cw_last, const float* scale_factors,
                                                           int32_t num_levels, float margin, int32_t check_orientation, int32_t* assigned,
                                                           int32_t* num_matches) {
-    if (!w || !cam || !curr || !num_matches || n_last < 0 || !pose_cw_curr || !pose_cw_last || !scale_factors || num_levels < 1 ||
-        num_levels > OVS_MAX_LEVELS || (cam->model != 0 && cam->model != 1))
-        return OVS_ERR_INVALID;
-    *num_matches = 0;
-    if (n_last == 0) return OVS_OK;
-    if (!assigned) return OVS_ERR_INVALID;
-    for (int i = 0; i < n_last; ++i) assigned[i] = -1;
-    const int n_curr = curr->n;
-    if (n_curr == 0) return OVS_OK;
-    if (!last_kps || !last_pos_w || !last_lm_desc) return OVS_ERR_INVALID;
-    if (curr->device != w->device) return OVS_ERR_INVALID;
-    if (n_curr > w->max_t || n_last > w->max_q) return OVS_ERR_CAPACITY;
-    OVS_HIP_TRY(hipSetDevice(w->device));
-    hipStream_t s = w->stream;
-    // motion direction (host, double): trans_wc = -rot_cw^T trans_cw; trans_lc = rot_lw trans_wc + trans_lw
-    const double* Rc = pose_cw_curr;
-    const double* tc = pose_cw_curr + 9;
-    const double twc[3] = {-((Rc[0] * tc[0] + Rc[3] * tc[1]) + Rc[6] * tc[2]), -((Rc[1] * tc[0] + Rc[4] * tc[1]) + Rc[7] * tc[2]),
-                           -((Rc[2] * tc[0] + Rc[5] * tc[1]) + Rc[8] * tc[2])};
-    const double* Rl = pose_cw_last;
-    const double tlc_z = ((Rl[6] * twc[0] + Rl[7] * twc[1]) + Rl[8] * twc[2]) + pose_cw_last[11];
-    const int forward = cam->setup == 0 ? 0 : (tlc_z > cam->true_baseline);
-    const int backward = cam->setup == 0 ? 0 : (-tlc_z > cam->true_baseline);
-    CamP cp{};
-    cp.model = cam->model;
-    cp.setup = cam->setup;
-    cp.fx = cam->fx;
-    cp.fy = cam->fy;
-    cp.cx = cam->cx;
-    cp.cy = cam->cy;
-    cp.fxb = cam->focal_x_baseline;
-    cp.cols = cam->cols;
-    cp.rows = cam->rows;
-    cp.min_x = curr->gpp.min_x;
-    cp.min_y = curr->gpp.min_y;
-    cp.max_x = curr->gpp.max_x;
-    cp.max_y = curr->gpp.max_y;
-    std::memcpy(cp.P, pose_cw_curr, sizeof(double) * 12);
-    float sf16[OVS_MAX_LEVELS];
-    for (int l = 0; l < OVS_MAX_LEVELS; ++l) sf16[l] = l < num_levels ? scale_factors[l] : 1.0f;
-    Stager stg(w);
-    const uint8_t* d_occ = stg.put(curr_occupied, (size_t)n_curr);
-    const ovs_keypoint* d_q_kps = stg.put(last_kps, (size_t)n_last);
-    const double* d_q_pos = stg.put(last_pos_w, (size_t)3 * n_last);
-    const uint8_t* d_q_desc = stg.put(last_lm_desc, (size_t)32 * n_last);
-    const float* d_sf = stg.put(sf16, (size_t)OVS_MAX_LEVELS);
-    // the query flags are written by k_reproject_queries (in place over last_valid when given: same index, read-then-write by one lane)
-    uint8_t* d_q_flag = last_valid ? const_cast<uint8_t*>(stg.put(last_valid, (size_t)n_last)) : stg.reserve<uint8_t>((size_t)n_last);
-    float* d_q_xy = stg.reserve<float>((size_t)2 * n_last);
-    float* d_q_f = stg.reserve<float>((size_t)n_last);
-    float* d_q_r = stg.reserve<float>((size_t)n_last);
-    int32_t* d_q_i = stg.reserve<int32_t>((size_t)n_last);
-    int32_t* d_q_i2 = stg.reserve<int32_t>((size_t)n_last);
-    if (stg.overflow) return OVS_ERR_CAPACITY;
-    OVS_HIP_TRY(stg.flush(s));
-    hipLaunchKernelGGL(k_reproject_queries, dim3((n_last + 255) / 256), dim3(256), 0, s, cp, d_q_kps, d_q_pos, (const uint8_t*)(last_valid ? d_q_flag : nullptr),
-                       n_last, margin, d_sf, num_levels, forward, backward, (const float*)nullptr, 0.0, 0.0, 0.0, 0.0f, d_q_xy, d_q_f, d_q_r, d_q_i, d_q_i2,
-                       d_q_flag);
-    OVS_HIP_TRY(hipGetLastError());
-    WinArgs a{};
-    a.t_kps = curr->d_kps;
-    a.t_desc = curr->d_desc;
-    a.t_occupied = d_occ;
-    a.t_x_right = curr->has_stereo ? curr->d_x_right : nullptr;
-    a.cell_start = curr->d_cell_start;
-    a.items = curr->d_items;
-    a.gp = curr->gp;
-    a.n_q = n_last;
-    a.q_xy = d_q_xy;
-    a.q_x_right = d_q_f;
-    a.q_valid = d_q_flag;
-    a.q_radius = d_q_r;
-    a.q_minl = d_q_i;
-    a.q_maxl = d_q_i2;
-    a.q_desc = d_q_desc;
-    a.margin = margin;
-    a.mode = kModeGeneric;
-    a.dead_from = dead_from_thr(OVS_HAMMING_DIST_THR_HIGH);
-    ovs_status st = build_lists(w, a, n_last, k_window_lists<false>, k_window_lists<true>, s);
-    if (st != OVS_OK) return st;
-    ResolveArgs ra{};
-    ra.offsets = w->d_offsets;
-    ra.keys = w->d_keys;
-    ra.n_q = n_last;
-    ra.n_t = n_curr;
-    ra.check_orientation = check_orientation;
-    ra.q_kps = d_q_kps;
-    ra.t_kps = curr->d_kps;
-    ra.assigned = w->d_assigned;
-    ra.num_matches = w->d_num;
-    ra.best_only_thr = OVS_HAMMING_DIST_THR_HIGH;
-    st = launch_resolve<kRuleBestOnly>(ra, s);
-    if (st != OVS_OK) return st;
-    return fetch_results(w, n_last, assigned, num_matches, s);
+    if (!curr) return OVS_ERR_INVALID;
+    return projection_match_current_and_last_frames_impl(w, curr, cam, &curr->gpp, nullptr, nullptr, nullptr, curr_occupied, curr->n, pose_cw_curr, last_kps,
+                                                         last_pos_w, last_lm_desc, last_valid, n_last, pose_cw_last, scale_factors, num_levels, margin,
+                                                         check_orientation, assigned, num_matches);
 }
-
-}   // extern "C"
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// Keyframe-side matchers: the host-array forms and their resident twins (_f, round 4). A twin takes an ovs_frame_dev handle wherever the
-// host form takes (grid parameters, keypoints, descriptors, stereo_x_right, n) of the TARGET frame / keyframe; everything else -- the
-// landmark side, poses, thresholds, outputs -- is unchanged, and so are the results (tests/test_gpu_resident.py: bit-equal to the host forms).
-// ---------------------------------------------------------------------------------------------------------------------------
-extern "C" {
 
 ovs_status ovs_fuse_replace_duplication(ovs_wmatcher* w, const ovs_camera* cam, const ovs_grid_params* gp, const ovs_keypoint* kps, const uint8_t* desc,
                                         const float* stereo_x_right, int32_t n, const double* pose_cw, const double* lm_pos_w, const float* lm_dist_min_max,
                                         const double* lm_normal, const uint8_t* lm_desc, const uint8_t* lm_valid, int32_t m, const float* scale_factors,
                                         const float* inv_level_sigma_sq, int32_t num_levels, float log_scale_factor, float margin, int32_t* best_idx,
                                         int32_t* num_fused) {
-    return fuse_replace_duplication_impl(w, nullptr, cam, gp, kps, desc, stereo_x_right, n, pose_cw, lm_pos_w, lm_dist_min_max, lm_normal, lm_desc, lm_valid, m,
-                                         scale_factors, inv_level_sigma_sq, num_levels, log_scale_factor, margin, best_idx, num_fused);
+    return fuse_duplication_impl(w, nullptr, kFuseReplace, cam, gp, kps, desc, stereo_x_right, n, pose_cw, lm_pos_w, lm_dist_min_max, lm_normal, lm_desc, lm_valid, m,
+                                 scale_factors, inv_level_sigma_sq, num_levels, log_scale_factor, margin, best_idx, num_fused);
 }
 ovs_status ovs_fuse_replace_duplication_f(ovs_wmatcher* w, const ovs_camera* cam, const ovs_frame_dev* keyfrm, const double* pose_cw, const double* lm_pos_w,
                                           const float* lm_dist_min_max, const double* lm_normal, const uint8_t* lm_desc, const uint8_t* lm_valid, int32_t m,
                                           const float* scale_factors, const float* inv_level_sigma_sq, int32_t num_levels, float log_scale_factor,
                                           float margin, int32_t* best_idx, int32_t* num_fused) {
     if (!keyfrm) return OVS_ERR_INVALID;
-    return fuse_replace_duplication_impl(w, keyfrm, cam, &keyfrm->gpp, nullptr, nullptr, nullptr, keyfrm->n, pose_cw, lm_pos_w, lm_dist_min_max, lm_normal, lm_desc,
-                                         lm_valid, m, scale_factors, inv_level_sigma_sq, num_levels, log_scale_factor, margin, best_idx, num_fused);
+    return fuse_duplication_impl(w, keyfrm, kFuseReplace, cam, &keyfrm->gpp, nullptr, nullptr, nullptr, keyfrm->n, pose_cw, lm_pos_w, lm_dist_min_max, lm_normal, lm_desc,
+                                 lm_valid, m, scale_factors, inv_level_sigma_sq, num_levels, log_scale_factor, margin, best_idx, num_fused);
+}
+
+ovs_status ovs_fuse_detect_duplication(ovs_wmatcher* w, const ovs_camera* cam, const ovs_grid_params* gp, const ovs_keypoint* kps, const uint8_t* desc, int32_t n,
+                                       const double* sim3_cw, const double* lm_pos_w, const float* lm_dist_min_max, const double* lm_normal,
+                                       const uint8_t* lm_desc, const uint8_t* lm_valid, int32_t m, const float* scale_factors, int32_t num_levels,
+                                       float log_scale_factor, float margin, int32_t* best_idx, int32_t* num_found) {
+    return fuse_duplication_impl(w, nullptr, kFuseDetect, cam, gp, kps, desc, nullptr, n, sim3_cw, lm_pos_w, lm_dist_min_max, lm_normal, lm_desc, lm_valid, m,
+                                 scale_factors, nullptr, num_levels, log_scale_factor, margin, best_idx, num_found);
+}
+ovs_status ovs_fuse_detect_duplication_f(ovs_wmatcher* w, const ovs_camera* cam, const ovs_frame_dev* keyfrm, const double* sim3_cw, const double* lm_pos_w,
+                                         const float* lm_dist_min_max, const double* lm_normal, const uint8_t* lm_desc, const uint8_t* lm_valid, int32_t m,
+                                         const float* scale_factors, int32_t num_levels, float log_scale_factor, float margin, int32_t* best_idx,
+                                         int32_t* num_found) {
+    if (!keyfrm) return OVS_ERR_INVALID;
+    return fuse_duplication_impl(w, keyfrm, kFuseDetect, cam, &keyfrm->gpp, nullptr, nullptr, nullptr, keyfrm->n, sim3_cw, lm_pos_w, lm_dist_min_max, lm_normal, lm_desc,
+                                 lm_valid, m, scale_factors, nullptr, num_levels, log_scale_factor, margin, best_idx, num_found);
 }
 
 ovs_status ovs_projection_match_frame_and_keyframe(ovs_wmatcher* w, const ovs_camera* cam, const ovs_grid_params* gp, const ovs_keypoint* curr_kps,
@@ -2638,22 +2240,6 @@ ovs_status ovs_projection_match_frame_and_keyframe_f(ovs_wmatcher* w, const ovs_
     return projection_match_frame_and_keyframe_impl(w, curr, cam, &curr->gpp, nullptr, nullptr, curr_occupied, curr->n, pose_cw_curr, kf_kps, kf_pos_w, kf_dist_min_max,
                                                     kf_lm_desc, kf_valid, n_kf, scale_factors, num_levels, log_scale_factor, margin, hamm_dist_thr,
                                                     check_orientation, assigned, num_matches);
-}
-
-ovs_status ovs_fuse_detect_duplication(ovs_wmatcher* w, const ovs_camera* cam, const ovs_grid_params* gp, const ovs_keypoint* kps, const uint8_t* desc, int32_t n,
-                                       const double* sim3_cw, const double* lm_pos_w, const float* lm_dist_min_max, const double* lm_normal,
-                                       const uint8_t* lm_desc, const uint8_t* lm_valid, int32_t m, const float* scale_factors, int32_t num_levels,
-                                       float log_scale_factor, float margin, int32_t* best_idx, int32_t* num_found) {
-    return fuse_detect_duplication_impl(w, nullptr, cam, gp, kps, desc, n, sim3_cw, lm_pos_w, lm_dist_min_max, lm_normal, lm_desc, lm_valid, m, scale_factors, num_levels,
-                                        log_scale_factor, margin, best_idx, num_found);
-}
-ovs_status ovs_fuse_detect_duplication_f(ovs_wmatcher* w, const ovs_camera* cam, const ovs_frame_dev* keyfrm, const double* sim3_cw, const double* lm_pos_w,
-                                         const float* lm_dist_min_max, const double* lm_normal, const uint8_t* lm_desc, const uint8_t* lm_valid, int32_t m,
-                                         const float* scale_factors, int32_t num_levels, float log_scale_factor, float margin, int32_t* best_idx,
-                                         int32_t* num_found) {
-    if (!keyfrm) return OVS_ERR_INVALID;
-    return fuse_detect_duplication_impl(w, keyfrm, cam, &keyfrm->gpp, nullptr, nullptr, keyfrm->n, sim3_cw, lm_pos_w, lm_dist_min_max, lm_normal, lm_desc, lm_valid, m,
-                                        scale_factors, num_levels, log_scale_factor, margin, best_idx, num_found);
 }
 
 ovs_status ovs_projection_match_by_sim3_transform(ovs_wmatcher* w, const ovs_camera* cam, const ovs_grid_params* gp, const ovs_keypoint* kps, const uint8_t* desc,
@@ -2699,7 +2285,15 @@ ovs_status ovs_projection_match_keyframes_mutually_f(ovs_wmatcher* w, const ovs_
                                                     matched_2_in_1, num_matches);
 }
 
-// bow_tree / robust::match_for_triangulation with both sides resident: only the per-call flags and the BoW feature vectors (node CSRs) travel
+ovs_status ovs_bow_match_frame_and_keyframe(ovs_wmatcher* w, const ovs_keypoint* kf_kps, const uint8_t* kf_desc, const uint8_t* kf_valid,
+                                            int32_t n_kf, const int32_t* kf_node_ids, const int32_t* kf_node_start,
+                                            const int32_t* kf_items, int32_t kf_nodes, const ovs_keypoint* frm_kps,
+                                            const uint8_t* frm_desc, int32_t n_frm, const int32_t* frm_node_ids,
+                                            const int32_t* frm_node_start, const int32_t* frm_items, int32_t frm_nodes, float lowe_ratio,
+                                            int32_t check_orientation, int32_t* matched_kf_in_frm, int32_t* num_matches) {
+    return bow_match_impl(w, nullptr, nullptr, 0, nullptr, nullptr, kf_kps, kf_desc, kf_valid, n_kf, kf_node_ids, kf_node_start, kf_items, kf_nodes, frm_kps, frm_desc, n_frm,
+                          frm_node_ids, frm_node_start, frm_items, frm_nodes, lowe_ratio, check_orientation, matched_kf_in_frm, num_matches);
+}
 ovs_status ovs_bow_match_frame_and_keyframe_f(ovs_wmatcher* w, const ovs_frame_dev* keyfrm, const uint8_t* kf_valid, const int32_t* kf_node_ids,
                                               const int32_t* kf_node_start, const int32_t* kf_items, int32_t kf_nodes, const ovs_frame_dev* frm,
                                               const int32_t* frm_node_ids, const int32_t* frm_node_start, const int32_t* frm_items, int32_t frm_nodes,
@@ -2708,6 +2302,15 @@ ovs_status ovs_bow_match_frame_and_keyframe_f(ovs_wmatcher* w, const ovs_frame_d
     return bow_match_impl(w, keyfrm, frm, 0, nullptr, nullptr, nullptr, nullptr, kf_valid, keyfrm->n, kf_node_ids, kf_node_start, kf_items, kf_nodes, nullptr, nullptr,
                           frm->n, frm_node_ids, frm_node_start, frm_items, frm_nodes, lowe_ratio, check_orientation, matched_kf_in_frm, num_matches);
 }
+
+ovs_status ovs_bow_match_keyframes(ovs_wmatcher* w, const ovs_keypoint* kps_1, const uint8_t* desc_1, const uint8_t* valid_1, int32_t n1,
+                                   const int32_t* node_ids_1, const int32_t* node_start_1, const int32_t* items_1, int32_t nodes_1,
+                                   const ovs_keypoint* kps_2, const uint8_t* desc_2, const uint8_t* valid_2, int32_t n2,
+                                   const int32_t* node_ids_2, const int32_t* node_start_2, const int32_t* items_2, int32_t nodes_2,
+                                   float lowe_ratio, int32_t check_orientation, int32_t* matched_2_in_1, int32_t* num_matches) {
+    return bow_match_impl(w, nullptr, nullptr, 1, valid_2, nullptr, kps_1, desc_1, valid_1, n1, node_ids_1, node_start_1, items_1, nodes_1, kps_2, desc_2, n2, node_ids_2,
+                          node_start_2, items_2, nodes_2, lowe_ratio, check_orientation, matched_2_in_1, num_matches);
+}
 ovs_status ovs_bow_match_keyframes_f(ovs_wmatcher* w, const ovs_frame_dev* keyfrm_1, const uint8_t* valid_1, const int32_t* node_ids_1,
                                      const int32_t* node_start_1, const int32_t* items_1, int32_t nodes_1, const ovs_frame_dev* keyfrm_2,
                                      const uint8_t* valid_2, const int32_t* node_ids_2, const int32_t* node_start_2, const int32_t* items_2, int32_t nodes_2,
@@ -2715,6 +2318,22 @@ ovs_status ovs_bow_match_keyframes_f(ovs_wmatcher* w, const ovs_frame_dev* keyfr
     if (!keyfrm_1 || !keyfrm_2) return OVS_ERR_INVALID;
     return bow_match_impl(w, keyfrm_1, keyfrm_2, 1, valid_2, nullptr, nullptr, nullptr, valid_1, keyfrm_1->n, node_ids_1, node_start_1, items_1, nodes_1, nullptr, nullptr,
                           keyfrm_2->n, node_ids_2, node_start_2, items_2, nodes_2, lowe_ratio, check_orientation, matched_2_in_1, num_matches);
+}
+
+ovs_status ovs_robust_match_for_triangulation(ovs_wmatcher* w, const ovs_keypoint* kps_1, const uint8_t* desc_1, const uint8_t* has_lm_1,
+                                              const float* x_right_1, const double* bearings_1, int32_t n1, const int32_t* node_ids_1,
+                                              const int32_t* node_start_1, const int32_t* items_1, int32_t nodes_1,
+                                              const ovs_keypoint* kps_2, const uint8_t* desc_2, const uint8_t* has_lm_2,
+                                              const float* x_right_2, const double* bearings_2, int32_t n2, const int32_t* node_ids_2,
+                                              const int32_t* node_start_2, const int32_t* items_2, int32_t nodes_2, const double* E_12,
+                                              const double* epipole_in_2, const float* scale_factors, int32_t num_levels,
+                                              int32_t check_orientation, int32_t* matched_2_in_1, int32_t* num_matches) {
+    if (!bearings_1 || !bearings_2 || !E_12 || !epipole_in_2 || !scale_factors || num_levels < 1 || num_levels > OVS_MAX_LEVELS || n1 < 0 || n2 < 0)
+        return OVS_ERR_INVALID;
+    const std::vector<uint8_t> v1 = no_landmark_mask(has_lm_1, n1), v2 = no_landmark_mask(has_lm_2, n2);
+    TriParams tp{x_right_1, x_right_2, bearings_1, bearings_2, E_12, epipole_in_2, scale_factors, num_levels};
+    return bow_match_impl(w, nullptr, nullptr, 1, v2.data(), &tp, kps_1, desc_1, v1.data(), n1, node_ids_1, node_start_1, items_1, nodes_1, kps_2, desc_2, n2,
+                          node_ids_2, node_start_2, items_2, nodes_2, 0.0f, check_orientation, matched_2_in_1, num_matches);
 }
 ovs_status ovs_robust_match_for_triangulation_f(ovs_wmatcher* w, const ovs_frame_dev* keyfrm_1, const uint8_t* has_lm_1, const int32_t* node_ids_1,
                                                 const int32_t* node_start_1, const int32_t* items_1, int32_t nodes_1, const ovs_frame_dev* keyfrm_2,
@@ -2725,26 +2344,11 @@ ovs_status ovs_robust_match_for_triangulation_f(ovs_wmatcher* w, const ovs_frame
         num_levels > OVS_MAX_LEVELS)
         return OVS_ERR_INVALID;
     const int n1 = keyfrm_1->n, n2 = keyfrm_2->n;
-    std::vector<uint8_t> v1((size_t)std::max(n1, 1), 1), v2((size_t)std::max(n2, 1), 1);   // "valid" for the bow kernels = NO landmark yet
-    if (has_lm_1)
-        for (int i = 0; i < n1; ++i) v1[i] = has_lm_1[i] ? 0 : 1;
-    if (has_lm_2)
-        for (int i = 0; i < n2; ++i) v2[i] = has_lm_2[i] ? 0 : 1;
+    const std::vector<uint8_t> v1 = no_landmark_mask(has_lm_1, n1), v2 = no_landmark_mask(has_lm_2, n2);
     TriParams tp{nullptr, nullptr, nullptr, nullptr, E_12, epipole_in_2, scale_factors, num_levels};
     return bow_match_impl(w, keyfrm_1, keyfrm_2, 1, v2.data(), &tp, nullptr, nullptr, v1.data(), n1, node_ids_1, node_start_1, items_1, nodes_1, nullptr, nullptr, n2,
                           node_ids_2, node_start_2, items_2, nodes_2, 0.0f, check_orientation, matched_2_in_1, num_matches);
 }
-
-// 3 doubles per keypoint (data::keyframe::bearings_), uploaded once. Call it before the handle is shared between threads.
-ovs_status ovs_frame_dev_attach_bearings(ovs_frame_dev* f, const double* bearings) {
-    if (!f || (f->n > 0 && !bearings)) return OVS_ERR_INVALID;
-    if (f->n == 0) return OVS_OK;
-    OVS_HIP_TRY(hipSetDevice(f->device));
-    if (!f->d_bearings) OVS_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&f->d_bearings), sizeof(double) * 3 * (size_t)f->cap));
-    OVS_HIP_TRY(hipMemcpy(f->d_bearings, bearings, sizeof(double) * 3 * (size_t)f->n, hipMemcpyHostToDevice));
-    return OVS_OK;
-}
-int32_t ovs_frame_dev_device(const ovs_frame_dev* f) { return f ? f->device : -1; }
 
 ovs_status ovs_match_set_variant(int32_t which, int32_t value) {
     if (value != 0 && value != 1) return OVS_ERR_INVALID;

@@ -31,11 +31,7 @@ def test_assign_keypoints_to_grid(match, synth, oracle, n, rows, cols):
     assert np.array_equal(start, want_start) and np.array_equal(items, want_items)
 
 
-@pytest.mark.parametrize("n,m,rows,cols,stereo", [(4000, 10000, 1920, 3840, False), (2000, 3000, 1080, 1920, True), (300, 50, 480, 752, False),
-                                                 (5, 2000, 480, 752, True)])
-@pytest.mark.parametrize("ratio", [0.8, 0.6])
-def test_projection_match_frame_and_landmarks(match, synth, oracle, n, m, rows, cols, stereo, ratio):
-    """BASELINE config 4 geometry (3840x1920 / 4000 keypoints / 10 000 landmarks, margin 5) and smaller / stereo cases."""
+def _frame_and_landmarks_scene(synth, n, m, rows, cols, stereo):
     k, d = synth.synth_keypoints(n, rows, cols, seed=11 * n + m)
     lm = synth.synth_landmarks(k, d, m, rows, cols, seed=m, n_from_frame=min(m, int(1.3 * n)), with_stereo=stereo)
     rng = np.random.default_rng(m)
@@ -47,6 +43,15 @@ def test_projection_match_frame_and_landmarks(match, synth, oracle, n, m, rows, 
         from_frame = lm["src"] >= 0
         agree = from_frame & (rng.random(m) < 0.8)
         lm["x_right"][agree] = xr[lm["src"][agree]] + rng.normal(0, 1.5, int(agree.sum())).astype(np.float32)
+    return k, d, lm, sf, occ, xr
+
+
+@pytest.mark.parametrize("n,m,rows,cols,stereo", [(4000, 10000, 1920, 3840, False), (2000, 3000, 1080, 1920, True), (300, 50, 480, 752, False),
+                                                 (5, 2000, 480, 752, True)])
+@pytest.mark.parametrize("ratio", [0.8, 0.6])
+def test_projection_match_frame_and_landmarks(match, synth, oracle, n, m, rows, cols, stereo, ratio):
+    """BASELINE config 4 geometry (3840x1920 / 4000 keypoints / 10 000 landmarks, margin 5) and smaller / stereo cases."""
+    k, d, lm, sf, occ, xr = _frame_and_landmarks_scene(synth, n, m, rows, cols, stereo)
     gp, ogp = match.grid_params(cols, rows), oracle.grid_params(cols, rows)
     w = match.projection(ratio, True, max_targets=4096, max_queries=10240)
     for margin in (5.0, 15.0):
@@ -601,3 +606,172 @@ def test_angle_keep_rule_variant_on_both_sides(match, synth, oracle):
         match.set_variant("angle_keep_rule", 0)
         oracle.match_set_variant("angle_keep_rule", 0)
     assert res[1][0] <= res[0][0] and res[1][1] <= res[0][1] and res[1] != res[0]
+
+
+def test_dev_forms_equal_host_forms(match, synth, oracle):
+    """The device-array entry points (ovs_projection_match_frame_and_landmarks_dev, ovs_area_match_in_consistent_area_dev: inputs and outputs
+    in HBM, the caller's stream) on the scenes of the host-form tests above: every output array equals the host form's, which is held to the
+    oracle here as well; prev_matched_xy bit for bit. The context's overflow word has no getter: that it stayed zero shows in the
+    results (an overflowed list is a truncated list) and in the host form's OVS_OK on the same context right behind the device form."""
+    import ctypes as C
+    import torch
+    from openvslam_amd import _lib
+    L = _lib.lib()
+    dev = torch.device("cuda:0")
+    keep = []
+
+    def up(a):   # host array -> device pointer (the tensor is kept alive in `keep`)
+        if a is None:
+            return None
+        t = torch.from_numpy(np.ascontiguousarray(a).reshape(-1).view(np.uint8).copy()).to(dev)
+        keep.append(t)
+        return t.data_ptr()
+
+    # projection::match_frame_and_landmarks, the stereo scene
+    n, m, rows, cols, ratio, margin = 2000, 3000, 1080, 1920, 0.8, 5.0
+    k, d, lm, sf, occ, xr = _frame_and_landmarks_scene(synth, n, m, rows, cols, True)
+    gp, ogp = match.grid_params(cols, rows), oracle.grid_params(cols, rows)
+    w = match.projection(ratio, True, max_targets=4096, max_queries=10240)
+    xy = np.ascontiguousarray(lm["xy"], np.float32)
+    lv = np.ascontiguousarray(lm["level"], np.int32)
+
+    def host():
+        return w.match_frame_and_landmarks(gp, k, d, sf, xy, lv, lm["desc"], margin, frm_stereo_x_right=xr, frm_occupied=occ,
+                                           lm_x_right=lm["x_right"], lm_valid=lm["valid"])
+
+    got, gn = host()
+    want, wn = oracle.projection_match_frame_and_landmarks(ogp, k, d, sf, xy, lv, lm["desc"], margin, ratio, frm_stereo_x_right=xr,
+                                                           frm_occupied=occ, lm_x_right=lm["x_right"], lm_valid=lm["valid"])
+    assert gn == wn and np.array_equal(got, want) and wn > n // 4
+    d_assigned = torch.full((m,), -7, dtype=torch.int32, device=dev)
+    d_num = torch.full((1,), -7, dtype=torch.int32, device=dev)
+    _lib.check(L.ovs_projection_match_frame_and_landmarks_dev(
+        w._h, C.byref(gp), up(k), up(d), up(xr), up(occ), n, up(xy), up(np.ascontiguousarray(lm["x_right"], np.float32)), up(lv),
+        up(np.ascontiguousarray(lm["desc"], np.uint8)), up(np.ascontiguousarray(lm["valid"], np.uint8)), m, sf.ctypes.data, len(sf), margin,
+        ratio, d_assigned.data_ptr(), d_num.data_ptr(), None), "ovs_projection_match_frame_and_landmarks_dev")
+    torch.cuda.synchronize()
+    assert int(d_num.cpu()[0]) == gn and np.array_equal(d_assigned.cpu().numpy(), got)
+    again, an = host()
+    assert an == gn and np.array_equal(again, got)
+
+    # area::match_in_consistent_area, two rounds: the second starts from the prev_matched_pts the first one updated
+    ka, da, kb, db = _two_frames(oracle, synth)
+    gp, ogp = match.grid_params(752, 480), oracle.grid_params(752, 480)
+    wa = match.area(0.9, True, max_targets=2048, max_queries=2048)
+    n1, n2 = len(ka), len(kb)
+    prev_h = np.ascontiguousarray(np.stack([ka["x"], ka["y"]], 1), np.float32)
+    prev_o = prev_h.copy()
+    d_prev = torch.from_numpy(prev_h.copy()).to(dev)
+    d_matched = torch.full((n1,), -7, dtype=torch.int32, device=dev)
+    p_k1, p_d1, p_k2, p_d2 = up(ka), up(da), up(kb), up(db)
+    for it in range(2):
+        hn, hgot = wa.match_in_consistent_area(gp, ka, da, kb, db, prev_h, 100)
+        wn, want = oracle.area_match_in_consistent_area(ogp, ka, da, kb, db, prev_o, 100, 0.9, True)
+        assert hn == wn and np.array_equal(hgot, want) and np.array_equal(prev_h.view(np.uint32), prev_o.view(np.uint32))
+        d_num.fill_(-7)
+        _lib.check(L.ovs_area_match_in_consistent_area_dev(wa._h, C.byref(gp), p_k1, p_d1, n1, p_k2, p_d2, n2, d_prev.data_ptr(),
+                                                           d_matched.data_ptr(), 100, 0.9, 1, d_num.data_ptr(), None),
+                   "ovs_area_match_in_consistent_area_dev")
+        torch.cuda.synchronize()
+        assert int(d_num.cpu()[0]) == hn and np.array_equal(d_matched.cpu().numpy(), hgot)
+        assert np.array_equal(d_prev.cpu().numpy().view(np.uint32), prev_h.view(np.uint32))
+    assert wn > 50
+
+
+def test_tight_capacity_every_host_entry_point(match, synth, oracle):
+    """Contexts created with max_targets == n and max_queries == m EXACTLY: every host-array entry point runs once, returns OVS_OK (the
+    wrappers raise on anything else) and the oracle's result -- the staging arena has room for every array of the largest call at full capacity."""
+    from openvslam_amd import _lib
+    lsf = float(np.log(np.float32(1.2)))
+
+    # assign_keypoints_to_grid and projection::match_frame_and_landmarks (stereo)
+    n, m, rows, cols = 2000, 3000, 1080, 1920
+    k, d, lm, sf, occ, xr = _frame_and_landmarks_scene(synth, n, m, rows, cols, True)
+    gp, ogp = match.grid_params(cols, rows), oracle.grid_params(cols, rows)
+    w = match.projection(0.8, True, max_targets=n, max_queries=m)
+    start, items = w.assign_keypoints_to_grid(gp, k)
+    want_start, want_items = oracle.assign_keypoints_to_grid(ogp, k)
+    assert np.array_equal(start, want_start) and np.array_equal(items, want_items)
+    got, gn = w.match_frame_and_landmarks(gp, k, d, sf, lm["xy"], lm["level"], lm["desc"], 5.0, frm_stereo_x_right=xr, frm_occupied=occ,
+                                          lm_x_right=lm["x_right"], lm_valid=lm["valid"])
+    want, wn = oracle.projection_match_frame_and_landmarks(ogp, k, d, sf, lm["xy"], lm["level"], lm["desc"], 5.0, 0.8, frm_stereo_x_right=xr,
+                                                           frm_occupied=occ, lm_x_right=lm["x_right"], lm_valid=lm["valid"])
+    assert gn == wn > 0 and np.array_equal(got, want)
+
+    # area::match_in_consistent_area, bow_tree::match_frame_and_keyframe / match_keyframes, robust::match_for_triangulation: two extracted frames
+    ka, da, kb, db = _two_frames(oracle, synth, shift=(3, 2))
+    n1, n2 = len(ka), len(kb)
+    gp, ogp = match.grid_params(752, 480), oracle.grid_params(752, 480)
+    pg = np.ascontiguousarray(np.stack([ka["x"], ka["y"]], 1), np.float32)
+    po = pg.copy()
+    gn, got = match.area(0.9, True, max_targets=n2, max_queries=n1).match_in_consistent_area(gp, ka, da, kb, db, pg, 100)
+    wn, want = oracle.area_match_in_consistent_area(ogp, ka, da, kb, db, po, 100, 0.9, True)
+    assert gn == wn > 0 and np.array_equal(got, want) and np.array_equal(pg.view(np.uint32), po.view(np.uint32))
+    fa, fb = synth.synth_bow(da, seed=1, n_nodes=120), synth.synth_bow(db, seed=1, n_nodes=120)
+    rng = np.random.default_rng(2)
+    v1, v2 = (rng.random(n1) < 0.85).astype(np.uint8), (rng.random(n2) < 0.85).astype(np.uint8)
+    wb = match.bow_tree(0.75, True, max_targets=n2, max_queries=n1)
+    gn, got = wb.match_frame_and_keyframe(ka, da, fa, kb, db, fb, v1)
+    wn, want = oracle.bow_match_frame_and_keyframe(ka, da, fa, kb, db, fb, 0.75, True, v1)
+    assert gn == wn > 0 and np.array_equal(got, want)
+    gn, got = wb.match_keyframes(ka, da, fa, kb, db, fb, v1, v2)
+    wn, want = oracle.bow_match_keyframes(ka, da, fa, kb, db, fb, 0.75, True, v1, v2)
+    assert gn == wn > 0 and np.array_equal(got, want)
+    # frame b is frame a moved by (3, 2) pixels: as two views, a sideways translation (R = I), bearings through a pinhole of focal length 500
+    def bearings(kp):
+        b = np.stack([(kp["x"].astype(np.float64) - 376.0) / 500.0, (kp["y"].astype(np.float64) - 240.0) / 500.0, np.ones(len(kp))], 1)
+        return b / np.linalg.norm(b, axis=1)[:, None]
+
+    t12 = np.array([3.0, 2.0, 0.0]) / np.sqrt(13.0)
+    E12 = np.array([[0, -t12[2], t12[1]], [t12[2], 0, -t12[0]], [-t12[1], t12[0], 0]])
+    x1 = np.where(rng.random(n1) < 0.4, ka["x"] - 10, -1.0).astype(np.float32)
+    x2 = np.where(rng.random(n2) < 0.4, kb["x"] - 10, -1.0).astype(np.float32)
+    sf = np.cumprod(np.concatenate([[1.0], np.full(7, 1.2)]).astype(np.float32)).astype(np.float32)
+    wt = match.robust_triangulation(0.6, True, max_targets=n2, max_queries=n1)
+    gn, pairs = wt.match_for_triangulation(ka, da, fa, bearings(ka), kb, db, fb, bearings(kb), E12, -t12, sf, 1 - v1, 1 - v2, x1, x2)
+    wn, want = oracle.robust_match_for_triangulation(ka, da, fa, bearings(ka), kb, db, fb, bearings(kb), E12, -t12, sf, True, 1 - v1, 1 - v2, x1, x2)
+    idx = np.nonzero(want >= 0)[0]
+    assert gn == wn > 0 and np.array_equal(pairs, np.stack([idx, want[idx]], 1))
+
+    # the reprojecting matchers and fuse: the Sim3 scene at scale 1 (its Sim3 is then the pose itself)
+    rows, cols, n, ck, cd, Tc, lpw, dmm, nrm, ld, valid, sf, (fx, fy, cx, cy) = _sim3_scene(synth, 0, 70, scale=1.0)
+    _, _, _, lk, _, _, Tl, _, _ = _last_and_current(synth, 0, rows, cols, n, 70, 0.0)
+    m = len(lk)
+    rng = np.random.default_rng(3)
+    occ = (rng.random(n) < 0.1).astype(np.uint8)
+    xr = np.where(rng.random(n) < 0.6, ck["x"] - rng.uniform(1, 40, n), -1.0).astype(np.float32)
+    ils = (1.0 / (sf * sf)).astype(np.float32)
+    cam, ocam = _lib.Camera(0, 1, fx, fy, cx, cy, 0.12 * fx, 0.12, cols, rows), oracle.Camera(0, 1, fx, fy, cx, cy, 0.12 * fx, 0.12, cols, rows)
+    gp, ogp = match.grid_params(cols, rows), oracle.grid_params(cols, rows)
+    w = match.projection(0.9, True, max_targets=n, max_queries=m)
+    got, gn = w.match_current_and_last_frames(cam, gp, ck, cd, Tc, lk, lpw, ld, Tl, sf, 7.0, curr_stereo_x_right=xr, curr_occupied=occ, last_valid=valid)
+    want, wn = oracle.projection_match_current_and_last_frames(ocam, ogp, ck, cd, Tc, lk, lpw, ld, Tl, sf, 7.0, True, curr_stereo_x_right=xr,
+                                                               curr_occupied=occ, last_valid=valid)
+    assert gn == wn > 0 and np.array_equal(got, want)
+    got, gn = w.match_frame_and_keyframe(cam, gp, ck, cd, Tc, lk, lpw, dmm, ld, sf, lsf, 10.0, 100, curr_occupied=occ, kf_valid=valid)
+    want, wn = oracle.projection_match_frame_and_keyframe(ocam, ogp, ck, cd, Tc, lk, lpw, dmm, ld, sf, lsf, 10.0, 100, True, curr_occupied=occ,
+                                                          kf_valid=valid)
+    assert gn == wn > 0 and np.array_equal(got, want)
+    got, gn = w.match_by_Sim3_transform(cam, gp, ck, cd, Tc, lpw, dmm, nrm, ld, sf, lsf, 5.0, keyfrm_occupied=occ, lm_valid=valid)
+    want, wn = oracle.projection_match_by_sim3_transform(ocam, ogp, ck, cd, Tc, lpw, dmm, nrm, ld, sf, lsf, 5.0, kf_occupied=occ, lm_valid=valid)
+    assert gn == wn > 0 and np.array_equal(got, want)
+    wf = match.fuse(0.6, max_targets=n, max_queries=m)
+    got, gn = wf.replace_duplication(cam, gp, ck, cd, Tc, lpw, dmm, nrm, ld, sf, ils, lsf, 3.0, keyfrm_stereo_x_right=xr, lm_valid=valid)
+    want, wn = oracle.fuse_replace_duplication(ocam, ogp, ck, cd, Tc, lpw, dmm, nrm, ld, sf, ils, lsf, 3.0, kf_stereo_x_right=xr, lm_valid=valid)
+    assert gn == wn > 0 and np.array_equal(got, want)
+    got, gn = wf.detect_duplication(cam, gp, ck, cd, Tc, lpw, dmm, nrm, ld, sf, lsf, 4.0, lm_valid=valid)
+    want, wn = oracle.fuse_detect_duplication(ocam, ogp, ck, cd, Tc, lpw, dmm, nrm, ld, sf, lsf, 4.0, lm_valid=valid)
+    assert gn == wn > 0 and np.array_equal(got, want)
+
+    # projection::match_keyframes_mutually: n1 == n2 == max_targets == max_queries; the keyframe against a copy of itself (Sim3_12 = identity),
+    # landmark i the one keypoint i was back-projected from (the scene lists them permuted)
+    own = np.empty(n, np.int64)   # lk[:n] are the keypoints ck in permuted order (same x, y): own[i] = the position of keypoint i among them
+    own[np.lexsort((ck["y"], ck["x"]))] = np.lexsort((lk["y"][:n], lk["x"][:n]))
+    assert np.array_equal(lk["x"][:n][own], ck["x"]) and np.array_equal(lk["y"][:n][own], ck["y"])
+    X, dm, l1, v = lpw[:n][own], np.ascontiguousarray(dmm[:n][own]), ld[:n][own], valid[:n][own]
+    cam, ocam = _lib.Camera(0, 0, fx, fy, cx, cy, 0.0, 0.0, cols, rows), oracle.Camera(0, 0, fx, fy, cx, cy, 0.0, 0.0, cols, rows)
+    wm = match.projection(0.9, False, max_targets=n, max_queries=n)
+    gn, got = wm.match_keyframes_mutually(cam, gp, ck, cd, Tc, X, dm, l1, v, ck, cd, Tc, X, dm, l1, v, 1.0, np.eye(3), np.zeros(3), sf, lsf, 7.5)
+    wn, want = oracle.projection_match_keyframes_mutually(ocam, ogp, ck, cd, Tc, X, dm, l1, v, ck, cd, Tc, X, dm, l1, v, 1.0, np.eye(3), np.zeros(3),
+                                                          sf, lsf, 7.5)
+    assert gn == wn > 0 and np.array_equal(got, want)
