@@ -31,8 +31,8 @@
 // chi-square gates (k_edge_gate) and the graph build's landmark-order pass (k_edges_by_slot, k_dup_check) on the device.
 // Round 5's three mergers are side-by-side only (a workgroup runs one of the two bodies, chosen by its index): the arithmetic of every block,
 // landmark and keyframe is what it was, the results are the same bits, and a trial is 332 instead of 386 us of kernels (profiles/r05ai_*).
-// Per-edge arithmetic is the expression sequence of k_ba_linearize / the oracle (every product individually rounded), so Hpl, Hll and bl
-// are bit-identical to the CPU oracle; Hpp, bp and chi2 are tree sums (1e-15 relative), identical from run to run.
+// Per-edge arithmetic is ba_edge.h's, shared with k_ba_linearize: the oracle's expression sequence (every product individually rounded), so
+// Hpl, Hll and bl are bit-identical to the CPU oracle; Hpp, bp and chi2 are tree sums (1e-15 relative), identical from run to run.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -42,161 +42,10 @@
 #include <mutex>
 #include <vector>
 
-#include "ovs_common.h"
-
-#define OVS_LAUNCH_TRY(name)                                  \
-    do {                                                      \
-        hipError_t _e = hipGetLastError();                    \
-        if (_e != hipSuccess) {                               \
-            ovs::set_last_error("launch of " name, _e);       \
-            return OVS_ERR_HIP;                               \
-        }                                                     \
-    } while (0)
+#include "ba_edge.h"
+#include "ba_internal.h"
 
 namespace ovs {
-
-// ba_solve.hip: the padded layout of the reduced camera system
-int dense_solve_pad(int n);
-size_t dense_solve_doubles(int n);
-
-struct GEdge {   // mono and stereo observations in one record; stereo iff index >= n_mono
-    int32_t pose, pt;
-    double ox, oy, oxr, w;
-};
-
-// Jacobians are carried as [3][6] arrays; the third row is zero for a mono edge (never read: dot3 stops at two rows)
-__device__ __forceinline__ double dot3(const double (&A)[3][6], int a, const double (&B)[3][6], int b, bool stereo) {
-    double s = A[0][a] * B[0][b];
-    s = s + A[1][a] * B[1][b];
-    if (stereo) s = s + A[2][a] * B[2][b];
-    return s;
-}
-
-// residual, Jacobians, Huber weight of one perspective edge -- the operation order of k_ba_linearize<2|3> (model 0) and of the CPU oracle
-__device__ __forceinline__ void edge_lin(const double* __restrict__ P, const double* __restrict__ X, const GEdge& ed, bool stereo,
-                                         const ovs_ba_cam& cam, double bf, double huber, double (&Jl)[3][6], double (&Jp)[3][6], double (&r)[3],
-                                         double& W, double& c2, double& rho0) {
-    const double qx = P[3], qy = P[4], qz = P[5], qw = P[6];
-    const double tx2 = 2 * qx, ty2 = 2 * qy, tz2 = 2 * qz;
-    const double twx = tx2 * qw, twy = ty2 * qw, twz = tz2 * qw;
-    const double txx = tx2 * qx, txy = ty2 * qx, txz = tz2 * qx;
-    const double tyy = ty2 * qy, tyz = tz2 * qy, tzz = tz2 * qz;
-    const double R[3][3] = {{1 - (tyy + tzz), txy - twz, txz + twy}, {txy + twz, 1 - (txx + tzz), tyz - twx}, {txz - twy, tyz + twx, 1 - (txx + tyy)}};
-    const double X0 = X[0], X1 = X[1], X2 = X[2];
-    const double x = R[0][0] * X0 + R[0][1] * X1 + R[0][2] * X2 + P[0];
-    const double y = R[1][0] * X0 + R[1][1] * X1 + R[1][2] * X2 + P[1];
-    const double z = R[2][0] * X0 + R[2][1] * X1 + R[2][2] * X2 + P[2];
-    const double invz = 1.0 / z, invz2 = invz * invz;
-    double er[3] = {0.0, 0.0, 0.0};
-    const double u = cam.fx * x * invz + cam.cx;
-    er[0] = ed.ox - u;
-    er[1] = ed.oy - (cam.fy * y * invz + cam.cy);
-    double ss = er[0] * er[0] + er[1] * er[1];
-    if (stereo) {
-        er[2] = ed.oxr - (u - bf * invz);
-        ss = ss + er[2] * er[2];
-    }
-    const double w = ed.w;
-    c2 = w * ss;
-    rho0 = c2;
-    double rho1 = 1.0;
-    const double dsqr = huber * huber;
-    if (huber > 0 && c2 > dsqr) {
-        const double sq = sqrt(c2);
-        rho0 = 2 * sq * huber - dsqr;
-        rho1 = huber / sq;
-    }
-#pragma unroll
-    for (int c = 0; c < 6; ++c) Jl[0][c] = Jl[1][c] = Jl[2][c] = 0.0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        Jl[0][c] = -invz * (cam.fx * R[0][c] - cam.fx * x * invz * R[2][c]);
-        Jl[1][c] = -invz * (cam.fy * R[1][c] - cam.fy * y * invz * R[2][c]);
-        Jl[2][c] = stereo ? Jl[0][c] - bf * R[2][c] * invz2 : 0.0;
-    }
-    Jp[0][0] = x * y * invz2 * cam.fx;
-    Jp[0][1] = -(1 + x * x * invz2) * cam.fx;
-    Jp[0][2] = y * invz * cam.fx;
-    Jp[0][3] = -invz * cam.fx;
-    Jp[0][4] = 0;
-    Jp[0][5] = x * invz2 * cam.fx;
-    Jp[1][0] = (1 + y * y * invz2) * cam.fy;
-    Jp[1][1] = -x * y * invz2 * cam.fy;
-    Jp[1][2] = -x * invz * cam.fy;
-    Jp[1][3] = 0;
-    Jp[1][4] = -invz * cam.fy;
-    Jp[1][5] = y * invz2 * cam.fy;
-    if (stereo) {
-        Jp[2][0] = Jp[0][0] - bf * y * invz2;
-        Jp[2][1] = Jp[0][1] + bf * x * invz2;
-        Jp[2][2] = Jp[0][2];
-        Jp[2][3] = Jp[0][3];
-        Jp[2][4] = 0;
-        Jp[2][5] = Jp[0][5] - bf * invz2;
-    } else {
-#pragma unroll
-        for (int c = 0; c < 6; ++c) Jp[2][c] = 0.0;
-    }
-    W = rho1 * w;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) r[k] = -W * er[k];
-}
-
-// the equirectangular edge (model 1; expected: src/openvslam/optimize/g2o/se3/equirectangular_reproj_edge.{h,cc}): the operation order of
-// k_ba_linearize's equirectangular model and of the CPU checker; cam = {cols, rows, -, -}; mono edges only (rows 2 stay zero)
-__device__ __forceinline__ void edge_lin_equirect(const double* __restrict__ P, const double* __restrict__ X, const GEdge& ed, const ovs_ba_cam& cam,
-                                                  double huber, double (&Jl)[3][6], double (&Jp)[3][6], double (&r)[3], double& W, double& c2,
-                                                  double& rho0) {
-    const double qx = P[3], qy = P[4], qz = P[5], qw = P[6];
-    const double tx2 = 2 * qx, ty2 = 2 * qy, tz2 = 2 * qz;
-    const double twx = tx2 * qw, twy = ty2 * qw, twz = tz2 * qw;
-    const double txx = tx2 * qx, txy = ty2 * qx, txz = tz2 * qx;
-    const double tyy = ty2 * qy, tyz = tz2 * qy, tzz = tz2 * qz;
-    const double R[3][3] = {{1 - (tyy + tzz), txy - twz, txz + twy}, {txy + twz, 1 - (txx + tzz), tyz - twx}, {txz - twy, tyz + twx, 1 - (txx + tyy)}};
-    const double X0 = X[0], X1 = X[1], X2 = X[2];
-    const double x = R[0][0] * X0 + R[0][1] * X1 + R[0][2] * X2 + P[0];
-    const double y = R[1][0] * X0 + R[1][1] * X1 + R[1][2] * X2 + P[1];
-    const double z = R[2][0] * X0 + R[2][1] * X1 + R[2][2] * X2 + P[2];
-    const double kPi = 3.14159265358979323846;
-    const double cols = cam.fx, rows = cam.fy;
-    const double L = sqrt((x * x + y * y) + z * z);
-    const double rxz = x * x + z * z;
-    const double theta = ovs_det_atan2(x, z);
-    const double phi = -ovs_det_asin(y / L);
-    const double e0 = ed.ox - cols * (0.5 + theta / (2.0 * kPi));
-    const double e1 = ed.oy - rows * (0.5 - phi / kPi);
-    const double w = ed.w;
-    c2 = w * (e0 * e0 + e1 * e1);
-    rho0 = c2;
-    double rho1 = 1.0;
-    const double dsqr = huber * huber;
-    if (huber > 0 && c2 > dsqr) {
-        const double sq = sqrt(c2);
-        rho0 = 2 * sq * huber - dsqr;
-        rho1 = huber / sq;
-    }
-    const double a0 = -(cols / (2.0 * kPi)) * (1.0 / rxz);
-    const double a1 = -(rows / kPi) * (1.0 / (L * sqrt(rxz)));
-    auto col = [&](double dx, double dy, double dz, double& j0, double& j1) {
-        const double dL = (1.0 / L) * ((x * dx + y * dy) + z * dz);
-        j0 = a0 * (z * dx - x * dz);
-        j1 = a1 * (L * dy - y * dL);
-    };
-#pragma unroll
-    for (int c = 0; c < 6; ++c) Jl[0][c] = Jl[1][c] = Jl[2][c] = Jp[2][c] = 0.0;
-    col(0.0, -z, y, Jp[0][0], Jp[1][0]);
-    col(z, 0.0, -x, Jp[0][1], Jp[1][1]);
-    col(-y, x, 0.0, Jp[0][2], Jp[1][2]);
-    col(1.0, 0.0, 0.0, Jp[0][3], Jp[1][3]);
-    col(0.0, 1.0, 0.0, Jp[0][4], Jp[1][4]);
-    col(0.0, 0.0, 1.0, Jp[0][5], Jp[1][5]);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) col(R[0][c], R[1][c], R[2][c], Jl[0][c], Jl[1][c]);
-    W = rho1 * w;
-    r[0] = -W * e0;
-    r[1] = -W * e1;
-    r[2] = 0.0;
-}
 
 struct GraphDev {   // device views shared by the kernels
     const GEdge* edges;
@@ -344,10 +193,7 @@ __device__ __forceinline__ void lin_pose_half(const GraphDev& g, const int half_
             if (lane == 63) s_part[wv][t] = x;
             ++t;
         }
-        double gq = Jp[0][a] * r[0];
-        gq = gq + Jp[1][a] * r[1];
-        if (stereo) gq = gq + Jp[2][a] * r[2];
-        const double x = wave_sum_lane63(gq);
+        const double x = wave_sum_lane63(dot3r(Jp, a, r, stereo));
         if (lane == 63) s_part[wv][t] = x;
         ++t;
     }
@@ -388,10 +234,7 @@ __device__ __forceinline__ void lin_landmark_wg(const GraphDev& g, const int wg,
                 for (int a = 0; a < 3; ++a) {
 #pragma unroll
                     for (int b = 0; b < 3; ++b) s_c[3 * a + b][tid] = W * dot3(Jl, a, Jl, b, stereo);
-                    double t = Jl[0][a] * r[0];
-                    t = t + Jl[1][a] * r[1];
-                    if (stereo) t = t + Jl[2][a] * r[2];
-                    s_c[9 + a][tid] = t;
+                    s_c[9 + a][tid] = dot3r(Jl, a, r, stereo);
                 }
                 s_c[12][tid] = c2;
                 s_c[13][tid] = rho0;
@@ -1285,36 +1128,14 @@ __global__ __launch_bounds__(256) void k_edge_chi2(GraphDev g, const double* __r
     if (e >= g.n_edge) return;
     const GEdge ed = g.edges[e];
     const bool stereo = e >= g.n_mono;
-    const double* P = poses + 7 * (size_t)ed.pose;
-    const double* X = points + 3 * (size_t)ed.pt;
-    const double qx = P[3], qy = P[4], qz = P[5], qw = P[6];
-    const double tx2 = 2 * qx, ty2 = 2 * qy, tz2 = 2 * qz;
-    const double twx = tx2 * qw, twy = ty2 * qw, twz = tz2 * qw;
-    const double txx = tx2 * qx, txy = ty2 * qx, txz = tz2 * qx;
-    const double tyy = ty2 * qy, tyz = tz2 * qy, tzz = tz2 * qz;
-    const double x = (1 - (tyy + tzz)) * X[0] + (txy - twz) * X[1] + (txz + twy) * X[2] + P[0];
-    const double y = (txy + twz) * X[0] + (1 - (txx + tzz)) * X[1] + (tyz - twx) * X[2] + P[1];
-    const double z = (txz - twy) * X[0] + (tyz + twx) * X[1] + (1 - (txx + tyy)) * X[2] + P[2];
+    double R[3][3], x, y, z, er[3], L;
+    edge_cam_point(poses + 7 * (size_t)ed.pose, points + 3 * (size_t)ed.pt, R, x, y, z);
     if (g.model == 1) {   // equirectangular: reproj_edge_wrapper::depth_is_positive() is true for this camera model
-        const double kPi = 3.14159265358979323846;
-        const double L = sqrt((x * x + y * y) + z * z);
-        const double theta = ovs_det_atan2(x, z);
-        const double phi = -ovs_det_asin(y / L);
-        const double q0 = ed.ox - g.cam.fx * (0.5 + theta / (2.0 * kPi));
-        const double q1 = ed.oy - g.cam.fy * (0.5 - phi / kPi);
-        chi2[e] = ed.w * (q0 * q0 + q1 * q1);
+        chi2[e] = ed.w * edge_residual_equirect(x, y, z, ed, g.cam, L, er);
         depth_pos[e] = 1;
         return;
     }
-    const double invz = 1.0 / z;
-    const double u = g.cam.fx * x * invz + g.cam.cx;
-    const double e0 = ed.ox - u, e1 = ed.oy - (g.cam.fy * y * invz + g.cam.cy);
-    double ss = e0 * e0 + e1 * e1;
-    if (stereo) {
-        const double e2 = ed.oxr - (u - g.bf * invz);
-        ss = ss + e2 * e2;
-    }
-    chi2[e] = ed.w * ss;
+    chi2[e] = ed.w * edge_residual(x, y, 1.0 / z, ed, stereo, g.cam, g.bf, er);
     depth_pos[e] = z > 0.0 ? 1 : 0;
 }
 
@@ -1361,67 +1182,32 @@ using namespace ovs;
 struct ovs_ba_graph {
     int device = 0;
     int n_pose = 0, n_pt = 0, n_mono = 0, n_stereo = 0, n_free = 0;
-    ovs_ba_cam cam{};
-    double bf = 0;
-    int model = 0;
     std::vector<uint8_t> fixed;
     std::vector<int32_t> slot, slot_pose;   // pose -> reduced-system block (-1 fixed); block -> pose
     // device: ONE allocation + ONE upload per graph (a dozen hipMalloc / hipMemcpy pairs cost more than the kernels of a whole LM trial)
     unsigned char* d_arena = nullptr;
     unsigned char* d_solver_arena = nullptr;
     size_t arena_cap = 0, solver_cap = 0;   // allocation sizes (the arenas come from / go back to g_ba_pool)
-    uint8_t* d_active = nullptr;
-    GEdge* d_edges = nullptr;
-    int32_t *d_lm_start = nullptr, *d_lm_edges = nullptr, *d_lm_nmono = nullptr, *d_pose_start = nullptr, *d_pose_edges = nullptr;
-    uint8_t* d_fixed = nullptr;
-    int32_t *d_pose_pt = nullptr, *d_pair_ab = nullptr, *d_slot_pose = nullptr, *d_slot_of_pose = nullptr, *d_fail = nullptr;
-    int32_t *d_lm_of_slot = nullptr, *d_lm_wg_first = nullptr, *d_chunk_kf = nullptr, *d_chunk_start = nullptr;   // k_linearize's work partition
-    double* d_pose_part = nullptr;
-    GEdge* d_ledges = nullptr;
-    int n_lm_wg = 0, n_chunks = 0;
-    int32_t* d_edge_of = nullptr;   // [n_free x n_pt], solver arena
+    GraphDev dev{};   // what the kernels see (arrays of d_arena, the partition's counts, the camera): filled once by graph_create
+    // arrays of d_arena the solver path's launches name besides `dev`
+    uint8_t* d_active = nullptr;   // dev.active, writable (k_edge_gate)
+    int32_t *d_pair_ab = nullptr, *d_slot_pose = nullptr, *d_slot_of_pose = nullptr;
+    int32_t* d_wg_pair = nullptr;   // [n_pair_wg] k_schur_l's work order: whole rows of the pair table per XCD, -1 = no pair
+    int n_pairs = 0, n_pair_wg = 0;
+    double* d_lm_tmp = nullptr;   // [4 n_pt] per-landmark partials: chi2 pair, max |diagonal|, the gain ratio's scale term
     // the pairs' common landmarks (k_pair_lists): [4 n_pairs + 1] offsets, one (edge of a, edge of b) per entry; pl_bound = sum over the landmarks of
     // n (n + 1) / 2, n = the landmark's edges (graph_create): no list can be longer
-    int32_t *d_pl_cnt = nullptr, *d_pl_off = nullptr;
-    int2* d_pl_ent = nullptr;
     size_t pl_bound = 0;
     bool pl_ready = false;   // the lists exist (solver work space created, bound within the cap)
-    int n_pairs = 0;
-    int32_t* d_wg_pair = nullptr;   // [n_pair_wg] k_schur_l's work order: whole rows of the pair table per XCD, -1 = no pair
-    int n_pair_wg = 0;
-    double* d_lm_tmp = nullptr;   // [4 n_pt] per-landmark partials: chi2 pair, max |diagonal|, the gain ratio's scale term
-    // solver work space (allocated on first use: ovs_ba_graph_linearize_dev alone does not need it)
+    // solver work space (d_solver_arena, allocated on first use: ovs_ba_graph_linearize_dev alone does not need it)
     double *d_Hinv = nullptr, *d_Y = nullptr, *d_S = nullptr, *d_rhs = nullptr, *d_dxp = nullptr, *d_scal = nullptr;
+    int32_t* d_fail = nullptr;      // two failure words, 256 bytes behind d_scal
+    int32_t* d_edge_of = nullptr;   // [n_free x n_pt]
+    int32_t *d_pl_cnt = nullptr, *d_pl_off = nullptr;
+    int2* d_pl_ent = nullptr;
     int s_pitch = 0;   // doubles per row of d_S
 
-    GraphDev view() const {
-        GraphDev g;
-        g.edges = d_edges;
-        g.n_mono = n_mono;
-        g.n_edge = n_mono + n_stereo;
-        g.n_pose = n_pose;
-        g.n_pt = n_pt;
-        g.lm_start = d_lm_start;
-        g.lm_edges = d_lm_edges;
-        g.lm_nmono = d_lm_nmono;
-        g.pose_start = d_pose_start;
-        g.pose_edges = d_pose_edges;
-        g.pose_pt = d_pose_pt;
-        g.fixed = d_fixed;
-        g.active = d_active;
-        g.ledges = d_ledges;
-        g.lm_of_slot = d_lm_of_slot;
-        g.lm_wg_first = d_lm_wg_first;
-        g.chunk_kf = d_chunk_kf;
-        g.chunk_start = d_chunk_start;
-        g.pose_part = d_pose_part;
-        g.n_lm_wg = n_lm_wg;
-        g.n_chunks = n_chunks;
-        g.cam = cam;
-        g.bf = bf;
-        g.model = model;
-        return g;
-    }
+    const GraphDev& view() const { return dev; }
     int n_edge() const { return n_mono + n_stereo; }
 };
 
@@ -1432,13 +1218,13 @@ namespace {
 ovs_status graph_linearize(ovs_ba_graph* g, const double* d_poses, const double* d_points, double huber_mono, double huber_stereo, double* d_Hpp,
                            double* d_bp, double* d_Hll, double* d_bl, double* d_Hpl, double* d_chi3, hipStream_t s, double* d_chi_mirror = nullptr,
                            bool trial_scale = false, unsigned long long* host_ll = nullptr, unsigned int seq = 0) {
-    const GraphDev v = g->view();
+    const GraphDev& v = g->view();
     // One launch for both halves (k_linearize2): config 5 0.0325 -> 0.0249 ms, a million edges 0.124 -> 0.1005 ms per linearisation against the
     // two launches of rounds 5-6 (a launch and its gap less; the Hpl records leave through LDS as whole lines; the keyframe side's stores and the
     // landmark side's LDS reductions overlap). Before the stores were coalesced the merged launch LOST at a million edges (0.131 against
     // 0.125 ms): the partial-line write requests of the keyframe side were what both halves queued behind.
-    const unsigned n_wg = (unsigned)(2 * g->n_chunks + g->n_lm_wg);
-    if (g->model == 1)
+    const unsigned n_wg = (unsigned)(2 * v.n_chunks + v.n_lm_wg);
+    if (v.model == 1)
         hipLaunchKernelGGL(k_linearize2<1>, dim3(n_wg), dim3(256), 0, s, v, d_poses, d_points, huber_mono, huber_stereo, d_Hpl, d_Hll, d_bl, g->d_lm_tmp, d_chi3);
     else
         hipLaunchKernelGGL(k_linearize2<0>, dim3(n_wg), dim3(256), 0, s, v, d_poses, d_points, huber_mono, huber_stereo, d_Hpl, d_Hll, d_bl, g->d_lm_tmp, d_chi3);
@@ -1555,9 +1341,6 @@ static ovs_status graph_create(int model, int32_t device, int32_t n_pose, const 
     g->n_pt = n_pt;
     g->n_mono = n_mono;
     g->n_stereo = n_stereo;
-    g->cam = *cam;
-    g->bf = focal_x_baseline;
-    g->model = model;
     g->fixed.assign((size_t)n_pose, 0);
     if (pose_fixed) g->fixed.assign(pose_fixed, pose_fixed + n_pose);
     g->slot.assign((size_t)n_pose, -1);
@@ -1572,40 +1355,29 @@ static ovs_status graph_create(int model, int32_t device, int32_t n_pose, const 
     // The image is laid out first and filled in place: no per-array vector, no second copy.
     // Round 6: the image is page-locked, so the edge records (4.8 of the 6.0 MB at config 5) go up while the host is still sorting.
     struct Scratch {
-        std::vector<int32_t> edge_pose, edge_pt, fl, fp, seen;
-        unsigned char* image = nullptr;   // page-locked
-        size_t image_cap = 0;
-        ~Scratch() {
-            if (image) (void)hipHostFree(image);
-        }
+        std::vector<int32_t> edge_pose, edge_pt, fl, fp;
+        ovs::PinnedBuffer image;
     };
     static thread_local Scratch sc;
-    size_t top = 0;
-    auto place = [&top](size_t bytes) {   // 256-byte aligned offsets
-        const size_t off = (top + 255) & ~(size_t)255;
-        top = off + std::max<size_t>(bytes, 1);
-        return off;
-    };
+    // One layout for the host image and the device arena: the arrays the host fills (uploaded as they are), then, on the device, scratch the
+    // kernels write; in the image, only the word the duplicate check's verdict comes down to.
+    ovs::ArenaLayout lay;
     const int nf = g->n_free, n_pairs = nf * (nf + 1) / 2;
-    const size_t o_edges = place(sizeof(GEdge) * (size_t)ne), o_lm_start = place(sizeof(int32_t) * ((size_t)n_pt + 1)),
-                 o_lm_edges = place(sizeof(int32_t) * (size_t)ne), o_lm_nmono = place(sizeof(int32_t) * (size_t)n_pt),
-                 o_pose_start = place(sizeof(int32_t) * ((size_t)n_pose + 1)), o_pose_edges = place(sizeof(int32_t) * (size_t)ne),
-                 o_fixed = place((size_t)n_pose), o_active = place((size_t)ne), o_slot_of_pose = place(sizeof(int32_t) * (size_t)n_pose),
-                 o_pose_pt = place(sizeof(int32_t) * (size_t)ne), o_pair_ab = place(sizeof(int32_t) * 2 * (size_t)n_pairs),
-                 o_slot_pose = place(sizeof(int32_t) * (size_t)nf), o_wg_pair = place(sizeof(int32_t) * 8 * ((size_t)n_pairs / 8 + (size_t)nf + 1));
-    // k_linearize's work partition (sizes are upper bounds: the tables are built below, from the counting sorts)
-    const size_t max_chunks = (size_t)ne / kPoseChunk + (size_t)n_pose;
-    const size_t o_lm_wg_first = place(sizeof(int32_t) * ((size_t)n_pt + 1)),
-                 o_chunk_kf = place(sizeof(int32_t) * max_chunks), o_chunk_start = place(sizeof(int32_t) * ((size_t)n_pose + 1));
-    const size_t upload_bytes = (top + 255) & ~(size_t)255;   // what the device reads before writing it ends here; scratch follows
-    const size_t o_dup_host = place(sizeof(unsigned long long));   // (host image only: where the duplicate check's word comes down to)
-    const size_t image_bytes = top;
-    top = upload_bytes;
-    const size_t o_lm_of_slot = place(sizeof(int32_t) * (size_t)ne), o_dup = place(sizeof(unsigned long long));
-    const size_t o_lm_tmp = place(sizeof(double) * 4 * (size_t)n_pt);
-    const size_t o_pose_part = place(sizeof(double) * 27 * 2 * max_chunks);   // (k_linearize2: one sum per HALF chunk)
-    const size_t o_ledges = place(sizeof(GEdge) * (size_t)ne);
-    const size_t arena_bytes = top;
+    const size_t max_chunks = (size_t)ne / kPoseChunk + (size_t)n_pose;   // (an upper bound: the partition is built below, from the counting sorts)
+    const size_t o_edges = lay.place<GEdge>((size_t)ne), o_lm_start = lay.place<int32_t>((size_t)n_pt + 1), o_lm_edges = lay.place<int32_t>((size_t)ne),
+                 o_lm_nmono = lay.place<int32_t>((size_t)n_pt), o_pose_start = lay.place<int32_t>((size_t)n_pose + 1),
+                 o_pose_edges = lay.place<int32_t>((size_t)ne), o_fixed = lay.place<uint8_t>((size_t)n_pose), o_active = lay.place<uint8_t>((size_t)ne),
+                 o_slot_of_pose = lay.place<int32_t>((size_t)n_pose), o_pose_pt = lay.place<int32_t>((size_t)ne),
+                 o_pair_ab = lay.place<int32_t>(2 * (size_t)n_pairs), o_slot_pose = lay.place<int32_t>((size_t)nf),
+                 o_wg_pair = lay.place<int32_t>(8 * ((size_t)n_pairs / 8 + (size_t)nf + 1)), o_lm_wg_first = lay.place<int32_t>((size_t)n_pt + 1),
+                 o_chunk_kf = lay.place<int32_t>(max_chunks), o_chunk_start = lay.place<int32_t>((size_t)n_pose + 1);
+    const size_t upload_bytes = lay.bytes();   // what the device reads before writing it ends here
+    ovs::ArenaLayout host = lay;
+    const size_t o_dup_host = host.place<unsigned long long>(1), image_bytes = host.bytes();
+    const size_t o_lm_of_slot = lay.place<int32_t>((size_t)ne), o_dup = lay.place<unsigned long long>(1), o_lm_tmp = lay.place<double>(4 * (size_t)n_pt),
+                 o_pose_part = lay.place<double>(27 * 2 * max_chunks),   // (k_linearize2: one sum per HALF chunk)
+                 o_ledges = lay.place<GEdge>((size_t)ne);
+    const size_t arena_bytes = lay.bytes();
 #define G_TRY(expr)                            \
     do {                                       \
         hipError_t _e = (expr);                \
@@ -1615,24 +1387,48 @@ static ovs_status graph_create(int model, int32_t device, int32_t n_pose, const 
             return OVS_ERR_HIP;                \
         }                                      \
     } while (0)
-    if (sc.image_cap < image_bytes) {
-        if (sc.image) (void)hipHostFree(sc.image);
-        sc.image = nullptr;
-        sc.image_cap = 0;
-        const size_t cap = image_bytes + image_bytes / 4;   // (head room: the next local map is a little larger more often than not)
-        G_TRY(hipHostMalloc(reinterpret_cast<void**>(&sc.image), cap, hipHostMallocDefault));
-        sc.image_cap = cap;
-    }
-    unsigned char* const img = sc.image;
+    G_TRY(sc.image.ensure(image_bytes, image_bytes + image_bytes / 4));   // (head room: the next local map is a little larger more often than not)
+    unsigned char* const img = sc.image.p;
     g->d_arena = g_ba_pool.take(device, arena_bytes, &g->arena_cap);
     G_TRY(g->d_arena ? hipSuccess : hipErrorOutOfMemory);
-    GEdge* const edges = reinterpret_cast<GEdge*>(img + o_edges);
-    int32_t* const lm_start = reinterpret_cast<int32_t*>(img + o_lm_start);
-    int32_t* const lm_edges = reinterpret_cast<int32_t*>(img + o_lm_edges);
-    int32_t* const lm_nmono = reinterpret_cast<int32_t*>(img + o_lm_nmono);
-    int32_t* const pose_start = reinterpret_cast<int32_t*>(img + o_pose_start);
-    int32_t* const pose_edges = reinterpret_cast<int32_t*>(img + o_pose_edges);
-    int32_t* const pose_pt = reinterpret_cast<int32_t*>(img + o_pose_pt);
+    using AL = ovs::ArenaLayout;
+    unsigned char* const A = g->d_arena;
+    {   // the kernels' view and the handle's own pointers, once
+        GraphDev& v = g->dev;
+        v.edges = AL::at<GEdge>(A, o_edges);
+        v.n_mono = n_mono;
+        v.n_edge = ne;
+        v.n_pose = n_pose;
+        v.n_pt = n_pt;
+        v.lm_start = AL::at<int32_t>(A, o_lm_start);
+        v.lm_edges = AL::at<int32_t>(A, o_lm_edges);
+        v.lm_nmono = AL::at<int32_t>(A, o_lm_nmono);
+        v.pose_start = AL::at<int32_t>(A, o_pose_start);
+        v.pose_edges = AL::at<int32_t>(A, o_pose_edges);
+        v.pose_pt = AL::at<int32_t>(A, o_pose_pt);
+        v.fixed = AL::at<uint8_t>(A, o_fixed);
+        v.active = g->d_active = AL::at<uint8_t>(A, o_active);
+        v.ledges = AL::at<GEdge>(A, o_ledges);
+        v.lm_of_slot = AL::at<int32_t>(A, o_lm_of_slot);
+        v.lm_wg_first = AL::at<int32_t>(A, o_lm_wg_first);
+        v.chunk_kf = AL::at<int32_t>(A, o_chunk_kf);
+        v.chunk_start = AL::at<int32_t>(A, o_chunk_start);
+        v.pose_part = AL::at<double>(A, o_pose_part);
+        v.cam = *cam;
+        v.bf = focal_x_baseline;
+        v.model = model;
+        g->d_lm_tmp = AL::at<double>(A, o_lm_tmp);
+        g->d_slot_of_pose = AL::at<int32_t>(A, o_slot_of_pose);
+        if (nf > 0) {
+            g->d_pair_ab = AL::at<int32_t>(A, o_pair_ab);
+            g->d_wg_pair = AL::at<int32_t>(A, o_wg_pair);
+            g->d_slot_pose = AL::at<int32_t>(A, o_slot_pose);
+        }
+    }
+    GEdge* const edges = AL::at<GEdge>(img, o_edges);
+    int32_t *const lm_start = AL::at<int32_t>(img, o_lm_start), *const lm_edges = AL::at<int32_t>(img, o_lm_edges),
+                   *const lm_nmono = AL::at<int32_t>(img, o_lm_nmono), *const pose_start = AL::at<int32_t>(img, o_pose_start),
+                   *const pose_edges = AL::at<int32_t>(img, o_pose_edges), *const pose_pt = AL::at<int32_t>(img, o_pose_pt);
     if (sc.edge_pose.size() < (size_t)ne) {
         sc.edge_pose.resize((size_t)ne);
         sc.edge_pt.resize((size_t)ne);
@@ -1678,7 +1474,7 @@ static ovs_status graph_create(int model, int32_t device, int32_t n_pose, const 
     }
     const double t_p1 = now();
     // the records are final: they travel (null stream, page-locked source: the call returns at once) under the remaining passes
-    const size_t early_bytes = std::min(upload_bytes, (o_edges + sizeof(GEdge) * (size_t)ne + 255) & ~(size_t)255);
+    const size_t early_bytes = o_lm_start;   // (the records are the image's first array: they end where the next one starts)
     if (ne > 0) G_TRY(hipMemcpyAsync(g->d_arena, img, early_bytes, hipMemcpyHostToDevice, nullptr));
     for (int j = 0; j < n_pt; ++j) lm_start[(size_t)j + 1] += lm_start[j];
     for (int k = 0; k < n_pose; ++k) pose_start[(size_t)k + 1] += pose_start[k];
@@ -1698,7 +1494,7 @@ static ovs_status graph_create(int model, int32_t device, int32_t n_pose, const 
     // landmark would need cross terms while Hpp / Hll / rhs would still count both, so such an edge list is refused -- moved to the device in
     // round 6: k_edges_by_slot, k_dup_check below.)
     {
-        int32_t* const wg_first = reinterpret_cast<int32_t*>(img + o_lm_wg_first);
+        int32_t* const wg_first = AL::at<int32_t>(img, o_lm_wg_first);
         int n_wg = 0, first = 0;
         size_t pl_bound = 0;
         for (int j = 0; j < n_pt; ++j) {
@@ -1711,18 +1507,17 @@ static ovs_status graph_create(int model, int32_t device, int32_t n_pose, const 
         }
         wg_first[n_wg++] = first;
         wg_first[n_wg] = n_pt;
-        g->n_lm_wg = n_wg;
+        g->dev.n_lm_wg = n_wg;
         g->pl_bound = pl_bound;
         // k_linearize2's keyframe side: chunks of kPoseChunk entries of a keyframe's edge list (two workgroups each)
-        int32_t* const chunk_kf = reinterpret_cast<int32_t*>(img + o_chunk_kf);
-        int32_t* const chunk_start = reinterpret_cast<int32_t*>(img + o_chunk_start);
+        int32_t *const chunk_kf = AL::at<int32_t>(img, o_chunk_kf), *const chunk_start = AL::at<int32_t>(img, o_chunk_start);
         int n_ch = 0;
         for (int k = 0; k < n_pose; ++k) {
             chunk_start[k] = n_ch;
             for (int i = pose_start[k]; i < pose_start[(size_t)k + 1]; i += kPoseChunk) chunk_kf[n_ch++] = k;
         }
         chunk_start[n_pose] = n_ch;
-        g->n_chunks = n_ch;
+        g->dev.n_chunks = n_ch;
     }
     const double t1 = now();
     std::memcpy(img + o_fixed, g->fixed.data(), (size_t)n_pose);
@@ -1730,7 +1525,7 @@ static ovs_status graph_create(int model, int32_t device, int32_t n_pose, const 
     std::memcpy(img + o_slot_of_pose, g->slot.data(), sizeof(int32_t) * (size_t)n_pose);   // keyframe -> block of the reduced system or -1
     // reduced system: the blocks (a, b), a <= b in slot order, one workgroup each (which landmarks two keyframes share is found on the device)
     if (nf > 0) {
-        int32_t* const pab = reinterpret_cast<int32_t*>(img + o_pair_ab);
+        int32_t* const pab = AL::at<int32_t>(img, o_pair_ab);
         // a-major: a row (a, a .. nf - 1) stays together (k_schur_l hands contiguous runs of pairs to one XCD) and starts with its longest list,
         // the diagonal pair's (all of a's landmarks). "All diagonal pairs first" was measured: no change.
         int p = 0;
@@ -1744,7 +1539,7 @@ static ovs_status graph_create(int model, int32_t device, int32_t n_pose, const 
         // k_schur_l's work order. Rows are dealt to the eight XCDs in serpentine order (rows 0 .. 7 to XCDs 0 .. 7, rows 8 .. 15 to XCDs 7 .. 0,
         // ...: row a has nf - a pairs, so the eight sums come out within a row's length of each other); XCD x's i-th pair is workgroup 8 i + x.
         {
-            int32_t* const wp = reinterpret_cast<int32_t*>(img + o_wg_pair);
+            int32_t* const wp = AL::at<int32_t>(img, o_wg_pair);
             int fill[8] = {0, 0, 0, 0, 0, 0, 0, 0};
             const int cap = n_pairs / 8 + nf + 1;
             for (int i = 0; i < 8 * cap; ++i) wp[i] = -1;
@@ -1763,28 +1558,12 @@ static ovs_status graph_create(int model, int32_t device, int32_t n_pose, const 
         const size_t from = ne > 0 ? early_bytes : 0;
         if (upload_bytes > from) G_TRY(hipMemcpyAsync(g->d_arena + from, img + from, upload_bytes - from, hipMemcpyHostToDevice, nullptr));
     }
-    unsigned char* A = g->d_arena;
-    g->d_edges = reinterpret_cast<GEdge*>(A + o_edges);
-    g->d_lm_start = reinterpret_cast<int32_t*>(A + o_lm_start);
-    g->d_lm_edges = reinterpret_cast<int32_t*>(A + o_lm_edges);
-    g->d_lm_nmono = reinterpret_cast<int32_t*>(A + o_lm_nmono);
-    g->d_pose_start = reinterpret_cast<int32_t*>(A + o_pose_start);
-    g->d_pose_edges = reinterpret_cast<int32_t*>(A + o_pose_edges);
-    g->d_fixed = A + o_fixed;
-    g->d_active = A + o_active;
-    g->d_lm_tmp = reinterpret_cast<double*>(A + o_lm_tmp);
-    g->d_lm_of_slot = reinterpret_cast<int32_t*>(A + o_lm_of_slot);
-    g->d_lm_wg_first = reinterpret_cast<int32_t*>(A + o_lm_wg_first);
-    g->d_chunk_kf = reinterpret_cast<int32_t*>(A + o_chunk_kf);
-    g->d_chunk_start = reinterpret_cast<int32_t*>(A + o_chunk_start);
-    g->d_pose_part = reinterpret_cast<double*>(A + o_pose_part);
-    g->d_ledges = reinterpret_cast<GEdge*>(A + o_ledges);
     if (ne > 0) {   // null stream: ordered behind the upload above and before whatever stream the caller linearises on (the wait costs ~10 us)
-        unsigned long long* const d_dup = reinterpret_cast<unsigned long long*>(A + o_dup);
-        hipLaunchKernelGGL(k_edges_by_slot, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, nullptr, g->d_edges, g->d_lm_edges, ne, g->d_ledges,
-                           g->d_lm_of_slot, d_dup);
+        unsigned long long* const d_dup = AL::at<unsigned long long>(A, o_dup);
+        hipLaunchKernelGGL(k_edges_by_slot, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, nullptr, g->dev.edges, g->dev.lm_edges, ne,
+                           AL::at<GEdge>(A, o_ledges), AL::at<int32_t>(A, o_lm_of_slot), d_dup);
         G_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_dup_check, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, nullptr, g->d_ledges, g->d_lm_start, ne, d_dup);
+        hipLaunchKernelGGL(k_dup_check, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, nullptr, g->dev.ledges, g->dev.lm_start, ne, d_dup);
         G_TRY(hipGetLastError());
         G_TRY(hipMemcpyAsync(img + o_dup_host, d_dup, sizeof(unsigned long long), hipMemcpyDeviceToHost, nullptr));
     }
@@ -1798,13 +1577,6 @@ static ovs_status graph_create(int model, int32_t device, int32_t n_pose, const 
             ovs_ba_graph_destroy(g);
             return OVS_ERR_INVALID;
         }
-    }
-    g->d_slot_of_pose = reinterpret_cast<int32_t*>(A + o_slot_of_pose);
-    g->d_pose_pt = reinterpret_cast<int32_t*>(A + o_pose_pt);
-    if (g->n_free > 0) {
-        g->d_pair_ab = reinterpret_cast<int32_t*>(A + o_pair_ab);
-        g->d_wg_pair = reinterpret_cast<int32_t*>(A + o_wg_pair);
-        g->d_slot_pose = reinterpret_cast<int32_t*>(A + o_slot_pose);
     }
 #undef G_TRY
     if (trace)
@@ -1845,7 +1617,6 @@ namespace ovs {
 // The reduced camera system is stored the way the device solver wants it (ba_solve.hip): pitch n_pad = 6 n_free rounded up to 16, an identity
 // block on the padding, the right-hand side as row n_pad, zero rows behind it. The padding survives a solve, so it is written once here.
 static ovs_status solver_workspace_create(ovs_ba_graph* g, hipStream_t s);
-ovs_status ba_graph_reset_system(ovs_ba_graph* g, hipStream_t s);
 
 ovs_status ba_graph_ensure_solver(ovs_ba_graph* g, hipStream_t s) {
     if (g->d_Hinv) return OVS_OK;
@@ -1862,44 +1633,45 @@ ovs_status ba_graph_ensure_solver(ovs_ba_graph* g, hipStream_t s) {
 static ovs_status solver_workspace_create(ovs_ba_graph* g, hipStream_t s) {
     const size_t ne = std::max<size_t>((size_t)g->n_edge(), 1);
     const int n = 6 * std::max(g->n_free, 1), n_pad = dense_solve_pad(n);
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t sys = dense_solve_doubles(n);
-    const size_t b_hinv = al(sizeof(double) * 9 * (size_t)g->n_pt), b_y = al(sizeof(double) * 18 * ne),
-                 b_s = al(sizeof(double) * (sys + 6 * (size_t)g->n_pose)), b_dxp = al(sizeof(double) * 6 * (size_t)g->n_pose),
-                 b_tab = al(sizeof(int32_t) * (size_t)std::max(g->n_free, 1) * (size_t)g->n_pt);
     const size_t n_lists = (size_t)4 * (size_t)std::max(g->n_pairs, 0);
     // the lists' offsets are 32-bit and their storage is sized by the bound: a map whose bound is beyond 2^28 entries (2 GB; e.g. hundreds of
     // keyframes that all observe the same landmarks) keeps the per-trial scan (k_schur) instead
     const bool pl_ok = g->pl_bound <= ((size_t)1 << 28);
-    const size_t b_plc = al(sizeof(int32_t) * (n_lists + 1)), b_ple = al(sizeof(int2) * (pl_ok ? std::max<size_t>(g->pl_bound, 1) : 1));
-    g->d_solver_arena = g_ba_pool.take(g->device, b_hinv + b_y + b_s + b_dxp + 512 + b_tab + 2 * b_plc + b_ple, &g->solver_cap);
+    ArenaLayout lay;
+    const size_t o_hinv = lay.place<double>(9 * (size_t)g->n_pt), o_y = lay.place<double>(18 * ne),
+                 o_s = lay.place<double>(dense_solve_doubles(n) + 6 * (size_t)g->n_pose),   // padded system
+                 o_dxp = lay.place<double>(6 * (size_t)g->n_pose),
+                 o_scal = lay.place<double>(32), o_fail = lay.place<int32_t>(64),   // (256 bytes each: one 264-byte download takes d_scal and both failure words)
+                 o_tab = lay.place<int32_t>((size_t)std::max(g->n_free, 1) * (size_t)g->n_pt), o_pl_cnt = lay.place<int32_t>(n_lists + 1),
+                 o_pl_off = lay.place<int32_t>(n_lists + 1), o_pl_ent = lay.place<int2>(pl_ok ? std::max<size_t>(g->pl_bound, 1) : 1);
+    g->d_solver_arena = g_ba_pool.take(g->device, lay.bytes(), &g->solver_cap);
     OVS_HIP_TRY(g->d_solver_arena ? hipSuccess : hipErrorOutOfMemory);
-    unsigned char* A = g->d_solver_arena;
-    g->d_Hinv = reinterpret_cast<double*>(A);
-    g->d_Y = reinterpret_cast<double*>(A + b_hinv);
-    g->d_S = reinterpret_cast<double*>(A + b_hinv + b_y);   // padded system
-    g->d_dxp = reinterpret_cast<double*>(A + b_hinv + b_y + b_s);
-    g->d_scal = reinterpret_cast<double*>(A + b_hinv + b_y + b_s + b_dxp);
-    g->d_fail = reinterpret_cast<int32_t*>(A + b_hinv + b_y + b_s + b_dxp + 256);
-    g->d_edge_of = reinterpret_cast<int32_t*>(A + b_hinv + b_y + b_s + b_dxp + 512);
+    unsigned char* const A = g->d_solver_arena;
+    g->d_Hinv = ArenaLayout::at<double>(A, o_hinv);
+    g->d_Y = ArenaLayout::at<double>(A, o_y);
+    g->d_S = ArenaLayout::at<double>(A, o_s);
+    g->d_dxp = ArenaLayout::at<double>(A, o_dxp);
+    g->d_scal = ArenaLayout::at<double>(A, o_scal);
+    g->d_fail = ArenaLayout::at<int32_t>(A, o_fail);
+    g->d_edge_of = ArenaLayout::at<int32_t>(A, o_tab);
+    g->d_pl_cnt = ArenaLayout::at<int32_t>(A, o_pl_cnt);
+    g->d_pl_off = ArenaLayout::at<int32_t>(A, o_pl_off);
+    g->d_pl_ent = ArenaLayout::at<int2>(A, o_pl_ent);
     OVS_HIP_TRY(hipMemsetAsync(g->d_fail, 0, 2 * sizeof(int32_t), s));   // both failure words (ba_graph_schur)
-    OVS_HIP_TRY(hipMemsetAsync(g->d_edge_of, 0xff, b_tab, s));   // -1
+    OVS_HIP_TRY(hipMemsetAsync(g->d_edge_of, 0xff, o_pl_cnt - o_tab, s));   // -1 (the table and its alignment padding)
     if (g->n_edge() > 0 && g->n_free > 0) {
-        hipLaunchKernelGGL(k_edge_table, dim3((g->n_edge() + 255) / 256), dim3(256), 0, s, g->d_edges, g->n_edge(), g->d_slot_of_pose, g->n_pt, g->d_edge_of);
+        hipLaunchKernelGGL(k_edge_table, dim3((g->n_edge() + 255) / 256), dim3(256), 0, s, g->dev.edges, g->n_edge(), g->d_slot_of_pose, g->n_pt, g->d_edge_of);
         OVS_LAUNCH_TRY("k_edge_table");
     }
-    g->d_pl_cnt = reinterpret_cast<int32_t*>(A + b_hinv + b_y + b_s + b_dxp + 512 + b_tab);
-    g->d_pl_off = reinterpret_cast<int32_t*>(A + b_hinv + b_y + b_s + b_dxp + 512 + b_tab + b_plc);
-    g->d_pl_ent = reinterpret_cast<int2*>(A + b_hinv + b_y + b_s + b_dxp + 512 + b_tab + 2 * b_plc);
     g->pl_ready = false;
     if (pl_ok && g->n_edge() > 0 && g->n_free > 0 && g->n_pairs > 0) {   // behind k_edge_table on the same stream
         g->pl_ready = true;
-        hipLaunchKernelGGL(k_pair_lists<false>, dim3(g->n_pairs), dim3(256), 0, s, g->d_pose_start, g->d_pose_edges, g->d_pose_pt, g->d_pair_ab, g->d_slot_pose,
+        hipLaunchKernelGGL(k_pair_lists<false>, dim3(g->n_pairs), dim3(256), 0, s, g->dev.pose_start, g->dev.pose_edges, g->dev.pose_pt, g->d_pair_ab, g->d_slot_pose,
                            g->d_edge_of, g->n_pt, g->d_pl_cnt, (const int32_t*)nullptr, (int2*)nullptr);
         OVS_LAUNCH_TRY("k_pair_lists<count>");
         hipLaunchKernelGGL(k_scan_i32, dim3(1), dim3(1024), 0, s, g->d_pl_cnt, (int)n_lists, g->d_pl_off);
         OVS_LAUNCH_TRY("k_scan_i32");
-        hipLaunchKernelGGL(k_pair_lists<true>, dim3(g->n_pairs), dim3(256), 0, s, g->d_pose_start, g->d_pose_edges, g->d_pose_pt, g->d_pair_ab, g->d_slot_pose,
+        hipLaunchKernelGGL(k_pair_lists<true>, dim3(g->n_pairs), dim3(256), 0, s, g->dev.pose_start, g->dev.pose_edges, g->dev.pose_pt, g->d_pair_ab, g->d_slot_pose,
                            g->d_edge_of, g->n_pt, (int32_t*)nullptr, g->d_pl_off, g->d_pl_ent);
         OVS_LAUNCH_TRY("k_pair_lists<fill>");
     }
@@ -1935,7 +1707,7 @@ ovs_status ba_graph_schur(ovs_ba_graph* g, const double* d_Hpp, const double* d_
     OVS_LAUNCH_TRY("k_lm_prepare");
     if (g->n_free > 0) {
         if (!tuning().ba_schur_lists || !g->pl_ready)
-            hipLaunchKernelGGL(k_schur, dim3(g->n_free + g->n_pairs), dim3(256), 0, s, v, g->n_free, g->d_pose_pt, g->d_pair_ab, g->d_slot_pose,
+            hipLaunchKernelGGL(k_schur, dim3(g->n_free + g->n_pairs), dim3(256), 0, s, v, g->n_free, g->dev.pose_pt, g->d_pair_ab, g->d_slot_pose,
                                g->d_edge_of, d_Hpp, d_bp, d_bl, d_Hpl, g->d_Y, lambda, g->s_pitch, g->d_S, g->d_rhs);
         else
             hipLaunchKernelGGL(k_schur_l, dim3(g->n_free + g->n_pair_wg), dim3(256), 0, s, v, g->n_free, g->d_pair_ab, g->d_slot_pose, g->d_pl_off,
@@ -1960,7 +1732,7 @@ ovs_status ba_graph_backsub(ovs_ba_graph* g, const double* d_Hpl, const double* 
 ovs_status ba_graph_trial_update(ovs_ba_graph* g, const double* d_T, const double* d_bp, const double* d_Hpl, const double* d_bl, double lambda,
                                  double* d_Tn, double* d_p7n, const double* d_X, double* d_Xn, hipStream_t s, int next_fail_word) {
     const GraphDev v = g->view();
-    hipLaunchKernelGGL(k_trial_update, dim3(1 + g->n_lm_wg), dim3(256), 0, s, v, d_T, g->d_slot_of_pose, g->d_rhs, d_bp, lambda, d_Tn, d_p7n, g->d_dxp,
+    hipLaunchKernelGGL(k_trial_update, dim3(1 + g->dev.n_lm_wg), dim3(256), 0, s, v, d_T, g->d_slot_of_pose, g->d_rhs, d_bp, lambda, d_Tn, d_p7n, g->d_dxp,
                        g->d_scal + 1, g->d_Hinv, d_Hpl, d_bl, d_X, d_Xn, g->d_lm_tmp + 3 * (size_t)g->n_pt, g->d_fail + next_fail_word);
     OVS_LAUNCH_TRY("k_trial_update");
     return OVS_OK;
@@ -1994,15 +1766,6 @@ ovs_status ba_graph_linearize(ovs_ba_graph* g, const double* d_poses, const doub
 }   // namespace ovs
 
 namespace ovs {
-struct BaGraphInfo {
-    int n_free;
-    const int32_t* slot;
-    double *d_S, *d_dxp, *d_scal;
-    int32_t* d_fail;
-    const int32_t* d_slot_of_pose;
-    int s_pitch;
-    double* d_rhs;
-};
 BaGraphInfo ba_graph_info(ovs_ba_graph* g) {
     return BaGraphInfo{g->n_free, g->slot.data(), g->d_S, g->d_dxp, g->d_scal, g->d_fail, g->d_slot_of_pose, g->s_pitch, g->d_rhs};
 }

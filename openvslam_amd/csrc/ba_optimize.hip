@@ -20,47 +20,16 @@
 #include <vector>
 
 #include "ba_host_math.h"
-#include "ovs_common.h"
-
-struct ovs_ba_graph;
+#include "ba_internal.h"
 
 namespace ovs {
-// ba_graph.hip
-ovs_status ba_graph_ensure_solver(ovs_ba_graph* g, hipStream_t s);
-ovs_status ba_graph_schur(ovs_ba_graph* g, const double* d_Hpp, const double* d_bp, const double* d_Hll, const double* d_bl, const double* d_Hpl,
-                          double lambda, hipStream_t s, int fail_word, bool clear_first);
-ovs_status ba_graph_backsub(ovs_ba_graph* g, const double* d_Hpl, const double* d_bl, double lambda, const double* d_X, double* d_Xn, hipStream_t s);
-ovs_status ba_graph_edge_chi2(ovs_ba_graph* g, const double* d_poses, const double* d_points, double* d_chi, uint8_t* d_depth, hipStream_t s);
-ovs_status ba_graph_edge_gate(ovs_ba_graph* g, double thr_mono, double thr_stereo, const double* d_chi, const uint8_t* d_depth, const double* d_chi_r1,
-                              const uint8_t* d_out1, bool use_final, uint8_t* d_out, bool write_active, int32_t* d_n_active, hipStream_t s);
-ovs_status ba_graph_linearize(ovs_ba_graph* g, const double* d_poses, const double* d_points, double huber_mono, double huber_stereo, double* d_Hpp,
-                              double* d_bp, double* d_Hll, double* d_bl, double* d_Hpl, double* d_chi3, hipStream_t s, double* d_chi_mirror = nullptr,
-                              bool trial_scale = false, unsigned long long* host_ll = nullptr, unsigned int seq = 0);
-ovs_status ba_graph_trial_update(ovs_ba_graph* g, const double* d_T, const double* d_bp, const double* d_Hpl, const double* d_bl, double lambda,
-                                 double* d_Tn, double* d_p7n, const double* d_X, double* d_Xn, hipStream_t s, int next_fail_word);
-struct BaGraphInfo {
-    int n_free;
-    const int32_t* slot;        // pose -> reduced block or -1
-    double *d_S, *d_dxp, *d_scal;   // S | rhs | bp copy;  6 per keyframe;  [0] landmarks' / [1] keyframes' part of the gain ratio's denominator
-    int32_t* d_fail;
-    const int32_t* d_slot_of_pose;
-    int s_pitch;                 // doubles per row of d_S (6 n_free rounded up to 16; ba_solve.hip's padded layout)
-    double* d_rhs;               // row s_pitch of the system
-};
-BaGraphInfo ba_graph_info(ovs_ba_graph* g);
-// ba_solve.hip
-int dense_solve_max_n();
-int dense_solve_pad(int n);
-size_t dense_solve_doubles(int n);
-ovs_status launch_dense_solve(double* d_S, int n, int32_t* d_fail, hipStream_t s, unsigned long long* d_tstats = nullptr);
-ovs_status ba_graph_reset_system(ovs_ba_graph* g, hipStream_t s);
-// where the reduced camera system is solved: 0 = on the device (k_chol_solve), 1 = on the host (ba_host_math.h cholesky_solve)
 std::atomic<int> g_lba_solver{0};
 }   // namespace ovs
 
 namespace {
 
 using namespace ovs_ba_host;
+using ovs::ArenaLayout;
 using ovs::set_last_error;
 
 // upstream: constexpr float chi_sq_2D = 5.99146, chi_sq_3D = 7.81473 and their float square roots, widened to double where g2o consumes them
@@ -79,6 +48,33 @@ struct DevBlocks {   // one linearisation in HBM: Hpp | bp | Hll | bl | Hpl | ch
     }
 };
 
+// A trial's outcome on the host. It sits in page-locked memory behind the system and the staging area (pin_layout): the copies and the last
+// kernel of a trial write it, the host reads it.
+struct TrialBlock {   // image of the solver arena's d_scal | d_fail: the ONE download per trial of OVS_BA_LL_NOTIFY=0
+    double scal[32];   // [0] landmarks' / [1] keyframes' part of the gain ratio's denominator, [2..4] the trial state's chi2 triple
+    int32_t fail[2];
+};
+static_assert(sizeof(TrialBlock) == 256 + 2 * sizeof(int32_t), "d_fail sits 256 bytes behind d_scal");
+struct Mailbox {
+    double chi[3];               // chi2, robustified chi2, the largest |diagonal entry| of the linearisation last read
+    double scale_lm, scale_kf;   // the gain ratio's denominator: the landmarks' and the keyframes' part
+    int32_t fail;                // the trial's failure word
+    TrialBlock blk;
+    volatile unsigned long long ll[16];   // k_reduce_scalars' flag-carrying words {seq : 32 | half a double : 32}, twelve in use
+};
+struct PinLayout {
+    size_t stage, mailbox, bytes;   // (the padded system | bp come first, at offset 0)
+};
+static PinLayout pin_layout(int n_pose) {
+    ArenaLayout lay;
+    PinLayout p;
+    lay.place<double>(ovs::dense_solve_doubles(6 * n_pose) + 6 * (size_t)n_pose);
+    p.stage = lay.place<double>(19 * (size_t)n_pose);   // the keyframes' records on their way up: 7 + 12 per keyframe
+    p.mailbox = lay.place<Mailbox>(1);
+    p.bytes = lay.bytes();
+    return p;
+}
+
 // Per-thread work space that only grows: local BA runs once per keyframe on the mapping thread, and a dozen hipMalloc / hipHostMalloc /
 // stream-create calls per call (3-5 ms) would cost as much as the optimisation itself.
 struct LmScratch {
@@ -86,28 +82,25 @@ struct LmScratch {
     hipStream_t stream = nullptr;
     unsigned char* d = nullptr;
     size_t d_cap = 0;
-    double* h_pin = nullptr;
-    size_t pin_cap = 0;
-    unsigned char* h_edge = nullptr;   // pinned: round 1's inlier count (4 bytes), then the final outlier flags (one byte per edge)
-    size_t edge_cap = 0;               // bytes (>= edges)
-    double* h_pts = nullptr;           // pinned: the landmarks on their way up (start of the call) and down (its end)
-    size_t pts_cap = 0;                // doubles
+    ovs::PinnedBuffer pin;    // pin_layout
+    ovs::PinnedBuffer edge;   // round 1's inlier count (4 bytes), then the final outlier flags (one byte per edge)
+    ovs::PinnedBuffer pts;    // the landmarks on their way up (start of the call) and down (its end)
     ~LmScratch() { release(); }
     void release() {
         if (d) (void)hipFree(d);
-        if (h_pin) (void)hipHostFree(h_pin);
-        if (h_edge) (void)hipHostFree(h_edge);
-        if (h_pts) (void)hipHostFree(h_pts);
-        h_pts = nullptr;
-        pts_cap = 0;
-        h_edge = nullptr;
-        edge_cap = 0;
-        if (stream) (void)hipStreamDestroy(stream);
         d = nullptr;
-        h_pin = nullptr;
+        d_cap = 0;
+        pin.release();
+        edge.release();
+        pts.release();
+        if (stream) (void)hipStreamDestroy(stream);
         stream = nullptr;
-        d_cap = pin_cap = 0;
     }
+};
+
+struct Trial {   // what one Levenberg-Marquardt trial tells the damping schedule
+    bool ok = false;
+    double temp_chi = 1.7976931348623157e308, scale = 1e-3;
 };
 
 struct Lm {
@@ -127,11 +120,12 @@ struct Lm {
     double *d_echi_r1 = nullptr, *d_echi_s = nullptr;
     uint8_t *d_out1 = nullptr, *d_outf = nullptr;
     int32_t* d_nact = nullptr;
-    double* h_pts = nullptr;   // LmScratch::h_pts
-    double* h_pin = nullptr;   // pinned: S | rhs | bp | staging | chi3 | scal | fail
-    size_t pin_doubles = 0, stage_off = 0;
-    unsigned char* h_edge = nullptr;   // LmScratch::h_edge
-    size_t edge_cap = 0;
+    double* h_pts = nullptr;     // LmScratch::pts
+    double* h_sys = nullptr;     // LmScratch::pin: S | rhs | bp as the host solver downloads them
+    double* h_stage = nullptr;   //                 the keyframes' records on their way up
+    Mailbox* mb = nullptr;       //                 a trial's outcome
+    unsigned char* h_edge = nullptr;   // LmScratch::edge
+    bool ll_notify = true;
 
     ovs_status init(int device, int np, int npt, size_t ne_max, const double* points) {
         static thread_local LmScratch sc;
@@ -143,79 +137,45 @@ struct Lm {
         }
         if (!sc.stream) OVS_HIP_TRY(hipStreamCreateWithFlags(&sc.stream, hipStreamNonBlocking));
         stream = sc.stream;
-        auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-        const size_t nb = al(sizeof(double) * DevBlocks::doubles(np, npt, ne_max)), b_p = al(sizeof(double) * 7 * np), b_x = al(sizeof(double) * 3 * npt),
-                     b_e = al(sizeof(double) * std::max<size_t>(ne_max, 1)), b_d = al(std::max<size_t>(ne_max, 1));
-        const size_t b_t = al(sizeof(double) * 12 * np);
-        const size_t need = 3 * nb + 3 * b_p + 3 * b_x + 3 * b_t + 3 * b_e + 3 * b_d + 256;
-        if (sc.d_cap < need) {
+        const size_t ne = std::max<size_t>(ne_max, 1), nd = DevBlocks::doubles(np, npt, ne_max);
+        ArenaLayout lay;
+        const size_t o_cur = lay.place<double>(nd), o_trial = lay.place<double>(nd), o_work = lay.place<double>(nd);
+        const size_t o_p = lay.place<double>(7 * (size_t)np), o_pn = lay.place<double>(7 * (size_t)np), o_pw = lay.place<double>(7 * (size_t)np);
+        const size_t o_x = lay.place<double>(3 * (size_t)npt), o_xn = lay.place<double>(3 * (size_t)npt), o_xw = lay.place<double>(3 * (size_t)npt);
+        const size_t o_t = lay.place<double>(12 * (size_t)np), o_tn = lay.place<double>(12 * (size_t)np), o_tw = lay.place<double>(12 * (size_t)np);
+        const size_t o_echi = lay.place<double>(ne), o_edepth = lay.place<uint8_t>(ne), o_echi_r1 = lay.place<double>(ne), o_echi_s = lay.place<double>(ne);
+        const size_t o_out1 = lay.place<uint8_t>(ne), o_outf = lay.place<uint8_t>(ne), o_nact = lay.place<int32_t>(1);
+        if (sc.d_cap < lay.bytes()) {
             if (sc.d) (void)hipFree(sc.d);
             sc.d = nullptr;
             sc.d_cap = 0;
-            OVS_HIP_TRY(hipMalloc(&sc.d, need));
-            sc.d_cap = need;
+            OVS_HIP_TRY(hipMalloc(&sc.d, lay.bytes()));
+            sc.d_cap = lay.bytes();
         }
-        unsigned char* A = sc.d;
-        cur.carve(reinterpret_cast<double*>(A), np, npt, ne_max);
-        trial.carve(reinterpret_cast<double*>(A + nb), np, npt, ne_max);
-        work.carve(reinterpret_cast<double*>(A + 2 * nb), np, npt, ne_max);
-        A += 3 * nb;
-        d_poses = reinterpret_cast<double*>(A);
-        d_poses_n = reinterpret_cast<double*>(A + b_p);
-        d_poses_w = reinterpret_cast<double*>(A + 2 * b_p);
-        A += 3 * b_p;
-        d_X = reinterpret_cast<double*>(A);
-        d_Xn = reinterpret_cast<double*>(A + b_x);
-        d_Xw = reinterpret_cast<double*>(A + 2 * b_x);
-        A += 3 * b_x;
-        d_T = reinterpret_cast<double*>(A);
-        d_Tn = reinterpret_cast<double*>(A + b_t);
-        d_Tw = reinterpret_cast<double*>(A + 2 * b_t);
-        A += 3 * b_t;
-        d_echi = reinterpret_cast<double*>(A);
-        d_edepth = A + b_e;
-        A += b_e + b_d;
-        d_echi_r1 = reinterpret_cast<double*>(A);
-        d_echi_s = reinterpret_cast<double*>(A + b_e);
-        A += 2 * b_e;
-        d_out1 = A;
-        d_outf = A + b_d;
-        d_nact = reinterpret_cast<int32_t*>(A + 2 * b_d);
-        // padded system | bp | staging of the keyframes' records (7 + 12 per keyframe) | chi3, scal, fail | a trial's result block (264 bytes)
-        stage_off = ovs::dense_solve_doubles(6 * np) + 6 * (size_t)np;
-        pin_doubles = stage_off + 19 * (size_t)np + 16 + 40 + 16;   // (+ 16: the trial's outcome as flag-carrying words, see run_round)
-        if (sc.pin_cap < pin_doubles) {
-            if (sc.h_pin) (void)hipHostFree(sc.h_pin);
-            sc.h_pin = nullptr;
-            sc.pin_cap = 0;
-            OVS_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sc.h_pin), sizeof(double) * pin_doubles, hipHostMallocDefault));
-            sc.pin_cap = pin_doubles;
-        }
-        h_pin = sc.h_pin;
-        const size_t ne = std::max<size_t>(ne_max, 1);
-        if (sc.edge_cap < ne) {   // (pageable std::vectors here cost a staged 0.9 MB copy and fresh pages twice per call: ~0.3 ms of a 7.7 ms call)
-            if (sc.h_edge) (void)hipHostFree(sc.h_edge);
-            sc.h_edge = nullptr;
-            sc.edge_cap = 0;
-            const size_t cap = (ne + 1023) & ~(size_t)1023;
-            OVS_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sc.h_edge), cap, hipHostMallocDefault));
-            sc.edge_cap = cap;
-        }
-        h_edge = sc.h_edge;
-        edge_cap = sc.edge_cap;
-        if (sc.pts_cap < (size_t)3 * npt) {
-            if (sc.h_pts) (void)hipHostFree(sc.h_pts);
-            sc.h_pts = nullptr;
-            sc.pts_cap = 0;
-            const size_t cap = ((size_t)3 * npt + (size_t)3 * npt / 4 + 511) & ~(size_t)511;
-            OVS_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sc.h_pts), sizeof(double) * cap, hipHostMallocDefault));
-            sc.pts_cap = cap;
-        }
-        h_pts = sc.h_pts;
+        cur.carve(ArenaLayout::at<double>(sc.d, o_cur), np, npt, ne_max);
+        trial.carve(ArenaLayout::at<double>(sc.d, o_trial), np, npt, ne_max);
+        work.carve(ArenaLayout::at<double>(sc.d, o_work), np, npt, ne_max);
+        d_poses = ArenaLayout::at<double>(sc.d, o_p), d_poses_n = ArenaLayout::at<double>(sc.d, o_pn), d_poses_w = ArenaLayout::at<double>(sc.d, o_pw);
+        d_X = ArenaLayout::at<double>(sc.d, o_x), d_Xn = ArenaLayout::at<double>(sc.d, o_xn), d_Xw = ArenaLayout::at<double>(sc.d, o_xw);
+        d_T = ArenaLayout::at<double>(sc.d, o_t), d_Tn = ArenaLayout::at<double>(sc.d, o_tn), d_Tw = ArenaLayout::at<double>(sc.d, o_tw);
+        d_echi = ArenaLayout::at<double>(sc.d, o_echi), d_echi_r1 = ArenaLayout::at<double>(sc.d, o_echi_r1), d_echi_s = ArenaLayout::at<double>(sc.d, o_echi_s);
+        d_edepth = sc.d + o_edepth, d_out1 = sc.d + o_out1, d_outf = sc.d + o_outf;
+        d_nact = ArenaLayout::at<int32_t>(sc.d, o_nact);
+        const PinLayout pl = pin_layout(np);
+        OVS_HIP_TRY(sc.pin.ensure(pl.bytes, pl.bytes));
+        h_sys = ArenaLayout::at<double>(sc.pin.p, 0);
+        h_stage = ArenaLayout::at<double>(sc.pin.p, pl.stage);
+        mb = ArenaLayout::at<Mailbox>(sc.pin.p, pl.mailbox);
+        // (pageable std::vectors here cost a staged 0.9 MB copy and fresh pages twice per call: ~0.3 ms of a 7.7 ms call)
+        OVS_HIP_TRY(sc.edge.ensure(ne, (ne + 1023) & ~(size_t)1023));
+        h_edge = sc.edge.p;
+        const size_t n3 = (size_t)3 * npt;
+        OVS_HIP_TRY(sc.pts.ensure(sizeof(double) * n3, sizeof(double) * ((n3 + n3 / 4 + 511) & ~(size_t)511)));
+        h_pts = reinterpret_cast<double*>(sc.pts.p);
         // through the page-locked block, no wait: the landmarks travel while the caller (ovs_local_ba_optimize) indexes the edges; the block is
         // written next at the end of the call, behind a dozen stream synchronisations
-        std::memcpy(h_pts, points, sizeof(double) * 3 * (size_t)npt);
-        OVS_HIP_TRY(hipMemcpyAsync(d_X, h_pts, sizeof(double) * 3 * (size_t)npt, hipMemcpyHostToDevice, stream));
+        std::memcpy(h_pts, points, sizeof(double) * n3);
+        OVS_HIP_TRY(hipMemcpyAsync(d_X, h_pts, sizeof(double) * n3, hipMemcpyHostToDevice, stream));
         return OVS_OK;
     }
 
@@ -234,7 +194,7 @@ struct Lm {
     ovs_status upload_poses(const std::vector<Pose>& T, double* dst, double* dst_rt) {
         std::vector<double> p7;
         pack_poses(T, p7);
-        double* const st7 = h_pin + stage_off;
+        double* const st7 = h_stage;
         std::memcpy(st7, p7.data(), sizeof(double) * p7.size());
         OVS_HIP_TRY(hipMemcpyAsync(dst, st7, sizeof(double) * p7.size(), hipMemcpyHostToDevice, stream));
         if (dst_rt) {
@@ -251,13 +211,207 @@ struct Lm {
     double huber_mono(bool robust) const { return robust ? (setup_type == 0 ? kSqrtChi2D : kSqrtChi3D) : 0.0; }
     double huber_stereo(bool robust) const { return robust ? kSqrtChi3D : 0.0; }
 
+    // Round 6: the trial's last kernel wrote the outcome into the mailbox as twelve words {seq | half a double}; poll them (no copy command, no
+    // stream wait). Every 4096 polls the stream is asked whether it still runs: a launch that died would otherwise never write the words.
+    // False: the stream went idle (or failed) without the words -- the copy path decides.
+    bool poll_flag_words(unsigned int seq, unsigned long long (&w)[12]) {
+        unsigned int spins = 0;
+        for (int i = 0; i < 12;) {
+            w[i] = mb->ll[i];
+            if ((unsigned int)(w[i] >> 32) == seq) {
+                ++i;
+                continue;
+            }
+            if ((++spins & 4095u) == 0u && hipStreamQuery(stream) != hipErrorNotReady) {   // idle (or failed): one last look
+                w[i] = mb->ll[i];
+                if ((unsigned int)(w[i] >> 32) != seq) return false;
+            }
+        }
+        return true;
+    }
+
+    // ---- one trial, the whole of it on the device: Schur complement, solve, keyframe / landmark updates, linearisation at the trial state (into
+    //      the `work` set: a failed solve must leave the last evaluated trial state, which edge_chi2 may still need, untouched)
+    ovs_status trial_on_device(ovs_ba_graph* g, const ovs::BaGraphInfo& gi, int n, double lambda, bool robust, Trial& r) {
+        const double t0 = now();
+        const int fw = n_trials & 1;   // the trials alternate between two failure words
+        ovs_status st = ovs::ba_graph_schur(g, cur.Hpp, cur.bp, cur.Hll, cur.bl, cur.Hpl, lambda, stream, fw, false);
+        if (st != OVS_OK) return st;
+        if (n > 0) {
+            st = ovs::launch_dense_solve(gi.d_S, n, gi.d_fail + fw, stream);
+            if (st != OVS_OK) return st;
+        }
+        st = ovs::ba_graph_trial_update(g, d_T, cur.bp, cur.Hpl, cur.bl, lambda, d_Tw, d_poses_w, d_X, d_Xw, stream, fw ^ 1);
+        if (st != OVS_OK) return st;
+        // the trial state's chi2 triple is mirrored next to the solver's scalars (gi.d_scal[2..4]; gi.d_fail sits 256 bytes behind gi.d_scal in
+        // the same arena): ONE 264-byte download per trial instead of three copies (round 5: two copy launches and their gaps less per trial).
+        // (One kernel writing the values straight into the page-locked block was measured in round 4 -- the system-scope flush at its end costs
+        // ~50 us per trial.)
+        static thread_local unsigned int ll_seq = 0;   // sequence number of a trial's words: per thread, like the page-locked block they land in
+        const unsigned int seq = ++ll_seq == 0u ? ++ll_seq : ll_seq;   // (never 0: the block starts zeroed)
+        st = ovs::ba_graph_linearize(g, d_poses_w, d_Xw, huber_mono(robust), huber_stereo(robust), work.Hpp, work.bp, work.Hll, work.bl, work.Hpl,
+                                     work.chi, stream, gi.d_scal + 2, true, ll_notify ? const_cast<unsigned long long*>(mb->ll) : nullptr, seq);
+        if (st != OVS_OK) return st;
+        unsigned long long w[12];
+        if (ll_notify && poll_flag_words(seq, w)) {
+            auto val = [&](int i) {
+                const unsigned long long bits = (w[2 * i] & 0xffffffffull) | (w[2 * i + 1] << 32);
+                double d;
+                std::memcpy(&d, &bits, sizeof(d));
+                return d;
+            };
+            mb->scale_lm = val(0);
+            mb->scale_kf = val(1);
+            mb->chi[0] = val(2);
+            mb->chi[1] = val(3);
+            mb->chi[2] = val(4);   // (the largest |diagonal| of the LANDMARKS only, not the full maximum of the start damping: nothing reads it after a trial)
+            mb->fail = (int32_t)(uint32_t)(w[10 + fw] & 0xffffffffull);
+        } else {
+            OVS_HIP_TRY(hipMemcpyAsync(&mb->blk, gi.d_scal, sizeof(TrialBlock), hipMemcpyDeviceToHost, stream));
+            OVS_HIP_TRY(hipStreamSynchronize(stream));   // (polling hipStreamQuery instead: the same 6.5-6.6 ms per call, round 5)
+            mb->scale_lm = mb->blk.scal[0];
+            mb->scale_kf = mb->blk.scal[1];
+            mb->chi[0] = mb->blk.scal[2];
+            mb->chi[1] = mb->blk.scal[3];
+            mb->chi[2] = mb->blk.scal[4];   // (the landmarks' largest |diagonal| only, as in the flag words)
+            mb->fail = mb->blk.fail[fw];
+        }
+        r.ok = mb->fail == 0;
+        if (!r.ok) {   // a failed factorisation may have left non-finite values in the padding, which no later trial rewrites
+            st = ovs::ba_graph_reset_system(g, stream);
+            if (st != OVS_OK) return st;
+        } else {
+            r.temp_chi = mb->chi[1];
+            r.scale = (mb->scale_kf + mb->scale_lm) + 1e-3;   // keyframes' part, then the landmarks' (g2o's computeScale order)
+            std::swap(trial, work);
+            std::swap(d_poses_n, d_poses_w);
+            std::swap(d_Xn, d_Xw);
+            std::swap(d_Tn, d_Tw);
+            err_at_trial = true;
+        }
+        t_trial += now() - t0;
+        return OVS_OK;
+    }
+    void accept_on_device() {
+        std::swap(d_X, d_Xn);
+        std::swap(d_poses, d_poses_n);
+        std::swap(d_T, d_Tn);
+        std::swap(cur, trial);
+    }
+
+    // ---- one trial with the reduced camera system solved on the host: 0.7 MB (S | rhs | bp) down, the keyframes' increments and records up,
+    //      k_backsub, the linearisation of the trial state
+    struct HostState {
+        std::vector<Pose>& T;   // the accepted keyframes
+        std::vector<Pose> Tn;   // the trial's
+        std::vector<double> S, rhs, dxp;
+    };
+    ovs_status trial_on_host(ovs_ba_graph* g, const ovs::BaGraphInfo& gi, int n, double lambda, bool robust, HostState& h, Trial& r) {
+        const double t0 = now();
+        ovs_status st = ovs::ba_graph_schur(g, cur.Hpp, cur.bp, cur.Hll, cur.bl, cur.Hpl, lambda, stream, 0, true);
+        if (st != OVS_OK) return st;
+        const size_t np_ = (size_t)gi.s_pitch, sys_rows = np_ + 1;   // S rows and the rhs row
+        const double* const h_bp = h_sys + sys_rows * np_;
+        if (n > 0) {
+            OVS_HIP_TRY(hipMemcpyAsync(h_sys, gi.d_S, sizeof(double) * sys_rows * np_, hipMemcpyDeviceToHost, stream));
+            OVS_HIP_TRY(hipMemcpyAsync(h_sys + sys_rows * np_, cur.bp, sizeof(double) * 6 * (size_t)n_pose, hipMemcpyDeviceToHost, stream));
+        }
+        OVS_HIP_TRY(hipMemcpyAsync(&mb->fail, gi.d_fail, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+        OVS_HIP_TRY(hipStreamSynchronize(stream));
+        r.ok = mb->fail == 0;
+        const double t1 = now();
+        t_schur += t1 - t0;
+        if (r.ok && n > 0) {
+            h.S.resize((size_t)n * n);
+            for (int i = 0; i < n; ++i) std::memcpy(&h.S[(size_t)i * n], h_sys + (size_t)i * np_, sizeof(double) * n);   // drop the padding
+            h.rhs.assign(h_sys + np_ * np_, h_sys + np_ * np_ + n);
+            r.ok = cholesky_solve(h.S, n, h.rhs);
+        }
+        const double t2 = now();
+        t_chol += t2 - t1;
+        if (r.ok) {
+            std::vector<double>& dxp = h.dxp;
+            dxp.assign((size_t)6 * n_pose, 0.0);
+            h.Tn = h.T;
+            for (int k = 0; k < n_pose; ++k)
+                if (gi.slot[k] >= 0) {
+                    for (int a = 0; a < 6; ++a) dxp[(size_t)6 * k + a] = h.rhs[(size_t)6 * gi.slot[k] + a];
+                    se3_oplus(h.Tn[k], &dxp[(size_t)6 * k]);
+                }
+            std::vector<double> p7;
+            pack_poses(h.Tn, p7);
+            OVS_HIP_TRY(hipMemcpyAsync(gi.d_dxp, dxp.data(), sizeof(double) * dxp.size(), hipMemcpyHostToDevice, stream));
+            OVS_HIP_TRY(hipMemcpyAsync(d_poses_n, p7.data(), sizeof(double) * p7.size(), hipMemcpyHostToDevice, stream));
+            st = ovs::ba_graph_backsub(g, cur.Hpl, cur.bl, lambda, d_X, d_Xn, stream);
+            if (st != OVS_OK) return st;
+            st = ovs::ba_graph_linearize(g, d_poses_n, d_Xn, huber_mono(robust), huber_stereo(robust), trial.Hpp, trial.bp, trial.Hll, trial.bl,
+                                         trial.Hpl, trial.chi, stream, nullptr, true);
+            if (st != OVS_OK) return st;
+            OVS_HIP_TRY(hipMemcpyAsync(mb->chi, trial.chi, sizeof(double) * 3, hipMemcpyDeviceToHost, stream));
+            OVS_HIP_TRY(hipMemcpyAsync(&mb->scale_lm, gi.d_scal, sizeof(double), hipMemcpyDeviceToHost, stream));
+            OVS_HIP_TRY(hipStreamSynchronize(stream));   // also covers dxp / p7 (locals)
+            r.temp_chi = mb->chi[1];
+            err_at_trial = true;   // computeActiveErrors() ran on the trial state (d_poses_n, d_Xn); cleared when it is accepted
+            double sc = 0;
+            for (int k = 0; k < n_pose; ++k)
+                if (gi.slot[k] >= 0)
+                    for (int a = 0; a < 6; ++a) sc += dxp[(size_t)6 * k + a] * (lambda * dxp[(size_t)6 * k + a] + h_bp[(size_t)6 * k + a]);
+            r.scale = (sc + mb->scale_lm) + 1e-3;
+        }
+        t_trial += now() - t2;
+        return OVS_OK;
+    }
+    void accept_on_host(HostState& h) {
+        h.T.swap(h.Tn);
+        std::swap(d_X, d_Xn);
+        std::swap(d_poses, d_poses_n);
+        std::swap(cur, trial);   // the accepted trial's blocks are the next iteration's system
+    }
+
+    // g2o's OptimizationAlgorithmLevenberg::solve around `trial` (one trial at damping lambda) and `accept` (the trial state becomes the
+    // estimate): the damping schedule of ORACLE_SPEC rule 25
+    template <class TrialFn, class AcceptFn>
+    ovs_status lm_iterate(TrialFn trial_fn, AcceptFn accept, int iters, const volatile uint8_t* stop, double lambda, double* current_chi, int* n_iter) {
+        double ni = 2;
+        for (int it = 0; it < iters; ++it) {
+            if (stop && *stop) break;
+            ++*n_iter;
+            double rho = 0;
+            int qmax = 0;
+            err_at_trial = false;   // solve() starts with computeActiveErrors() at the current estimate
+            do {
+                ++n_trials;
+                Trial r;
+                const ovs_status st = trial_fn(lambda, r);
+                if (st != OVS_OK) return st;
+                rho = (*current_chi - r.temp_chi) / r.scale;
+                if (r.ok && rho > 0 && std::isfinite(r.temp_chi)) {
+                    double alpha = 1.0 - std::pow(2 * rho - 1, 3.0);
+                    alpha = std::min(alpha, 2.0 / 3.0);
+                    lambda *= std::max(1.0 / 3.0, alpha);
+                    ni = 2;
+                    *current_chi = r.temp_chi;
+                    accept();
+                    err_at_trial = false;   // the trial state is the estimate now
+                } else {
+                    lambda *= ni;
+                    ni *= 2;
+                    if (!std::isfinite(lambda)) break;
+                }
+                ++qmax;
+            } while (rho < 0 && qmax < 10 && !(stop && *stop));
+            if (qmax == 10 || rho == 0 || !std::isfinite(lambda)) break;
+        }
+        return OVS_OK;
+    }
+
     // one optimizer.optimize(iters) call on graph g. Returns the number of iterations entered.
     ovs_status run_round(ovs_ba_graph* g, std::vector<Pose>& T, int iters, bool robust, const volatile uint8_t* stop, double* chi_start,
                          double* chi_end, int* n_iter) {
         ovs_status st = ovs::ba_graph_ensure_solver(g, stream);   // (before ba_graph_info: the work space is allocated on first use)
         if (st != OVS_OK) return st;
         const ovs::BaGraphInfo gi = ovs::ba_graph_info(g);
-        const int nf = gi.n_free, n = 6 * nf;
+        const int n = 6 * gi.n_free;
         // the reduced camera system is solved where ovs_local_ba_set_solver says; systems beyond the one-workgroup solver's LDS go to the host
         const bool dev_solve = ovs::g_lba_solver.load(std::memory_order_relaxed) == 0 && n <= ovs::dense_solve_max_n();
         st = upload_poses(T, d_poses, dev_solve ? d_T : nullptr);
@@ -268,215 +422,26 @@ struct Lm {
         st = ovs::ba_graph_linearize(g, d_poses, d_X, huber_mono(robust), huber_stereo(robust), cur.Hpp, cur.bp, cur.Hll, cur.bl, cur.Hpl, cur.chi,
                                      stream);
         if (st != OVS_OK) return st;
-        double* h_chi = h_pin + pin_doubles - 16 - 40 - 16;
-        double* h_blk = h_pin + pin_doubles - 40 - 16;
-        volatile unsigned long long* const h_ll = reinterpret_cast<volatile unsigned long long*>(h_pin + pin_doubles - 16);
-        static thread_local unsigned int ll_seq = 0;   // sequence number of a trial's words: per thread, like the page-locked block they land in
-        for (int i = 0; i < 16; ++i) h_ll[i] = 0ull;    // (the stream is idle here; whatever the block's last user left cannot pass for a word)
-        const bool ll_notify = ovs::tuning().ba_ll_notify;   // OVS_BA_LL_NOTIFY=0: a trial's outcome through a D2H copy and a stream synchronisation
-        // (rounds 4-5); one download per trial: [0] landmarks' / [1] keyframes' gain-ratio parts, [2..4] chi2 triple, byte 256: fail flag
-        OVS_HIP_TRY(hipMemcpyAsync(h_chi, cur.chi, sizeof(double) * 3, hipMemcpyDeviceToHost, stream));
+        for (int i = 0; i < 16; ++i) mb->ll[i] = 0ull;   // (the stream is idle here; whatever the block's last user left cannot pass for a word)
+        ll_notify = ovs::tuning().ba_ll_notify;   // OVS_BA_LL_NOTIFY=0: a trial's outcome through a D2H copy and a stream synchronisation (rounds 4-5)
+        OVS_HIP_TRY(hipMemcpyAsync(mb->chi, cur.chi, sizeof(double) * 3, hipMemcpyDeviceToHost, stream));
         OVS_HIP_TRY(hipStreamSynchronize(stream));
-        double current_chi = h_chi[1];
+        double current_chi = mb->chi[1];
         *chi_start = current_chi;
         *chi_end = current_chi;
         *n_iter = 0;
         err_at_trial = false;
         if (iters <= 0) return OVS_OK;
-        // computeLambdaInit: tau * the largest diagonal entry of the active vertices' Hessian blocks
-        double lambda = 1e-5 * h_chi[2], ni = 2;
-        std::vector<double> S, rhs, dxp((size_t)6 * n_pose, 0.0);
-        std::vector<Pose> Tn;
-        for (int it = 0; it < iters; ++it) {
-            if (stop && *stop) break;
-            ++*n_iter;
-            double rho = 0;
-            int qmax = 0;
-            err_at_trial = false;   // solve() starts with computeActiveErrors() at the current estimate
-            do {
-                const double t0 = now();
-                ++n_trials;
-                const int fw = dev_solve ? (n_trials & 1) : 0;   // the device solver's trials alternate between two failure words
-                st = ovs::ba_graph_schur(g, cur.Hpp, cur.bp, cur.Hll, cur.bl, cur.Hpl, lambda, stream, fw, !dev_solve);
-                if (st != OVS_OK) return st;
-                int32_t* h_fail = reinterpret_cast<int32_t*>(h_chi + 8);
-                if (dev_solve) {
-                    // ---- the whole trial on the device: solve, keyframe / landmark updates, linearisation at the trial state (into the
-                    //      `work` set: a failed solve must leave the last evaluated trial state, which edge_chi2 may still need, untouched)
-                    if (n > 0) {
-                        st = ovs::launch_dense_solve(gi.d_S, n, gi.d_fail + fw, stream);
-                        if (st != OVS_OK) return st;
-                    }
-                    st = ovs::ba_graph_trial_update(g, d_T, cur.bp, cur.Hpl, cur.bl, lambda, d_Tw, d_poses_w, d_X, d_Xw, stream, fw ^ 1);
-                    if (st != OVS_OK) return st;
-                    // the trial state's chi2 triple is mirrored next to the solver's scalars (gi.d_scal[2..4]; gi.d_fail sits 256 bytes behind
-                    // gi.d_scal in the same arena): ONE 260-byte download per trial instead of three copies (round 5: two copy launches and their
-                    // gaps less per trial). (One kernel writing the values straight into the page-locked block was measured in round 4 -- the
-                    // system-scope flush at its end costs ~50 us per trial.)
-                    const unsigned int seq = ++ll_seq == 0u ? ++ll_seq : ll_seq;   // (never 0: the block starts zeroed)
-                    st = ovs::ba_graph_linearize(g, d_poses_w, d_Xw, huber_mono(robust), huber_stereo(robust), work.Hpp, work.bp, work.Hll, work.bl,
-                                                 work.Hpl, work.chi, stream, gi.d_scal + 2, true,
-                                                 ll_notify ? const_cast<unsigned long long*>(h_ll) : nullptr, seq);
-                    if (st != OVS_OK) return st;
-                    bool polled = false;
-                    if (ll_notify) {
-                        // Round 6: the trial's last kernel wrote the outcome into the page-locked block as twelve words {seq | half a double};
-                        // poll them (no copy command, no stream wait). Every 4096 polls the stream is asked whether it still runs: a launch
-                        // that died would otherwise never write the words.
-                        unsigned long long w[12];
-                        unsigned int spins = 0;
-                        bool dead = false;
-                        for (int i = 0; i < 12 && !dead;) {
-                            w[i] = h_ll[i];
-                            if ((unsigned int)(w[i] >> 32) == seq) {
-                                ++i;
-                                continue;
-                            }
-                            if ((++spins & 4095u) == 0u) {
-                                const hipError_t q = hipStreamQuery(stream);
-                                if (q != hipErrorNotReady) {   // idle (or failed): one last look, then the copy path decides
-                                    w[i] = h_ll[i];
-                                    if ((unsigned int)(w[i] >> 32) == seq) continue;
-                                    dead = true;
-                                }
-                            }
-                        }
-                        if (!dead) {
-                            auto val = [&](int i) {
-                                const unsigned long long bits = (w[2 * i] & 0xffffffffull) | (w[2 * i + 1] << 32);
-                                double d;
-                                std::memcpy(&d, &bits, sizeof(d));
-                                return d;
-                            };
-                            h_chi[4] = val(0);
-                            h_chi[5] = val(1);
-                            h_chi[0] = val(2);
-                            h_chi[1] = val(3);
-                            h_chi[2] = val(4);   // (the largest |diagonal| of the LANDMARKS only, not the full maximum of the
-                                                 //  start damping above: nothing reads it after a trial)
-                            const uint32_t f2[2] = {(uint32_t)(w[10] & 0xffffffffull), (uint32_t)(w[11] & 0xffffffffull)};
-                            *h_fail = (int32_t)f2[fw];
-                            polled = true;
-                        }
-                    }
-                    if (!polled) {
-                        OVS_HIP_TRY(hipMemcpyAsync(h_blk, gi.d_scal, 256 + 2 * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-                        OVS_HIP_TRY(hipStreamSynchronize(stream));   // (polling hipStreamQuery instead: the same 6.5-6.6 ms per call, round 5)
-                        h_chi[0] = h_blk[2];
-                        h_chi[1] = h_blk[3];
-                        h_chi[2] = h_blk[4];   // (mirror[2]: the landmarks' largest |diagonal| only, as in host_ll word 4)
-                        h_chi[4] = h_blk[0];
-                        h_chi[5] = h_blk[1];
-                        *h_fail = reinterpret_cast<const int32_t*>(reinterpret_cast<const unsigned char*>(h_blk) + 256)[fw];
-                    }
-                    const bool ok = *h_fail == 0;
-                    double temp_chi = 1.7976931348623157e308, scale = 1e-3;
-                    if (!ok) {   // a failed factorisation may have left non-finite values in the padding, which no later trial rewrites
-                        st = ovs::ba_graph_reset_system(g, stream);
-                        if (st != OVS_OK) return st;
-                    }
-                    if (ok) {
-                        temp_chi = h_chi[1];
-                        scale = (h_chi[5] + h_chi[4]) + 1e-3;   // keyframes' part, then the landmarks' (g2o's computeScale order)
-                        std::swap(trial, work);
-                        std::swap(d_poses_n, d_poses_w);
-                        std::swap(d_Xn, d_Xw);
-                        std::swap(d_Tn, d_Tw);
-                        err_at_trial = true;
-                    }
-                    t_trial += now() - t0;
-                    rho = (current_chi - temp_chi) / scale;
-                    if (ok && rho > 0 && std::isfinite(temp_chi)) {
-                        double alpha = 1.0 - std::pow(2 * rho - 1, 3.0);
-                        alpha = std::min(alpha, 2.0 / 3.0);
-                        lambda *= std::max(1.0 / 3.0, alpha);
-                        ni = 2;
-                        current_chi = temp_chi;
-                        std::swap(d_X, d_Xn);
-                        std::swap(d_poses, d_poses_n);
-                        std::swap(d_T, d_Tn);
-                        std::swap(cur, trial);
-                        err_at_trial = false;
-                    } else {
-                        lambda *= ni;
-                        ni *= 2;
-                        if (!std::isfinite(lambda)) break;
-                    }
-                    ++qmax;
-                    continue;
-                }
-                const size_t np_ = (size_t)gi.s_pitch, sys_rows = np_ + 1;   // S rows and the rhs row
-                double* const h_bp_w = h_pin + sys_rows * np_;
-                if (n > 0) {
-                    OVS_HIP_TRY(hipMemcpyAsync(h_pin, gi.d_S, sizeof(double) * sys_rows * np_, hipMemcpyDeviceToHost, stream));
-                    OVS_HIP_TRY(hipMemcpyAsync(h_bp_w, cur.bp, sizeof(double) * 6 * (size_t)n_pose, hipMemcpyDeviceToHost, stream));
-                }
-                OVS_HIP_TRY(hipMemcpyAsync(h_fail, gi.d_fail, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-                OVS_HIP_TRY(hipStreamSynchronize(stream));
-                bool ok = *h_fail == 0;
-                const double t1 = now();
-                t_schur += t1 - t0;
-                const double* h_bp = h_bp_w;
-                if (ok && n > 0) {
-                    S.resize((size_t)n * n);
-                    for (int i = 0; i < n; ++i) std::memcpy(&S[(size_t)i * n], h_pin + (size_t)i * np_, sizeof(double) * n);   // drop the padding
-                    rhs.assign(h_pin + np_ * np_, h_pin + np_ * np_ + n);
-                    ok = cholesky_solve(S, n, rhs);
-                }
-                const double t2 = now();
-                t_chol += t2 - t1;
-                double temp_chi = 1.7976931348623157e308;
-                double scale = 1e-3;
-                if (ok) {
-                    std::fill(dxp.begin(), dxp.end(), 0.0);
-                    Tn = T;
-                    for (int k = 0; k < n_pose; ++k)
-                        if (gi.slot[k] >= 0) {
-                            for (int a = 0; a < 6; ++a) dxp[(size_t)6 * k + a] = rhs[(size_t)6 * gi.slot[k] + a];
-                            se3_oplus(Tn[k], &dxp[(size_t)6 * k]);
-                        }
-                    std::vector<double> p7;
-                    pack_poses(Tn, p7);
-                    OVS_HIP_TRY(hipMemcpyAsync(gi.d_dxp, dxp.data(), sizeof(double) * dxp.size(), hipMemcpyHostToDevice, stream));
-                    OVS_HIP_TRY(hipMemcpyAsync(d_poses_n, p7.data(), sizeof(double) * p7.size(), hipMemcpyHostToDevice, stream));
-                    st = ovs::ba_graph_backsub(g, cur.Hpl, cur.bl, lambda, d_X, d_Xn, stream);
-                    if (st != OVS_OK) return st;
-                    st = ovs::ba_graph_linearize(g, d_poses_n, d_Xn, huber_mono(robust), huber_stereo(robust), trial.Hpp, trial.bp, trial.Hll,
-                                                 trial.bl, trial.Hpl, trial.chi, stream, nullptr, true);
-                    if (st != OVS_OK) return st;
-                    OVS_HIP_TRY(hipMemcpyAsync(h_chi, trial.chi, sizeof(double) * 3, hipMemcpyDeviceToHost, stream));
-                    OVS_HIP_TRY(hipMemcpyAsync(h_chi + 4, gi.d_scal, sizeof(double), hipMemcpyDeviceToHost, stream));
-                    OVS_HIP_TRY(hipStreamSynchronize(stream));   // also covers dxp / p7 (locals)
-                    temp_chi = h_chi[1];
-                    err_at_trial = true;   // computeActiveErrors() ran on the trial state (d_poses_n, d_Xn); cleared below if it is accepted
-                    double sc = 0;
-                    for (int k = 0; k < n_pose; ++k)
-                        if (gi.slot[k] >= 0)
-                            for (int a = 0; a < 6; ++a) sc += dxp[(size_t)6 * k + a] * (lambda * dxp[(size_t)6 * k + a] + h_bp[(size_t)6 * k + a]);
-                    scale = (sc + h_chi[4]) + 1e-3;
-                }
-                t_trial += now() - t2;
-                rho = (current_chi - temp_chi) / scale;
-                if (ok && rho > 0 && std::isfinite(temp_chi)) {
-                    double alpha = 1.0 - std::pow(2 * rho - 1, 3.0);
-                    alpha = std::min(alpha, 2.0 / 3.0);
-                    lambda *= std::max(1.0 / 3.0, alpha);
-                    ni = 2;
-                    current_chi = temp_chi;
-                    T.swap(Tn);
-                    std::swap(d_X, d_Xn);
-                    std::swap(d_poses, d_poses_n);
-                    std::swap(cur, trial);   // the accepted trial's blocks are the next iteration's system
-                    err_at_trial = false;    // the trial state is the estimate now
-                } else {
-                    lambda *= ni;
-                    ni *= 2;
-                    if (!std::isfinite(lambda)) break;
-                }
-                ++qmax;
-            } while (rho < 0 && qmax < 10 && !(stop && *stop));
-            if (qmax == 10 || rho == 0 || !std::isfinite(lambda)) break;
+        const double lambda0 = 1e-5 * mb->chi[2];   // computeLambdaInit: tau * the largest diagonal entry of the active vertices' Hessian blocks
+        if (dev_solve) {
+            st = lm_iterate([&](double lambda, Trial& r) { return trial_on_device(g, gi, n, lambda, robust, r); }, [&] { accept_on_device(); }, iters,
+                            stop, lambda0, &current_chi, n_iter);
+        } else {
+            HostState h{T, {}, {}, {}, {}};
+            st = lm_iterate([&](double lambda, Trial& r) { return trial_on_host(g, gi, n, lambda, robust, h, r); }, [&] { accept_on_host(h); }, iters,
+                            stop, lambda0, &current_chi, n_iter);
         }
+        if (st != OVS_OK) return st;
         *chi_end = current_chi;
         if (dev_solve) {   // the accepted keyframe state comes back once per round
             std::vector<double> rt((size_t)12 * n_pose);

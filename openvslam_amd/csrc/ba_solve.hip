@@ -43,16 +43,7 @@
 #include <mutex>
 #include <vector>
 
-#include "ovs_common.h"
-
-#define OVS_LAUNCH_TRY(name)                                  \
-    do {                                                      \
-        hipError_t _e = hipGetLastError();                    \
-        if (_e != hipSuccess) {                               \
-            ovs::set_last_error("launch of " name, _e);       \
-            return OVS_ERR_HIP;                               \
-        }                                                     \
-    } while (0)
+#include "ba_internal.h"
 
 namespace ovs {
 

@@ -244,6 +244,136 @@ def test_graph_equirect_matches_oracle(oracle):
     assert np.allclose(got["chi2"][:2], want["chi2"], rtol=1e-12)
 
 
+_EDGE_MODEL_SCENES = {}
+
+
+def _edge_model_scene(kind):
+    """The smallest scene that crosses every partition boundary of k_linearize2: 3 keyframes, 600 landmarks. Keyframe 0 observes all 600 (one
+    full 512-entry chunk and a partial one), keyframe 1 observes 257 (one entry over a half chunk), keyframe 2 observes 70 and is fixed;
+    landmark 0 is observed by all three. kind: "mono" | "stereo" (a third of the edges stereo) | "equirect".
+    Returns (poses, fixed, points, mono edges ordered by keyframe, stereo edges ordered by keyframe, cam or None, bf)."""
+    if kind in _EDGE_MODEL_SCENES:
+        return _EDGE_MODEL_SCENES[kind]
+    from openvslam_amd import ba
+    if kind == "equirect":
+        poses, _, pts, e = _equirect_scene(31, n_pose=3, n_pt=600, obs_per_pose=600)
+        d, cam = None, None
+    else:
+        d = synth_local_ba(n_pose=3, n_pt=600, obs_per_pose=600, seed=31, pose_noise=0.02, point_noise=0.02, n_fixed=0)
+        poses, pts, e, cam = d["poses"], d["points"], d["edges"], d["cam"]
+    rng = np.random.default_rng(32)
+    keep = np.zeros(len(e), bool)
+    for k, n in ((0, 600), (1, 257), (2, 70)):
+        idx = np.flatnonzero(e["pose_idx"] == k)
+        idx = idx[np.argsort(e["point_idx"][idx], kind="stable")]
+        keep[idx[0]] = True                                  # landmark 0
+        keep[rng.choice(idx[1:], n - 1, replace=False)] = True
+    e = e[keep]
+    e = np.ascontiguousarray(e[np.lexsort((e["point_idx"], e["pose_idx"]))])
+    assert np.bincount(e["pose_idx"]).tolist() == [600, 257, 70] and (e["point_idx"] == 0).sum() == 3
+    if kind != "equirect":   # gross outliers for the chi-square gates (as test_ba._lba_scene plants them)
+        bad = rng.random(len(e)) < 0.04
+        e["obs_x"][bad] += rng.choice([-1, 1], int(bad.sum())) * rng.uniform(15, 60, int(bad.sum()))
+    st, bf = np.zeros(0, ba.EDGE_STEREO_DTYPE), 0.0
+    if kind == "stereo":
+        bf = 0.12 * cam[0]
+        st, e = _stereo_edges(dict(d, edges=e), bf, frac=1.0 / 3.0, seed=33)
+        e = np.ascontiguousarray(e)
+        assert len(st) > 250 and len(e) > 550
+    fixed = np.array([0, 0, 1], np.uint8)
+    _EDGE_MODEL_SCENES[kind] = (poses, fixed, pts, e, st, cam, bf)
+    return _EDGE_MODEL_SCENES[kind]
+
+
+def _graph_blocks(kind, poses, fixed, pts, mono, st, cam, bf, hm, hs):
+    """One linearisation through the graph path (k_linearize2): dict of numpy blocks, Hpl in edge order (mono, then stereo)."""
+    import ctypes as C
+    import torch
+    from openvslam_amd import _lib, ba
+    P, X = torch.from_numpy(poses).cuda(), torch.from_numpy(pts).cuda()
+    if kind != "equirect":
+        g = ba.graph(len(poses), fixed, len(pts), mono, cam, st if len(st) else None, bf)
+        out = g.linearize_dev(P, X, hm, hs)
+        torch.cuda.synchronize()
+        return {k: t.cpu().numpy().copy() for k, t in ba.graph.views(out, g.n_pose, g.n_pt, g.n_edge).items()}
+    L = _lib.lib()
+    h = C.c_void_p()
+    _lib.check(L.ovs_ba_graph_create_equirect(0, len(poses), fixed.ctypes.data_as(C.c_void_p), len(pts), mono.ctypes.data_as(C.c_void_p), len(mono),
+                                              1920, 960, C.byref(h)), "ovs_ba_graph_create_equirect")
+    try:
+        o = dict(Hpp=torch.zeros((len(poses), 6, 6), dtype=torch.float64, device="cuda"), bp=torch.zeros((len(poses), 6), dtype=torch.float64, device="cuda"),
+                 Hll=torch.zeros((len(pts), 3, 3), dtype=torch.float64, device="cuda"), bl=torch.zeros((len(pts), 3), dtype=torch.float64, device="cuda"),
+                 Hpl=torch.zeros((len(mono), 6, 3), dtype=torch.float64, device="cuda"), chi2=torch.zeros(3, dtype=torch.float64, device="cuda"))
+        _lib.check(L.ovs_ba_graph_linearize_dev(h, P.data_ptr(), X.data_ptr(), hm, 0.0, o["Hpp"].data_ptr(), o["bp"].data_ptr(), o["Hll"].data_ptr(),
+                                                o["bl"].data_ptr(), o["Hpl"].data_ptr(), o["chi2"].data_ptr(), None), "linearize")
+        torch.cuda.synchronize()
+        got = {k: v.cpu().numpy() for k, v in o.items()}
+        got["chi2"] = got["chi2"][:2]
+        return got
+    finally:
+        L.ovs_ba_graph_destroy(h)
+
+
+@pytest.mark.parametrize("huber", [True, False])
+@pytest.mark.parametrize("kind", ["mono", "stereo", "equirect"])
+def test_edge_model_call_sites_agree_per_edge(oracle, kind, huber):
+    """The edge model has one definition (ba_edge.h) and four call sites: k_ba_linearize<2|3>, both sides of k_linearize2 and k_edge_chi2 (the
+    last one: test_edge_model_chi2_gates_match_oracle). Per edge they and the oracle must give the same bits, with the edges ordered by keyframe
+    (the wave-contiguous Hpl store) and shuffled (the per-lane store): Hpl equal between ovs_ba_linearize*, the graph and the oracle; the
+    graph's Hll / bl equal to the oracle's sequential sums; Hpp / bp / chi2 (tree sums) at 1e-13 as in
+    test_graph_linearize_is_deterministic_and_matches_oracle."""
+    from oracle import lba
+    from openvslam_amd import ba
+    poses, fixed, pts, mono0, st0, cam, bf = _edge_model_scene(kind)
+    hm = (lba.SQRT_CHI2_MONO if huber else 0.0)
+    hs = (lba.SQRT_CHI2_STEREO if huber else 0.0)
+    for shuffled in (False, True):
+        mono, st = mono0, st0
+        if shuffled:
+            rng = np.random.default_rng(34)
+            mono = np.ascontiguousarray(mono0[rng.permutation(len(mono0))])
+            st = np.ascontiguousarray(st0[rng.permutation(len(st0))])
+        if kind == "equirect":
+            want = oracle.ba_linearize_equirect(poses, fixed, pts, mono, 1920, 960, hm)
+            flat = ba.linearize_equirect(poses, fixed, pts, mono, 1920, 960, hm)["Hpl"]
+        else:
+            want = oracle.ba_linearize(poses, fixed, pts, mono, cam, hm)
+            flat = ba.linearize(poses, fixed, pts, mono, cam, hm)["Hpl"]
+            if len(st):
+                s = oracle.ba_linearize_stereo(poses, fixed, pts, st, cam, bf, hs)
+                for k in ("Hpp", "bp", "Hll", "bl", "chi2"):
+                    want[k] = want[k] + s[k]
+                want["Hpl"] = np.concatenate([want["Hpl"], s["Hpl"]])
+                flat = np.concatenate([flat, ba.linearize_stereo(poses, fixed, pts, st, cam, bf, hs)["Hpl"]])
+        got = _graph_blocks(kind, poses, fixed, pts, mono, st, cam, bf, hm, hs)
+        assert np.abs(want["Hpl"]).max() > 0 and want["chi2"][0] > 0
+        assert np.array_equal(flat, want["Hpl"]), shuffled
+        assert np.array_equal(got["Hpl"], want["Hpl"]), shuffled
+        for k in ("Hll", "bl"):
+            assert np.array_equal(got[k], want[k]), (k, shuffled)
+        for k in ("Hpp", "bp", "chi2"):
+            scale = np.abs(want[k]).max()
+            assert np.allclose(got[k][:len(want[k])], want[k], rtol=1e-13, atol=1e-13 * scale), (k, shuffled)
+
+
+def test_edge_model_chi2_gates_match_oracle(oracle):
+    """k_edge_chi2's use of the edge model: ovs_local_ba_optimize on the perspective scenes of test_edge_model_call_sites_agree_per_edge gives
+    the oracle's iteration counts and outlier flags (the tolerances of test_local_ba_optimize)."""
+    from oracle import lba
+    from openvslam_amd import ba
+    for kind in ("mono", "stereo"):
+        poses, fixed, pts, mono, st, cam, bf = _edge_model_scene(kind)
+        got = ba.local_ba_optimize(poses, fixed, pts, mono, cam, st, bf)
+        want = lba.local_ba_optimize(poses, fixed, pts, mono, cam, st, bf)
+        assert np.array_equal(got["info"][4:], want["info"][4:]) and want["info"][4] >= 1, kind
+        assert np.allclose(got["info"][:4], want["info"][:4], rtol=1e-7), kind
+        assert np.allclose(got["poses"], want["poses"], rtol=1e-7, atol=1e-8), kind
+        assert np.allclose(got["points"], want["points"], rtol=1e-7, atol=1e-8), kind
+        for k in ("mono_outlier", "stereo_outlier"):
+            assert (got[k] != want[k]).sum() <= max(1, len(want[k]) // 5000), (kind, k)
+        assert np.array_equal(got["poses"][2], poses[2])
+
+
 def test_local_ba_force_stop_and_bad_args():
     from openvslam_amd import ba
     from test_ba import _lba_scene
