@@ -652,6 +652,30 @@ ovs_status ovs_bow_transform(ovs_vocab* v, const uint8_t* desc, int32_t n, int32
 ovs_status ovs_bow_transform_dev(ovs_vocab* v, const uint8_t* d_desc, const int32_t* d_counts, int32_t batch, int32_t cap, int32_t levelsup,
                                  int32_t* d_word_id, double* d_weight, int32_t* d_node_id, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * BoW keyframe database.  replaces: the scoring half of data::bow_database::acquire_loop_candidates(keyframe*, float) and
+ *   acquire_relocalization_candidates(frame*) (src/openvslam/data/bow_database.{h,cc}): DBoW2 L1Scoring::score of the query's BowVector
+ *   against every registered keyframe's, the count of shared words, and the common-word gate (rules 1 to 3).
+ * A handle keeps up to max_keyframes vectors of up to max_words (word_id ascending, value) entries resident in HBM; one internal mutex
+ * serialises the calls on a handle. Word-id lists must be strictly ascending and non-negative, values finite (OVS_ERR_INVALID);
+ * n > max_words, a full database and a `cap` below the number of results are OVS_ERR_CAPACITY (nothing is truncated, no output is
+ * written). Everything but `cap` against the survivors of ovs_bowdb_query is decided before any launch.
+ * ovs_bowdb_query: the keyframes with num_common >= 1 outside reject_ids (keyframe ids; unknown ones are ignored) whose
+ *   (float)num_common > 0.8f * (float)max_common, ascending keyframe id; *max_common = the maximum over the non-rejected keyframes.
+ * ovs_bowdb_score_all: every registered keyframe, ascending id (num_common 0 and score +0.0 where no word is shared).
+ * Scores are bit-exact: the terms of a keyframe are added one after the other in ascending word id, in f64, nothing fused. */
+typedef struct ovs_bowdb ovs_bowdb;
+ovs_status ovs_bowdb_create(int32_t device, int32_t max_keyframes, int32_t max_words, ovs_bowdb** out);
+ovs_status ovs_bowdb_destroy(ovs_bowdb* db);
+ovs_status ovs_bowdb_add(ovs_bowdb* db, int32_t keyframe_id, const int32_t* word_ids, const double* values, int32_t n);
+ovs_status ovs_bowdb_erase(ovs_bowdb* db, int32_t keyframe_id);
+ovs_status ovs_bowdb_clear(ovs_bowdb* db);
+ovs_status ovs_bowdb_size(ovs_bowdb* db, int32_t* n);
+ovs_status ovs_bowdb_query(ovs_bowdb* db, const int32_t* q_ids, const double* q_values, int32_t nq, const int32_t* reject_ids, int32_t n_reject,
+                           int32_t* out_ids, int32_t* out_num_common, double* out_scores, int32_t cap, int32_t* n_out, int32_t* max_common);
+ovs_status ovs_bowdb_score_all(ovs_bowdb* db, const int32_t* q_ids, const double* q_values, int32_t nq, int32_t* out_ids, int32_t* out_num_common,
+                               double* out_scores, int32_t cap, int32_t* n_out);
+
 /* replaces: the optimisation inside  void optimize::local_bundle_adjuster::optimize(data::keyframe* curr_keyfrm, bool* const
  *               force_stop_flag) const  (src/openvslam/optimize/local_bundle_adjuster.{h,cc}): everything between the graph build and the
  * write-back, i.e. optimizer.optimize(num_first_iter) with Huber kernels (ONE delta per rig: setup_type 0 = Monocular -> sqrtf(5.99146f),

@@ -109,6 +109,14 @@ SYMBOLS = {
     "ovs_vocab_load_file": (_i32, [_i32, C.c_char_p, _i32, C.POINTER(_vp), C.POINTER(_i32)]),
     "ovs_bow_transform": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     "ovs_bow_transform_dev": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "ovs_bowdb_create": (_i32, [_i32, _i32, _i32, C.POINTER(_vp)]),
+    "ovs_bowdb_destroy": (_i32, [_vp]),
+    "ovs_bowdb_add": (_i32, [_vp, _i32, _vp, _vp, _i32]),
+    "ovs_bowdb_erase": (_i32, [_vp, _i32]),
+    "ovs_bowdb_clear": (_i32, [_vp]),
+    "ovs_bowdb_size": (_i32, [_vp, C.POINTER(_i32)]),
+    "ovs_bowdb_query": (_i32, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
+    "ovs_bowdb_score_all": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, C.POINTER(_i32)]),
     "ovs_local_ba_optimize": (_i32, [_i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, C.c_double, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ovs_local_ba_optimize_equirect": (_i32, [_i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ovs_ba_linearize_stereo": (_i32, [_i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -98,3 +98,104 @@ def load_vocabulary(path, max_features=8192, device=0):
     """data::bow_vocabulary from a file: parse + upload (the C ABI does both in ovs_vocab_load_file; this mirror keeps the host arrays)."""
     tree, _ = load_vocabulary_tree(path)
     return vocabulary(tree, max_features=max_features, device=device)
+
+
+def _f32(x):
+    return float(np.float32(x))
+
+
+class bow_database:
+    """data::bow_database (expected: src/openvslam/data/bow_database.{h,cc}) with the keyframes' BoW vectors resident in HBM: one launch scores
+    the query against every registered keyframe (ovs_bowdb_query: L1 score, shared-word count, common-word gate; csrc/bow_db.hip), the
+    score gate and the covisibility totals run here over the survivors (rules 1 to 6).
+    A bow_vec is the {word: value} map `assemble` returns; `top_covisibilities` is a callable id -> at most 10 ids, strongest first."""
+
+    def __init__(self, max_keyframes, max_words=4096, device=0):
+        self._L = _lib.lib()
+        _lib.require_device()
+        self.max_keyframes, self.max_words = int(max_keyframes), int(max_words)
+        h = C.c_void_p()
+        _lib.check(self._L.ovs_bowdb_create(device, self.max_keyframes, self.max_words, C.byref(h)), "ovs_bowdb_create")
+        self._h = h
+        self._ids = np.zeros(self.max_keyframes, np.int32)
+        self._common = np.zeros(self.max_keyframes, np.int32)
+        self._scores = np.zeros(self.max_keyframes, np.float64)
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._L.ovs_bowdb_destroy(h)
+
+    @staticmethod
+    def _arrays(bow_vec):
+        words = sorted(bow_vec)
+        return np.array(words, np.int32), np.array([bow_vec[w] for w in words], np.float64)
+
+    def add_keyframe(self, id, bow_vec):
+        w, v = self._arrays(bow_vec)
+        _lib.check(self._L.ovs_bowdb_add(self._h, int(id), _p(w), _p(v), len(w)), "ovs_bowdb_add")
+
+    def erase_keyframe(self, id):
+        _lib.check(self._L.ovs_bowdb_erase(self._h, int(id)), "ovs_bowdb_erase")
+
+    def clear(self):
+        _lib.check(self._L.ovs_bowdb_clear(self._h), "ovs_bowdb_clear")
+
+    def __len__(self):
+        n = C.c_int32()
+        _lib.check(self._L.ovs_bowdb_size(self._h, C.byref(n)), "ovs_bowdb_size")
+        return n.value
+
+    def score_all(self, bow_vec):
+        """[(keyframe id, num_common, score)] for every registered keyframe, ascending id (the measurement and test entry)."""
+        w, v = self._arrays(bow_vec)
+        n = C.c_int32()
+        _lib.check(self._L.ovs_bowdb_score_all(self._h, _p(w), _p(v), len(w), _p(self._ids), _p(self._common), _p(self._scores),
+                                               self.max_keyframes, C.byref(n)), "ovs_bowdb_score_all")
+        n = n.value
+        return list(zip(self._ids[:n].tolist(), self._common[:n].tolist(), self._scores[:n].tolist()))
+
+    def query(self, bow_vec, reject_ids=()):
+        """Rules 2 and 3: (survivors [(keyframe id, num_common, score)] ascending id, max_common)."""
+        w, v = self._arrays(bow_vec)
+        rej = np.array(list(reject_ids), np.int32)
+        n, mc = C.c_int32(), C.c_int32()
+        _lib.check(self._L.ovs_bowdb_query(self._h, _p(w), _p(v), len(w), _p(rej), len(rej), _p(self._ids), _p(self._common), _p(self._scores),
+                                           self.max_keyframes, C.byref(n), C.byref(mc)), "ovs_bowdb_query")
+        n = n.value
+        return list(zip(self._ids[:n].tolist(), self._common[:n].tolist(), self._scores[:n].tolist())), mc.value
+
+    def _candidates(self, bow_vec, reject_ids, top_covisibilities, min_score):
+        survivors, _ = self.query(bow_vec, reject_ids)
+        min_score = _f32(min_score)
+        scores = {}
+        for kid, _, sc in survivors:            # rule 4: upstream stores the score in a float
+            sc = _f32(sc)
+            if sc >= min_score:
+                scores[kid] = sc
+        if not scores:
+            return []
+        records = []
+        for c in sorted(scores):                # rule 5, ascending keyframe id
+            total, best = scores[c], c
+            for n in list(top_covisibilities(c))[:10]:
+                if n not in scores:
+                    continue
+                total = _f32(total + scores[n])
+                if scores[best] < scores[n]:
+                    best = n
+            records.append((total, best))
+        thr = _f32(np.float32(0.75) * np.float32(max(t for t, _ in records)))
+        out = []
+        for total, best in records:             # rule 6
+            if total > thr and best not in out:
+                out.append(best)
+        return out
+
+    def acquire_loop_candidates(self, qry_id, bow_vec, connected_ids, top_covisibilities, min_score):
+        """bow_database::acquire_loop_candidates(qry_keyfrm, min_score): keyframe ids."""
+        return self._candidates(bow_vec, [int(qry_id)] + [int(k) for k in connected_ids], top_covisibilities, min_score)
+
+    def acquire_relocalization_candidates(self, bow_vec, top_covisibilities):
+        """bow_database::acquire_relocalization_candidates(qry_frm): keyframe ids."""
+        return self._candidates(bow_vec, [], top_covisibilities, 0.0)

@@ -2,6 +2,7 @@
 // (expected: src/openvslam/data/{frame,keyframe,landmark}.h, src/openvslam/camera/base.h). In an OpenVSLAM checkout the real
 // headers are used instead and the shim bodies compile unchanged.
 #pragma once
+#include <algorithm>
 #include <memory>
 #include <map>
 #include <mutex>
@@ -62,6 +63,7 @@ public:
 };
 
 using bow_feature_vector = std::map<unsigned int, std::vector<unsigned int>>;   // DBoW2::FeatureVector
+using bow_vector = std::map<unsigned int, double>;                              // DBoW2::BowVector
 
 class landmark {
 public:
@@ -158,17 +160,24 @@ public:
     std::vector<float> inv_level_sigma_sq_;
     float log_scale_factor_ = 0;
     camera::base* camera_ = nullptr;
+    unsigned int id_ = 0;
+    bow_vector bow_vec_;
     bow_feature_vector bow_feat_vec_;
     Mat44_t cam_pose_cw_;
     void set_cam_pose(const Mat44_t& cam_pose_cw) { cam_pose_cw_ = cam_pose_cw; }
 };
 
 class keyframe;
-// data::graph_node: only the covisibility list local_bundle_adjuster walks
+// data::graph_node: the covisibility list local_bundle_adjuster walks (strongest first), and what bow_database reads of it
 class graph_node {
 public:
     std::vector<keyframe*> get_covisibilities() const { return covisibilities_; }
+    std::vector<keyframe*> get_top_n_covisibilities(const unsigned int num_covisibilities) const {
+        return std::vector<keyframe*>(covisibilities_.begin(), covisibilities_.begin() + std::min<size_t>(num_covisibilities, covisibilities_.size()));
+    }
+    std::set<keyframe*> get_connected_keyframes() const { return connected_keyfrms_; }
     std::vector<keyframe*> covisibilities_;
+    std::set<keyframe*> connected_keyfrms_;   // every keyframe sharing a landmark (upstream: the keys of connected_keyfrms_and_weights_)
 };
 
 class keyframe {
@@ -179,7 +188,7 @@ public:
         : device_cache_(frm.device_cache_), num_keypts_(frm.num_keypts_), keypts_(frm.keypts_), undist_keypts_(frm.undist_keypts_),
           stereo_x_right_(frm.stereo_x_right_), bearings_(frm.bearings_), descriptors_(frm.descriptors_), landmarks_(frm.landmarks_),
           scale_factors_(frm.scale_factors_), inv_level_sigma_sq_(frm.inv_level_sigma_sq_), log_scale_factor_(frm.log_scale_factor_),
-          camera_(frm.camera_), bow_feat_vec_(frm.bow_feat_vec_), cam_pose_cw_(frm.cam_pose_cw_) {}
+          camera_(frm.camera_), bow_vec_(frm.bow_vec_), bow_feat_vec_(frm.bow_feat_vec_), cam_pose_cw_(frm.cam_pose_cw_) {}
     std::shared_ptr<frame_device_cache> device_cache_ = std::make_shared<frame_device_cache>();
     unsigned int id_ = 0;
     bool will_be_erased() const { return will_be_erased_; }
@@ -202,6 +211,7 @@ public:
     std::vector<float> inv_level_sigma_sq_;
     float log_scale_factor_ = 0;
     camera::base* camera_ = nullptr;
+    bow_vector bow_vec_;
     bow_feature_vector bow_feat_vec_;
     Mat44_t cam_pose_cw_;
     Mat44_t get_cam_pose() const { return cam_pose_cw_; }

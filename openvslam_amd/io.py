@@ -231,3 +231,18 @@ def local_ba_problem(db, curr_keyfrm_id):
             "cam": np.array([cam["fx"], cam["fy"], cam["cx"], cam["cy"]], np.float64), "focal_x_baseline": float(cam.get("focal_x_baseline", 0.0)),
             "setup_type": {"Monocular": 0, "Stereo": 1, "RGBD": 2}.get(cam.get("setup_type", "Monocular"), 0),
             "keyfrm_ids": keyfrm_ids, "lm_ids": lm_ids, "n_local": len(local)}
+
+
+def top_covisibilities_of(map_db, n=10):
+    """graph_node::get_top_n_covisibilities(n) of a loaded map as the callable bow_database.acquire_* take: id -> at most n ids, strongest first."""
+    return lambda keyfrm_id: map_db.covisibilities(keyfrm_id)[:n]
+
+
+def bow_database_of(map_db, vocabulary, levelsup=4, max_words=4096, device=0):
+    """data::bow_database filled from a loaded map, as upstream's map loader registers every keyframe (compute_bow from the stored
+    descriptors, then bow_db->add_keyframe), in ascending keyframe id. Query it with top_covisibilities_of(map_db)."""
+    from .bow import bow_database
+    db = bow_database(max(len(map_db.keyframes), 1), max_words=max_words, device=device)
+    for kid in sorted(map_db.keyframes):
+        db.add_keyframe(kid, vocabulary.transform(map_db.keyframes[kid].descs, levelsup)[0])
+    return db
