@@ -676,6 +676,32 @@ ovs_status ovs_bowdb_query(ovs_bowdb* db, const int32_t* q_ids, const double* q_
 ovs_status ovs_bowdb_score_all(ovs_bowdb* db, const int32_t* q_ids, const double* q_values, int32_t nq, int32_t* out_ids, int32_t* out_num_common,
                                double* out_scores, int32_t cap, int32_t* n_out);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Sim3 RANSAC for loop-candidate verification.  replaces: solve::sim3_solver::find_via_ransac(max_num_iter) with the constructor's
+ *   reprojections, compute_Sim3 (Horn's closed form on three matches) and count_inliers (src/openvslam/solve/sim3_solver.{h,cc}), for a
+ *   BATCH of (current keyframe 1, candidate keyframe 2) problems in two launches (rules 1 to 4).
+ * ovs_sim3_create: a handle for up to max_problems problems of max_total_matches matches together (replaces: the constructor's
+ *   allocations); one internal mutex serialises the calls on a handle.
+ * ovs_sim3_solve_batch: problem p owns matches [offsets[p], offsets[p + 1]) (offsets[0] = 0, non-decreasing). p1 / p2: 3 doubles per match,
+ *   the landmark in camera-1 / camera-2 coordinates (sim3_solver's common_pts_in_keyfrm_1_ / _2_); thr1 / thr2: upstream's
+ *   chi_sq_x_sigma_sq_1_ / _2_ = 9.21 * level_sigma_sq[octave], as floats; cams_1 / cams_2: one camera per problem and side (model 0 reads
+ *   fx fy cx cy, model 1 cols rows). seed: upstream draws from random_device; here hypothesis h of problem p is a function of (seed, p, h).
+ *   Outputs per problem: valid (solution_is_valid_), best_iter (the winning hypothesis, -1 if invalid), num_inliers, rot_12 (9, row-major:
+ *   get_best_rotation_12), trans_12 (3: get_best_translation_12), scale_12 (get_best_scale_12); inlier_flags: one byte per match. An
+ *   invalid problem returns identity, zero, 1.0, flags 0. Results are bit-exact functions of (inputs, seed, p): problem p of a batch, solved
+ *   alone under the seed `seed + 0x9E3779B97F4A7C15 * (p << 22)`, gives the same result.
+ * OVS_ERR_INVALID: a NULL required pointer, offsets not starting at 0 or decreasing, max_num_iter < 1 or > 2^20, min_num_inliers < 0, an unknown
+ *   camera model, non-finite fx fy cx cy (model 0) or cols / rows < 1 (model 1). OVS_ERR_CAPACITY: more problems or matches than the handle
+ *   was created for (nothing is truncated, no output is written). Both are decided before any launch. A problem with fewer than 3 matches
+ *   is not an error: it is invalid. */
+typedef struct ovs_sim3 ovs_sim3;
+ovs_status ovs_sim3_create(int32_t device, int32_t max_problems, int32_t max_total_matches, ovs_sim3** out);
+ovs_status ovs_sim3_destroy(ovs_sim3* s);
+ovs_status ovs_sim3_solve_batch(ovs_sim3* s, int32_t n_problems, const int32_t* offsets, const double* p1, const double* p2, const float* thr1,
+                                const float* thr2, const ovs_camera* cams_1, const ovs_camera* cams_2, int32_t fix_scale, int32_t min_num_inliers,
+                                int32_t max_num_iter, uint64_t seed, int32_t* out_valid, int32_t* out_best_iter, int32_t* out_num_inliers,
+                                double* out_rot_12, double* out_trans_12, double* out_scale_12, uint8_t* out_inlier_flags);
+
 /* replaces: the optimisation inside  void optimize::local_bundle_adjuster::optimize(data::keyframe* curr_keyfrm, bool* const
  *               force_stop_flag) const  (src/openvslam/optimize/local_bundle_adjuster.{h,cc}): everything between the graph build and the
  * write-back, i.e. optimizer.optimize(num_first_iter) with Huber kernels (ONE delta per rig: setup_type 0 = Monocular -> sqrtf(5.99146f),

@@ -157,6 +157,7 @@ public:
     std::vector<landmark*> landmarks_;
     std::vector<bool> outlier_flags_;
     std::vector<float> scale_factors_;
+    std::vector<float> level_sigma_sq_;
     std::vector<float> inv_level_sigma_sq_;
     float log_scale_factor_ = 0;
     camera::base* camera_ = nullptr;
@@ -187,7 +188,7 @@ public:
     explicit keyframe(const frame& frm)
         : device_cache_(frm.device_cache_), num_keypts_(frm.num_keypts_), keypts_(frm.keypts_), undist_keypts_(frm.undist_keypts_),
           stereo_x_right_(frm.stereo_x_right_), bearings_(frm.bearings_), descriptors_(frm.descriptors_), landmarks_(frm.landmarks_),
-          scale_factors_(frm.scale_factors_), inv_level_sigma_sq_(frm.inv_level_sigma_sq_), log_scale_factor_(frm.log_scale_factor_),
+          scale_factors_(frm.scale_factors_), level_sigma_sq_(frm.level_sigma_sq_), inv_level_sigma_sq_(frm.inv_level_sigma_sq_), log_scale_factor_(frm.log_scale_factor_),
           camera_(frm.camera_), bow_vec_(frm.bow_vec_), bow_feat_vec_(frm.bow_feat_vec_), cam_pose_cw_(frm.cam_pose_cw_) {}
     std::shared_ptr<frame_device_cache> device_cache_ = std::make_shared<frame_device_cache>();
     unsigned int id_ = 0;
@@ -208,6 +209,7 @@ public:
     cv::Mat descriptors_;
     std::vector<landmark*> landmarks_;
     std::vector<float> scale_factors_;
+    std::vector<float> level_sigma_sq_;   // scale_factors_[l]^2 (solve::sim3_solver's thresholds)
     std::vector<float> inv_level_sigma_sq_;
     float log_scale_factor_ = 0;
     camera::base* camera_ = nullptr;

@@ -1,0 +1,535 @@
+// sim3_solve.hip -- solve::sim3_solver (expected: src/openvslam/solve/sim3_solver.{h,cc}): find_via_ransac over a batch of loop candidates
+// (loop_detector runs it once per candidate between bow_tree::match_keyframes and projection::match_by_Sim3_transform). Rules: DESIGN.md 3.9.
+//
+// A problem is one (keyframe 1, keyframe 2) pair with n matches: p1 / p2 (the landmark in camera-1 / camera-2 coordinates), thr1 / thr2 and a
+// camera per side. Everything is f64, every operation rounded on its own (the unit is built with -ffp-contract=off).
+//
+// k_sim3_hypotheses: grid (blocks of kHypPerWave hypotheses, problems), one wavefront per workgroup. Lane l < kHypPerWave solves hypothesis
+// h = block * kHypPerWave + l in registers: the counter-based sampler, Horn's closed form with the 4 x 4 cyclic Jacobi unrolled on
+// compile-time indices (no local array is indexed dynamically: no scratch), and leaves the model's 17 distinct doubles (R12, t12, s12, s21,
+// t21; R21 is R12 read by columns) in LDS. The wave then walks its models with the lanes over the matches: the two observations u1, u2 of a
+// round of 64 matches are projected once and kept in registers, every model is a broadcast LDS read, the inlier count of a (model, round)
+// is ballot + popcount -- a wave-uniform integer -- and lane m keeps model m's total. A hypothesis's key is (count << 32) | (0xFFFFFFFF - h):
+// the largest count wins, the lowest h on a tie. The wave takes the maximum of its keys by shuffles, the lane that holds it copies its
+// model to the wave's record in memory (136 bytes per wave) and publishes the key with ONE integer atomicMax, in whatever order the waves
+// finish. No floating-point atomics, no waiting between workgroups.
+// k_sim3_finish: one workgroup per problem; the winner is its wave's best, so its model is read back from that wave's record -- the doubles the
+// hypothesis kernel counted with, not a recomputation (the closed form is a 20 us chain of dependent f64 operations: DESIGN.md 3.9). The
+// threads write the flags of their matches with the same inlier function, thread 0 the model, into the page-locked result block.
+#include <cmath>
+#include <cstring>
+#include <mutex>
+
+#include "ovs_common.h"
+
+namespace {
+
+constexpr int kHypPerWave = 4;      // hypotheses per wavefront (measured against 8, 16, 32 and 64)
+constexpr int kModelDoubles = 17;   // R12 9, t12 3, s12, s21, t21 3
+constexpr int kMaxIter = 1 << 20;   // h takes 20 bits of the sampler's counter
+constexpr int kFinishThreads = 256;
+
+// one side's camera as the kernels read it: perspective (fx, fy, cx, cy) or equirectangular ((double)cols, (double)rows, -, -)
+struct CamRec {
+    double a, b, c, d;
+    int32_t model, pad;
+};
+static_assert(sizeof(CamRec) == 40, "CamRec is laid out in the staged block by the host");
+
+// per problem in the result block
+struct ResultRec {
+    double rot[9], trans[3], scale;
+    int32_t valid, best_iter, num_inliers, pad;
+};
+static_assert(sizeof(ResultRec) == 120, "ResultRec is read by the host");
+
+// The staged block of one call, sections in this order (each a multiple of 8 bytes but the last): keys u64 [P] (zero), cameras CamRec [2 P]
+// (side 1 then side 2 of a problem), p1 f64 [3 T], p2 f64 [3 T], thr1 f32 [T'], thr2 f32 [T'], offsets i32 [P + 1]; T' = T rounded up to even.
+struct Layout {
+    size_t keys, cams, p1, p2, thr1, thr2, offsets, bytes;
+};
+__host__ __device__ inline Layout layout_of(int P, int T) {
+    const size_t Te = ((size_t)T + 1) & ~(size_t)1;
+    Layout l;
+    l.keys = 0;
+    l.cams = l.keys + 8 * (size_t)P;
+    l.p1 = l.cams + sizeof(CamRec) * 2 * (size_t)P;
+    l.p2 = l.p1 + 24 * (size_t)T;
+    l.thr1 = l.p2 + 24 * (size_t)T;
+    l.thr2 = l.thr1 + 4 * Te;
+    l.offsets = l.thr2 + 4 * Te;
+    l.bytes = l.offsets + 4 * ((size_t)P + 1);
+    return l;
+}
+
+struct Model {
+    double R[9], t12[3], s12, s21, t21[3];
+};
+
+__device__ __forceinline__ uint64_t mix64(uint64_t z) {   // the splitmix64 finaliser
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// rule 1: three distinct indices below n (n >= 3), no rejection loop
+__device__ __forceinline__ void sample3(uint64_t seed, uint32_t p, uint32_t h, uint32_t n, uint32_t& i0, uint32_t& i1, uint32_t& i2) {
+    const uint64_t G = 0x9E3779B97F4A7C15ull;
+    const uint64_t base = seed + G * (((((uint64_t)p) << 20) + h) * 4 + 1);
+    i0 = (uint32_t)(mix64(base) % n);
+    i1 = (uint32_t)(mix64(base + G) % (n - 1));
+    if (i1 >= i0) ++i1;
+    i2 = (uint32_t)(mix64(base + G * 2) % (n - 2));
+    const uint32_t lo = i0 < i1 ? i0 : i1, hi = i0 < i1 ? i1 : i0;
+    if (i2 >= lo) ++i2;
+    if (i2 >= hi) ++i2;
+}
+
+// one Jacobi rotation on the pair (P, Q), the operations of essential_solver.h::compute_E_21: columns, then rows, then V
+template <int P, int Q>
+__device__ __forceinline__ void jacobi_rotate(double (&A)[4][4], double (&V)[4][4]) {
+    const double apq = A[P][Q];
+    if (apq == 0.0) return;
+    const double theta = (A[Q][Q] - A[P][P]) / (2.0 * apq);
+    const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const double akp = A[k][P], akq = A[k][Q];
+        A[k][P] = c * akp - s * akq;
+        A[k][Q] = s * akp + c * akq;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const double apk = A[P][k], aqk = A[Q][k];
+        A[P][k] = c * apk - s * aqk;
+        A[Q][k] = s * apk + c * aqk;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const double vkp = V[k][P], vkq = V[k][Q];
+        V[k][P] = c * vkp - s * vkq;
+        V[k][Q] = s * vkp + c * vkq;
+    }
+}
+
+__device__ __forceinline__ double dot3(double a0, double a1, double a2, double b0, double b1, double b2) { return (a0 * b0 + a1 * b1) + a2 * b2; }
+
+// rule 2: Horn's closed form on the three sampled matches of hypothesis h
+__device__ __forceinline__ Model solve_hypothesis(const double* __restrict__ p1, const double* __restrict__ p2, uint32_t n, uint64_t seed, uint32_t p,
+                                                  uint32_t h, bool fix_scale) {
+    uint32_t idx[3];
+    sample3(seed, p, h, n, idx[0], idx[1], idx[2]);
+    double a[3][3], b[3][3];   // [k][axis]
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int x = 0; x < 3; ++x) {
+            a[k][x] = p1[3 * (size_t)idx[k] + x];
+            b[k][x] = p2[3 * (size_t)idx[k] + x];
+        }
+    double c1[3], c2[3];
+#pragma unroll
+    for (int x = 0; x < 3; ++x) {
+        c1[x] = ((a[0][x] + a[1][x]) + a[2][x]) / 3.0;
+        c2[x] = ((b[0][x] + b[1][x]) + b[2][x]) / 3.0;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int x = 0; x < 3; ++x) {
+            a[k][x] = a[k][x] - c1[x];
+            b[k][x] = b[k][x] - c2[x];
+        }
+    double M[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) M[r][c] = (b[0][r] * a[0][c] + b[1][r] * a[1][c]) + b[2][r] * a[2][c];
+    double A[4][4], V[4][4];
+    A[0][0] = (M[0][0] + M[1][1]) + M[2][2];
+    A[0][1] = M[1][2] - M[2][1];
+    A[0][2] = M[2][0] - M[0][2];
+    A[0][3] = M[0][1] - M[1][0];
+    A[1][1] = (M[0][0] - M[1][1]) - M[2][2];
+    A[1][2] = M[0][1] + M[1][0];
+    A[1][3] = M[2][0] + M[0][2];
+    A[2][2] = (-M[0][0] + M[1][1]) - M[2][2];
+    A[2][3] = M[1][2] + M[2][1];
+    A[3][3] = (-M[0][0] - M[1][1]) + M[2][2];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            if (c < r) A[r][c] = A[c][r];
+            V[r][c] = r == c ? 1.0 : 0.0;
+        }
+#pragma unroll 1
+    for (int sweep = 0; sweep < 8; ++sweep) {
+        jacobi_rotate<0, 1>(A, V);
+        jacobi_rotate<0, 2>(A, V);
+        jacobi_rotate<0, 3>(A, V);
+        jacobi_rotate<1, 2>(A, V);
+        jacobi_rotate<1, 3>(A, V);
+        jacobi_rotate<2, 3>(A, V);
+    }
+    // the eigenvector of the largest diagonal entry, lowest index on a tie (selects, not an indexed read)
+    double best = A[0][0], q0 = V[0][0], q1 = V[1][0], q2 = V[2][0], q3 = V[3][0];
+#pragma unroll
+    for (int i = 1; i < 4; ++i) {
+        const bool take = A[i][i] > best;
+        best = take ? A[i][i] : best;
+        q0 = take ? V[0][i] : q0;
+        q1 = take ? V[1][i] : q1;
+        q2 = take ? V[2][i] : q2;
+        q3 = take ? V[3][i] : q3;
+    }
+    const double nrm = sqrt(((q0 * q0 + q1 * q1) + q2 * q2) + q3 * q3);
+    const double w = q0 / nrm, x = q1 / nrm, y = q2 / nrm, z = q3 / nrm;
+    Model m;
+    m.R[0] = 1.0 - 2.0 * (y * y + z * z);
+    m.R[1] = 2.0 * (x * y - w * z);
+    m.R[2] = 2.0 * (x * z + w * y);
+    m.R[3] = 2.0 * (x * y + w * z);
+    m.R[4] = 1.0 - 2.0 * (x * x + z * z);
+    m.R[5] = 2.0 * (y * z - w * x);
+    m.R[6] = 2.0 * (x * z - w * y);
+    m.R[7] = 2.0 * (y * z + w * x);
+    m.R[8] = 1.0 - 2.0 * (x * x + y * y);
+    if (fix_scale) {
+        m.s12 = 1.0;
+    } else {
+        double num[3], den[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double r0 = dot3(m.R[0], m.R[1], m.R[2], b[k][0], b[k][1], b[k][2]);
+            const double r1 = dot3(m.R[3], m.R[4], m.R[5], b[k][0], b[k][1], b[k][2]);
+            const double r2 = dot3(m.R[6], m.R[7], m.R[8], b[k][0], b[k][1], b[k][2]);
+            num[k] = dot3(a[k][0], a[k][1], a[k][2], r0, r1, r2);
+            den[k] = dot3(r0, r1, r2, r0, r1, r2);
+        }
+        m.s12 = ((num[0] + num[1]) + num[2]) / ((den[0] + den[1]) + den[2]);
+    }
+#pragma unroll
+    for (int r = 0; r < 3; ++r) m.t12[r] = c1[r] - m.s12 * dot3(m.R[3 * r], m.R[3 * r + 1], m.R[3 * r + 2], c2[0], c2[1], c2[2]);
+    m.s21 = 1.0 / m.s12;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) m.t21[r] = -m.s21 * dot3(m.R[r], m.R[3 + r], m.R[6 + r], m.t12[0], m.t12[1], m.t12[2]);
+    return m;
+}
+
+// rule 3's projections
+__device__ __forceinline__ void project(const CamRec& cam, double x, double y, double z, double& u, double& v) {
+    if (cam.model == 0) {
+        u = cam.a * x / z + cam.c;
+        v = cam.b * y / z + cam.d;
+    } else {
+        const double kPi = 3.14159265358979323846;
+        const double L = sqrt((x * x + y * y) + z * z);
+        const double theta = ovs_det_atan2(x, z);
+        const double phi = -ovs_det_asin(y / L);
+        u = cam.a * (0.5 + theta / (2.0 * kPi));
+        v = cam.b * (0.5 - phi / kPi);
+    }
+}
+
+// one match as the inlier test reads it: the two points, their own projections and the two thresholds widened to f64
+struct Match {
+    double p1[3], p2[3], u1x, u1y, u2x, u2y, thr1, thr2;
+};
+__device__ __forceinline__ Match load_match(const CamRec& cam1, const CamRec& cam2, const double* __restrict__ p1, const double* __restrict__ p2,
+                                            const float* __restrict__ thr1, const float* __restrict__ thr2, size_t i) {
+    Match m;
+#pragma unroll
+    for (int x = 0; x < 3; ++x) {
+        m.p1[x] = p1[3 * i + x];
+        m.p2[x] = p2[3 * i + x];
+    }
+    m.thr1 = (double)thr1[i];
+    m.thr2 = (double)thr2[i];
+    project(cam1, m.p1[0], m.p1[1], m.p1[2], m.u1x, m.u1y);
+    project(cam2, m.p2[0], m.p2[1], m.p2[2], m.u2x, m.u2y);
+    return m;
+}
+
+// rule 3: a NaN anywhere leaves every comparison false
+__device__ __forceinline__ bool is_inlier(const CamRec& cam1, const CamRec& cam2, const Match& m, const double* R, const double* t12, double s12,
+                                          double s21, const double* t21) {
+    const double x1 = s12 * dot3(R[0], R[1], R[2], m.p2[0], m.p2[1], m.p2[2]) + t12[0];
+    const double y1 = s12 * dot3(R[3], R[4], R[5], m.p2[0], m.p2[1], m.p2[2]) + t12[1];
+    const double z1 = s12 * dot3(R[6], R[7], R[8], m.p2[0], m.p2[1], m.p2[2]) + t12[2];
+    const double x2 = s21 * dot3(R[0], R[3], R[6], m.p1[0], m.p1[1], m.p1[2]) + t21[0];
+    const double y2 = s21 * dot3(R[1], R[4], R[7], m.p1[0], m.p1[1], m.p1[2]) + t21[1];
+    const double z2 = s21 * dot3(R[2], R[5], R[8], m.p1[0], m.p1[1], m.p1[2]) + t21[2];
+    double v1x, v1y, v2x, v2y;
+    project(cam1, x1, y1, z1, v1x, v1y);
+    project(cam2, x2, y2, z2, v2x, v2y);
+    const double d1x = m.u1x - v1x, d1y = m.u1y - v1y, d2x = m.u2x - v2x, d2y = m.u2y - v2y;
+    const double e1 = d1x * d1x + d1y * d1y, e2 = d2x * d2x + d2y * d2y;
+    bool ok = e1 < m.thr1 && e2 < m.thr2;
+    if (cam1.model == 0) ok = ok && m.p1[2] > 0.0 && z1 > 0.0;
+    if (cam2.model == 0) ok = ok && m.p2[2] > 0.0 && z2 > 0.0;
+    return ok;
+}
+
+__global__ __launch_bounds__(64) void k_sim3_hypotheses(uint8_t* __restrict__ block, int P, int T, int fix_scale, int max_iter, uint64_t seed,
+                                                        double* __restrict__ wave_models) {
+    __shared__ double models[kHypPerWave * kModelDoubles];
+    const Layout lay = layout_of(P, T);
+    const int p = blockIdx.y;
+    const int32_t* offsets = reinterpret_cast<const int32_t*>(block + lay.offsets);
+    const int off = offsets[p], n = offsets[p + 1] - off;
+    if (n < 3) return;   // rule 4: invalid, k_sim3_finish says so
+    const CamRec cam1 = reinterpret_cast<const CamRec*>(block + lay.cams)[2 * p], cam2 = reinterpret_cast<const CamRec*>(block + lay.cams)[2 * p + 1];
+    const double* p1 = reinterpret_cast<const double*>(block + lay.p1) + 3 * (size_t)off;
+    const double* p2 = reinterpret_cast<const double*>(block + lay.p2) + 3 * (size_t)off;
+    const float* thr1 = reinterpret_cast<const float*>(block + lay.thr1) + off;
+    const float* thr2 = reinterpret_cast<const float*>(block + lay.thr2) + off;
+    const int lane = threadIdx.x;
+    const int h0 = blockIdx.x * kHypPerWave;
+    const int nh = min(kHypPerWave, max_iter - h0);   // >= 1 by the grid's size
+    if (lane < nh) {
+        const Model m = solve_hypothesis(p1, p2, (uint32_t)n, seed, (uint32_t)p, (uint32_t)(h0 + lane), fix_scale != 0);
+        double* dst = models + lane * kModelDoubles;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) dst[k] = m.R[k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            dst[9 + k] = m.t12[k];
+            dst[14 + k] = m.t21[k];
+        }
+        dst[12] = m.s12;
+        dst[13] = m.s21;
+    }
+    __syncthreads();
+    int count = 0;   // lane m: the inliers of model m
+    for (int base = 0; base < n; base += 64) {
+        const bool have = base + lane < n;
+        const Match mt = load_match(cam1, cam2, p1, p2, thr1, thr2, (size_t)(have ? base + lane : 0));
+        for (int m = 0; m < nh; ++m) {
+            const double* md = models + m * kModelDoubles;   // the same address in every lane: a broadcast read
+            const bool inl = have && is_inlier(cam1, cam2, mt, md, md + 9, md[12], md[13], md + 14);
+            const int c = __popcll(__ballot(inl));
+            if (lane == m) count += c;
+        }
+    }
+    const unsigned long long key =
+        lane < nh ? ((unsigned long long)(uint32_t)count << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)(h0 + lane)) : 0ull;   // never 0 for a hypothesis
+    unsigned long long best = key;
+#pragma unroll
+    for (int d = 32; d; d >>= 1) {
+        const unsigned long long other = __shfl_xor(best, d);
+        best = other > best ? other : best;
+    }
+    if (key == best) {   // one lane: the keys of a wave differ in h
+        double* dst = wave_models + ((size_t)p * gridDim.x + blockIdx.x) * kModelDoubles;
+        const double* src = models + lane * kModelDoubles;
+#pragma unroll
+        for (int k = 0; k < kModelDoubles; ++k) dst[k] = src[k];
+        atomicMax(reinterpret_cast<unsigned long long*>(block + lay.keys) + p, key);
+    }
+}
+
+__global__ __launch_bounds__(kFinishThreads) void k_sim3_finish(const uint8_t* __restrict__ block, int P, int T, int min_inliers, int waves_per_problem,
+                                                                const double* __restrict__ wave_models, ResultRec* __restrict__ out,
+                                                                uint8_t* __restrict__ out_flags) {
+    const Layout lay = layout_of(P, T);
+    const int p = blockIdx.x;
+    const int32_t* offsets = reinterpret_cast<const int32_t*>(block + lay.offsets);
+    const int off = offsets[p], n = offsets[p + 1] - off;
+    const unsigned long long key = reinterpret_cast<const unsigned long long*>(block + lay.keys)[p];
+    const int count = (int)(key >> 32);
+    const uint32_t h = 0xFFFFFFFFu - (uint32_t)key;
+    const bool valid = n >= 3 && n >= min_inliers && count >= min_inliers;   // rule 4 (n < 3: the key is still zero and never read)
+    if (!valid) {
+        for (int i = threadIdx.x; i < n; i += kFinishThreads) out_flags[off + i] = 0;
+        if (threadIdx.x == 0) {
+            ResultRec r;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) r.rot[k] = (k % 4 == 0) ? 1.0 : 0.0;
+            r.trans[0] = r.trans[1] = r.trans[2] = 0.0;
+            r.scale = 1.0;
+            r.valid = 0;
+            r.best_iter = -1;
+            r.num_inliers = 0;
+            r.pad = 0;
+            out[p] = r;
+        }
+        return;
+    }
+    const CamRec cam1 = reinterpret_cast<const CamRec*>(block + lay.cams)[2 * p], cam2 = reinterpret_cast<const CamRec*>(block + lay.cams)[2 * p + 1];
+    const double* p1 = reinterpret_cast<const double*>(block + lay.p1) + 3 * (size_t)off;
+    const double* p2 = reinterpret_cast<const double*>(block + lay.p2) + 3 * (size_t)off;
+    const float* thr1 = reinterpret_cast<const float*>(block + lay.thr1) + off;
+    const float* thr2 = reinterpret_cast<const float*>(block + lay.thr2) + off;
+    const double* md = wave_models + ((size_t)p * waves_per_problem + h / kHypPerWave) * kModelDoubles;   // the winner is its wave's best
+    double m[kModelDoubles];
+#pragma unroll
+    for (int k = 0; k < kModelDoubles; ++k) m[k] = md[k];
+    for (int i = threadIdx.x; i < n; i += kFinishThreads) {
+        const Match mt = load_match(cam1, cam2, p1, p2, thr1, thr2, (size_t)i);
+        out_flags[off + i] = is_inlier(cam1, cam2, mt, m, m + 9, m[12], m[13], m + 14) ? 1 : 0;
+    }
+    if (threadIdx.x == 0) {
+        ResultRec r;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) r.rot[k] = m[k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) r.trans[k] = m[9 + k];
+        r.scale = m[12];
+        r.valid = 1;
+        r.best_iter = (int32_t)h;
+        r.num_inliers = count;
+        r.pad = 0;
+        out[p] = r;
+    }
+}
+
+}   // namespace
+
+struct ovs_sim3 {
+    int device = 0;
+    int max_problems = 0, max_total_matches = 0;
+    std::mutex mu;
+    hipStream_t stream = nullptr;
+    uint8_t *d_block = nullptr, *h_block = nullptr;   // the staged block (Layout) and its page-locked twin
+    double* d_wave_models = nullptr;                  // [problem][wave] the model of the wave's best hypothesis; grows with problems x max_num_iter
+    size_t wave_models_cap = 0;                       // in records of kModelDoubles
+    // results, page-locked and mapped: k_sim3_finish writes them, the host reads them after the stream has drained
+    ResultRec *h_result = nullptr, *m_result = nullptr;
+    uint8_t *h_flags = nullptr, *m_flags = nullptr;
+};
+
+namespace {
+
+void sim3_free(ovs_sim3* s) {
+    if (!s) return;
+    hipFree(s->d_block);
+    hipFree(s->d_wave_models);
+    if (s->h_block) hipHostFree(s->h_block);
+    if (s->h_result) hipHostFree(s->h_result);
+    if (s->h_flags) hipHostFree(s->h_flags);
+    if (s->stream) hipStreamDestroy(s->stream);
+    delete s;
+}
+
+bool camera_ok(const ovs_camera& c, CamRec* rec) {
+    rec->pad = 0;
+    rec->model = c.model;
+    if (c.model == 0) {
+        if (!std::isfinite(c.fx) || !std::isfinite(c.fy) || !std::isfinite(c.cx) || !std::isfinite(c.cy)) return false;
+        rec->a = c.fx, rec->b = c.fy, rec->c = c.cx, rec->d = c.cy;
+        return true;
+    }
+    if (c.model == 1) {
+        if (c.cols < 1 || c.rows < 1) return false;
+        rec->a = (double)c.cols, rec->b = (double)c.rows, rec->c = 0.0, rec->d = 0.0;
+        return true;
+    }
+    return false;
+}
+
+}   // namespace
+
+extern "C" {
+
+ovs_status ovs_sim3_create(int32_t device, int32_t max_problems, int32_t max_total_matches, ovs_sim3** out) {
+    if (!out || max_problems < 1 || max_total_matches < 1) return OVS_ERR_INVALID;
+    *out = nullptr;
+    if (max_problems > 65535) return OVS_ERR_INVALID;   // a grid's y extent
+    if (ovs_device_count() <= device || device < 0) return OVS_ERR_NO_DEVICE;
+    OVS_HIP_TRY(hipSetDevice(device));
+    ovs_sim3* s = new ovs_sim3();
+    s->device = device;
+    s->max_problems = max_problems;
+    s->max_total_matches = max_total_matches;
+    const size_t block_bytes = layout_of(max_problems, max_total_matches).bytes;
+    hipError_t e = hipSuccess;
+#define D_TRY(expr)                                      \
+    if ((e = ovs::fault_filter(expr)) != hipSuccess) {   \
+        ovs::set_last_error(#expr, e);                   \
+        sim3_free(s);                                    \
+        return OVS_ERR_HIP;                              \
+    }
+    D_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+    D_TRY(hipMalloc(&s->d_block, block_bytes));
+    s->wave_models_cap = (size_t)max_problems * (256 / kHypPerWave);   // 256 iterations per problem without growing
+    D_TRY(hipMalloc(&s->d_wave_models, sizeof(double) * kModelDoubles * s->wave_models_cap));
+    D_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_block), block_bytes, hipHostMallocDefault));
+    D_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_result), sizeof(ResultRec) * (size_t)max_problems, hipHostMallocMapped));
+    D_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->m_result), s->h_result, 0));
+    D_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_flags), (size_t)max_total_matches, hipHostMallocMapped));
+    D_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->m_flags), s->h_flags, 0));
+#undef D_TRY
+    *out = s;
+    return OVS_OK;
+}
+
+ovs_status ovs_sim3_destroy(ovs_sim3* s) {
+    if (!s) return OVS_ERR_INVALID;
+    hipSetDevice(s->device);
+    sim3_free(s);
+    return OVS_OK;
+}
+
+ovs_status ovs_sim3_solve_batch(ovs_sim3* s, int32_t n_problems, const int32_t* offsets, const double* p1, const double* p2, const float* thr1,
+                                const float* thr2, const ovs_camera* cams_1, const ovs_camera* cams_2, int32_t fix_scale, int32_t min_num_inliers,
+                                int32_t max_num_iter, uint64_t seed, int32_t* out_valid, int32_t* out_best_iter, int32_t* out_num_inliers,
+                                double* out_rot_12, double* out_trans_12, double* out_scale_12, uint8_t* out_inlier_flags) {
+    // every argument error is decided here, before the device is touched
+    if (!s || n_problems < 0 || max_num_iter < 1 || max_num_iter > kMaxIter || min_num_inliers < 0) return OVS_ERR_INVALID;
+    if (n_problems == 0) return OVS_OK;
+    if (!offsets || !cams_1 || !cams_2 || !out_valid || !out_best_iter || !out_num_inliers || !out_rot_12 || !out_trans_12 || !out_scale_12)
+        return OVS_ERR_INVALID;
+    if (offsets[0] != 0) return OVS_ERR_INVALID;
+    for (int32_t p = 0; p < n_problems; ++p)
+        if (offsets[p + 1] < offsets[p]) return OVS_ERR_INVALID;
+    const int32_t T = offsets[n_problems];
+    if (T > 0 && (!p1 || !p2 || !thr1 || !thr2 || !out_inlier_flags)) return OVS_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (n_problems > s->max_problems || T > s->max_total_matches) return OVS_ERR_CAPACITY;   // nothing is truncated
+    const Layout lay = layout_of(n_problems, T);
+    CamRec* cams = reinterpret_cast<CamRec*>(s->h_block + lay.cams);
+    for (int32_t p = 0; p < n_problems; ++p)
+        if (!camera_ok(cams_1[p], &cams[2 * p]) || !camera_ok(cams_2[p], &cams[2 * p + 1])) return OVS_ERR_INVALID;
+    std::memset(s->h_block + lay.keys, 0, 8 * (size_t)n_problems);
+    if (T > 0) {
+        std::memcpy(s->h_block + lay.p1, p1, 24 * (size_t)T);
+        std::memcpy(s->h_block + lay.p2, p2, 24 * (size_t)T);
+        std::memcpy(s->h_block + lay.thr1, thr1, 4 * (size_t)T);
+        std::memcpy(s->h_block + lay.thr2, thr2, 4 * (size_t)T);
+    }
+    std::memcpy(s->h_block + lay.offsets, offsets, 4 * ((size_t)n_problems + 1));
+    OVS_HIP_TRY(hipSetDevice(s->device));
+    hipStream_t st = s->stream;
+    const int blocks = (max_num_iter + kHypPerWave - 1) / kHypPerWave;
+    const size_t records = (size_t)n_problems * (size_t)blocks;
+    if (records > s->wave_models_cap) {   // the stream is idle: every call ends in a synchronise
+        OVS_HIP_TRY(hipFree(s->d_wave_models));
+        s->d_wave_models = nullptr;
+        s->wave_models_cap = 0;
+        OVS_HIP_TRY(hipMalloc(&s->d_wave_models, sizeof(double) * kModelDoubles * records));
+        s->wave_models_cap = records;
+    }
+    OVS_HIP_TRY(hipMemcpyAsync(s->d_block, s->h_block, lay.bytes, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_sim3_hypotheses, dim3(blocks, n_problems), dim3(64), 0, st, s->d_block, n_problems, T, fix_scale ? 1 : 0, max_num_iter, seed,
+                       s->d_wave_models);
+    OVS_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_sim3_finish, dim3(n_problems), dim3(kFinishThreads), 0, st, s->d_block, n_problems, T, min_num_inliers, blocks,
+                       s->d_wave_models, s->m_result, s->m_flags);
+    OVS_HIP_TRY(hipGetLastError());
+    OVS_HIP_TRY(hipStreamSynchronize(st));
+    for (int32_t p = 0; p < n_problems; ++p) {
+        const ResultRec& r = s->h_result[p];
+        out_valid[p] = r.valid;
+        out_best_iter[p] = r.best_iter;
+        out_num_inliers[p] = r.num_inliers;
+        std::memcpy(out_rot_12 + 9 * (size_t)p, r.rot, sizeof(r.rot));
+        std::memcpy(out_trans_12 + 3 * (size_t)p, r.trans, sizeof(r.trans));
+        out_scale_12[p] = r.scale;
+    }
+    if (T > 0) std::memcpy(out_inlier_flags, s->h_flags, (size_t)T);
+    return OVS_OK;
+}
+
+}   // extern "C"

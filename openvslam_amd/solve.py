@@ -1,0 +1,130 @@
+"""solve::sim3_solver (expected: src/openvslam/solve/sim3_solver.{h,cc}) on the MI355X: the RANSAC the loop detector runs on every loop
+candidate between bow_tree::match_keyframes and projection::match_by_Sim3_transform. All candidates of a keyframe go to the device in ONE
+call (ovs_sim3_solve_batch, csrc/sim3_solve.hip): two launches whatever their number. DESIGN.md 3.9 has the rules; the results are
+bit-exact functions of (inputs, seed, position in the batch)."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+
+DEFAULT_SEED = 0x53696D33   # upstream draws from random_device; here a run is reproducible
+_G = 0x9E3779B97F4A7C15
+_MASK = (1 << 64) - 1
+
+
+def _p(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def problem_seed(seed, p):
+    """The seed under which problem p of a batch, solved ALONE (as problem 0), draws the samples it draws in the batch (rule 1)."""
+    return (seed + _G * (p << 22)) & _MASK
+
+
+def camera(model=0, fx=0.0, fy=0.0, cx=0.0, cy=0.0, cols=0, rows=0):
+    """ovs_camera for one side: model 0 (perspective: fx fy cx cy) or 1 (equirectangular: cols rows)."""
+    return _lib.Camera(int(model), 0, float(fx), float(fy), float(cx), float(cy), 0.0, 0.0, int(cols), int(rows))
+
+
+def _transform(pose_cw, pos_w):
+    """rot_cw * pos_w + trans_cw, per point, in upstream's order of operations (Eigen: the row's products added left to right, then the translation)."""
+    T = np.asarray(pose_cw, np.float64)
+    P = np.ascontiguousarray(pos_w, np.float64).reshape(-1, 3)
+    out = np.empty_like(P)
+    for r in range(3):
+        out[:, r] = ((T[r, 0] * P[:, 0] + T[r, 1] * P[:, 1]) + T[r, 2] * P[:, 2]) + T[r, 3]
+    return out
+
+
+def problem_from_keyframes(pose_cw_1, pose_cw_2, pos_w_1, pos_w_2, octaves_1, octaves_2, level_sigma_sq_1, level_sigma_sq_2, cam_1, cam_2):
+    """What sim3_solver's constructor collects for the matched landmark pairs (lm_1[i], lm_2[i]): common_pts_in_keyfrm_1_ / _2_ (each
+    landmark in its own keyframe's camera) and chi_sq_x_sigma_sq_1_ / _2_ = 9.21 * level_sigma_sq[octave of the landmark's keypoint], narrowed
+    to float. pose_cw_*: 4 x 4 (or 3 x 4) world -> camera; pos_w_*: (n, 3); octaves_*: (n,); level_sigma_sq_*: per level."""
+    s1 = np.asarray(level_sigma_sq_1, np.float32)[np.asarray(octaves_1, np.int64)]
+    s2 = np.asarray(level_sigma_sq_2, np.float32)[np.asarray(octaves_2, np.int64)]
+    return dict(p1=_transform(pose_cw_1, pos_w_1), p2=_transform(pose_cw_2, pos_w_2), thr1=(9.21 * s1.astype(np.float64)).astype(np.float32),
+                thr2=(9.21 * s2.astype(np.float64)).astype(np.float32), cam_1=cam_1, cam_2=cam_2)
+
+
+class _handle:
+    """ovs_sim3 with its capacity."""
+
+    def __init__(self, max_problems, max_total_matches, device=0):
+        self._L = _lib.lib()
+        _lib.require_device()
+        self.max_problems, self.max_total_matches = int(max_problems), int(max_total_matches)
+        h = C.c_void_p()
+        _lib.check(self._L.ovs_sim3_create(device, self.max_problems, self.max_total_matches, C.byref(h)), "ovs_sim3_create")
+        self._h = h
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._L.ovs_sim3_destroy(h)
+
+
+def solve_sim3_batch(problems, fix_scale, min_num_inliers=20, max_num_iter=200, seed=DEFAULT_SEED, handle=None, device=0):
+    """find_via_ransac for every problem (dicts as problem_from_keyframes returns them) in one call: a list of dicts valid, best_iter,
+    num_inliers, rot_12 (3 x 3), trans_12 (3), scale_12, inlier_flags (n, bool). `handle`: a _handle to reuse (the loop detector keeps one)."""
+    P = len(problems)
+    if P == 0:
+        return []
+    counts = [len(np.asarray(q["thr1"])) for q in problems]
+    offsets = np.zeros(P + 1, np.int32)
+    offsets[1:] = np.cumsum(counts)
+    T = int(offsets[-1])
+    cat = lambda key, dt, w: np.ascontiguousarray(np.concatenate([np.asarray(q[key], dt).reshape(-1, w) for q in problems]) if T else np.zeros((0, w), dt))
+    p1, p2, thr1, thr2 = cat("p1", np.float64, 3), cat("p2", np.float64, 3), cat("thr1", np.float32, 1), cat("thr2", np.float32, 1)
+    if len(p1) != T or len(p2) != T or len(thr2) != T:
+        raise ValueError("p1, p2, thr1 and thr2 of a problem must have one entry per match")
+    cams_1 = (_lib.Camera * P)(*[q["cam_1"] for q in problems])
+    cams_2 = (_lib.Camera * P)(*[q["cam_2"] for q in problems])
+    if handle is None:
+        handle = _handle(P, max(T, 1), device)
+    valid, best_iter, num = np.zeros(P, np.int32), np.zeros(P, np.int32), np.zeros(P, np.int32)
+    rot, trans, scale, flags = np.zeros((P, 3, 3)), np.zeros((P, 3)), np.zeros(P), np.zeros(max(T, 1), np.uint8)
+    _lib.check(handle._L.ovs_sim3_solve_batch(handle._h, P, _p(offsets), _p(p1), _p(p2), _p(thr1), _p(thr2), cams_1, cams_2, 1 if fix_scale else 0,
+                                              int(min_num_inliers), int(max_num_iter), int(seed) & _MASK, _p(valid), _p(best_iter), _p(num), _p(rot),
+                                              _p(trans), _p(scale), _p(flags)), "ovs_sim3_solve_batch")
+    return [dict(valid=bool(valid[i]), best_iter=int(best_iter[i]), num_inliers=int(num[i]), rot_12=rot[i].copy(), trans_12=trans[i].copy(),
+                 scale_12=float(scale[i]), inlier_flags=flags[offsets[i]:offsets[i + 1]].astype(bool)) for i in range(P)]
+
+
+class sim3_solver:
+    """solve::sim3_solver over one problem: the constructor takes what upstream's collects from the two keyframes (see
+    problem_from_keyframes), find_via_ransac runs the device RANSAC, the getters are upstream's."""
+
+    def __init__(self, p1, p2, thr1, thr2, cam_1, cam_2, fix_scale, min_num_inliers=20, device=0):
+        self._problem = dict(p1=p1, p2=p2, thr1=thr1, thr2=thr2, cam_1=cam_1, cam_2=cam_2)
+        self._fix_scale, self._min_num_inliers, self._device = bool(fix_scale), int(min_num_inliers), device
+        self._result = None
+
+    def find_via_ransac(self, max_num_iter, seed=DEFAULT_SEED):
+        self._result = solve_sim3_batch([self._problem], self._fix_scale, self._min_num_inliers, max_num_iter, seed, device=self._device)[0]
+
+    def _get(self, key):
+        if self._result is None:
+            raise RuntimeError("find_via_ransac has not run")
+        return self._result[key]
+
+    def solution_is_valid(self):
+        return self._result is not None and self._result["valid"]
+
+    def get_best_rotation_12(self):
+        return self._get("rot_12")
+
+    def get_best_translation_12(self):
+        return self._get("trans_12")
+
+    def get_best_scale_12(self):
+        return self._get("scale_12")
+
+    def get_inlier_flags(self):
+        return self._get("inlier_flags")
+
+    def get_best_iter(self):
+        return self._get("best_iter")
+
+    def get_num_inliers(self):
+        return self._get("num_inliers")
