@@ -185,9 +185,9 @@ def orb_descriptors(blurred, xs, ys, angles_deg, pattern):
 def hamming_matrix(a, b):
     """All-pairs Hamming distances of two sets of 256-bit descriptors, (len(a), len(b)): |x ^ y| = |x| + |y| - 2 x.y over the bit vectors
     (an integer matrix product -- no popcount, no xor)."""
-    A = np.unpackbits(np.asarray(a, np.uint8).reshape(-1, 32), axis=1).astype(np.int32)
-    B = np.unpackbits(np.asarray(b, np.uint8).reshape(-1, 32), axis=1).astype(np.int32)
-    return A.sum(1)[:, None] + B.sum(1)[None, :] - 2 * (A @ B.T)
+    A = np.unpackbits(np.asarray(a, np.uint8).reshape(-1, 32), axis=1).astype(np.float32)      # sums of at most 256 ones: exact in float, and a BLAS product
+    B = np.unpackbits(np.asarray(b, np.uint8).reshape(-1, 32), axis=1).astype(np.float32)
+    return (A.sum(1)[:, None] + B.sum(1)[None, :] - 2 * (A @ B.T)).astype(np.int32)
 
 
 def robust_brute_force_match(desc_frm, desc_kf, kf_valid=None, lowe_ratio=0.8, frm_valid=None):
@@ -644,16 +644,29 @@ def fuse_replace_duplication(model, cam, cols, rows, xs, ys, octaves, desc, pose
 
 
 # ---- rule 20: match::stereo::compute ----------------------------------------------------------------------------------------------------------
+# outcome of one left keypoint (stereo_compute(..., trace=True)), in the order the rule decides them
+(ST_NO_ROW_CANDIDATES, ST_X_LEFT_NEGATIVE, ST_NO_GATED_CANDIDATE, ST_HAMMING, ST_RIGHT_WINDOW_OUT, ST_LEFT_WINDOW_OUT, ST_END_SHIFT, ST_DISP_NEGATIVE,
+ ST_DISP_MAX, ST_ACCEPTED, ST_DROPPED, ST_DELTA) = range(12)
+STEREO_TRACE_DTYPE = np.dtype([("code", "<i4"), ("row_candidates", "<i4"), ("best_right", "<i4"), ("best_hamming", "<i4"), ("hamming_ties", "<i4"),
+                               ("costs", "<f4", (11,)), ("shift", "<i4"), ("delta", "<f4"), ("disp", "<f4"), ("clamped", "?"), ("half", "?"),
+                               ("cx_l", "<i4"), ("cy_l", "<i4"), ("cx_r", "<i4")])
+
+
 def stereo_compute(pyr_left, pyr_right, kps_left, desc_left, kps_right, desc_right, scale_factors, inv_scale_factors, focal_x_baseline,
-                   true_baseline, outlier_factor=2.0, parabola_double=False):
+                   true_baseline, outlier_factor=2.0, parabola_double=False, trace=False):
     """(stereo_x_right, depths) per left keypoint (-1 where there is none). pyr_* = the extractors' level images (lists of uint8 arrays);
-    keypoints as structured arrays with x, y, octave."""
+    keypoints as structured arrays with x, y, octave. trace=True: a third value, one STEREO_TRACE_DTYPE record per left keypoint -- the ST_* outcome
+    and the numbers behind it: candidates of its row, best Hamming distance and how many gated candidates tie for it, the 11 window costs, the
+    chosen shift index, delta, disp (before the clamp), whether the 0.01 clamp fired, whether a scaled coordinate was an exact .5 before rounding."""
     F = np.float32
     nl = len(kps_left)
     rows0 = pyr_left[0].shape[0]
     xr_out, depth_out = np.full(nl, -1.0, F), np.full(nl, -1.0, F)
+    tr = np.zeros(nl, STEREO_TRACE_DTYPE)
+    tr["best_right"] = tr["best_hamming"] = tr["shift"] = -1
+    tr["costs"] = tr["delta"] = tr["disp"] = np.nan
     if nl == 0 or len(kps_right) == 0:
-        return xr_out, depth_out
+        return (xr_out, depth_out, tr) if trace else (xr_out, depth_out)
     D = hamming_matrix(desc_left, desc_right)
     sf, isf = np.asarray(scale_factors, F), np.asarray(inv_scale_factors, F)
     xr_all, yr, oct_r = np.asarray(kps_right["x"], F), np.asarray(kps_right["y"], F), np.asarray(kps_right["octave"])
@@ -664,22 +677,40 @@ def stereo_compute(pyr_left, pyr_right, kps_left, desc_left, kps_right, desc_rig
     max_disp = F(focal_x_baseline) / F(true_baseline)
     accepted = []                                             # (L1 distance, left keypoint)
     for i in range(nl):
+        t = tr[i]
         x_l, y_l, lvl = F(kps_left["x"][i]), F(kps_left["y"][i]), int(kps_left["octave"][i])
         row = int(y_l)
         cand = np.nonzero((row_lo <= row) & (row <= row_hi))[0]
+        t["row_candidates"] = len(cand)
+        if len(cand) == 0:
+            t["code"] = ST_NO_ROW_CANDIDATES
+            continue
+        if x_l < 0:
+            t["code"] = ST_X_LEFT_NEGATIVE
+            continue
         cand = cand[np.abs(oct_r[cand] - lvl) <= 1]
         cand = cand[(xr_all[cand] >= x_l - max_disp) & (xr_all[cand] <= x_l)]
-        if len(cand) == 0 or x_l < 0:
+        if len(cand) == 0:
+            t["code"] = ST_NO_GATED_CANDIDATE
             continue
         d = D[i, cand]
         b = int(np.argmin(d))
+        t["best_right"], t["best_hamming"], t["hamming_ties"] = cand[b], d[b], int((d == d[b]).sum())
         if d[b] >= 75:
+            t["code"] = ST_HAMMING
             continue
         # sub-pixel: slide an 11 x 11 window (centre value removed) over the right level image, shifts -5 .. +5
         s = isf[lvl]
-        cx_l, cy_l, cx_r = int(np.rint(x_l * s)), int(np.rint(y_l * s)), int(np.rint(xr_all[cand[b]] * s))
+        scaled = np.array([x_l * s, y_l * s, xr_all[cand[b]] * s], F)
+        t["half"] = bool((scaled - np.floor(scaled) == F(0.5)).any())
+        cx_l, cy_l, cx_r = (int(v) for v in np.rint(scaled))
+        t["cx_l"], t["cy_l"], t["cx_r"] = cx_l, cy_l, cx_r
         img_l, img_r = pyr_left[lvl], pyr_right[lvl]
         if not (0 <= cx_r - 10 and cx_r + 11 < img_r.shape[1]):
+            t["code"] = ST_RIGHT_WINDOW_OUT
+            continue
+        if not (0 <= cy_l - 5 and cy_l + 5 < img_l.shape[0] and 0 <= cx_l - 5 and cx_l + 5 < img_l.shape[1]):
+            t["code"] = ST_LEFT_WINDOW_OUT
             continue
         win_l = img_l[cy_l - 5:cy_l + 6, cx_l - 5:cx_l + 6].astype(F)
         win_l = win_l - win_l[5, 5]
@@ -688,7 +719,9 @@ def stereo_compute(pyr_left, pyr_right, kps_left, desc_left, kps_right, desc_rig
             win_r = img_r[cy_l - 5:cy_l + 6, cx_r + shift - 5:cx_r + shift + 6].astype(F)
             cost[k] = np.abs(win_l - (win_r - win_r[5, 5])).sum(dtype=np.float64)      # integers < 2^24: exact in any order
         k = int(np.argmin(cost))
+        t["costs"], t["shift"] = cost, k
         if k == 0 or k == 10:
+            t["code"] = ST_END_SHIFT
             continue
         c1, c2, c3 = cost[k - 1], cost[k], cost[k + 1]
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -696,15 +729,21 @@ def stereo_compute(pyr_left, pyr_right, kps_left, desc_left, kps_right, desc_rig
                 delta = F((float(c1) - float(c3)) / (2.0 * (float(c1) + float(c3) - 2.0 * float(c2))))
             else:
                 delta = (c1 - c3) / (F(2.0) * (c1 + c3 - F(2.0) * c2))
+        t["delta"] = delta
         if delta < -1 or 1 < delta:
+            t["code"] = ST_DELTA
             continue
         x_r = sf[lvl] * (F(cx_r) + F(k - 5) + delta)
         disp = x_l - x_r
+        t["disp"] = disp
         if not (0 <= disp < max_disp):
+            t["code"] = ST_DISP_NEGATIVE if disp < 0 else ST_DISP_MAX
             continue
         if disp <= 0:
             disp, x_r = F(0.01), x_l - F(0.01)
+            t["clamped"] = True
         xr_out[i], depth_out[i] = x_r, F(focal_x_baseline) / disp
+        t["code"] = ST_ACCEPTED
         accepted.append((float(c2), i))
     if accepted:
         dists = sorted(a[0] for a in accepted)
@@ -712,7 +751,8 @@ def stereo_compute(pyr_left, pyr_right, kps_left, desc_left, kps_right, desc_rig
         for c, i in accepted:
             if F(outlier_factor) * F(median) < F(c):
                 xr_out[i] = depth_out[i] = -1.0
-    return xr_out, depth_out
+                tr["code"][i] = ST_DROPPED
+    return (xr_out, depth_out, tr) if trace else (xr_out, depth_out)
 
 
 # ---- rule 27: the loop closer's matchers -------------------------------------------------------------------------------------------------------
