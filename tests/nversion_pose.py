@@ -81,13 +81,14 @@ def _robust_sum(c2, delta):
     return np.where(c2 > delta * delta, 2 * np.sqrt(c2) * delta - delta * delta, c2).sum()
 
 
-def pose_optimize_equirect(T0, obs, cols, rows):
+def pose_optimize_equirect(T0, obs, cols, rows, trace=None):
     """Equirectangular frames (monocular rig: Huber sqrtf(5.99146f), gate 5.99146f)."""
-    return pose_optimize(T0, obs, (float(cols), float(rows), 0.0, 0.0), 0.0, 0, _edges_equirect)
+    return pose_optimize(T0, obs, (float(cols), float(rows), 0.0, 0.0), 0.0, 0, _edges_equirect, trace=trace)
 
 
-def pose_optimize(T0, obs, cam, bf=0.0, setup_type=None, edges=None, reset_each_round=False):
-    """Returns (pose 3x4, outlier flags, num_valid) as the C oracle's ovo_pose_optimize."""
+def pose_optimize(T0, obs, cam, bf=0.0, setup_type=None, edges=None, reset_each_round=False, trace=None):
+    """Returns (pose 3x4, outlier flags, num_valid) as the C oracle's ovo_pose_optimize. trace: a list that receives, per round run, (number of
+    inliers after its re-classification, [per iteration: (trials made, solves that succeeded, last gain ratio)])."""
     edges = edges or _edges
     if setup_type is None:
         setup_type = 1 if bf != 0.0 else 0
@@ -107,6 +108,7 @@ def pose_optimize(T0, obs, cam, bf=0.0, setup_type=None, edges=None, reset_each_
         lam, ni = 0.0, 2.0
         Rn, tn = R, t
         err_at_trial = False
+        its = []
         for it in range(10):
             err_at_trial = False
             e, J, _ = edges(R, t, o, cam, bf)
@@ -121,7 +123,7 @@ def pose_optimize(T0, obs, cam, bf=0.0, setup_type=None, edges=None, reset_each_
             chi = _robust_sum(c2, delta)
             if it == 0:
                 lam, ni = 1e-5 * np.abs(np.diag(H)).max(), 2.0
-            rho, qmax = 0.0, 0
+            rho, qmax, solved = 0.0, 0, 0
             while True:
                 A = H + lam * np.eye(6)
                 ok = True
@@ -132,6 +134,7 @@ def pose_optimize(T0, obs, cam, bf=0.0, setup_type=None, edges=None, reset_each_
                     ok = False
                 temp, scale = np.finfo(float).max, 1e-3
                 if ok:
+                    solved += 1
                     E, et = _se3_exp(dx)
                     Rn, tn = E @ R, E @ t + et
                     temp = _robust_sum(_chi2(Rn, tn, o, cam, bf, edges)[0], delta)
@@ -149,6 +152,7 @@ def pose_optimize(T0, obs, cam, bf=0.0, setup_type=None, edges=None, reset_each_
                 qmax += 1
                 if not (rho < 0 and qmax < 10):
                     break
+            its.append((qmax, solved, rho))
             if qmax == 10 or rho == 0:
                 break
         # re-classification: previous outliers at the estimate, inliers where their errors were last computed (the last trial state)
@@ -158,6 +162,8 @@ def pose_optimize(T0, obs, cam, bf=0.0, setup_type=None, edges=None, reset_each_
         out = np.where(st, CHI2_3D, CHI2_2D) < c2
         active = ~out
         num_bad = int(out.sum())
+        if trace is not None:
+            trace.append((n - num_bad, its))
         if n - num_bad < 5:
             break
     return np.concatenate([R, t[:, None]], 1), out, n - num_bad
