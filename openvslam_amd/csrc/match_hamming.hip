@@ -4,9 +4,9 @@
 // Upstream's loop is sequential: keyframe keypoints (idx_2) in order, each scanning ALL frame keypoints (idx_1) that no
 // earlier idx_2 has claimed, keeping best / second-best distance with strict `<`, accepting iff
 // best <= HAMMING_DIST_THR_LOW and !(lowe_ratio * second < best). Exact parallel form used here:
-//   1. k_hamming_near (the O(n1*n2) part, integer VALU-bound): one lane per idx_2; the idx_1 descriptor is wave-uniform, so
-//      it is fetched with SCALAR loads (s_load_dwordx8) and XORed straight from SGPRs: 8 v_xor + 8 v_bcnt_u32_b32 (with
-//      accumulate) per pair, no LDS, no shuffles. Only distances that can influence the outcome are kept: d <= near_thr,
+//   1. k_hamming_near (the O(n1*n2) part): all-pairs distances as an exact FP4 contraction on the matrix cores, 32 x 32 pairs per
+//      v_mfma_scale_f32_32x32x64_f8f6f4 chain (section 1 below); the selectable popcount form k_hamming_near_popc (section 1b) is
+//      the vector-ALU statement of the same stage. Only distances that can influence the outcome are kept: d <= near_thr,
 //      where near_thr = max(THR_LOW, tau-1) and tau is the smallest `second` for which the ratio test can no longer
 //      reject a best <= THR_LOW. Those are rare (the true match and near-duplicates): a short per-query list.
 //   2. k_bf_resolve: one workgroup per problem replays the claim order in parallel rounds. A pending query finalises in a
@@ -50,50 +50,70 @@ __device__ __forceinline__ void topk_insert(uint32_t e, uint32_t (&t)[kTopK]) {
 }
 
 // ---- 1. all pairs, near lists -------------------------------------------------------------------------------------
-// The O(n1 * n2) part runs on the matrix cores. A 256-bit Hamming distance is an exact integer dot product: with the frame
-// descriptor a expanded to {0, 1} bytes and the keyframe descriptor b to {+1, -1} bytes (bit set -> +1),
-//     sum_k a_k * b_k = |a & b| - |a & ~b| = 2 |a & b| - |a|,   d(a, b) = |a| + |b| - 2 |a & b| = |b| - sum_k a_k * b_k,
-// so one v_mfma_i32_32x32x32_i8 chain of 8 steps (K = 256) yields the 32 x 32 distances of a tile, bit-exact in int32. The kernel
-// is compute-bound (n1 pairs per 32 bytes of keyframe descriptor), which is what the matrix core is for; nothing is approximated.
+// The O(n1 * n2) part runs on the matrix cores. A 256-bit Hamming distance is an exact dot product: with BOTH descriptors expanded to
+// one FP4 (E2M1) element per bit -- bit clear -> 0b0010 (+1.0), bit set -> 0b1010 (-1.0); the subnormal code is never used --
+//     sum_k a_k * b_k = (#equal bits) - (#differing bits) = 256 - 2 d(a, b),        d(a, b) = (256 - sum) / 2,
+// so one chain of 4 v_mfma_scale_f32_32x32x64_f8f6f4 (cbsz:4 blgp:4 = FP4 on both sides, both scales E8M0 127 = 1.0; K = 4 x 64 = 256)
+// yields the 32 x 32 distances of a tile: every partial sum is an integer of magnitude <= 256, exact in the f32 accumulator. The FP4
+// form takes K = 64 in the 32 cycles (16 passes) the i8 form v_mfma_i32_32x32x32_i8 spends on K = 32: half the matrix instructions of
+// the round-2 i8 kernel, half the expansion work (one 32-bit word -> 4 VGPRs of nibbles per K step) and half the query registers; no
+// popcount of b is needed. The kernel is compute-bound (n1 pairs per 32 bytes of keyframe descriptor); nothing is approximated.
 //   * Workgroup = 4 waves x 64 queries (idx_2) each = 256 queries; every wave scans ALL frame descriptors (idx_1) in tiles of 32.
-//   * The wave's 64 queries live in registers as two B operands (2 x 8 steps x 4 VGPRs of +-1 bytes), expanded once.
-//   * Per 32-descriptor tile a lane loads 16 raw bytes (row = lane & 31, half = lane >> 5), expands them step by step into the
-//     A operand (4 VGPRs of 0/1 bytes: shift + and per VGPR -- the order of the 256 bit positions along K is free as long as A
-//     and B use the same one, so byte v of a VGPR takes bit (base + v) of each of the word's four bytes) and feeds TWO MFMAs
-//     (one per query tile). 64 + ~20 VALU and 16 MFMA per 2048 pairs, against 16 VALU per PAIR on the vector path.
-//   * C layout (guide 3, fragment layout): lane holds column (query) lane & 31, rows (frame keypoints) (r & 3) + 8 (r >> 2) +
-//     4 (lane >> 5). A pair is near iff acc >= |b| - near_thr: one v_max3 per two pairs and one branch per tile on the common path.
-//   * Near pairs (rare) go to the query's list; the list keeps its four segments so the resolver's layout is unchanged (now:
-//     C-tile half x first / second half of the tiles -- one writer lane per segment, so the fill counts are registers). At the end
-//     each thread builds one query's sorted top-8 from the entries its own wave wrote.
-// History (round 2, config 2, 128 problems of 2000 x 2000): scalar-cache + v_bcnt vector path 0.303 ms (0.57 of its VALU issue
-// floor); LDS-broadcast vector path 0.394 ms; see DESIGN.md for this kernel's numbers.
+//   * The wave's 64 queries live in registers as two B operands (2 x 4 steps x 4 VGPRs of FP4 nibbles), expanded once.
+//   * Per 32-descriptor tile a lane loads 16 raw bytes (row = lane & 31, half = lane >> 5); K step s expands word s of them with
+//     expand_fp4 (the same function as the query side: VGPR v holds bits v, v + 4, ... of the word, one per nibble, so the order of
+//     the 256 bit positions along K is the same on both sides whatever the instruction's element-to-k map is, as long as it is the
+//     same map for A and B -- tests/test_gpu_near_fp4.py decides every bit position once) and feeds TWO MFMAs (one per query tile).
+//   * C layout (guide 3, fragment layout; dtype-independent): lane holds column (query) lane & 31, rows (frame keypoints) (r & 3) +
+//     8 (r >> 2) + 4 (lane >> 5). A pair is near iff acc >= 256 - 2 near_thr (a float bound; +inf for an inactive query): one v_max3
+//     per two pairs and one branch per tile on the common path. The accumulators are converted to distances once, in drain.
+//   * Near pairs (rare) go to the query's list; the list keeps its four segments so the resolver's layout is unchanged (C-tile half x
+//     first / second half of the tiles -- one writer lane per segment, so the fill counts are registers). At the end each thread
+//     builds one query's sorted top-8 from the entries its own wave wrote.
+// Counted (rocprofv3 counters, 128 problems of ~2000 x 2000 per launch): 8 MFMA and 114 VALU per wave and 32-row tile (2048 pairs),
+// against 16 and 158 for the i8 form of round 2. The tile loop itself is 28 VALU of expansion (shift + v_and_or_b32 per VGPR, the
+// unshifted one v_and_or_b32 alone), 16 v_maximum3_f32 + 2 compares of near test and about 10 of addressing; the rest is the queue, its
+// drains and the final top-8. The matrix pipe is busy 32 cycles per instruction; VALU and MFMA still overlap little (co-execution
+// 0.41 of the MFMA cycles), so the kernel's time is close to the SUM of the two streams and every VALU instruction removed counts.
+// Measured and not kept: a 96-slot ring drained from 32 queued columns (31 KB of LDS instead of 39, 96 VGPRs, 5 waves per SIMD):
+// 0.22 ms alone against 0.20, the step unchanged (docs/HISTORY.md).
+// History (config 2, 128 problems of 2000 x 2000): scalar-cache + v_bcnt vector path 0.303 ms; LDS-broadcast vector path 0.394 ms.
 typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
+typedef int v8i __attribute__((ext_vector_type(8)));
+typedef float v16f __attribute__((ext_vector_type(16)));
 
 constexpr int kNearQueries = 256;   // queries per workgroup (4 waves x 2 tiles of 32)
 constexpr int kQueueSlots = 128;    // per-wave ring of queued C-tile columns (drained 64 at a time)
 static_assert(kNearSplit == 4, "segment counts are stored as one uint4 per query");
 
-// step s of the K loop covers bits (s & 1) * 4 + v (v = 0..3: the VGPR) of every byte of word s >> 1 of the lane's 16-byte half
-__device__ __forceinline__ v4i expand01(uint32_t w, int base) {
+// One 32-bit word -> 32 FP4 elements (the operand of one K step, either side): nibble n of VGPR v is 0b0010 | bit (4 n + v) << 3,
+// i.e. +1.0 for a clear bit and -1.0 for a set one. `ones` is 0x22222222 held in a VGPR (fp4_ones): with one of the two constants in
+// a register each VGPR is v_lshlrev + v_and_or_b32 (the last one v_and_or_b32 alone), 7 VALU per word; as two literals hipcc emits
+// shift, and, or: 11.
+__device__ __forceinline__ v4i expand_fp4(uint32_t w, uint32_t ones) {
     v4i r;
-    r[0] = (int)((w >> base) & 0x01010101u);
-    r[1] = (int)((w >> (base + 1)) & 0x01010101u);
-    r[2] = (int)((w >> (base + 2)) & 0x01010101u);
-    r[3] = (int)((w >> (base + 3)) & 0x01010101u);
+    r[0] = (int)(((w << 3) & 0x88888888u) | ones);
+    r[1] = (int)(((w << 2) & 0x88888888u) | ones);
+    r[2] = (int)(((w << 1) & 0x88888888u) | ones);
+    r[3] = (int)((w & 0x88888888u) | ones);
     return r;
 }
-// 0/1 bytes -> +1 / -1 bytes: 0xFF - 0xFE * z per byte (no carries: every byte product is <= 0xFE)
-__device__ __forceinline__ v4i to_pm1(v4i z) {
-    v4i r;
+__device__ __forceinline__ uint32_t fp4_ones() {
+    uint32_t c = 0x22222222u;
+    asm volatile("" : "+v"(c));   // no instruction: only hides the value from constant folding
+    return c;
+}
+__device__ __forceinline__ v16f mfma_fp4(v4i a, v4i b, v16f c) {
+    // the builtin is typed for the widest (FP8) operands; with FP4 on a side the instruction reads its first 4 VGPRs only (the rest undefined)
+    const v8i a8 = __builtin_shufflevector(a, a, 0, 1, 2, 3, -1, -1, -1, -1), b8 = __builtin_shufflevector(b, b, 0, 1, 2, 3, -1, -1, -1, -1);
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, c, 4, 4, 0, 127, 0, 127);   // FP4 x FP4, both scales 2^0
+}
+// IEEE maximum (v_maximum3_f32, one per two values): fmaxf would first canonicalise each of its inputs, one more VALU per value
+__device__ __forceinline__ float max16(const v16f& c) {
+    float m = __builtin_elementwise_maximum(c[0], c[1]);
 #pragma unroll
-    for (int v = 0; v < 4; ++v) r[v] = (int)~((uint32_t)z[v] * 0xFEu);
-    return r;
-}
-__device__ __forceinline__ int max16(const v16i& c) {
-    return max(max(max(max(c[0], c[1]), max(c[2], c[3])), max(max(c[4], c[5]), max(c[6], c[7]))),
-               max(max(max(c[8], c[9]), max(c[10], c[11])), max(max(c[12], c[13]), max(c[14], c[15]))));
+    for (int r = 2; r < 16; ++r) m = __builtin_elementwise_maximum(m, c[r]);
+    return m;
 }
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_hamming_near(const uint8_t* __restrict__ desc_1, size_t stride_1,
@@ -103,9 +123,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                                                      uint32_t* __restrict__ near_cnt, uint32_t* __restrict__ near_list,
                                                      uint32_t* __restrict__ near_top, int chunks, int total_wg) {
     __shared__ uint32_t s_segcnt[kNearSplit][kNearQueries];
-    __shared__ int4 s_queue[4][4][kQueueSlots];    // per wave: queued C-tile columns, [quarter of the 16 accumulators][slot]
+    __shared__ float4 s_queue[4][4][kQueueSlots];  // per wave: queued C-tile columns, [quarter of the 16 accumulators][slot]
     __shared__ uint32_t s_qmeta[4][kQueueSlots];   // tile << 8 | half << 6 | query of the wave
-    __shared__ int2 s_ctx[4][64];                  // per query of the wave: acceptance bound, |b|
+    __shared__ float s_ctx[4][64];                 // per query of the wave: acceptance bound on the accumulator (+inf: inactive)
     // XCD-major work order (workgroup b runs on XCD b % 8): XCD k takes the k-th contiguous eighth of the (problem, chunk) sequence,
     // so the chunks of one problem share one L2
     const int per_xcd = gridDim.x >> 3;
@@ -119,27 +139,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     for (int w = 0; w < kNearSplit; ++w) s_segcnt[w][tid] = 0;
     __syncthreads();
 
-    // ---- this wave's 64 queries -> two B operands (+-1 bytes), |b| and the per-lane acceptance bound
+    // ---- this wave's 64 queries -> two B operands (FP4 nibbles) and the per-lane acceptance bound
     const int q_wave = chunk_id * kNearQueries + wv * 64;
-    v4i qb[2][8];
-    int need[2], pcq[2];
+    const uint32_t ones = fp4_ones();
+    v4i qb[2][4];
+    float need[2];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
         const int q = q_wave + u * 32 + col;
         const bool act = q < n2 && (!valid_2 || valid_2[(size_t)p * (stride_2 / 32) + q]);
-        const uint4* src = reinterpret_cast<const uint4*>(desc_2 + (size_t)p * stride_2 + (size_t)(q < n2 ? q : 0) * 32);
-        const uint4 lo = src[0], hi = src[1];
-        pcq[u] = __builtin_popcount(lo.x) + __builtin_popcount(lo.y) + __builtin_popcount(lo.z) + __builtin_popcount(lo.w) +
-                 __builtin_popcount(hi.x) + __builtin_popcount(hi.y) + __builtin_popcount(hi.z) + __builtin_popcount(hi.w);
-        const uint4 mine = half ? hi : lo;
+        const uint4 mine = *reinterpret_cast<const uint4*>(desc_2 + (size_t)p * stride_2 + (size_t)(q < n2 ? q : 0) * 32 + half * 16);
         const uint32_t w4[4] = {mine.x, mine.y, mine.z, mine.w};
 #pragma unroll
-        for (int s = 0; s < 8; ++s) qb[u][s] = to_pm1(expand01(w4[s >> 1], (s & 1) * 4));
-        need[u] = act ? pcq[u] - (int)near_thr : 0x7FFFFFFF;   // inactive query: no accumulator value reaches the bound
+        for (int s = 0; s < 4; ++s) qb[u][s] = expand_fp4(w4[s], ones);
+        need[u] = act ? (float)(256 - 2 * (int)near_thr) : __builtin_inff();   // d <= near_thr <=> acc >= 256 - 2 near_thr; inactive query: never
     }
     if (half == 0) {
 #pragma unroll
-        for (int u = 0; u < 2; ++u) s_ctx[wv][u * 32 + col] = make_int2(need[u], pcq[u]);
+        for (int u = 0; u < 2; ++u) s_ctx[wv][u * 32 + col] = need[u];
     }
     // s_ctx / s_queue / s_qmeta are written by some lanes of a wave and read by OTHER lanes of the same wave: a wavefront-scope release /
     // acquire pair plus a wave barrier states that hand-over to the compiler (no instruction is emitted: a wave's DS operations execute
@@ -165,25 +182,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             const int e = (q_head + lane) & (kQueueSlots - 1);
             const uint32_t meta = s_qmeta[wv][e];
             const int tile_e = (int)(meta >> 8), half_e = (int)(meta >> 6) & 1, qi = (int)(meta & 63u);
-            const int2 ctx = s_ctx[wv][qi];
-            int v[16];
+            const float bound = s_ctx[wv][qi];
+            float v[16];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const int4 x = s_queue[wv][k][e];
+                const float4 x = s_queue[wv][k][e];
                 v[4 * k] = x.x; v[4 * k + 1] = x.y; v[4 * k + 2] = x.z; v[4 * k + 3] = x.w;
             }
             uint32_t nh = 0;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) nh += v[r] >= ctx.x ? 1u : 0u;
+            for (int r = 0; r < 16; ++r) nh += v[r] >= bound ? 1u : 0u;
             const int seg = 2 * half_e + (tile_e >= phase_tiles ? 1 : 0);
             uint32_t slot = atomicAdd(&s_segcnt[seg][wv * 64 + qi], nh);
             uint32_t* dst = near_list + (((size_t)p * max_n2 + (q_wave + qi)) * kNearSplit + seg) * kNearSeg;
             const int j_base = tile_e * 32 + 4 * half_e;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                if (v[r] >= ctx.x) {
+                if (v[r] >= bound) {
                     // past kNearSeg the segment counts as overflowed (the resolver then rescans that query): the clamp only keeps the store in bounds
-                    dst[min(slot, (uint32_t)kNearSeg - 1u)] = ((uint32_t)(ctx.y - v[r]) << 16) | (uint32_t)(j_base + (r & 3) + 8 * (r >> 2));
+                    dst[min(slot, (uint32_t)kNearSeg - 1u)] = ((uint32_t)((256 - (int)v[r]) >> 1) << 16) | (uint32_t)(j_base + (r & 3) + 8 * (r >> 2));
                     ++slot;
                 }
             }
@@ -209,21 +226,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             const int j0 = tile << 5;
             const uint32_t w4[4] = {raw.x, raw.y, raw.z, raw.w};
             if (it + 1 < n_tiles) raw = load_rows(tile_next << 5);   // next tile's bytes are in flight under this tile's MFMAs
-            v16i acc[2];
-            acc[0] = (v16i){0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+            v16f acc[2];
+            acc[0] = (v16f){0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
             acc[1] = acc[0];
 #pragma unroll
-            for (int s = 0; s < 8; ++s) {
-                const v4i a = expand01(w4[s >> 1], (s & 1) * 4);
-                acc[0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, qb[0][s], acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, qb[1][s], acc[1], 0, 0, 0);
+            for (int s = 0; s < 4; ++s) {
+                const v4i a = expand_fp4(w4[s], ones);
+                acc[0] = mfma_fp4(a, qb[0][s], acc[0]);
+                acc[1] = mfma_fp4(a, qb[1][s], acc[1]);
             }
             if (j0 + 32 > n1) {   // last, partial tile (wave-uniform): rows past n1 can never be near
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const bool in = j0 + (r & 3) + 8 * (r >> 2) + 4 * half < n1;
-                    acc[0][r] = in ? acc[0][r] : (int)0x80000000;
-                    acc[1][r] = in ? acc[1][r] : (int)0x80000000;
+                    acc[0][r] = in ? acc[0][r] : -__builtin_inff();
+                    acc[1][r] = in ? acc[1][r] : -__builtin_inff();
                 }
             }
 #pragma unroll
@@ -237,7 +254,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                         s_qmeta[wv][e] = ((uint32_t)tile << 8) | (uint32_t)(half << 6) | (uint32_t)(u * 32 + col);
 #pragma unroll
                         for (int k = 0; k < 4; ++k)
-                            s_queue[wv][k][e] = make_int4(acc[u][4 * k], acc[u][4 * k + 1], acc[u][4 * k + 2], acc[u][4 * k + 3]);
+                            s_queue[wv][k][e] = make_float4(acc[u][4 * k], acc[u][4 * k + 1], acc[u][4 * k + 2], acc[u][4 * k + 3]);
                     }
                     q_tail += __builtin_popcountll(m);
                     if (q_tail - q_head >= 64) drain(64);   // at most 63 were queued before this column set: never more than 127 entries

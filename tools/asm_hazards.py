@@ -157,8 +157,8 @@ def _f64_mfma(i):
     return i.mnem.startswith("v_mfma_f64_16x16x4")
 
 
-def _i8_mfma(i):
-    return i.mnem.startswith("v_mfma_i32_32x32x32_i8")
+def _i8_mfma(i):   # the 8-pass 32x32 forms: i8 (K = 32) and the block-scaled f8f6f4 instruction (K = 64; k_hamming_near feeds it FP4)
+    return i.mnem.startswith(("v_mfma_i32_32x32x32_i8", "v_mfma_scale_f32_32x32x64_f8f6f4"))
 
 
 RULES = [
@@ -169,7 +169,8 @@ RULES = [
     Rule("valu_mfma", "VALU write -> MFMA A/B/C operand", Ins.is_valu, Ins.is_mfma, ("valu_mfma_ab", "valu_mfma_c")),
     Rule("mfma64_valu", "v_mfma_f64_16x16x4_f64 result -> VALU read", _f64_mfma, Ins.is_valu, ("mfma64_valu",)),
     Rule("mfma64_mem", "v_mfma_f64_16x16x4_f64 result -> LDS / memory instruction", _f64_mfma, Ins.is_mem, ("mfma64_global", "mfma64_lds")),
-    Rule("mfma8_valu", "v_mfma_i32_32x32x32_i8 result -> VALU read", _i8_mfma, Ins.is_valu, ("mfma8_valu",)),
+    Rule("mfma8_valu", "v_mfma_i32_32x32x32_i8 / v_mfma_scale_f32_32x32x64_f8f6f4 (FP4) result -> VALU read", _i8_mfma, Ins.is_valu,
+         ("mfma8_valu", "mfma4_valu")),
     Rule("valu_readlane", "VALU write -> v_readlane / v_readfirstlane", Ins.is_valu, lambda i: i.mnem.startswith(("v_readlane_", "v_readfirstlane_")),
          ("valu_readfirstlane", "valu_readlane")),
     Rule("m0_ldsdma", "SALU write of m0 -> LDS-DMA load", lambda i: i.mnem.startswith("s_") and ("m0", 0) in i.dst,
@@ -182,7 +183,9 @@ PROBES = r"""
 #include <hip/hip_runtime.h>
 typedef double v4d __attribute__((ext_vector_type(4)));
 typedef int v4i __attribute__((ext_vector_type(4)));
+typedef int v8i __attribute__((ext_vector_type(8)));
 typedef int v16i __attribute__((ext_vector_type(16)));
+typedef float v16f __attribute__((ext_vector_type(16)));
 #define PROBE extern "C" __global__ void __launch_bounds__(64)
 // (`old` comes from memory: a v_mov writing it would be the nearer VALU write, and hipcc pads for that one too)
 PROBE valu_dpp32(const int* in, int* out) {
@@ -233,6 +236,12 @@ PROBE mfma8_valu(const v4i* in, int* out) {
     for (int i = 0; i < 16; ++i) c[i] = 0;
     const v16i d = __builtin_amdgcn_mfma_i32_32x32x32_i8(in[threadIdx.x], in[threadIdx.x + 64], c, 0, 0, 0);
     out[threadIdx.x] = d[0] ^ in[threadIdx.x + 128].x;
+}
+PROBE mfma4_valu(const v8i* in, float* out) {
+    v16f c;
+    for (int i = 0; i < 16; ++i) c[i] = 0.f;
+    const v16f d = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(in[threadIdx.x], in[threadIdx.x + 64], c, 4, 4, 0, 127, 0, 127);
+    out[threadIdx.x] = d[0] * out[threadIdx.x + 64];
 }
 PROBE valu_readfirstlane(const int* in, int* out) {
     const int x = in[threadIdx.x] ^ in[threadIdx.x + 64];
