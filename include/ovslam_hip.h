@@ -702,6 +702,31 @@ ovs_status ovs_sim3_solve_batch(ovs_sim3* s, int32_t n_problems, const int32_t* 
                                 int32_t max_num_iter, uint64_t seed, int32_t* out_valid, int32_t* out_best_iter, int32_t* out_num_inliers,
                                 double* out_rot_12, double* out_trans_12, double* out_scale_12, uint8_t* out_inlier_flags);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * EPnP RANSAC for relocalisation.  replaces: solve::pnp_solver::find_via_ransac(max_num_iter, recompute) with EPnP on four sampled matches,
+ *   the inlier count and the refit over the winner's inliers (src/openvslam/solve/pnp_solver.{h,cc}), for a BATCH of (current frame,
+ *   candidate keyframe) problems in two launches (rules 1 to 6).
+ * ovs_pnp_create: a handle for up to max_problems problems of max_total_matches matches together (replaces: the constructor's
+ *   allocations); one internal mutex serialises the calls on a handle.
+ * ovs_pnp_solve_batch: problem p owns matches [offsets[p], offsets[p + 1]) (offsets[0] = 0, non-decreasing). bearings: 3 doubles per match,
+ *   the frame keypoint's bearing (pnp_solver's valid_bearings_); pos_w: 3 doubles per match, the matched landmark in the world;
+ *   max_cos_errors: upstream's max_cos_errors_ = cos(scale_factors[octave] * 1 degree), one double per match. recompute: upstream's flag,
+ *   non-zero refits the pose over the winner's inliers. seed: upstream draws from random_device; here hypothesis h of problem p is a function
+ *   of (seed, p, h). Outputs per problem: valid (solution_is_valid_), best_iter (the winning hypothesis, -1 if invalid), num_inliers, rot_cw
+ *   (9, row-major: get_best_rotation), trans_cw (3: get_best_translation); inlier_flags: one byte per match. An invalid problem returns
+ *   identity, zero, flags 0. Results are bit-exact functions of (inputs, seed, p): problem p of a batch, solved alone under the seed
+ *   `seed + 0x9E3779B97F4A7C15 * (p << 23)`, gives the same result.
+ * OVS_ERR_INVALID: a NULL required pointer, offsets not starting at 0 or decreasing, max_num_iter < 1 or > 2^20, min_num_inliers < 0.
+ *   OVS_ERR_CAPACITY: more problems or matches than the handle was created for (nothing is truncated, no output is written). Both are
+ *   decided before any launch. A problem with fewer than 4 matches is not an error: it is invalid. */
+typedef struct ovs_pnp ovs_pnp;
+ovs_status ovs_pnp_create(int32_t device, int32_t max_problems, int32_t max_total_matches, ovs_pnp** out);
+ovs_status ovs_pnp_destroy(ovs_pnp* s);
+ovs_status ovs_pnp_solve_batch(ovs_pnp* s, int32_t n_problems, const int32_t* offsets, const double* bearings, const double* pos_w,
+                               const double* max_cos_errors, int32_t min_num_inliers, int32_t max_num_iter, int32_t recompute, uint64_t seed,
+                               int32_t* out_valid, int32_t* out_best_iter, int32_t* out_num_inliers, double* out_rot_cw, double* out_trans_cw,
+                               uint8_t* out_inlier_flags);
+
 /* replaces: the optimisation inside  void optimize::local_bundle_adjuster::optimize(data::keyframe* curr_keyfrm, bool* const
  *               force_stop_flag) const  (src/openvslam/optimize/local_bundle_adjuster.{h,cc}): everything between the graph build and the
  * write-back, i.e. optimizer.optimize(num_first_iter) with Huber kernels (ONE delta per rig: setup_type 0 = Monocular -> sqrtf(5.99146f),

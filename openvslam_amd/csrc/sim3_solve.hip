@@ -21,6 +21,7 @@
 #include <mutex>
 
 #include "ovs_common.h"
+#include "solve_internal.inc"
 
 namespace {
 
@@ -66,12 +67,6 @@ struct Model {
     double R[9], t12[3], s12, s21, t21[3];
 };
 
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {   // the splitmix64 finaliser
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 // rule 1: three distinct indices below n (n >= 3), no rejection loop
 __device__ __forceinline__ void sample3(uint64_t seed, uint32_t p, uint32_t h, uint32_t n, uint32_t& i0, uint32_t& i1, uint32_t& i2) {
     const uint64_t G = 0x9E3779B97F4A7C15ull;
@@ -84,36 +79,6 @@ __device__ __forceinline__ void sample3(uint64_t seed, uint32_t p, uint32_t h, u
     if (i2 >= lo) ++i2;
     if (i2 >= hi) ++i2;
 }
-
-// one Jacobi rotation on the pair (P, Q), the operations of essential_solver.h::compute_E_21: columns, then rows, then V
-template <int P, int Q>
-__device__ __forceinline__ void jacobi_rotate(double (&A)[4][4], double (&V)[4][4]) {
-    const double apq = A[P][Q];
-    if (apq == 0.0) return;
-    const double theta = (A[Q][Q] - A[P][P]) / (2.0 * apq);
-    const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const double akp = A[k][P], akq = A[k][Q];
-        A[k][P] = c * akp - s * akq;
-        A[k][Q] = s * akp + c * akq;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const double apk = A[P][k], aqk = A[Q][k];
-        A[P][k] = c * apk - s * aqk;
-        A[Q][k] = s * apk + c * aqk;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const double vkp = V[k][P], vkq = V[k][Q];
-        V[k][P] = c * vkp - s * vkq;
-        V[k][Q] = s * vkp + c * vkq;
-    }
-}
-
-__device__ __forceinline__ double dot3(double a0, double a1, double a2, double b0, double b1, double b2) { return (a0 * b0 + a1 * b1) + a2 * b2; }
 
 // rule 2: Horn's closed form on the three sampled matches of hypothesis h
 __device__ __forceinline__ Model solve_hypothesis(const double* __restrict__ p1, const double* __restrict__ p2, uint32_t n, uint64_t seed, uint32_t p,
@@ -146,56 +111,8 @@ __device__ __forceinline__ Model solve_hypothesis(const double* __restrict__ p1,
     for (int r = 0; r < 3; ++r)
 #pragma unroll
         for (int c = 0; c < 3; ++c) M[r][c] = (b[0][r] * a[0][c] + b[1][r] * a[1][c]) + b[2][r] * a[2][c];
-    double A[4][4], V[4][4];
-    A[0][0] = (M[0][0] + M[1][1]) + M[2][2];
-    A[0][1] = M[1][2] - M[2][1];
-    A[0][2] = M[2][0] - M[0][2];
-    A[0][3] = M[0][1] - M[1][0];
-    A[1][1] = (M[0][0] - M[1][1]) - M[2][2];
-    A[1][2] = M[0][1] + M[1][0];
-    A[1][3] = M[2][0] + M[0][2];
-    A[2][2] = (-M[0][0] + M[1][1]) - M[2][2];
-    A[2][3] = M[1][2] + M[2][1];
-    A[3][3] = (-M[0][0] - M[1][1]) + M[2][2];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            if (c < r) A[r][c] = A[c][r];
-            V[r][c] = r == c ? 1.0 : 0.0;
-        }
-#pragma unroll 1
-    for (int sweep = 0; sweep < 8; ++sweep) {
-        jacobi_rotate<0, 1>(A, V);
-        jacobi_rotate<0, 2>(A, V);
-        jacobi_rotate<0, 3>(A, V);
-        jacobi_rotate<1, 2>(A, V);
-        jacobi_rotate<1, 3>(A, V);
-        jacobi_rotate<2, 3>(A, V);
-    }
-    // the eigenvector of the largest diagonal entry, lowest index on a tie (selects, not an indexed read)
-    double best = A[0][0], q0 = V[0][0], q1 = V[1][0], q2 = V[2][0], q3 = V[3][0];
-#pragma unroll
-    for (int i = 1; i < 4; ++i) {
-        const bool take = A[i][i] > best;
-        best = take ? A[i][i] : best;
-        q0 = take ? V[0][i] : q0;
-        q1 = take ? V[1][i] : q1;
-        q2 = take ? V[2][i] : q2;
-        q3 = take ? V[3][i] : q3;
-    }
-    const double nrm = sqrt(((q0 * q0 + q1 * q1) + q2 * q2) + q3 * q3);
-    const double w = q0 / nrm, x = q1 / nrm, y = q2 / nrm, z = q3 / nrm;
     Model m;
-    m.R[0] = 1.0 - 2.0 * (y * y + z * z);
-    m.R[1] = 2.0 * (x * y - w * z);
-    m.R[2] = 2.0 * (x * z + w * y);
-    m.R[3] = 2.0 * (x * y + w * z);
-    m.R[4] = 1.0 - 2.0 * (x * x + z * z);
-    m.R[5] = 2.0 * (y * z - w * x);
-    m.R[6] = 2.0 * (x * z - w * y);
-    m.R[7] = 2.0 * (y * z + w * x);
-    m.R[8] = 1.0 - 2.0 * (x * x + y * y);
+    horn_rotation(M, m.R);
     if (fix_scale) {
         m.s12 = 1.0;
     } else {

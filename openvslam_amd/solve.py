@@ -1,8 +1,15 @@
-"""solve::sim3_solver (expected: src/openvslam/solve/sim3_solver.{h,cc}) on the MI355X: the RANSAC the loop detector runs on every loop
+"""solve/ on the MI355X: the two RANSAC solvers whose candidates come in batches.
+
+solve::sim3_solver (expected: src/openvslam/solve/sim3_solver.{h,cc}) on the MI355X: the RANSAC the loop detector runs on every loop
 candidate between bow_tree::match_keyframes and projection::match_by_Sim3_transform. All candidates of a keyframe go to the device in ONE
 call (ovs_sim3_solve_batch, csrc/sim3_solve.hip): two launches whatever their number. DESIGN.md 3.9 has the rules; the results are
-bit-exact functions of (inputs, seed, position in the batch)."""
+bit-exact functions of (inputs, seed, position in the batch).
+
+solve::pnp_solver (expected: src/openvslam/solve/pnp_solver.{h,cc}): the EPnP RANSAC the relocaliser runs on every candidate keyframe between
+bow_tree::match_frame_and_keyframe and the pose optimiser. All candidates go to the device in ONE call (ovs_pnp_solve_batch,
+csrc/pnp_solve.hip): two launches whatever their number. DESIGN.md 3.10 has the rules; bit-exact in the same sense."""
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -119,6 +126,108 @@ class sim3_solver:
 
     def get_best_scale_12(self):
         return self._get("scale_12")
+
+    def get_inlier_flags(self):
+        return self._get("inlier_flags")
+
+    def get_best_iter(self):
+        return self._get("best_iter")
+
+    def get_num_inliers(self):
+        return self._get("num_inliers")
+
+
+# ---- solve::pnp_solver
+PNP_DEFAULT_SEED = 0x45506E50   # upstream draws from random_device; here a run is reproducible
+
+
+def pnp_problem_seed(seed, p):
+    """The seed under which problem p of a batch, solved ALONE (as problem 0), draws the samples it draws in the batch (3.10 rule 1)."""
+    return (seed + _G * (p << 23)) & _MASK
+
+
+def pnp_problem(bearings, octaves, pos_w, scale_factors):
+    """What pnp_solver's constructor keeps for the matched (keypoint, landmark) pairs: the bearings, the landmarks in the world and
+    max_cos_errors_ = cos(scale_factors[octave] * 1 degree) (math.cos: the C library's, as the C++ class calls it). bearings, pos_w: (n, 3);
+    octaves: (n,); scale_factors: per level, floats."""
+    sf = np.asarray(scale_factors, np.float32)
+    deg = math.pi / 180.0
+    return dict(bearings=np.ascontiguousarray(bearings, np.float64).reshape(-1, 3), pos_w=np.ascontiguousarray(pos_w, np.float64).reshape(-1, 3),
+                max_cos_error=np.array([math.cos(float(sf[int(o)]) * deg) for o in np.asarray(octaves).ravel()], np.float64))
+
+
+class _pnp_handle:
+    """ovs_pnp with its capacity."""
+
+    def __init__(self, max_problems, max_total_matches, device=0):
+        self._L = _lib.lib()
+        _lib.require_device()
+        self.max_problems, self.max_total_matches = int(max_problems), int(max_total_matches)
+        h = C.c_void_p()
+        _lib.check(self._L.ovs_pnp_create(device, self.max_problems, self.max_total_matches, C.byref(h)), "ovs_pnp_create")
+        self._h = h
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._L.ovs_pnp_destroy(h)
+
+
+def solve_pnp_batch(problems, min_num_inliers=10, max_num_iter=30, recompute=True, seed=PNP_DEFAULT_SEED, handle=None, device=0):
+    """find_via_ransac for every problem (dicts as pnp_problem returns them) in one call: a list of dicts valid, best_iter, num_inliers,
+    rot_cw (3 x 3), trans_cw (3), inlier_flags (n, bool). `handle`: a _pnp_handle to reuse (the relocaliser keeps one)."""
+    P = len(problems)
+    if P == 0:
+        return []
+    counts = [len(np.asarray(q["max_cos_error"])) for q in problems]
+    offsets = np.zeros(P + 1, np.int32)
+    offsets[1:] = np.cumsum(counts)
+    T = int(offsets[-1])
+    cat = lambda key, w: np.ascontiguousarray(np.concatenate([np.asarray(q[key], np.float64).reshape(-1, w) for q in problems]) if T else np.zeros((0, w)))
+    bearings, pos_w, max_cos = cat("bearings", 3), cat("pos_w", 3), cat("max_cos_error", 1)
+    if len(bearings) != T or len(pos_w) != T:
+        raise ValueError("bearings, pos_w and max_cos_error of a problem must have one entry per match")
+    if handle is None:
+        handle = _pnp_handle(P, max(T, 1), device)
+    valid, best_iter, num = np.zeros(P, np.int32), np.zeros(P, np.int32), np.zeros(P, np.int32)
+    rot, trans, flags = np.zeros((P, 3, 3)), np.zeros((P, 3)), np.zeros(max(T, 1), np.uint8)
+    _lib.check(handle._L.ovs_pnp_solve_batch(handle._h, P, _p(offsets), _p(bearings), _p(pos_w), _p(max_cos), int(min_num_inliers), int(max_num_iter),
+                                             1 if recompute else 0, int(seed) & _MASK, _p(valid), _p(best_iter), _p(num), _p(rot), _p(trans), _p(flags)),
+               "ovs_pnp_solve_batch")
+    return [dict(valid=bool(valid[i]), best_iter=int(best_iter[i]), num_inliers=int(num[i]), rot_cw=rot[i].copy(), trans_cw=trans[i].copy(),
+                 inlier_flags=flags[offsets[i]:offsets[i + 1]].astype(bool)) for i in range(P)]
+
+
+class pnp_solver:
+    """solve::pnp_solver over one problem: the constructor takes what upstream's does (the valid bearings, their keypoints' octaves, the
+    landmarks and the scale factors), find_via_ransac runs the device RANSAC, the getters are upstream's."""
+
+    def __init__(self, valid_bearings, valid_octaves, valid_landmarks, scale_factors, min_num_inliers=10, device=0):
+        self._problem = pnp_problem(valid_bearings, valid_octaves, valid_landmarks, scale_factors)
+        self._min_num_inliers, self._device = int(min_num_inliers), device
+        self._result = None
+
+    def find_via_ransac(self, max_num_iter, recompute=True, seed=PNP_DEFAULT_SEED):
+        self._result = solve_pnp_batch([self._problem], self._min_num_inliers, max_num_iter, recompute, seed, device=self._device)[0]
+
+    def _get(self, key):
+        if self._result is None:
+            raise RuntimeError("find_via_ransac has not run")
+        return self._result[key]
+
+    def solution_is_valid(self):
+        return self._result is not None and self._result["valid"]
+
+    def get_best_rotation(self):
+        return self._get("rot_cw")
+
+    def get_best_translation(self):
+        return self._get("trans_cw")
+
+    def get_best_cam_pose(self):
+        T = np.eye(4)
+        T[:3, :3], T[:3, 3] = self._get("rot_cw"), self._get("trans_cw")
+        return T
 
     def get_inlier_flags(self):
         return self._get("inlier_flags")

@@ -1,0 +1,381 @@
+"""The sequential EPnP RANSAC reference (tests/pnp_ref.py; DESIGN.md 3.10, rules 1 to 6) checked on its own: the sampler, EPnP on exact data, the
+fixed Jacobi sweeps, an N-version check of the refit against numpy.linalg.eigh / lstsq, the planted pose on the scenes -- and the condition the
+device tests rest on: every scene they use keeps every cosine 1e-10 away from its threshold, so no last-bit difference could flip a flag.
+Plus the C ABI's argument errors, which are decided before the device is touched, and the C++ class's degraded result when its device is
+absent."""
+import ctypes as C
+import functools
+import math
+import os
+import random
+import subprocess
+
+import numpy as np
+import pytest
+
+import pnp_ref
+import pnp_scene_io
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SEED, ITERS = 2468, 30
+FOCAL = 458.0
+TRUE_ANGLE, TRUE_AXIS, TRUE_T = 0.4, (1.0, 2.0, -1.0), (0.3, -0.2, 0.5)
+MARGIN_MIN = 1e-10
+# EPnP on exact data: the reference's own worst error over the scenes of test_epnp_returns_the_planted_pose_on_exact_data was 7.5e-14
+# (measured), the bound 100 times that and below the 1e-9 the rules allow
+EXACT_WORST, EXACT_BOUND = 7.5e-14, 7.5e-12
+
+
+def scale_factors(num_levels=8, scale_factor=1.2):
+    """orb_params' table as upstream fills it, in float: scale_factors[l] = scale_factors[l - 1] * 1.2f."""
+    sf = [np.float32(1.0)]
+    for _ in range(1, num_levels):
+        sf.append(np.float32(sf[-1] * np.float32(scale_factor)))
+    return [float(s) for s in sf]
+
+
+def rotation(angle=TRUE_ANGLE, axis=TRUE_AXIS):
+    nrm = math.sqrt(sum(v * v for v in axis))
+    h = angle / 2.0
+    return pnp_ref.rotation_of(math.cos(h), *(math.sin(h) * v / nrm for v in axis))
+
+
+def to_world(R, t, pc):
+    """R^T (pc - t)"""
+    return tuple(sum(R[3 * k + x] * (pc[k] - t[k]) for k in range(3)) for x in range(3))
+
+
+def scene(n, noise_px=0.5, outlier_fraction=0.3, rng_seed=0, coplanar=False, identical=False):
+    """n matches of a relocalisation candidate: landmarks at 4 to 9 m in front of the camera, which stands at the true pose; the keypoints
+    with Gaussian noise of `noise_px` pixels at f = 458, `outlier_fraction` of them looking at another random point; octaves 0 to 7 at scale
+    factor 1.2. coplanar: every landmark has the world z = 2 exactly; identical: one landmark everywhere."""
+    rng = random.Random(1000 * n + rng_seed)
+    R, sf = rotation(), scale_factors()
+    point = lambda: (rng.uniform(-3.0, 3.0), rng.uniform(-2.0, 2.0), rng.uniform(4.0, 9.0))
+    outliers = set(rng.sample(range(n), int(outlier_fraction * n)))
+    bearings, pos_w, octaves = [], [], []
+    for i in range(n):
+        pc = point()
+        w = to_world(R, TRUE_T, pc)
+        if coplanar:   # the plane z_w = 2, seen from the true pose: the centred z is exactly zero, an eigenvalue exactly zero, the control
+            w = (w[0], w[1], 2.0)   # point matrix singular: x / 0 from there on
+            pc = tuple(pnp_ref.dot3(R[3 * r], R[3 * r + 1], R[3 * r + 2], *w) + TRUE_T[r] for r in range(3))
+        seen = point() if i in outliers else pc
+        u, v = seen[0] / seen[2] + rng.gauss(0.0, noise_px / FOCAL), seen[1] / seen[2] + rng.gauss(0.0, noise_px / FOCAL)
+        nrm = math.sqrt(u * u + v * v + 1.0)
+        bearings.append((u / nrm, v / nrm, 1.0 / nrm))
+        pos_w.append(w)
+        octaves.append(rng.randrange(8))
+    if identical:   # one point everywhere, with coordinates whose sums are exact: every centred point is exactly zero
+        pos_w = [(1.0, -0.5, 6.0)] * n
+    return dict(bearings=bearings, pos_w=pos_w, octaves=octaves, max_cos_error=[pnp_ref.max_cos_error(sf[o]) for o in octaves])
+
+
+# Every (scene, min_num_inliers) the device tests use. name -> (problem builder, min_num_inliers)
+CASES = {
+    "n4": (lambda: scene(4, noise_px=0.0, outlier_fraction=0.0), 3),
+    "n5": (lambda: scene(5, noise_px=0.0, outlier_fraction=0.0), 4),
+    "n63": (lambda: scene(63), 10),
+    "n64": (lambda: scene(64), 10),
+    "n65": (lambda: scene(65), 10),
+    "n100": (lambda: scene(100), 10),
+    "n257": (lambda: scene(257), 10),
+    "n65_noisy": (lambda: scene(65, noise_px=8.0, rng_seed=1), 10),   # 8 px of noise: the counts differ from hypothesis to hypothesis
+    "clean": (lambda: scene(30, noise_px=0.0, outlier_fraction=0.0), 10),
+    "too_few_inliers": (lambda: scene(24, outlier_fraction=0.8, rng_seed=3), 10),
+    "coplanar": (lambda: scene(20, outlier_fraction=0.0, coplanar=True), 4),
+    "identical": (lambda: scene(12, identical=True), 4),
+    "empty": (lambda: scene(0), 10),
+    "three": (lambda: scene(3, outlier_fraction=0.0), 3),
+}
+CASE_ITERS = {"n65_noisy": 200}
+EDGE_ITERS = (1, 2, 30, 200)   # a workgroup takes ONE hypothesis: 1 is "at", 2 "one above"; "one below" is 0, which the ABI refuses (error contract)
+EDGE_H, EDGE_COUNT = 482, 43
+
+
+def edge_seed(max_num_iter):
+    """The seed under which the LAST of the first max_num_iter hypotheses of "n65_noisy" wins. Moving the seed by 8 G d moves the hypothesis
+    numbers by d (rule 1), and under SEED hypothesis 482 has 43 inliers, more than each of the 199 before it (found once with the reference;
+    test_edge_seeds_put_the_winner_last holds it to that)."""
+    return (SEED + pnp_ref.G * 8 * (EDGE_H - (max_num_iter - 1))) & pnp_ref.MASK
+
+
+# the device tests' batch: (case, position); one min_num_inliers for all of them
+BATCH, BATCH_MIN_INLIERS = [("n65", 0), ("empty", 1), ("n4", 2), ("three", 3), ("n64", 4)], 10
+SHIM_CASES = ["n64", "n65"]   # the C++ program's candidates, single and as a batch (positions 0 and 1)
+
+
+@functools.lru_cache(maxsize=None)
+def problem(name):
+    return CASES[name][0]()
+
+
+@functools.lru_cache(maxsize=None)
+def evaluated(name, seed=SEED, p=0):
+    """(counts per hypothesis, margin, off-diagonal ratio) of a case: computed once, shared by the CPU and the device tests."""
+    return pnp_ref.evaluate(problem(name), seed, CASE_ITERS.get(name, ITERS), p)
+
+
+@functools.lru_cache(maxsize=None)
+def _finished(name, max_num_iter, seed, p, min_num_inliers, recompute):
+    counts = evaluated(name, seed, p)[0]
+    k = len(counts) if max_num_iter is None else max_num_iter
+    assert k <= len(counts) or not counts
+    info = {}
+    r = pnp_ref.finish(problem(name), counts[:k], seed, CASES[name][1] if min_num_inliers is None else min_num_inliers, recompute, p, info)
+    return r, info
+
+
+def expected(name, max_num_iter=None, seed=SEED, p=0, min_num_inliers=None, recompute=True):
+    """The reference result of a case for the first max_num_iter hypotheses (they are independent: a prefix of the counts)."""
+    return _finished(name, max_num_iter, seed, p, min_num_inliers, recompute)[0]
+
+
+def refit_info(name, max_num_iter=None, seed=SEED, p=0, min_num_inliers=None):
+    """The refit's margin and off-diagonal ratio ({} where no refit ran)."""
+    return _finished(name, max_num_iter, seed, p, min_num_inliers, True)[1]
+
+
+def second_seed():
+    """The first seed after SEED under which the reference's winner on "n65" is another hypothesis."""
+    return SEED + 1
+
+
+def every_use(name):
+    """Every (max_num_iter, seed, p, min_num_inliers) under which a device test solves the case."""
+    uses = [(None, SEED, 0, None)]
+    if name == "n65":
+        uses.append((None, second_seed(), 0, None))
+    if name == "n65_noisy":
+        uses += [(k, edge_seed(k), 0, None) for k in EDGE_ITERS]
+    if name in SHIM_CASES:
+        uses.append((None, SEED, SHIM_CASES.index(name), None))
+    uses += [(None, SEED, p, BATCH_MIN_INLIERS) for case, p in BATCH if case == name]
+    return uses
+
+
+def angle_to_truth(R):
+    T = rotation()
+    trace = sum(R[i] * T[i] for i in range(9))   # tr(R_est^T R_true)
+    return math.degrees(math.acos(max(-1.0, min(1.0, (trace - 1.0) / 2.0))))
+
+
+# ---- rule 1
+@pytest.mark.parametrize("n", [4, 5, 6, 64, 1000])
+def test_sampler_gives_four_distinct_indices_in_range(n):
+    seen = set()
+    for h in range(10000):
+        idx = pnp_ref.sample(SEED, h % 7, h, n)
+        assert len(set(idx)) == 4 and all(0 <= i < n for i in idx), (h, idx)
+        seen.update(idx)
+    assert len(seen) == n   # every index is drawn
+
+
+def test_sampler_is_a_function_of_seed_problem_and_hypothesis():
+    G, MASK = pnp_ref.G, pnp_ref.MASK
+    a = [pnp_ref.sample(SEED, 2, h, 100) for h in range(50)]
+    assert a == [pnp_ref.sample(SEED, 2, h, 100) for h in range(50)]
+    assert a != [pnp_ref.sample(SEED + 1, 2, h, 100) for h in range(50)] and a != [pnp_ref.sample(SEED, 3, h, 100) for h in range(50)]
+    # problem p of a batch solved alone: the seed moved by G * (p << 23) draws the same samples as problem 0
+    assert a == [pnp_ref.sample((SEED + G * (2 << 23)) & MASK, 0, h, 100) for h in range(50)]
+    # the seed moved by 8 G d moves the hypothesis numbers by d
+    assert a[7:] == [pnp_ref.sample((SEED + G * 8 * 7) & MASK, 2, h, 100) for h in range(43)]
+    from openvslam_amd import solve
+    assert solve.pnp_problem_seed(SEED, 2) == (SEED + G * (2 << 23)) & MASK
+
+
+# ---- rule 2
+def exact_scene(rng, n):
+    axis = tuple(rng.gauss(0.0, 1.0) for _ in range(3))
+    R, t = rotation(rng.uniform(0.1, 1.0), axis), tuple(rng.uniform(-1.0, 1.0) for _ in range(3))
+    pc = [(rng.uniform(-3.0, 3.0), rng.uniform(-2.0, 2.0), rng.uniform(4.0, 9.0)) for _ in range(n)]
+    return R, t, [to_world(R, t, q) for q in pc], [(q[0] / q[2], q[1] / q[2]) for q in pc]
+
+
+@functools.lru_cache(maxsize=None)
+def exact_data_errors():
+    rng = random.Random(7)
+    worst = {}
+    for n in (5, 6, 8, 30, 100):
+        for _ in range(20):
+            R, t, pw, uv = exact_scene(rng, n)
+            R2, t2 = pnp_ref.epnp(pw, uv)
+            worst[n] = max(worst.get(n, 0.0), max(abs(a - b) for a, b in zip(list(R) + list(t), R2 + t2)))
+    return worst
+
+
+def test_epnp_returns_the_planted_pose_on_exact_data():
+    """n = 4 is left out on purpose: the null space of M^T M has four dimensions there and EPnP is approximate."""
+    worst = exact_data_errors()
+    print("worst |pose - planted| per n:", worst)
+    assert EXACT_BOUND <= 100 * EXACT_WORST * (1 + 1e-12) and EXACT_BOUND <= 1e-9
+    assert max(worst.values()) <= EXACT_BOUND
+    assert max(worst.values()) <= EXACT_WORST   # the measured value the bound was derived from still holds
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_fixed_sweeps_diagonalise_every_hypothesis_and_refit(name):
+    for k, seed, p, mi in every_use(name):
+        off = evaluated(name, seed, p)[2]
+        off_refit = refit_info(name, k, seed, p, mi).get("off", 0.0)
+        print(name, k, seed, p, "off-diagonal / max|A| =", off, "refit", off_refit)
+        assert off <= 1e-13 and off_refit <= 1e-13
+
+
+def _eigh(N):
+    w, v = np.linalg.eigh(np.array(N))
+    return [[float(w[i]) if i == j else 0.0 for j in range(len(w))] for i in range(len(w))], [[float(x) for x in row] for row in v]
+
+
+def _lstsq(rows, b):
+    return [float(x) for x in np.linalg.lstsq(np.array(rows), np.array(b), rcond=None)[0]]
+
+
+def noise_amplification(prob, flags):
+    """How much further than on exact data two correct eigensolvers may part on this refit. The pose is a function of the eigenvectors of the
+    four smallest eigenvalues of M^T M, one by one (the betas weigh each on its own). By Davis and Kahan a perturbation E of the matrix turns
+    the vector of eigenvalue k by at most about |E| / gap_k, gap_k the distance to the nearest other eigenvalue. The exact-data bound
+    already contains 1 / gap of the exact twin of this scene (the same landmarks seen without noise); the amplification is the ratio of the
+    two smallest relative gaps among the first five eigenvalues, exact twin over noisy scene, and at least 1."""
+    idx = [i for i, f in enumerate(flags) if f]
+    R = rotation()
+
+    def rel_gap(uv):
+        pws = [prob["pos_w"][i] for i in idx]
+        n = len(pws)
+        c0 = np.mean(pws, axis=0)
+        d = np.array(pws) - c0
+        w, v = np.linalg.eigh(d.T @ d)
+        C = np.array([np.sqrt(w[k] / n) * v[:, k] for k in range(3)]).T
+        a = np.linalg.solve(C, d.T).T
+        a = np.concatenate([1.0 - a.sum(1, keepdims=True), a], 1)
+        M = np.zeros((2 * n, 12))
+        for i in range(n):
+            for j in range(4):
+                M[2 * i, 3 * j], M[2 * i, 3 * j + 2] = a[i, j], -a[i, j] * uv[i][0]
+                M[2 * i + 1, 3 * j + 1], M[2 * i + 1, 3 * j + 2] = a[i, j], -a[i, j] * uv[i][1]
+        lam = np.linalg.eigvalsh(M.T @ M)
+        return float(min(lam[k + 1] - lam[k] for k in range(4)) / lam[-1])
+    noisy = [pnp_ref.image_coords(prob)[i] for i in idx]
+    exact = []
+    for i in idx:
+        pc = [pnp_ref.dot3(R[3 * r], R[3 * r + 1], R[3 * r + 2], *prob["pos_w"][i]) + TRUE_T[r] for r in range(3)]
+        exact.append((pc[0] / pc[2], pc[1] / pc[2]))
+    return max(1.0, rel_gap(exact) / rel_gap(noisy))
+
+
+@pytest.mark.parametrize("name", ["n64", "n257"])
+def test_numpy_eigh_and_lstsq_give_the_same_refit(name):
+    """Only the refit: within the degenerate null space of a four-point sample the basis depends on the eigensolver."""
+    prob = problem(name)
+    counts = evaluated(name)[0]
+    r = expected(name, recompute=False)
+    assert r["best_iter"] == counts.index(max(counts))
+    Rj, tj = pnp_ref.refit(prob, r["flags"])
+    Rn, tn = pnp_ref.refit(prob, r["flags"], eig=_eigh, lsq=_lstsq)
+    amp = noise_amplification(prob, r["flags"])
+    diff = max(abs(a - b) for a, b in zip(Rj + tj, Rn + tn))
+    print(name, "amplification", amp, "difference", diff, "bound", EXACT_BOUND * amp)
+    assert diff <= EXACT_BOUND * amp
+    assert pnp_ref.flags_of(prob, Rj, tj) == pnp_ref.flags_of(prob, Rn, tn) == expected(name)["flags"]
+
+
+@pytest.mark.parametrize("name", ["n65", "n257"])
+def test_winner_is_the_planted_pose(name):
+    r = expected(name)
+    n = len(problem(name)["pos_w"])
+    print(name, "winner", r["best_iter"], "inliers %d / %d" % (r["num_inliers"], n), "angle", angle_to_truth(r["R"]))
+    assert r["valid"] and r["num_inliers"] >= 0.5 * n and sum(r["flags"]) == r["num_inliers"]
+    assert angle_to_truth(r["R"]) <= 1.0
+
+
+# ---- the condition for the device tests
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_every_device_scene_keeps_its_distance_from_the_thresholds(name):
+    for k, seed, p, mi in every_use(name):
+        margin = evaluated(name, seed, p)[1]
+        refit = refit_info(name, k, seed, p, mi).get("margin", float("inf"))
+        print(name, k, seed, p, "margin", margin, "refit", refit)
+        assert margin >= MARGIN_MIN and refit >= MARGIN_MIN
+
+
+def test_cases_are_what_their_names_say():
+    assert [len(problem(k)["pos_w"]) for k in ("n4", "n5", "n63", "n64", "n65", "n100", "n257", "empty", "three")] == [4, 5, 63, 64, 65, 100, 257, 0, 3]
+    assert 64 < expected("n100")["num_inliers"] < 128 < expected("n257")["num_inliers"] and expected("n65")["num_inliers"] < 64
+    assert not expected("too_few_inliers")["valid"] and max(evaluated("too_few_inliers")[0]) < 10
+    clean = evaluated("clean")[0]
+    assert clean.count(30) > 10 and expected("clean")["best_iter"] == clean.index(30) == 0 and expected("clean")["num_inliers"] == 30
+    assert expected("n65")["best_iter"] != expected("n65", seed=second_seed())["best_iter"] and expected("n65", seed=second_seed())["valid"]
+    noisy = evaluated("n65_noisy")[0]
+    assert len(set(noisy)) > 10   # the counts differ from hypothesis to hypothesis
+    a, b = expected("n65_noisy"), expected("n65_noisy", recompute=False)
+    assert a["valid"] and b["valid"] and a["best_iter"] == b["best_iter"] and pnp_ref.pose_bits(a["R"], a["t"]) != pnp_ref.pose_bits(b["R"], b["t"])
+    for name in ("n4", "n5", "n63", "n64", "n65", "n100", "n257", "n65_noisy", "clean"):
+        assert expected(name)["valid"], name
+    for name in ("coplanar", "identical"):   # every hypothesis is NaN: no cosine compares
+        assert set(evaluated(name)[0]) == {0} and evaluated(name)[1] == float("inf")
+
+
+@pytest.mark.parametrize("max_num_iter", EDGE_ITERS)
+def test_edge_seeds_put_the_winner_last(max_num_iter):
+    seed = edge_seed(max_num_iter)
+    counts = evaluated("n65_noisy", seed)[0]
+    r = expected("n65_noisy", max_num_iter, seed)
+    assert r["valid"] and r["best_iter"] == max_num_iter - 1 and counts[max_num_iter - 1] == EDGE_COUNT
+    assert max(counts[:max_num_iter - 1], default=-1) < EDGE_COUNT
+
+
+def test_invalid_output_convention():
+    for n in (0, 3):
+        r, margin = pnp_ref.find_via_ransac(scene(n, outlier_fraction=0.0), ITERS, SEED, 0)
+        assert r == dict(pnp_ref.INVALID, flags=[0] * n) and margin == float("inf")
+    assert expected("n4", p=2, min_num_inliers=BATCH_MIN_INLIERS) == dict(pnp_ref.INVALID, flags=[0] * 4)   # n < min_num_inliers
+    assert expected("coplanar") == dict(pnp_ref.INVALID, flags=[0] * 20)
+    assert expected("identical") == dict(pnp_ref.INVALID, flags=[0] * 12)
+    z = {w[2] for w in problem("coplanar")["pos_w"]}
+    assert z == {2.0} and len(set(problem("identical")["pos_w"])) == 1
+    r = expected("identical", min_num_inliers=0)   # min_num_inliers = 0 keeps it "valid": the winner is hypothesis 0 with no inlier and a NaN
+    assert r["valid"] == 1 and r["best_iter"] == 0 and r["num_inliers"] == 0 and r["flags"] == [0] * 12 and r["R"][0] != r["R"][0]   # pose
+
+
+# ---- the C ABI without a device in the way: every argument error is decided before the device is touched
+def test_abi_argument_errors_come_before_the_device():
+    from openvslam_amd import _lib, solve
+    L = _lib.lib()
+    INVALID, NO_DEVICE = -1, -2
+    h = C.c_void_p()
+    assert L.ovs_pnp_create(0, 0, 100, C.byref(h)) == INVALID and L.ovs_pnp_create(0, 4, 0, C.byref(h)) == INVALID
+    assert L.ovs_pnp_create(0, 4, 100, None) == INVALID
+    assert L.ovs_pnp_create(99, 4, 100, C.byref(h)) == NO_DEVICE and not h      # no such device, here or on a GPU box
+    assert L.ovs_pnp_create(-1, 4, 100, C.byref(h)) == NO_DEVICE and not h
+    assert L.ovs_pnp_destroy(None) == INVALID
+    off = np.array([0, 4], np.int32)
+    p = np.ones((4, 3))
+    out_i, out_d, fl = np.zeros(4, np.int32), np.zeros(16), np.zeros(4, np.uint8)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    assert L.ovs_pnp_solve_batch(None, 1, vp(off), vp(p), vp(p), vp(p), 10, 30, 1, 1, vp(out_i), vp(out_i), vp(out_i), vp(out_d), vp(out_d),
+                                 vp(fl)) == INVALID
+    with pytest.raises(_lib.OvsError):   # the Python mirror raises: no device at all here, no device 99 anywhere
+        solve._pnp_handle(4, 16, device=99)
+
+
+def test_python_constructor_mirror():
+    from openvslam_amd import solve
+    q = problem("n64")
+    got = solve.pnp_problem(q["bearings"], q["octaves"], q["pos_w"], scale_factors())
+    assert got["max_cos_error"].tolist() == q["max_cos_error"] and got["bearings"].tolist() == [list(b) for b in q["bearings"]]
+    assert got["max_cos_error"][q["octaves"].index(0)] == math.cos(math.pi / 180.0)
+
+
+def test_cpp_class_degrades_without_its_device(tmp_path):
+    """The wrapper alone: on a device that does not exist the class answers solution_is_valid() == false instead of throwing."""
+    cpp = os.path.join(ROOT, "openvslam_amd", "cpp")
+    subprocess.check_call(["make", "-s", "-C", cpp, "test_pnp_shim"])
+    pnp_scene_io.write_scene(tmp_path / "scene.bin", [problem(k) for k in SHIM_CASES], scale_factors(), 10, ITERS, True, SEED)
+    r = subprocess.run([os.path.join(cpp, "test_pnp_shim"), str(tmp_path / "scene.bin"), str(tmp_path / "out.bin"), "99"], capture_output=True,
+                       text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    got = pnp_scene_io.read_results(tmp_path / "out.bin", len(SHIM_CASES))
+    for g, k in zip(got["single"] + got["batch"], SHIM_CASES * 2):
+        assert g == pnp_scene_io.as_bits(dict(pnp_ref.INVALID, flags=[0] * len(problem(k)["pos_w"])))
+    assert "ABI calls failed 3, degraded 3" in r.stdout   # two single calls and the batch
