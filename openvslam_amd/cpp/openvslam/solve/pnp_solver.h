@@ -13,17 +13,16 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
-#include <mutex>
 #include <stdexcept>
 #include <vector>
 
 #include "../data/frame_stub.h"
-#include "../util/device_policy.h"
+#include "ransac_context.h"
 
 namespace openvslam {
 namespace solve {
 
-class pnp_solver {
+class pnp_solver : private ransac_result {
 public:
     //! upstream: keeps the bearings and the landmarks and max_cos_errors_ = cos(scale_factors[octave] * 1 degree) per keypoint
     //! (eigen_alloc_vector<Vec3_t> upstream; std::vector here)
@@ -45,12 +44,7 @@ public:
 
     void set_seed(const uint64_t seed) { seed_ = seed; }
     //! the HIP device the solvers run on (process-wide; 0 unless an integration places the tracker elsewhere)
-    static void set_device(const int device) {
-        context& c = ctx();
-        std::lock_guard<std::mutex> lock(c.mu);
-        c.drop();
-        c.device = device;
-    }
+    static void set_device(const int device) { ctx().set_device(device); }
 
     void find_via_ransac(const unsigned int max_num_iter, const bool recompute = true) { find_via_ransac_batch({this}, max_num_iter, recompute); }
 
@@ -71,26 +65,18 @@ public:
             offsets.push_back(offsets.back() + (int32_t)s->num_matches_);
         }
         const int32_t P = (int32_t)solvers.size(), T = offsets.back();
-        std::vector<int32_t> valid((size_t)P), best_iter((size_t)P), num_inliers((size_t)P);
-        std::vector<uint8_t> flags((size_t)std::max(T, 1));
-        context& c = ctx();
-        std::lock_guard<std::mutex> lock(c.mu);
-        if (!util::run_guarded("ovs_pnp_solve_batch", [&] {
-                const ovs_status st = c.ensure(P, T);
-                if (st != OVS_OK) return st;
-                return ovs_pnp_solve_batch(c.handle, P, offsets.data(), bearings.data(), pos_w.data(), max_cos.data(), (int32_t)first.min_num_inliers_,
-                                           (int32_t)std::min<unsigned int>(max_num_iter, 1u << 30), recompute ? 1 : 0, first.seed_, valid.data(),
-                                           best_iter.data(), num_inliers.data(), rot.data(), trans.data(), flags.data());
-            }, [&] { c.drop(); }))
+        ransac_batch_out out(P, T);
+        if (!ctx().run("ovs_pnp_solve_batch", P, T, [&](ovs_pnp* handle) {
+                return ovs_pnp_solve_batch(handle, P, offsets.data(), bearings.data(), pos_w.data(), max_cos.data(), (int32_t)first.min_num_inliers_,
+                                           (int32_t)std::min<unsigned int>(max_num_iter, 1u << 30), recompute ? 1 : 0, first.seed_, out.valid.data(),
+                                           out.best_iter.data(), out.num_inliers.data(), rot.data(), trans.data(), out.flags.data());
+            }))
             return;   // every solver stays as reset() left it: solution_is_valid() == false
         for (int32_t p = 0; p < P; ++p) {
             pnp_solver& s = *solvers[(size_t)p];
-            s.solution_is_valid_ = valid[(size_t)p] != 0;
-            s.best_iter_ = best_iter[(size_t)p];
-            s.num_inliers_ = (unsigned int)num_inliers[(size_t)p];
+            s.take(out, p, offsets[(size_t)p]);
             for (int i = 0; i < 9; ++i) s.best_rot_cw_.m[i] = rot[9 * (size_t)p + (size_t)i];
             for (int i = 0; i < 3; ++i) s.best_trans_cw_(i) = trans[3 * (size_t)p + (size_t)i];
-            for (unsigned int i = 0; i < s.num_matches_; ++i) s.is_inlier_match_[i] = flags[(size_t)offsets[(size_t)p] + i] != 0;
         }
     }
 
@@ -112,35 +98,12 @@ public:
 
 private:
     void reset() {
-        solution_is_valid_ = false;
-        best_iter_ = -1;
-        num_inliers_ = 0;
+        ransac_result::reset(num_matches_);
         best_rot_cw_ = Mat33_t();
         best_trans_cw_ = Vec3_t();
-        is_inlier_match_.assign(num_matches_, false);
     }
 
-    // the process's handle: created on first use, enlarged when a batch outgrows it, dropped after a device failure
-    struct context {
-        std::mutex mu;
-        int device = 0;
-        ovs_pnp* handle = nullptr;
-        int32_t max_problems = 0, max_total_matches = 0;
-        ovs_status ensure(int32_t P, int32_t T) {
-            if (handle && P <= max_problems && T <= max_total_matches) return OVS_OK;
-            drop();
-            const int32_t mp = std::max<int32_t>(16, 2 * P), mt = std::max<int32_t>(4096, 2 * T);
-            const ovs_status st = ovs_pnp_create(device, mp, mt, &handle);
-            if (st == OVS_OK) max_problems = mp, max_total_matches = mt;
-            return st;
-        }
-        void drop() {
-            if (handle) ovs_pnp_destroy(handle);
-            handle = nullptr;
-            max_problems = max_total_matches = 0;
-        }
-        ~context() { drop(); }
-    };
+    using context = ransac_context<ovs_pnp, ovs_pnp_create, ovs_pnp_destroy>;
     static context& ctx() {
         static context c;
         return c;
@@ -150,12 +113,8 @@ private:
     uint64_t seed_ = 0x45506E50ull;
     std::vector<double> valid_bearings_, valid_landmarks_;   // 3 per match
     std::vector<double> max_cos_errors_;
-    bool solution_is_valid_ = false;
-    int best_iter_ = -1;
-    unsigned int num_inliers_ = 0;
     Mat33_t best_rot_cw_;
     Vec3_t best_trans_cw_;
-    std::vector<bool> is_inlier_match_;
 };
 
 }   // namespace solve

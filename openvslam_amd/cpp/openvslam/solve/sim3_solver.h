@@ -11,18 +11,17 @@
 
 #include <algorithm>
 #include <cstdint>
-#include <mutex>
 #include <stdexcept>
 #include <vector>
 
 #include "../data/frame_stub.h"
 #include "../match/window_ctx.h"
-#include "../util/device_policy.h"
+#include "ransac_context.h"
 
 namespace openvslam {
 namespace solve {
 
-class sim3_solver {
+class sim3_solver : private ransac_result {
 public:
     //! upstream: collects, for every keypoint idx1 of keyfrm_1 with a landmark and a matched landmark of keyfrm_2, both landmarks in their own
     //! keyframe's camera coordinates and 9.21 * level_sigma_sq of the two keypoints' octaves
@@ -52,12 +51,7 @@ public:
 
     void set_seed(const uint64_t seed) { seed_ = seed; }
     //! the HIP device the solvers run on (process-wide; 0 unless an integration places the loop closer elsewhere)
-    static void set_device(const int device) {
-        context& c = ctx();
-        std::lock_guard<std::mutex> lock(c.mu);
-        c.drop();
-        c.device = device;
-    }
+    static void set_device(const int device) { ctx().set_device(device); }
 
     void find_via_ransac(const unsigned int max_num_iter) { find_via_ransac_batch({this}, max_num_iter); }
 
@@ -83,28 +77,20 @@ public:
             cams_2.push_back(match::detail::camera_of(s->keyfrm_2_->camera_));
         }
         const int32_t P = (int32_t)solvers.size(), T = offsets.back();
-        std::vector<int32_t> valid((size_t)P), best_iter((size_t)P), num_inliers((size_t)P);
-        std::vector<uint8_t> flags((size_t)std::max(T, 1));
-        context& c = ctx();
-        std::lock_guard<std::mutex> lock(c.mu);
-        if (!util::run_guarded("ovs_sim3_solve_batch", [&] {
-                const ovs_status st = c.ensure(P, T);
-                if (st != OVS_OK) return st;
-                return ovs_sim3_solve_batch(c.handle, P, offsets.data(), p1.data(), p2.data(), thr1.data(), thr2.data(), cams_1.data(), cams_2.data(),
+        ransac_batch_out out(P, T);
+        if (!ctx().run("ovs_sim3_solve_batch", P, T, [&](ovs_sim3* handle) {
+                return ovs_sim3_solve_batch(handle, P, offsets.data(), p1.data(), p2.data(), thr1.data(), thr2.data(), cams_1.data(), cams_2.data(),
                                             first.fix_scale_ ? 1 : 0, (int32_t)first.min_num_inliers_, (int32_t)std::min<unsigned int>(max_num_iter, 1u << 30),
-                                            first.seed_, valid.data(), best_iter.data(), num_inliers.data(), rot.data(), trans.data(), scale.data(),
-                                            flags.data());
-            }, [&] { c.drop(); }))
+                                            first.seed_, out.valid.data(), out.best_iter.data(), out.num_inliers.data(), rot.data(), trans.data(),
+                                            scale.data(), out.flags.data());
+            }))
             return;   // every solver stays as reset() left it: solution_is_valid() == false
         for (int32_t p = 0; p < P; ++p) {
             sim3_solver& s = *solvers[(size_t)p];
-            s.solution_is_valid_ = valid[(size_t)p] != 0;
-            s.best_iter_ = best_iter[(size_t)p];
-            s.num_inliers_ = (unsigned int)num_inliers[(size_t)p];
+            s.take(out, p, offsets[(size_t)p]);
             for (int i = 0; i < 9; ++i) s.best_rot_12_.m[i] = rot[9 * (size_t)p + (size_t)i];
             for (int i = 0; i < 3; ++i) s.best_trans_12_(i) = trans[3 * (size_t)p + (size_t)i];
             s.best_scale_12_ = scale[(size_t)p];
-            for (unsigned int i = 0; i < s.num_common_pts_; ++i) s.is_inlier_match_[i] = flags[(size_t)offsets[(size_t)p] + i] != 0;
         }
     }
 
@@ -124,36 +110,13 @@ private:
         for (int r = 0; r < 3; ++r) out.push_back(((pose_cw(r, 0) * pos_w(0) + pose_cw(r, 1) * pos_w(1)) + pose_cw(r, 2) * pos_w(2)) + pose_cw(r, 3));
     }
     void reset() {
-        solution_is_valid_ = false;
-        best_iter_ = -1;
-        num_inliers_ = 0;
+        ransac_result::reset(num_common_pts_);
         best_rot_12_ = Mat33_t();
         best_trans_12_ = Vec3_t();
         best_scale_12_ = 1.0;
-        is_inlier_match_.assign(num_common_pts_, false);
     }
 
-    // the process's handle: created on first use, enlarged when a batch outgrows it, dropped after a device failure
-    struct context {
-        std::mutex mu;
-        int device = 0;
-        ovs_sim3* handle = nullptr;
-        int32_t max_problems = 0, max_total_matches = 0;
-        ovs_status ensure(int32_t P, int32_t T) {
-            if (handle && P <= max_problems && T <= max_total_matches) return OVS_OK;
-            drop();
-            const int32_t mp = std::max<int32_t>(16, 2 * P), mt = std::max<int32_t>(4096, 2 * T);
-            const ovs_status st = ovs_sim3_create(device, mp, mt, &handle);
-            if (st == OVS_OK) max_problems = mp, max_total_matches = mt;
-            return st;
-        }
-        void drop() {
-            if (handle) ovs_sim3_destroy(handle);
-            handle = nullptr;
-            max_problems = max_total_matches = 0;
-        }
-        ~context() { drop(); }
-    };
+    using context = ransac_context<ovs_sim3, ovs_sim3_create, ovs_sim3_destroy>;
     static context& ctx() {
         static context c;
         return c;
@@ -167,13 +130,9 @@ private:
     std::vector<double> common_pts_in_keyfrm_1_, common_pts_in_keyfrm_2_;   // 3 per pair
     std::vector<float> chi_sq_x_sigma_sq_1_, chi_sq_x_sigma_sq_2_;
     std::vector<unsigned int> matched_indices_1_;
-    bool solution_is_valid_ = false;
-    int best_iter_ = -1;
-    unsigned int num_inliers_ = 0;
     Mat33_t best_rot_12_;
     Vec3_t best_trans_12_;
     double best_scale_12_ = 1.0;
-    std::vector<bool> is_inlier_match_;
 };
 
 }   // namespace solve

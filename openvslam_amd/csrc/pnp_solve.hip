@@ -19,7 +19,6 @@
 // flags and the inliers compacted by rank (ballot + prefix popcount), rule 5's EPnP over them, the flags again, the result.
 #include <cmath>
 #include <cstring>
-#include <mutex>
 
 #include "ovs_common.h"
 #include "solve_internal.inc"
@@ -28,15 +27,6 @@ namespace {
 
 constexpr int kSweeps = 8;          // every symmetric eigenproblem (DESIGN.md 3.10 rule 2)
 constexpr int kModelDoubles = 12;   // R 9, t 3
-constexpr int kMaxIter = 1 << 20;   // h takes 20 bits of the sampler's counter
-
-// per problem in the result block
-struct ResultRec {
-    double rot[9], trans[3];
-    int32_t valid, best_iter, num_inliers, pad;
-};
-static_assert(sizeof(ResultRec) == 112, "ResultRec is read by the host");
-
 // The staged block of one call, sections in this order: keys u64 [P] (zero), bearings f64 [3 T], pos_w f64 [3 T], max_cos_error f64 [T],
 // offsets i32 [P + 1].
 struct Layout {
@@ -58,24 +48,6 @@ struct Lds {
     double A[144], V[144], vec[48];
     int32_t idx[4];
 };
-
-// rule 1: four distinct indices below n (n >= 4), no rejection loop
-__device__ __forceinline__ void sample4(uint64_t seed, uint32_t p, uint32_t h, uint32_t n, uint32_t (&i)[4]) {
-    const uint64_t G = 0x9E3779B97F4A7C15ull;
-    const uint64_t base = seed + G * (((((uint64_t)p) << 20) + h) * 8 + 1);
-    i[0] = (uint32_t)(mix64(base) % n);
-    i[1] = (uint32_t)(mix64(base + G) % (n - 1));
-    if (i[1] >= i[0]) ++i[1];
-    i[2] = (uint32_t)(mix64(base + G * 2) % (n - 2));
-    const uint32_t lo = min(i[0], i[1]), hi = max(i[0], i[1]);
-    if (i[2] >= lo) ++i[2];
-    if (i[2] >= hi) ++i[2];
-    i[3] = (uint32_t)(mix64(base + G * 3) % (n - 3));
-    const uint32_t s0 = min(lo, i[2]), s2 = max(hi, i[2]), s1 = max(lo, min(hi, i[2]));   // the earlier three in ascending order
-    if (i[3] >= s0) ++i[3];
-    if (i[3] >= s1) ++i[3];
-    if (i[3] >= s2) ++i[3];
-}
 
 // rule 6's tree: lane 0's value is ((p0 + p32) + (p16 + p48)) + ... ; every lane ends with the same bits
 __device__ __forceinline__ double wave_sum(double x) {
@@ -148,12 +120,7 @@ __device__ __forceinline__ void jacobi12(Lds& sh, int lane) {
                 const double apq = sh.A[p * 12 + q];
                 const bool rot = apq != 0.0;   // wave-uniform
                 double c = 1.0, s = 0.0;
-                if (rot) {
-                    const double theta = (sh.A[q * 12 + q] - sh.A[p * 12 + p]) / (2.0 * apq);
-                    const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                    c = 1.0 / sqrt(t * t + 1.0);
-                    s = t * c;
-                }
+                if (rot) jacobi_angle(sh.A[p * 12 + p], sh.A[q * 12 + q], apq, c, s);
                 if (rot && lane < 12) {
                     const double akp = sh.A[lane * 12 + p], akq = sh.A[lane * 12 + q];
                     sh.A[lane * 12 + p] = c * akp - s * akq;
@@ -501,15 +468,14 @@ __global__ __launch_bounds__(64) void k_pnp_hypotheses(uint8_t* __restrict__ blo
     __shared__ Lds sh;
     const Layout lay = layout_of(P, T);
     const int p = blockIdx.y, h = blockIdx.x, lane = threadIdx.x;
-    const int32_t* offsets = reinterpret_cast<const int32_t*>(block + lay.offsets);
-    const int off = offsets[p], n = offsets[p + 1] - off;
+    const auto [off, n] = problem_span(block, lay.offsets, p);
     if (n < 4) return;   // rule 4: invalid, k_pnp_finish says so
     const double* bearings = reinterpret_cast<const double*>(block + lay.bearings) + 3 * (size_t)off;
     const double* pos_w = reinterpret_cast<const double*>(block + lay.pos_w) + 3 * (size_t)off;
     const double* max_cos = reinterpret_cast<const double*>(block + lay.max_cos) + off;
     if (lane == 0) {
         uint32_t i[4];
-        sample4(seed, (uint32_t)p, (uint32_t)h, (uint32_t)n, i);
+        sample_distinct<4, 8>(seed, (uint32_t)p, (uint32_t)h, (uint32_t)n, i);   // rule 1
 #pragma unroll
         for (int k = 0; k < 4; ++k) sh.idx[k] = (int32_t)i[k];
     }
@@ -528,8 +494,7 @@ __global__ __launch_bounds__(64) void k_pnp_hypotheses(uint8_t* __restrict__ blo
         for (int k = 0; k < 9; ++k) dst[k] = R[k];
 #pragma unroll
         for (int k = 0; k < 3; ++k) dst[9 + k] = t[k];
-        const unsigned long long key = ((unsigned long long)(uint32_t)count << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)h);   // never 0
-        atomicMax(reinterpret_cast<unsigned long long*>(block + lay.keys) + p, key);
+        atomicMax(reinterpret_cast<unsigned long long*>(block + lay.keys) + p, hypothesis_key(count, (uint32_t)h));
     }
 }
 
@@ -539,25 +504,13 @@ __global__ __launch_bounds__(64) void k_pnp_finish(const uint8_t* __restrict__ b
     __shared__ Lds sh;
     const Layout lay = layout_of(P, T);
     const int p = blockIdx.x, lane = threadIdx.x;
-    const int32_t* offsets = reinterpret_cast<const int32_t*>(block + lay.offsets);
-    const int off = offsets[p], n = offsets[p + 1] - off;
+    const auto [off, n] = problem_span(block, lay.offsets, p);
     const unsigned long long key = reinterpret_cast<const unsigned long long*>(block + lay.keys)[p];
-    int count = (int)(key >> 32);
-    const uint32_t h = 0xFFFFFFFFu - (uint32_t)key;
+    int count = key_count(key);
+    const uint32_t h = key_iter(key);
     const bool valid = n >= 4 && n >= min_inliers && count >= min_inliers;   // rule 4 (n < 4: the key is still zero and never read)
     if (!valid) {
-        for (int i = lane; i < n; i += 64) out_flags[off + i] = 0;
-        if (lane == 0) {
-            ResultRec r;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) r.rot[k] = (k % 4 == 0) ? 1.0 : 0.0;
-            r.trans[0] = r.trans[1] = r.trans[2] = 0.0;
-            r.valid = 0;
-            r.best_iter = -1;
-            r.num_inliers = 0;
-            r.pad = 0;
-            out[p] = r;
-        }
+        write_invalid(out_flags + off, n, 64, out + p);
         return;
     }
     const double* bearings = reinterpret_cast<const double*>(block + lay.bearings) + 3 * (size_t)off;
@@ -608,6 +561,7 @@ __global__ __launch_bounds__(64) void k_pnp_finish(const uint8_t* __restrict__ b
         for (int k = 0; k < 9; ++k) r.rot[k] = R[k];
 #pragma unroll
         for (int k = 0; k < 3; ++k) r.trans[k] = t[k];
+        r.scale = 1.0;
         r.valid = 1;
         r.best_iter = (int32_t)h;
         r.num_inliers = count;
@@ -618,129 +572,52 @@ __global__ __launch_bounds__(64) void k_pnp_finish(const uint8_t* __restrict__ b
 
 }   // namespace
 
-struct ovs_pnp {
-    int device = 0;
-    int max_problems = 0, max_total_matches = 0;
-    std::mutex mu;
-    hipStream_t stream = nullptr;
-    uint8_t *d_block = nullptr, *h_block = nullptr;   // the staged block (Layout) and its page-locked twin
-    double* d_wave_models = nullptr;                  // [problem][hypothesis] the wave's model; grows with problems x max_num_iter
-    size_t wave_models_cap = 0;                       // in records of kModelDoubles
-    int32_t* d_inlier_idx = nullptr;                  // [max_total_matches] the winner's inliers by rank, per problem at its offset
-    // results, page-locked and mapped: k_pnp_finish writes them, the host reads them after the stream has drained
-    ResultRec *h_result = nullptr, *m_result = nullptr;
-    uint8_t *h_flags = nullptr, *m_flags = nullptr;
+struct ovs_pnp : ransac_handle {
+    int32_t* d_inlier_idx = nullptr;   // [max_total_matches] the winner's inliers by rank, per problem at its offset
+    ~ovs_pnp() { hipFree(d_inlier_idx); }
 };
-
-namespace {
-
-void pnp_free(ovs_pnp* s) {
-    if (!s) return;
-    hipFree(s->d_block);
-    hipFree(s->d_wave_models);
-    hipFree(s->d_inlier_idx);
-    if (s->h_block) hipHostFree(s->h_block);
-    if (s->h_result) hipHostFree(s->h_result);
-    if (s->h_flags) hipHostFree(s->h_flags);
-    if (s->stream) hipStreamDestroy(s->stream);
-    delete s;
-}
-
-}   // namespace
 
 extern "C" {
 
 ovs_status ovs_pnp_create(int32_t device, int32_t max_problems, int32_t max_total_matches, ovs_pnp** out) {
-    if (!out || max_problems < 1 || max_total_matches < 1) return OVS_ERR_INVALID;
-    *out = nullptr;
-    if (max_problems > 65535) return OVS_ERR_INVALID;   // a grid's y extent
-    if (ovs_device_count() <= device || device < 0) return OVS_ERR_NO_DEVICE;
-    OVS_HIP_TRY(hipSetDevice(device));
-    ovs_pnp* s = new ovs_pnp();
-    s->device = device;
-    s->max_problems = max_problems;
-    s->max_total_matches = max_total_matches;
-    const size_t block_bytes = layout_of(max_problems, max_total_matches).bytes;
-    hipError_t e = hipSuccess;
-#define D_TRY(expr)                                      \
-    if ((e = ovs::fault_filter(expr)) != hipSuccess) {   \
-        ovs::set_last_error(#expr, e);                   \
-        pnp_free(s);                                     \
-        return OVS_ERR_HIP;                              \
+    const ovs_status st = ransac_create(device, max_problems, max_total_matches, layout_of(max_problems, max_total_matches).bytes,
+                                        (size_t)max_problems * 64,   // 64 iterations per problem without growing
+                                        kModelDoubles, out);
+    if (st != OVS_OK) return st;
+    const hipError_t e = ovs::fault_filter(hipMalloc(&(*out)->d_inlier_idx, sizeof(int32_t) * (size_t)max_total_matches));
+    if (e != hipSuccess) {
+        ovs::set_last_error("hipMalloc(d_inlier_idx)", e);
+        delete *out;
+        *out = nullptr;
+        return OVS_ERR_HIP;
     }
-    D_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    D_TRY(hipMalloc(&s->d_block, block_bytes));
-    s->wave_models_cap = (size_t)max_problems * 64;   // 64 iterations per problem without growing
-    D_TRY(hipMalloc(&s->d_wave_models, sizeof(double) * kModelDoubles * s->wave_models_cap));
-    D_TRY(hipMalloc(&s->d_inlier_idx, sizeof(int32_t) * (size_t)max_total_matches));
-    D_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_block), block_bytes, hipHostMallocDefault));
-    D_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_result), sizeof(ResultRec) * (size_t)max_problems, hipHostMallocMapped));
-    D_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->m_result), s->h_result, 0));
-    D_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_flags), (size_t)max_total_matches, hipHostMallocMapped));
-    D_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->m_flags), s->h_flags, 0));
-#undef D_TRY
-    *out = s;
     return OVS_OK;
 }
 
-ovs_status ovs_pnp_destroy(ovs_pnp* s) {
-    if (!s) return OVS_ERR_INVALID;
-    hipSetDevice(s->device);
-    pnp_free(s);
-    return OVS_OK;
-}
+ovs_status ovs_pnp_destroy(ovs_pnp* s) { return ransac_destroy(s); }
 
 ovs_status ovs_pnp_solve_batch(ovs_pnp* s, int32_t n_problems, const int32_t* offsets, const double* bearings, const double* pos_w,
                                const double* max_cos_errors, int32_t min_num_inliers, int32_t max_num_iter, int32_t recompute, uint64_t seed,
                                int32_t* out_valid, int32_t* out_best_iter, int32_t* out_num_inliers, double* out_rot_cw, double* out_trans_cw,
                                uint8_t* out_inlier_flags) {
-    // every argument error is decided here, before the device is touched
-    if (!s || n_problems < 0 || max_num_iter < 1 || max_num_iter > kMaxIter || min_num_inliers < 0) return OVS_ERR_INVALID;
-    if (n_problems == 0) return OVS_OK;
-    if (!offsets || !out_valid || !out_best_iter || !out_num_inliers || !out_rot_cw || !out_trans_cw) return OVS_ERR_INVALID;
-    if (offsets[0] != 0) return OVS_ERR_INVALID;
-    for (int32_t p = 0; p < n_problems; ++p)
-        if (offsets[p + 1] < offsets[p]) return OVS_ERR_INVALID;
-    const int32_t T = offsets[n_problems];
-    if (T > 0 && (!bearings || !pos_w || !max_cos_errors || !out_inlier_flags)) return OVS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(s->mu);
-    if (n_problems > s->max_problems || T > s->max_total_matches) return OVS_ERR_CAPACITY;   // nothing is truncated
-    const Layout lay = layout_of(n_problems, T);
-    std::memset(s->h_block + lay.keys, 0, 8 * (size_t)n_problems);
-    if (T > 0) {
-        std::memcpy(s->h_block + lay.bearings, bearings, 24 * (size_t)T);
-        std::memcpy(s->h_block + lay.pos_w, pos_w, 24 * (size_t)T);
-        std::memcpy(s->h_block + lay.max_cos, max_cos_errors, 8 * (size_t)T);
-    }
-    std::memcpy(s->h_block + lay.offsets, offsets, 4 * ((size_t)n_problems + 1));
-    OVS_HIP_TRY(hipSetDevice(s->device));
-    hipStream_t st = s->stream;
-    const size_t records = (size_t)n_problems * (size_t)max_num_iter;
-    if (records > s->wave_models_cap) {   // the stream is idle: every call ends in a synchronise
-        OVS_HIP_TRY(hipFree(s->d_wave_models));
-        s->d_wave_models = nullptr;
-        s->wave_models_cap = 0;
-        OVS_HIP_TRY(hipMalloc(&s->d_wave_models, sizeof(double) * kModelDoubles * records));
-        s->wave_models_cap = records;
-    }
-    OVS_HIP_TRY(hipMemcpyAsync(s->d_block, s->h_block, lay.bytes, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_pnp_hypotheses, dim3(max_num_iter, n_problems), dim3(64), 0, st, s->d_block, n_problems, T, max_num_iter, seed,
-                       s->d_wave_models);
-    OVS_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_pnp_finish, dim3(n_problems), dim3(64), 0, st, s->d_block, n_problems, T, min_num_inliers, max_num_iter, recompute ? 1 : 0,
-                       s->d_wave_models, s->d_inlier_idx, s->m_result, s->m_flags);
-    OVS_HIP_TRY(hipGetLastError());
-    OVS_HIP_TRY(hipStreamSynchronize(st));
-    for (int32_t p = 0; p < n_problems; ++p) {
-        const ResultRec& r = s->h_result[p];
-        out_valid[p] = r.valid;
-        out_best_iter[p] = r.best_iter;
-        out_num_inliers[p] = r.num_inliers;
-        std::memcpy(out_rot_cw + 9 * (size_t)p, r.rot, sizeof(r.rot));
-        std::memcpy(out_trans_cw + 3 * (size_t)p, r.trans, sizeof(r.trans));
-    }
-    if (T > 0) std::memcpy(out_inlier_flags, s->h_flags, (size_t)T);
-    return OVS_OK;
+    const auto stage = [&](uint8_t* h_block, const Layout& lay, int32_t T) {
+        if (T > 0) {
+            std::memcpy(h_block + lay.bearings, bearings, 24 * (size_t)T);
+            std::memcpy(h_block + lay.pos_w, pos_w, 24 * (size_t)T);
+            std::memcpy(h_block + lay.max_cos, max_cos_errors, 8 * (size_t)T);
+        }
+        return OVS_OK;
+    };
+    const auto hypotheses = [&](hipStream_t st, int, int32_t T) {
+        hipLaunchKernelGGL(k_pnp_hypotheses, dim3(max_num_iter, n_problems), dim3(64), 0, st, s->d_block, n_problems, T, max_num_iter, seed,
+                           s->d_wave_models);
+    };
+    const auto finish = [&](hipStream_t st, int, int32_t T) {
+        hipLaunchKernelGGL(k_pnp_finish, dim3(n_problems), dim3(64), 0, st, s->d_block, n_problems, T, min_num_inliers, max_num_iter, recompute ? 1 : 0,
+                           s->d_wave_models, s->d_inlier_idx, s->m_result, s->m_flags);
+    };
+    return run_batch(s, n_problems, offsets, {}, {bearings, pos_w, max_cos_errors}, min_num_inliers, max_num_iter, 1, layout_of,
+                     {out_valid, out_best_iter, out_num_inliers, out_rot_cw, out_trans_cw, nullptr, out_inlier_flags}, stage, hypotheses, finish);
 }
 
 }   // extern "C"

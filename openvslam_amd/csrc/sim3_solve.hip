@@ -18,7 +18,6 @@
 // threads write the flags of their matches with the same inlier function, thread 0 the model, into the page-locked result block.
 #include <cmath>
 #include <cstring>
-#include <mutex>
 
 #include "ovs_common.h"
 #include "solve_internal.inc"
@@ -27,7 +26,6 @@ namespace {
 
 constexpr int kHypPerWave = 4;      // hypotheses per wavefront (measured against 8, 16, 32 and 64)
 constexpr int kModelDoubles = 17;   // R12 9, t12 3, s12, s21, t21 3
-constexpr int kMaxIter = 1 << 20;   // h takes 20 bits of the sampler's counter
 constexpr int kFinishThreads = 256;
 
 // one side's camera as the kernels read it: perspective (fx, fy, cx, cy) or equirectangular ((double)cols, (double)rows, -, -)
@@ -36,13 +34,6 @@ struct CamRec {
     int32_t model, pad;
 };
 static_assert(sizeof(CamRec) == 40, "CamRec is laid out in the staged block by the host");
-
-// per problem in the result block
-struct ResultRec {
-    double rot[9], trans[3], scale;
-    int32_t valid, best_iter, num_inliers, pad;
-};
-static_assert(sizeof(ResultRec) == 120, "ResultRec is read by the host");
 
 // The staged block of one call, sections in this order (each a multiple of 8 bytes but the last): keys u64 [P] (zero), cameras CamRec [2 P]
 // (side 1 then side 2 of a problem), p1 f64 [3 T], p2 f64 [3 T], thr1 f32 [T'], thr2 f32 [T'], offsets i32 [P + 1]; T' = T rounded up to even.
@@ -67,24 +58,11 @@ struct Model {
     double R[9], t12[3], s12, s21, t21[3];
 };
 
-// rule 1: three distinct indices below n (n >= 3), no rejection loop
-__device__ __forceinline__ void sample3(uint64_t seed, uint32_t p, uint32_t h, uint32_t n, uint32_t& i0, uint32_t& i1, uint32_t& i2) {
-    const uint64_t G = 0x9E3779B97F4A7C15ull;
-    const uint64_t base = seed + G * (((((uint64_t)p) << 20) + h) * 4 + 1);
-    i0 = (uint32_t)(mix64(base) % n);
-    i1 = (uint32_t)(mix64(base + G) % (n - 1));
-    if (i1 >= i0) ++i1;
-    i2 = (uint32_t)(mix64(base + G * 2) % (n - 2));
-    const uint32_t lo = i0 < i1 ? i0 : i1, hi = i0 < i1 ? i1 : i0;
-    if (i2 >= lo) ++i2;
-    if (i2 >= hi) ++i2;
-}
-
 // rule 2: Horn's closed form on the three sampled matches of hypothesis h
 __device__ __forceinline__ Model solve_hypothesis(const double* __restrict__ p1, const double* __restrict__ p2, uint32_t n, uint64_t seed, uint32_t p,
                                                   uint32_t h, bool fix_scale) {
     uint32_t idx[3];
-    sample3(seed, p, h, n, idx[0], idx[1], idx[2]);
+    sample_distinct<3, 4>(seed, p, h, n, idx);   // rule 1
     double a[3][3], b[3][3];   // [k][axis]
 #pragma unroll
     for (int k = 0; k < 3; ++k)
@@ -194,8 +172,7 @@ __global__ __launch_bounds__(64) void k_sim3_hypotheses(uint8_t* __restrict__ bl
     __shared__ double models[kHypPerWave * kModelDoubles];
     const Layout lay = layout_of(P, T);
     const int p = blockIdx.y;
-    const int32_t* offsets = reinterpret_cast<const int32_t*>(block + lay.offsets);
-    const int off = offsets[p], n = offsets[p + 1] - off;
+    const auto [off, n] = problem_span(block, lay.offsets, p);
     if (n < 3) return;   // rule 4: invalid, k_sim3_finish says so
     const CamRec cam1 = reinterpret_cast<const CamRec*>(block + lay.cams)[2 * p], cam2 = reinterpret_cast<const CamRec*>(block + lay.cams)[2 * p + 1];
     const double* p1 = reinterpret_cast<const double*>(block + lay.p1) + 3 * (size_t)off;
@@ -230,8 +207,7 @@ __global__ __launch_bounds__(64) void k_sim3_hypotheses(uint8_t* __restrict__ bl
             if (lane == m) count += c;
         }
     }
-    const unsigned long long key =
-        lane < nh ? ((unsigned long long)(uint32_t)count << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)(h0 + lane)) : 0ull;   // never 0 for a hypothesis
+    const unsigned long long key = lane < nh ? hypothesis_key(count, (uint32_t)(h0 + lane)) : 0ull;
     unsigned long long best = key;
 #pragma unroll
     for (int d = 32; d; d >>= 1) {
@@ -252,26 +228,13 @@ __global__ __launch_bounds__(kFinishThreads) void k_sim3_finish(const uint8_t* _
                                                                 uint8_t* __restrict__ out_flags) {
     const Layout lay = layout_of(P, T);
     const int p = blockIdx.x;
-    const int32_t* offsets = reinterpret_cast<const int32_t*>(block + lay.offsets);
-    const int off = offsets[p], n = offsets[p + 1] - off;
+    const auto [off, n] = problem_span(block, lay.offsets, p);
     const unsigned long long key = reinterpret_cast<const unsigned long long*>(block + lay.keys)[p];
-    const int count = (int)(key >> 32);
-    const uint32_t h = 0xFFFFFFFFu - (uint32_t)key;
+    const int count = key_count(key);
+    const uint32_t h = key_iter(key);
     const bool valid = n >= 3 && n >= min_inliers && count >= min_inliers;   // rule 4 (n < 3: the key is still zero and never read)
     if (!valid) {
-        for (int i = threadIdx.x; i < n; i += kFinishThreads) out_flags[off + i] = 0;
-        if (threadIdx.x == 0) {
-            ResultRec r;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) r.rot[k] = (k % 4 == 0) ? 1.0 : 0.0;
-            r.trans[0] = r.trans[1] = r.trans[2] = 0.0;
-            r.scale = 1.0;
-            r.valid = 0;
-            r.best_iter = -1;
-            r.num_inliers = 0;
-            r.pad = 0;
-            out[p] = r;
-        }
+        write_invalid(out_flags + off, n, kFinishThreads, out + p);
         return;
     }
     const CamRec cam1 = reinterpret_cast<const CamRec*>(block + lay.cams)[2 * p], cam2 = reinterpret_cast<const CamRec*>(block + lay.cams)[2 * p + 1];
@@ -304,31 +267,9 @@ __global__ __launch_bounds__(kFinishThreads) void k_sim3_finish(const uint8_t* _
 
 }   // namespace
 
-struct ovs_sim3 {
-    int device = 0;
-    int max_problems = 0, max_total_matches = 0;
-    std::mutex mu;
-    hipStream_t stream = nullptr;
-    uint8_t *d_block = nullptr, *h_block = nullptr;   // the staged block (Layout) and its page-locked twin
-    double* d_wave_models = nullptr;                  // [problem][wave] the model of the wave's best hypothesis; grows with problems x max_num_iter
-    size_t wave_models_cap = 0;                       // in records of kModelDoubles
-    // results, page-locked and mapped: k_sim3_finish writes them, the host reads them after the stream has drained
-    ResultRec *h_result = nullptr, *m_result = nullptr;
-    uint8_t *h_flags = nullptr, *m_flags = nullptr;
-};
+struct ovs_sim3 : ransac_handle {};
 
 namespace {
-
-void sim3_free(ovs_sim3* s) {
-    if (!s) return;
-    hipFree(s->d_block);
-    hipFree(s->d_wave_models);
-    if (s->h_block) hipHostFree(s->h_block);
-    if (s->h_result) hipHostFree(s->h_result);
-    if (s->h_flags) hipHostFree(s->h_flags);
-    if (s->stream) hipStreamDestroy(s->stream);
-    delete s;
-}
 
 bool camera_ok(const ovs_camera& c, CamRec* rec) {
     rec->pad = 0;
@@ -351,102 +292,39 @@ bool camera_ok(const ovs_camera& c, CamRec* rec) {
 extern "C" {
 
 ovs_status ovs_sim3_create(int32_t device, int32_t max_problems, int32_t max_total_matches, ovs_sim3** out) {
-    if (!out || max_problems < 1 || max_total_matches < 1) return OVS_ERR_INVALID;
-    *out = nullptr;
-    if (max_problems > 65535) return OVS_ERR_INVALID;   // a grid's y extent
-    if (ovs_device_count() <= device || device < 0) return OVS_ERR_NO_DEVICE;
-    OVS_HIP_TRY(hipSetDevice(device));
-    ovs_sim3* s = new ovs_sim3();
-    s->device = device;
-    s->max_problems = max_problems;
-    s->max_total_matches = max_total_matches;
-    const size_t block_bytes = layout_of(max_problems, max_total_matches).bytes;
-    hipError_t e = hipSuccess;
-#define D_TRY(expr)                                      \
-    if ((e = ovs::fault_filter(expr)) != hipSuccess) {   \
-        ovs::set_last_error(#expr, e);                   \
-        sim3_free(s);                                    \
-        return OVS_ERR_HIP;                              \
-    }
-    D_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    D_TRY(hipMalloc(&s->d_block, block_bytes));
-    s->wave_models_cap = (size_t)max_problems * (256 / kHypPerWave);   // 256 iterations per problem without growing
-    D_TRY(hipMalloc(&s->d_wave_models, sizeof(double) * kModelDoubles * s->wave_models_cap));
-    D_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_block), block_bytes, hipHostMallocDefault));
-    D_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_result), sizeof(ResultRec) * (size_t)max_problems, hipHostMallocMapped));
-    D_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->m_result), s->h_result, 0));
-    D_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_flags), (size_t)max_total_matches, hipHostMallocMapped));
-    D_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->m_flags), s->h_flags, 0));
-#undef D_TRY
-    *out = s;
-    return OVS_OK;
+    return ransac_create(device, max_problems, max_total_matches, layout_of(max_problems, max_total_matches).bytes,
+                         (size_t)max_problems * (256 / kHypPerWave),   // 256 iterations per problem without growing
+                         kModelDoubles, out);
 }
 
-ovs_status ovs_sim3_destroy(ovs_sim3* s) {
-    if (!s) return OVS_ERR_INVALID;
-    hipSetDevice(s->device);
-    sim3_free(s);
-    return OVS_OK;
-}
+ovs_status ovs_sim3_destroy(ovs_sim3* s) { return ransac_destroy(s); }
 
 ovs_status ovs_sim3_solve_batch(ovs_sim3* s, int32_t n_problems, const int32_t* offsets, const double* p1, const double* p2, const float* thr1,
                                 const float* thr2, const ovs_camera* cams_1, const ovs_camera* cams_2, int32_t fix_scale, int32_t min_num_inliers,
                                 int32_t max_num_iter, uint64_t seed, int32_t* out_valid, int32_t* out_best_iter, int32_t* out_num_inliers,
                                 double* out_rot_12, double* out_trans_12, double* out_scale_12, uint8_t* out_inlier_flags) {
-    // every argument error is decided here, before the device is touched
-    if (!s || n_problems < 0 || max_num_iter < 1 || max_num_iter > kMaxIter || min_num_inliers < 0) return OVS_ERR_INVALID;
-    if (n_problems == 0) return OVS_OK;
-    if (!offsets || !cams_1 || !cams_2 || !out_valid || !out_best_iter || !out_num_inliers || !out_rot_12 || !out_trans_12 || !out_scale_12)
-        return OVS_ERR_INVALID;
-    if (offsets[0] != 0) return OVS_ERR_INVALID;
-    for (int32_t p = 0; p < n_problems; ++p)
-        if (offsets[p + 1] < offsets[p]) return OVS_ERR_INVALID;
-    const int32_t T = offsets[n_problems];
-    if (T > 0 && (!p1 || !p2 || !thr1 || !thr2 || !out_inlier_flags)) return OVS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(s->mu);
-    if (n_problems > s->max_problems || T > s->max_total_matches) return OVS_ERR_CAPACITY;   // nothing is truncated
-    const Layout lay = layout_of(n_problems, T);
-    CamRec* cams = reinterpret_cast<CamRec*>(s->h_block + lay.cams);
-    for (int32_t p = 0; p < n_problems; ++p)
-        if (!camera_ok(cams_1[p], &cams[2 * p]) || !camera_ok(cams_2[p], &cams[2 * p + 1])) return OVS_ERR_INVALID;
-    std::memset(s->h_block + lay.keys, 0, 8 * (size_t)n_problems);
-    if (T > 0) {
-        std::memcpy(s->h_block + lay.p1, p1, 24 * (size_t)T);
-        std::memcpy(s->h_block + lay.p2, p2, 24 * (size_t)T);
-        std::memcpy(s->h_block + lay.thr1, thr1, 4 * (size_t)T);
-        std::memcpy(s->h_block + lay.thr2, thr2, 4 * (size_t)T);
-    }
-    std::memcpy(s->h_block + lay.offsets, offsets, 4 * ((size_t)n_problems + 1));
-    OVS_HIP_TRY(hipSetDevice(s->device));
-    hipStream_t st = s->stream;
-    const int blocks = (max_num_iter + kHypPerWave - 1) / kHypPerWave;
-    const size_t records = (size_t)n_problems * (size_t)blocks;
-    if (records > s->wave_models_cap) {   // the stream is idle: every call ends in a synchronise
-        OVS_HIP_TRY(hipFree(s->d_wave_models));
-        s->d_wave_models = nullptr;
-        s->wave_models_cap = 0;
-        OVS_HIP_TRY(hipMalloc(&s->d_wave_models, sizeof(double) * kModelDoubles * records));
-        s->wave_models_cap = records;
-    }
-    OVS_HIP_TRY(hipMemcpyAsync(s->d_block, s->h_block, lay.bytes, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_sim3_hypotheses, dim3(blocks, n_problems), dim3(64), 0, st, s->d_block, n_problems, T, fix_scale ? 1 : 0, max_num_iter, seed,
-                       s->d_wave_models);
-    OVS_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_sim3_finish, dim3(n_problems), dim3(kFinishThreads), 0, st, s->d_block, n_problems, T, min_num_inliers, blocks,
-                       s->d_wave_models, s->m_result, s->m_flags);
-    OVS_HIP_TRY(hipGetLastError());
-    OVS_HIP_TRY(hipStreamSynchronize(st));
-    for (int32_t p = 0; p < n_problems; ++p) {
-        const ResultRec& r = s->h_result[p];
-        out_valid[p] = r.valid;
-        out_best_iter[p] = r.best_iter;
-        out_num_inliers[p] = r.num_inliers;
-        std::memcpy(out_rot_12 + 9 * (size_t)p, r.rot, sizeof(r.rot));
-        std::memcpy(out_trans_12 + 3 * (size_t)p, r.trans, sizeof(r.trans));
-        out_scale_12[p] = r.scale;
-    }
-    if (T > 0) std::memcpy(out_inlier_flags, s->h_flags, (size_t)T);
-    return OVS_OK;
+    const auto stage = [&](uint8_t* h_block, const Layout& lay, int32_t T) {
+        CamRec* cams = reinterpret_cast<CamRec*>(h_block + lay.cams);
+        for (int32_t p = 0; p < n_problems; ++p)
+            if (!camera_ok(cams_1[p], &cams[2 * p]) || !camera_ok(cams_2[p], &cams[2 * p + 1])) return OVS_ERR_INVALID;
+        if (T > 0) {
+            std::memcpy(h_block + lay.p1, p1, 24 * (size_t)T);
+            std::memcpy(h_block + lay.p2, p2, 24 * (size_t)T);
+            std::memcpy(h_block + lay.thr1, thr1, 4 * (size_t)T);
+            std::memcpy(h_block + lay.thr2, thr2, 4 * (size_t)T);
+        }
+        return OVS_OK;
+    };
+    const auto hypotheses = [&](hipStream_t st, int blocks, int32_t T) {
+        hipLaunchKernelGGL(k_sim3_hypotheses, dim3(blocks, n_problems), dim3(64), 0, st, s->d_block, n_problems, T, fix_scale ? 1 : 0, max_num_iter, seed,
+                           s->d_wave_models);
+    };
+    const auto finish = [&](hipStream_t st, int blocks, int32_t T) {
+        hipLaunchKernelGGL(k_sim3_finish, dim3(n_problems), dim3(kFinishThreads), 0, st, s->d_block, n_problems, T, min_num_inliers, blocks,
+                           s->d_wave_models, s->m_result, s->m_flags);
+    };
+    return run_batch(s, n_problems, offsets, {cams_1, cams_2, out_scale_12}, {p1, p2, thr1, thr2}, min_num_inliers, max_num_iter, kHypPerWave, layout_of,
+                     {out_valid, out_best_iter, out_num_inliers, out_rot_12, out_trans_12, out_scale_12, out_inlier_flags}, stage, hypotheses, finish);
 }
 
 }   // extern "C"

@@ -1,19 +1,102 @@
-// solve_internal.inc -- what the RANSAC solvers of solve/ share on the device (sim3_solve.hip, pnp_solve.hip): the counter-based sampler's
-// mixer, the cyclic Jacobi rotation and Horn's quaternion form of the absolute orientation. DESIGN.md 3.9 rule 2 fixes every operation;
-// the units are built with -ffp-contract=off. (An .inc, not an .h: bench.py fingerprints every .h of this directory into the committed
-// counters of the extractor and matcher stages, which include none of this.)
+// solve_internal.inc -- what the RANSAC solvers of solve/ share (sim3_solve.hip, pnp_solve.hip). On the device: the counter-based sampler,
+// the hypothesis key, the result record and its invalid form, the cyclic Jacobi rotation and Horn's quaternion form of the absolute
+// orientation. DESIGN.md 3.9 rule 2 fixes every operation; the units are built with -ffp-contract=off. On the host: ransac_handle, the
+// batch scaffold under both C ABIs (create, reserve_models, run_batch). A solver supplies its model, its two kernels, the Layout of its
+// staged block, and to run_batch what stages its arrays and what launches its kernels. (An .inc, not an .h: bench.py fingerprints every
+// .h of this directory into the committed counters of the extractor and matcher stages, which include none of this.)
 #pragma once
 #include <cmath>
 #include <cstdint>
+#include <cstring>
+#include <initializer_list>
+#include <mutex>
 
 #include <hip/hip_runtime.h>
 
+#include "ovs_common.h"
+
 namespace {
+
+constexpr int kMaxIter = 1 << 20;   // h takes 20 bits of the sampler's counter
 
 __device__ __forceinline__ uint64_t mix64(uint64_t z) {   // the splitmix64 finaliser
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
+}
+
+// rule 1: K distinct indices below n (n >= K), no rejection loop. Draw k is below n - k and steps over the earlier indices in ascending
+// order; `sorted` holds them by compare-exchange on compile-time indices (no local array is indexed dynamically: no scratch). STRIDE is the
+// solver's share of the counter per hypothesis (4 for Sim3, 8 for EPnP: solve.problem_seed, solve.pnp_problem_seed).
+template <int K, int STRIDE>
+__device__ __forceinline__ void sample_distinct(uint64_t seed, uint32_t p, uint32_t h, uint32_t n, uint32_t (&idx)[K]) {
+    const uint64_t G = 0x9E3779B97F4A7C15ull;
+    const uint64_t base = seed + G * (((((uint64_t)p) << 20) + h) * STRIDE + 1);
+    uint32_t sorted[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        uint32_t v = (uint32_t)(mix64(base + G * k) % (n - k));
+#pragma unroll
+        for (int j = 0; j < k; ++j)
+            if (v >= sorted[j]) ++v;
+        idx[k] = v;
+#pragma unroll
+        for (int j = 0; j < k; ++j) {
+            const uint32_t lo = min(sorted[j], v);
+            v = max(sorted[j], v);
+            sorted[j] = lo;
+        }
+        sorted[k] = v;
+    }
+}
+
+// a hypothesis's key: the largest count wins an integer atomicMax, the lowest h on a tie; never 0 for a hypothesis
+__device__ __forceinline__ unsigned long long hypothesis_key(int count, uint32_t h) {
+    return ((unsigned long long)(uint32_t)count << 32) | (unsigned long long)(0xFFFFFFFFu - h);
+}
+__device__ __forceinline__ int key_count(unsigned long long key) { return (int)(key >> 32); }
+__device__ __forceinline__ uint32_t key_iter(unsigned long long key) { return 0xFFFFFFFFu - (uint32_t)key; }
+
+// problem p's first match and number of matches, from the offsets section i32 [P + 1] of the staged block
+struct Span {
+    int off, n;
+};
+__device__ __forceinline__ Span problem_span(const uint8_t* __restrict__ block, size_t offsets_at, int p) {
+    const int32_t* offsets = reinterpret_cast<const int32_t*>(block + offsets_at);
+    const int off = offsets[p];
+    return {off, offsets[p + 1] - off};
+}
+
+// per problem in the result block; a solver without a scale leaves it at 1.0
+struct ResultRec {
+    double rot[9], trans[3], scale;
+    int32_t valid, best_iter, num_inliers, pad;
+};
+static_assert(sizeof(ResultRec) == 120, "ResultRec is read by the host");
+
+// rule 4's invalid output, by the finish kernel's whole workgroup of `threads`: the problem's flags zeroed, the record by thread 0
+__device__ __forceinline__ void write_invalid(uint8_t* __restrict__ flags, int n, int threads, ResultRec* __restrict__ out) {
+    for (int i = threadIdx.x; i < n; i += threads) flags[i] = 0;
+    if (threadIdx.x == 0) {
+        ResultRec r;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) r.rot[k] = (k % 4 == 0) ? 1.0 : 0.0;
+        r.trans[0] = r.trans[1] = r.trans[2] = 0.0;
+        r.scale = 1.0;
+        r.valid = 0;
+        r.best_iter = -1;
+        r.num_inliers = 0;
+        r.pad = 0;
+        *out = r;
+    }
+}
+
+// the rotation (c, s) that zeroes the off-diagonal entry apq != 0 of a symmetric matrix with the diagonal entries app, aqq
+__device__ __forceinline__ void jacobi_angle(double app, double aqq, double apq, double& c, double& s) {
+    const double theta = (aqq - app) / (2.0 * apq);
+    const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+    c = 1.0 / sqrt(t * t + 1.0);
+    s = t * c;
 }
 
 // one Jacobi rotation on the pair (P, Q) of an N x N symmetric matrix held in registers, the operations of
@@ -22,9 +105,8 @@ template <int N, int P, int Q>
 __device__ __forceinline__ void jacobi_rotate(double (&A)[N][N], double (&V)[N][N]) {
     const double apq = A[P][Q];
     if (apq == 0.0) return;
-    const double theta = (A[Q][Q] - A[P][P]) / (2.0 * apq);
-    const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+    double c, s;
+    jacobi_angle(A[P][P], A[Q][Q], apq, c, s);
 #pragma unroll
     for (int k = 0; k < N; ++k) {
         const double akp = A[k][P], akq = A[k][Q];
@@ -99,6 +181,147 @@ __device__ __forceinline__ void horn_rotation(const double (&M)[3][3], double (&
     R[6] = 2.0 * (x * z - w * y);
     R[7] = 2.0 * (y * z + w * x);
     R[8] = 1.0 - 2.0 * (x * x + y * y);
+}
+
+// ---- the host side: one handle and one batch call under ovs_sim3_* and ovs_pnp_*
+struct ransac_handle {
+    int device = 0;
+    int max_problems = 0, max_total_matches = 0;
+    std::mutex mu;
+    hipStream_t stream = nullptr;
+    uint8_t *d_block = nullptr, *h_block = nullptr;   // the staged block (the solver's Layout) and its page-locked twin
+    double* d_wave_models = nullptr;                  // [problem][wave] the model of the wave's best hypothesis; grows with problems x max_num_iter
+    size_t wave_models_cap = 0;                       // in records of model_doubles
+    int model_doubles = 0;
+    // results, page-locked and mapped: the finish kernel writes them, the host reads them after the stream has drained
+    ResultRec *h_result = nullptr, *m_result = nullptr;
+    uint8_t *h_flags = nullptr, *m_flags = nullptr;
+
+    ransac_handle() = default;
+    ransac_handle(const ransac_handle&) = delete;
+    ~ransac_handle() {
+        hipFree(d_block);
+        hipFree(d_wave_models);
+        if (h_block) hipHostFree(h_block);
+        if (h_result) hipHostFree(h_result);
+        if (h_flags) hipHostFree(h_flags);
+        if (stream) hipStreamDestroy(stream);
+    }
+
+    // room for `records` models; the stream is idle: every call ends in a synchronise
+    ovs_status reserve_models(size_t records) {
+        if (records <= wave_models_cap) return OVS_OK;
+        if (d_wave_models) OVS_HIP_TRY(hipFree(d_wave_models));
+        d_wave_models = nullptr;
+        wave_models_cap = 0;
+        OVS_HIP_TRY(hipMalloc(&d_wave_models, sizeof(double) * model_doubles * records));
+        wave_models_cap = records;
+        return OVS_OK;
+    }
+};
+
+// H: ovs_sim3 or ovs_pnp. block_bytes: the solver's Layout at full capacity; initial_records: the models that fit without growing
+template <class H>
+ovs_status ransac_create(int32_t device, int32_t max_problems, int32_t max_total_matches, size_t block_bytes, size_t initial_records,
+                         int model_doubles, H** out) {
+    if (!out || max_problems < 1 || max_total_matches < 1) return OVS_ERR_INVALID;
+    *out = nullptr;
+    if (max_problems > 65535) return OVS_ERR_INVALID;   // a grid's y extent
+    if (ovs_device_count() <= device || device < 0) return OVS_ERR_NO_DEVICE;
+    OVS_HIP_TRY(hipSetDevice(device));
+    H* s = new H();
+    s->device = device;
+    s->max_problems = max_problems;
+    s->max_total_matches = max_total_matches;
+    s->model_doubles = model_doubles;
+    hipError_t e = hipSuccess;
+#define D_TRY(expr)                                      \
+    if ((e = ovs::fault_filter(expr)) != hipSuccess) {   \
+        ovs::set_last_error(#expr, e);                   \
+        delete s;                                        \
+        return OVS_ERR_HIP;                              \
+    }
+    D_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+    D_TRY(hipMalloc(&s->d_block, block_bytes));
+    if (s->reserve_models(initial_records) != OVS_OK) {
+        delete s;
+        return OVS_ERR_HIP;
+    }
+    D_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_block), block_bytes, hipHostMallocDefault));
+    D_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_result), sizeof(ResultRec) * (size_t)max_problems, hipHostMallocMapped));
+    D_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->m_result), s->h_result, 0));
+    D_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_flags), (size_t)max_total_matches, hipHostMallocMapped));
+    D_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->m_flags), s->h_flags, 0));
+#undef D_TRY
+    *out = s;
+    return OVS_OK;
+}
+
+template <class H>
+ovs_status ransac_destroy(H* s) {
+    if (!s) return OVS_ERR_INVALID;
+    hipSetDevice(s->device);
+    delete s;
+    return OVS_OK;
+}
+
+// where a call's results go: the caller's arrays of the C ABI (scale: nullptr for a solver that has none)
+struct BatchOut {
+    int32_t *valid, *best_iter, *num_inliers;
+    double *rot, *trans, *scale;
+    uint8_t* flags;
+};
+
+inline bool all_set(std::initializer_list<const void*> pointers) {
+    for (const void* q : pointers)
+        if (!q) return false;
+    return true;
+}
+
+// One solve_batch call. `required`: the solver's own pointers that every call needs; `per_match`: its match arrays, needed once there is a
+// match. stage(h_block, layout, T) copies the solver's arrays into the page-locked block and may refuse them (OVS_ERR_INVALID);
+// hypotheses(stream, waves_per_problem, T) and finish(stream, waves_per_problem, T) launch the solver's two kernels. The order of decisions is the
+// ABI's: argument errors before the lock, OVS_ERR_CAPACITY before anything is staged, and no output is touched on any error.
+template <class Layout, class Stage, class Hypotheses, class Finish>
+ovs_status run_batch(ransac_handle* s, int32_t n_problems, const int32_t* offsets, std::initializer_list<const void*> required,
+                     std::initializer_list<const void*> per_match, int32_t min_num_inliers, int32_t max_num_iter, int hyp_per_wave,
+                     Layout (*layout_of)(int, int), const BatchOut& o, Stage stage, Hypotheses hypotheses, Finish finish) {
+    // every argument error is decided here, before the device is touched
+    if (!s || n_problems < 0 || max_num_iter < 1 || max_num_iter > kMaxIter || min_num_inliers < 0) return OVS_ERR_INVALID;
+    if (n_problems == 0) return OVS_OK;
+    if (!offsets || !o.valid || !o.best_iter || !o.num_inliers || !o.rot || !o.trans || !all_set(required)) return OVS_ERR_INVALID;
+    if (offsets[0] != 0) return OVS_ERR_INVALID;
+    for (int32_t p = 0; p < n_problems; ++p)
+        if (offsets[p + 1] < offsets[p]) return OVS_ERR_INVALID;
+    const int32_t T = offsets[n_problems];
+    if (T > 0 && (!o.flags || !all_set(per_match))) return OVS_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (n_problems > s->max_problems || T > s->max_total_matches) return OVS_ERR_CAPACITY;   // nothing is truncated
+    const Layout lay = layout_of(n_problems, T);
+    const ovs_status staged = stage(s->h_block, lay, T);
+    if (staged != OVS_OK) return staged;
+    std::memset(s->h_block + lay.keys, 0, 8 * (size_t)n_problems);
+    std::memcpy(s->h_block + lay.offsets, offsets, 4 * ((size_t)n_problems + 1));
+    OVS_HIP_TRY(hipSetDevice(s->device));
+    const int waves = (max_num_iter + hyp_per_wave - 1) / hyp_per_wave;
+    if (s->reserve_models((size_t)n_problems * (size_t)waves) != OVS_OK) return OVS_ERR_HIP;
+    OVS_HIP_TRY(hipMemcpyAsync(s->d_block, s->h_block, lay.bytes, hipMemcpyHostToDevice, s->stream));
+    hypotheses(s->stream, waves, T);
+    OVS_HIP_TRY(hipGetLastError());
+    finish(s->stream, waves, T);
+    OVS_HIP_TRY(hipGetLastError());
+    OVS_HIP_TRY(hipStreamSynchronize(s->stream));
+    for (int32_t p = 0; p < n_problems; ++p) {
+        const ResultRec& r = s->h_result[p];
+        o.valid[p] = r.valid;
+        o.best_iter[p] = r.best_iter;
+        o.num_inliers[p] = r.num_inliers;
+        std::memcpy(o.rot + 9 * (size_t)p, r.rot, sizeof(r.rot));
+        std::memcpy(o.trans + 3 * (size_t)p, r.trans, sizeof(r.trans));
+        if (o.scale) o.scale[p] = r.scale;
+    }
+    if (T > 0) std::memcpy(o.flags, s->h_flags, (size_t)T);
+    return OVS_OK;
 }
 
 }   // namespace

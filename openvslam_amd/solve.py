@@ -54,61 +54,80 @@ def problem_from_keyframes(pose_cw_1, pose_cw_2, pos_w_1, pos_w_2, octaves_1, oc
                 thr2=(9.21 * s2.astype(np.float64)).astype(np.float32), cam_1=cam_1, cam_2=cam_2)
 
 
-class _handle:
-    """ovs_sim3 with its capacity."""
+class _ransac_handle:
+    """A solver's device handle (ovs_sim3 or ovs_pnp: `_abi` is the prefix of its create / destroy / solve_batch) with its capacity."""
+    _abi = None
 
     def __init__(self, max_problems, max_total_matches, device=0):
         self._L = _lib.lib()
         _lib.require_device()
         self.max_problems, self.max_total_matches = int(max_problems), int(max_total_matches)
         h = C.c_void_p()
-        _lib.check(self._L.ovs_sim3_create(device, self.max_problems, self.max_total_matches, C.byref(h)), "ovs_sim3_create")
+        _lib.check(getattr(self._L, self._abi + "_create")(device, self.max_problems, self.max_total_matches, C.byref(h)), self._abi + "_create")
         self._h = h
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
         if h:
-            self._L.ovs_sim3_destroy(h)
+            getattr(self._L, self._abi + "_destroy")(h)
+
+
+class _handle(_ransac_handle):
+    """ovs_sim3 with its capacity."""
+    _abi = "ovs_sim3"
+
+
+class _pnp_handle(_ransac_handle):
+    """ovs_pnp with its capacity."""
+    _abi = "ovs_pnp"
+
+
+def _solve_batch(handle_type, problems, arrays, count_key, error, middle, suffix, with_scale, handle, device):
+    """One solve_batch call of handle_type's ABI over `problems`. arrays: (key, dtype, width) of the per-match arrays in the ABI's order,
+    count_key the one whose length is a problem's number of matches, error the ValueError's text when another disagrees; middle: the ABI's
+    arguments between the arrays and the outputs; the returned dicts name the pose rot_<suffix>, trans_<suffix> (and scale_<suffix>)."""
+    P = len(problems)
+    if P == 0:
+        return []
+    offsets = np.zeros(P + 1, np.int32)
+    offsets[1:] = np.cumsum([len(np.asarray(q[count_key])) for q in problems])
+    T = int(offsets[-1])
+    cat = lambda key, dt, w: np.ascontiguousarray(np.concatenate([np.asarray(q[key], dt).reshape(-1, w) for q in problems]) if T else np.zeros((0, w), dt))
+    packed = [cat(*a) for a in arrays]
+    if any(len(a) != T for a in packed):
+        raise ValueError(error)
+    if handle is None:
+        handle = handle_type(P, max(T, 1), device)
+    valid, best_iter, num = np.zeros(P, np.int32), np.zeros(P, np.int32), np.zeros(P, np.int32)
+    rot, trans, flags = np.zeros((P, 3, 3)), np.zeros((P, 3)), np.zeros(max(T, 1), np.uint8)
+    scale = [np.zeros(P)] if with_scale else []
+    name = handle_type._abi + "_solve_batch"
+    _lib.check(getattr(handle._L, name)(handle._h, P, _p(offsets), *map(_p, packed), *middle, _p(valid), _p(best_iter), _p(num), _p(rot), _p(trans), *map(_p, scale),
+                                        _p(flags)), name)
+    rot_key, trans_key, scale_key = "rot_" + suffix, "trans_" + suffix, "scale_" + suffix
+    out = []
+    for i in range(P):
+        r = {"valid": bool(valid[i]), "best_iter": int(best_iter[i]), "num_inliers": int(num[i]), rot_key: rot[i].copy(), trans_key: trans[i].copy()}
+        if with_scale:
+            r[scale_key] = float(scale[0][i])
+        r["inlier_flags"] = flags[offsets[i]:offsets[i + 1]].astype(bool)
+        out.append(r)
+    return out
 
 
 def solve_sim3_batch(problems, fix_scale, min_num_inliers=20, max_num_iter=200, seed=DEFAULT_SEED, handle=None, device=0):
     """find_via_ransac for every problem (dicts as problem_from_keyframes returns them) in one call: a list of dicts valid, best_iter,
     num_inliers, rot_12 (3 x 3), trans_12 (3), scale_12, inlier_flags (n, bool). `handle`: a _handle to reuse (the loop detector keeps one)."""
-    P = len(problems)
-    if P == 0:
-        return []
-    counts = [len(np.asarray(q["thr1"])) for q in problems]
-    offsets = np.zeros(P + 1, np.int32)
-    offsets[1:] = np.cumsum(counts)
-    T = int(offsets[-1])
-    cat = lambda key, dt, w: np.ascontiguousarray(np.concatenate([np.asarray(q[key], dt).reshape(-1, w) for q in problems]) if T else np.zeros((0, w), dt))
-    p1, p2, thr1, thr2 = cat("p1", np.float64, 3), cat("p2", np.float64, 3), cat("thr1", np.float32, 1), cat("thr2", np.float32, 1)
-    if len(p1) != T or len(p2) != T or len(thr2) != T:
-        raise ValueError("p1, p2, thr1 and thr2 of a problem must have one entry per match")
-    cams_1 = (_lib.Camera * P)(*[q["cam_1"] for q in problems])
-    cams_2 = (_lib.Camera * P)(*[q["cam_2"] for q in problems])
-    if handle is None:
-        handle = _handle(P, max(T, 1), device)
-    valid, best_iter, num = np.zeros(P, np.int32), np.zeros(P, np.int32), np.zeros(P, np.int32)
-    rot, trans, scale, flags = np.zeros((P, 3, 3)), np.zeros((P, 3)), np.zeros(P), np.zeros(max(T, 1), np.uint8)
-    _lib.check(handle._L.ovs_sim3_solve_batch(handle._h, P, _p(offsets), _p(p1), _p(p2), _p(thr1), _p(thr2), cams_1, cams_2, 1 if fix_scale else 0,
-                                              int(min_num_inliers), int(max_num_iter), int(seed) & _MASK, _p(valid), _p(best_iter), _p(num), _p(rot),
-                                              _p(trans), _p(scale), _p(flags)), "ovs_sim3_solve_batch")
-    return [dict(valid=bool(valid[i]), best_iter=int(best_iter[i]), num_inliers=int(num[i]), rot_12=rot[i].copy(), trans_12=trans[i].copy(),
-                 scale_12=float(scale[i]), inlier_flags=flags[offsets[i]:offsets[i + 1]].astype(bool)) for i in range(P)]
+    cams_1 = (_lib.Camera * len(problems))(*[q["cam_1"] for q in problems])
+    cams_2 = (_lib.Camera * len(problems))(*[q["cam_2"] for q in problems])
+    return _solve_batch(_handle, problems, [("p1", np.float64, 3), ("p2", np.float64, 3), ("thr1", np.float32, 1), ("thr2", np.float32, 1)], "thr1",
+                        "p1, p2, thr1 and thr2 of a problem must have one entry per match",
+                        [cams_1, cams_2, 1 if fix_scale else 0, int(min_num_inliers), int(max_num_iter), int(seed) & _MASK], "12", True, handle, device)
 
 
-class sim3_solver:
-    """solve::sim3_solver over one problem: the constructor takes what upstream's collects from the two keyframes (see
-    problem_from_keyframes), find_via_ransac runs the device RANSAC, the getters are upstream's."""
-
-    def __init__(self, p1, p2, thr1, thr2, cam_1, cam_2, fix_scale, min_num_inliers=20, device=0):
-        self._problem = dict(p1=p1, p2=p2, thr1=thr1, thr2=thr2, cam_1=cam_1, cam_2=cam_2)
-        self._fix_scale, self._min_num_inliers, self._device = bool(fix_scale), int(min_num_inliers), device
-        self._result = None
-
-    def find_via_ransac(self, max_num_iter, seed=DEFAULT_SEED):
-        self._result = solve_sim3_batch([self._problem], self._fix_scale, self._min_num_inliers, max_num_iter, seed, device=self._device)[0]
+class _ransac_solver:
+    """What the two solver classes share: the result of find_via_ransac and upstream's getters that both have."""
+    _result = None
 
     def _get(self, key):
         if self._result is None:
@@ -118,15 +137,6 @@ class sim3_solver:
     def solution_is_valid(self):
         return self._result is not None and self._result["valid"]
 
-    def get_best_rotation_12(self):
-        return self._get("rot_12")
-
-    def get_best_translation_12(self):
-        return self._get("trans_12")
-
-    def get_best_scale_12(self):
-        return self._get("scale_12")
-
     def get_inlier_flags(self):
         return self._get("inlier_flags")
 
@@ -135,6 +145,27 @@ class sim3_solver:
 
     def get_num_inliers(self):
         return self._get("num_inliers")
+
+
+class sim3_solver(_ransac_solver):
+    """solve::sim3_solver over one problem: the constructor takes what upstream's collects from the two keyframes (see
+    problem_from_keyframes), find_via_ransac runs the device RANSAC, the getters are upstream's."""
+
+    def __init__(self, p1, p2, thr1, thr2, cam_1, cam_2, fix_scale, min_num_inliers=20, device=0):
+        self._problem = dict(p1=p1, p2=p2, thr1=thr1, thr2=thr2, cam_1=cam_1, cam_2=cam_2)
+        self._fix_scale, self._min_num_inliers, self._device = bool(fix_scale), int(min_num_inliers), device
+
+    def find_via_ransac(self, max_num_iter, seed=DEFAULT_SEED):
+        self._result = solve_sim3_batch([self._problem], self._fix_scale, self._min_num_inliers, max_num_iter, seed, device=self._device)[0]
+
+    def get_best_rotation_12(self):
+        return self._get("rot_12")
+
+    def get_best_translation_12(self):
+        return self._get("trans_12")
+
+    def get_best_scale_12(self):
+        return self._get("scale_12")
 
 
 # ---- solve::pnp_solver
@@ -156,67 +187,24 @@ def pnp_problem(bearings, octaves, pos_w, scale_factors):
                 max_cos_error=np.array([math.cos(float(sf[int(o)]) * deg) for o in np.asarray(octaves).ravel()], np.float64))
 
 
-class _pnp_handle:
-    """ovs_pnp with its capacity."""
-
-    def __init__(self, max_problems, max_total_matches, device=0):
-        self._L = _lib.lib()
-        _lib.require_device()
-        self.max_problems, self.max_total_matches = int(max_problems), int(max_total_matches)
-        h = C.c_void_p()
-        _lib.check(self._L.ovs_pnp_create(device, self.max_problems, self.max_total_matches, C.byref(h)), "ovs_pnp_create")
-        self._h = h
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            self._L.ovs_pnp_destroy(h)
-
-
 def solve_pnp_batch(problems, min_num_inliers=10, max_num_iter=30, recompute=True, seed=PNP_DEFAULT_SEED, handle=None, device=0):
     """find_via_ransac for every problem (dicts as pnp_problem returns them) in one call: a list of dicts valid, best_iter, num_inliers,
     rot_cw (3 x 3), trans_cw (3), inlier_flags (n, bool). `handle`: a _pnp_handle to reuse (the relocaliser keeps one)."""
-    P = len(problems)
-    if P == 0:
-        return []
-    counts = [len(np.asarray(q["max_cos_error"])) for q in problems]
-    offsets = np.zeros(P + 1, np.int32)
-    offsets[1:] = np.cumsum(counts)
-    T = int(offsets[-1])
-    cat = lambda key, w: np.ascontiguousarray(np.concatenate([np.asarray(q[key], np.float64).reshape(-1, w) for q in problems]) if T else np.zeros((0, w)))
-    bearings, pos_w, max_cos = cat("bearings", 3), cat("pos_w", 3), cat("max_cos_error", 1)
-    if len(bearings) != T or len(pos_w) != T:
-        raise ValueError("bearings, pos_w and max_cos_error of a problem must have one entry per match")
-    if handle is None:
-        handle = _pnp_handle(P, max(T, 1), device)
-    valid, best_iter, num = np.zeros(P, np.int32), np.zeros(P, np.int32), np.zeros(P, np.int32)
-    rot, trans, flags = np.zeros((P, 3, 3)), np.zeros((P, 3)), np.zeros(max(T, 1), np.uint8)
-    _lib.check(handle._L.ovs_pnp_solve_batch(handle._h, P, _p(offsets), _p(bearings), _p(pos_w), _p(max_cos), int(min_num_inliers), int(max_num_iter),
-                                             1 if recompute else 0, int(seed) & _MASK, _p(valid), _p(best_iter), _p(num), _p(rot), _p(trans), _p(flags)),
-               "ovs_pnp_solve_batch")
-    return [dict(valid=bool(valid[i]), best_iter=int(best_iter[i]), num_inliers=int(num[i]), rot_cw=rot[i].copy(), trans_cw=trans[i].copy(),
-                 inlier_flags=flags[offsets[i]:offsets[i + 1]].astype(bool)) for i in range(P)]
+    return _solve_batch(_pnp_handle, problems, [("bearings", np.float64, 3), ("pos_w", np.float64, 3), ("max_cos_error", np.float64, 1)], "max_cos_error",
+                        "bearings, pos_w and max_cos_error of a problem must have one entry per match",
+                        [int(min_num_inliers), int(max_num_iter), 1 if recompute else 0, int(seed) & _MASK], "cw", False, handle, device)
 
 
-class pnp_solver:
+class pnp_solver(_ransac_solver):
     """solve::pnp_solver over one problem: the constructor takes what upstream's does (the valid bearings, their keypoints' octaves, the
     landmarks and the scale factors), find_via_ransac runs the device RANSAC, the getters are upstream's."""
 
     def __init__(self, valid_bearings, valid_octaves, valid_landmarks, scale_factors, min_num_inliers=10, device=0):
         self._problem = pnp_problem(valid_bearings, valid_octaves, valid_landmarks, scale_factors)
         self._min_num_inliers, self._device = int(min_num_inliers), device
-        self._result = None
 
     def find_via_ransac(self, max_num_iter, recompute=True, seed=PNP_DEFAULT_SEED):
         self._result = solve_pnp_batch([self._problem], self._min_num_inliers, max_num_iter, recompute, seed, device=self._device)[0]
-
-    def _get(self, key):
-        if self._result is None:
-            raise RuntimeError("find_via_ransac has not run")
-        return self._result[key]
-
-    def solution_is_valid(self):
-        return self._result is not None and self._result["valid"]
 
     def get_best_rotation(self):
         return self._get("rot_cw")
@@ -228,12 +216,3 @@ class pnp_solver:
         T = np.eye(4)
         T[:3, :3], T[:3, 3] = self._get("rot_cw"), self._get("trans_cw")
         return T
-
-    def get_inlier_flags(self):
-        return self._get("inlier_flags")
-
-    def get_best_iter(self):
-        return self._get("best_iter")
-
-    def get_num_inliers(self):
-        return self._get("num_inliers")

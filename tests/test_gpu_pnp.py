@@ -10,8 +10,8 @@ import pytest
 
 import pnp_ref
 import pnp_scene_io
-from test_pnp_ref import (BATCH, BATCH_MIN_INLIERS, CASE_ITERS, CASES, EDGE_ITERS, ITERS, SEED, SHIM_CASES, edge_seed, expected, problem,
-                          scale_factors, second_seed)
+from test_pnp_ref import (BATCH, BATCH_MIN_INLIERS, CASE_ITERS, CASES, EDGE_ITERS, GROW_ITERS, ITERS, SEED, SHIM_CASES, edge_seed, expected,
+                          problem, scale_factors, second_seed)
 
 pytestmark = pytest.mark.gpu
 
@@ -119,6 +119,15 @@ def test_same_seed_same_bytes_other_seed_other_winner(solve):
     assert a == b
     c = of_device(run(solve, "n65", seed=second_seed(), handle=h))
     assert c == of_reference(expected("n65", seed=second_seed())) and c["best_iter"] != a["best_iter"]
+
+
+# ---- the models' buffer grows on a live handle
+def test_models_grow_on_a_live_handle(solve):
+    """A handle for one problem holds 64 models, one per hypothesis: GROW_ITERS needs 65. The calls before and after it are unchanged."""
+    h = solve._pnp_handle(1, 70)
+    got = [of_device(run(solve, "n65_noisy", k, handle=h)) for k in (ITERS, GROW_ITERS, ITERS)]
+    assert got == [of_reference(expected("n65_noisy", k)) for k in (ITERS, GROW_ITERS, ITERS)]
+    assert got[0] == got[2] and got[1]["valid"] == 1
 
 
 # ---- capacity and argument errors leave the handle usable

@@ -10,8 +10,8 @@ import pytest
 
 import sim3_ref
 import sim3_scene_io
-from test_sim3_ref import (BATCH, BATCH_MIN_INLIERS, CASE_ITERS, CASES, EDGE_ITERS, ITERS, SEED, SEED_2, edge_seed, expected, keyframe_pair,
-                           level_sigma_sq, problem)
+from test_sim3_ref import (BATCH, BATCH_MIN_INLIERS, CASE_ITERS, CASES, EDGE_ITERS, GROW_ITERS, ITERS, SEED, SEED_2, edge_seed, expected,
+                           keyframe_pair, level_sigma_sq, problem)
 
 pytestmark = pytest.mark.gpu
 
@@ -99,6 +99,15 @@ def test_same_seed_same_bytes_other_seed_other_winner(solve):
     assert a == b
     c = of_device(run(solve, "n65", seed=SEED_2, handle=h))
     assert c == of_reference(expected("n65", seed=SEED_2)) and c["best_iter"] != a["best_iter"]
+
+
+# ---- the models' buffer grows on a live handle
+def test_models_grow_on_a_live_handle(solve):
+    """A handle for one problem holds 64 records of four hypotheses: GROW_ITERS needs 65. The calls before and after it are unchanged."""
+    h = solve._handle(1, 70)
+    got = [of_device(run(solve, "n65_noisy", k, handle=h)) for k in (ITERS, GROW_ITERS, ITERS)]
+    assert got == [of_reference(expected("n65_noisy", k)) for k in (ITERS, GROW_ITERS, ITERS)]
+    assert got[0] == got[2] and got[1]["valid"] == 1
 
 
 # ---- capacity and argument errors leave the handle usable

@@ -91,6 +91,7 @@ CASES = {
 CASE_ITERS = {"n65_noisy": 200}
 EDGE_ITERS = (1, 2, 30, 200)   # a workgroup takes ONE hypothesis: 1 is "at", 2 "one above"; "one below" is 0, which the ABI refuses (error contract)
 EDGE_H, EDGE_COUNT = 482, 43
+GROW_ITERS = 65   # one hypothesis past the 64 a handle for one problem is created with: "n65_noisy" under SEED on a live handle
 
 
 def edge_seed(max_num_iter):
@@ -147,7 +148,7 @@ def every_use(name):
     if name == "n65":
         uses.append((None, second_seed(), 0, None))
     if name == "n65_noisy":
-        uses += [(k, edge_seed(k), 0, None) for k in EDGE_ITERS]
+        uses += [(k, edge_seed(k), 0, None) for k in EDGE_ITERS] + [(k, SEED, 0, None) for k in (ITERS, GROW_ITERS)]
     if name in SHIM_CASES:
         uses.append((None, SEED, SHIM_CASES.index(name), None))
     uses += [(None, SEED, p, BATCH_MIN_INLIERS) for case, p in BATCH if case == name]
