@@ -84,6 +84,10 @@ ovs_status ovs_orb_tables(const ovs_orb* h, float* scale_factors, float* inv_sca
  * `skip_calls` further HIP runtime calls that the library checks on a run-time path, the next `n_calls` of them still execute but are
  * REPORTED as failed (hipErrorLaunchFailure -> OVS_ERR_HIP), any thread. (0, 0) disarms. Nothing else in the library reads it. */
 ovs_status ovs_debug_inject_hip_failures(int32_t skip_calls, int32_t n_calls);
+/* Test hook for resource lifetime (tests/test_gpu_lifecycle.py): the streams, events, device and page-locked blocks that the library's handles
+ * and per-thread work spaces hold at this moment, process-wide. The arena pools, the brute-force matcher and the stage profilers' events are
+ * outside the count. */
+int64_t ovs_debug_live_resources(void);
 
 /* Upper bound on the keypoints one frame can produce (sum over levels of N_level + 3; 2 N_level + 3 after
  * ovs_orb_set_variant(OVS_VARIANT_TREE_SWITCH_FACTOR, 1) -- ask again after changing that variant): size outputs with this. */

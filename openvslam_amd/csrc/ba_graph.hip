@@ -39,11 +39,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <vector>
 
 #include "ba_edge.h"
 #include "ba_internal.h"
+#include "owned_internal.inc"
 
 namespace ovs {
 
@@ -1334,7 +1336,8 @@ static ovs_status graph_create(int model, int32_t device, int32_t n_pose, const 
     const bool trace = ovs::tuning().ba_trace;
     auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t0 = now();
-    ovs_ba_graph* g = new (std::nothrow) ovs_ba_graph();
+    std::unique_ptr<ovs_ba_graph, decltype(&ovs_ba_graph_destroy)> owner(new (std::nothrow) ovs_ba_graph(), &ovs_ba_graph_destroy);
+    ovs_ba_graph* const g = owner.get();
     if (!g) return OVS_ERR_INVALID;
     g->device = device;
     g->n_pose = n_pose;
@@ -1378,19 +1381,10 @@ static ovs_status graph_create(int model, int32_t device, int32_t n_pose, const 
                  o_pose_part = lay.place<double>(27 * 2 * max_chunks),   // (k_linearize2: one sum per HALF chunk)
                  o_ledges = lay.place<GEdge>((size_t)ne);
     const size_t arena_bytes = lay.bytes();
-#define G_TRY(expr)                            \
-    do {                                       \
-        hipError_t _e = (expr);                \
-        if (_e != hipSuccess) {                \
-            ovs::set_last_error(#expr, _e);    \
-            ovs_ba_graph_destroy(g);           \
-            return OVS_ERR_HIP;                \
-        }                                      \
-    } while (0)
-    G_TRY(sc.image.ensure(image_bytes, image_bytes + image_bytes / 4));   // (head room: the next local map is a little larger more often than not)
+    OVS_HIP_TRY_RAW(sc.image.ensure(image_bytes, image_bytes + image_bytes / 4));   // (head room: the next local map is a little larger more often than not)
     unsigned char* const img = sc.image.p;
     g->d_arena = g_ba_pool.take(device, arena_bytes, &g->arena_cap);
-    G_TRY(g->d_arena ? hipSuccess : hipErrorOutOfMemory);
+    OVS_HIP_TRY_RAW(g->d_arena ? hipSuccess : hipErrorOutOfMemory);
     using AL = ovs::ArenaLayout;
     unsigned char* const A = g->d_arena;
     {   // the kernels' view and the handle's own pointers, once
@@ -1469,13 +1463,12 @@ static ovs_status graph_create(int model, int32_t device, int32_t n_pose, const 
     }
     if (bad_index) {
         ovs::set_last_error_text("ovs_ba_graph_create: an edge's keyframe or landmark index is out of range");
-        ovs_ba_graph_destroy(g);
         return OVS_ERR_INVALID;
     }
     const double t_p1 = now();
     // the records are final: they travel (null stream, page-locked source: the call returns at once) under the remaining passes
     const size_t early_bytes = o_lm_start;   // (the records are the image's first array: they end where the next one starts)
-    if (ne > 0) G_TRY(hipMemcpyAsync(g->d_arena, img, early_bytes, hipMemcpyHostToDevice, nullptr));
+    if (ne > 0) OVS_HIP_TRY_RAW(hipMemcpyAsync(g->d_arena, img, early_bytes, hipMemcpyHostToDevice, nullptr));
     for (int j = 0; j < n_pt; ++j) lm_start[(size_t)j + 1] += lm_start[j];
     for (int k = 0; k < n_pose; ++k) pose_start[(size_t)k + 1] += pose_start[k];
     sc.fl.assign(lm_start, lm_start + n_pt);
@@ -1556,34 +1549,32 @@ static ovs_status graph_create(int model, int32_t device, int32_t n_pose, const 
     const double t2 = now();
     {
         const size_t from = ne > 0 ? early_bytes : 0;
-        if (upload_bytes > from) G_TRY(hipMemcpyAsync(g->d_arena + from, img + from, upload_bytes - from, hipMemcpyHostToDevice, nullptr));
+        if (upload_bytes > from) OVS_HIP_TRY_RAW(hipMemcpyAsync(g->d_arena + from, img + from, upload_bytes - from, hipMemcpyHostToDevice, nullptr));
     }
     if (ne > 0) {   // null stream: ordered behind the upload above and before whatever stream the caller linearises on (the wait costs ~10 us)
         unsigned long long* const d_dup = AL::at<unsigned long long>(A, o_dup);
         hipLaunchKernelGGL(k_edges_by_slot, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, nullptr, g->dev.edges, g->dev.lm_edges, ne,
                            AL::at<GEdge>(A, o_ledges), AL::at<int32_t>(A, o_lm_of_slot), d_dup);
-        G_TRY(hipGetLastError());
+        OVS_HIP_TRY_RAW(hipGetLastError());
         hipLaunchKernelGGL(k_dup_check, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, nullptr, g->dev.ledges, g->dev.lm_start, ne, d_dup);
-        G_TRY(hipGetLastError());
-        G_TRY(hipMemcpyAsync(img + o_dup_host, d_dup, sizeof(unsigned long long), hipMemcpyDeviceToHost, nullptr));
+        OVS_HIP_TRY_RAW(hipGetLastError());
+        OVS_HIP_TRY_RAW(hipMemcpyAsync(img + o_dup_host, d_dup, sizeof(unsigned long long), hipMemcpyDeviceToHost, nullptr));
     }
-    G_TRY(hipStreamSynchronize(nullptr));   // the image is this thread's next graph's as well: nothing of it may still be on its way
+    OVS_HIP_TRY_RAW(hipStreamSynchronize(nullptr));   // the image is this thread's next graph's as well: nothing of it may still be on its way
     if (ne > 0) {
         unsigned long long dup;
         std::memcpy(&dup, img + o_dup_host, sizeof(dup));
         if (dup != ~0ull) {
             ovs::set_last_error_text("ovs_ba_graph_create: keyframe " + std::to_string((uint32_t)dup) + " has two edges to landmark " +
                                      std::to_string((uint32_t)(dup >> 32)));
-            ovs_ba_graph_destroy(g);
             return OVS_ERR_INVALID;
         }
     }
-#undef G_TRY
     if (trace)
         std::fprintf(stderr, "[ovs_ba_graph_create] %.2f ms: edge records + histograms %.2f, scatter %.2f, landmark-order pass %.2f, other arrays %.2f, rest of "
                              "the %.1f MB upload + k_edges_by_slot %.2f\n",
                      now() - t0, t_p1 - t0, t_p2 - t_p1, t1 - t_p2, t2 - t1, upload_bytes / 1e6, now() - t2);
-    *out = g;
+    *out = owner.release();
     return OVS_OK;
 }
 

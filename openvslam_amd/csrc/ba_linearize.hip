@@ -17,6 +17,7 @@
 
 #include "ba_edge.h"
 #include "ba_internal.h"
+#include "owned_internal.inc"
 
 namespace ovs {
 
@@ -213,44 +214,28 @@ ovs_status linearize_from_host(int model, int32_t device, const double* poses, c
     const size_t i_pose = in.place<double>(7 * np), i_pt = in.place<double>(3 * npt), i_e = in.place<Edge>(ne1), i_f = in.place<uint8_t>(np);
     const size_t o_Hpp = out.place<double>(36 * np), o_bp = out.place<double>(6 * np), o_Hll = out.place<double>(9 * npt),
                  o_bl = out.place<double>(3 * npt), o_Hpl = out.place<double>(18 * ne1), o_chi = out.place<double>(2);
+    ovs::Owned tmp;
     unsigned char *d_in = nullptr, *d_out = nullptr;
-    OVS_HIP_TRY(hipMalloc(&d_in, in.bytes()));
-    hipError_t er = hipMalloc(&d_out, out.bytes());
-    if (er != hipSuccess) {
-        hipFree(d_in);
-        ovs::set_last_error("hipMalloc(out)", er);
-        return OVS_ERR_HIP;
-    }
-    ovs_status st = OVS_OK;
-    do {
-#define BA_TRY(expr)                              \
-    if ((er = (expr)) != hipSuccess) {            \
-        ovs::set_last_error(#expr, er);           \
-        st = OVS_ERR_HIP;                         \
-        break;                                    \
-    }
-        BA_TRY(hipMemcpy(d_in + i_pose, poses, sizeof(double) * 7 * np, hipMemcpyHostToDevice));
-        BA_TRY(hipMemcpy(d_in + i_pt, points, sizeof(double) * 3 * npt, hipMemcpyHostToDevice));
-        if (n_edge) BA_TRY(hipMemcpy(d_in + i_e, edges, sizeof(Edge) * ne, hipMemcpyHostToDevice));
-        if (pose_fixed) BA_TRY(hipMemcpy(d_in + i_f, pose_fixed, np, hipMemcpyHostToDevice));
-        st = linearize_on_device(model, ArenaLayout::at<double>(d_in, i_pose), pose_fixed ? d_in + i_f : nullptr, n_pose,
-                                 ArenaLayout::at<double>(d_in, i_pt), n_pt, ArenaLayout::at<Edge>(d_in, i_e), n_edge, cam, bf, huber_delta, false,
-                                 ArenaLayout::at<double>(d_out, o_Hpp), ArenaLayout::at<double>(d_out, o_bp), ArenaLayout::at<double>(d_out, o_Hll),
-                                 ArenaLayout::at<double>(d_out, o_bl), ArenaLayout::at<double>(d_out, o_Hpl), ArenaLayout::at<double>(d_out, o_chi),
-                                 nullptr);
-        if (st != OVS_OK) break;
-        BA_TRY(hipDeviceSynchronize());
-        BA_TRY(hipMemcpy(Hpp, d_out + o_Hpp, sizeof(double) * 36 * np, hipMemcpyDeviceToHost));
-        BA_TRY(hipMemcpy(bp, d_out + o_bp, sizeof(double) * 6 * np, hipMemcpyDeviceToHost));
-        BA_TRY(hipMemcpy(Hll, d_out + o_Hll, sizeof(double) * 9 * npt, hipMemcpyDeviceToHost));
-        BA_TRY(hipMemcpy(bl, d_out + o_bl, sizeof(double) * 3 * npt, hipMemcpyDeviceToHost));
-        if (n_edge) BA_TRY(hipMemcpy(Hpl, d_out + o_Hpl, sizeof(double) * 18 * ne, hipMemcpyDeviceToHost));
-        BA_TRY(hipMemcpy(chi2, d_out + o_chi, sizeof(double) * 2, hipMemcpyDeviceToHost));
-#undef BA_TRY
-    } while (0);
-    hipFree(d_in);
-    hipFree(d_out);
-    return st;
+    OVS_HIP_TRY(tmp.dev(&d_in, in.bytes()));
+    OVS_HIP_TRY_RAW(tmp.dev(&d_out, out.bytes()));
+    OVS_HIP_TRY_RAW(hipMemcpy(d_in + i_pose, poses, sizeof(double) * 7 * np, hipMemcpyHostToDevice));
+    OVS_HIP_TRY_RAW(hipMemcpy(d_in + i_pt, points, sizeof(double) * 3 * npt, hipMemcpyHostToDevice));
+    if (n_edge) OVS_HIP_TRY_RAW(hipMemcpy(d_in + i_e, edges, sizeof(Edge) * ne, hipMemcpyHostToDevice));
+    if (pose_fixed) OVS_HIP_TRY_RAW(hipMemcpy(d_in + i_f, pose_fixed, np, hipMemcpyHostToDevice));
+    const ovs_status st = linearize_on_device(model, ArenaLayout::at<double>(d_in, i_pose), pose_fixed ? d_in + i_f : nullptr, n_pose,
+                                              ArenaLayout::at<double>(d_in, i_pt), n_pt, ArenaLayout::at<Edge>(d_in, i_e), n_edge, cam, bf, huber_delta, false,
+                                              ArenaLayout::at<double>(d_out, o_Hpp), ArenaLayout::at<double>(d_out, o_bp), ArenaLayout::at<double>(d_out, o_Hll),
+                                              ArenaLayout::at<double>(d_out, o_bl), ArenaLayout::at<double>(d_out, o_Hpl), ArenaLayout::at<double>(d_out, o_chi),
+                                              nullptr);
+    if (st != OVS_OK) return st;
+    OVS_HIP_TRY_RAW(hipDeviceSynchronize());
+    OVS_HIP_TRY_RAW(hipMemcpy(Hpp, d_out + o_Hpp, sizeof(double) * 36 * np, hipMemcpyDeviceToHost));
+    OVS_HIP_TRY_RAW(hipMemcpy(bp, d_out + o_bp, sizeof(double) * 6 * np, hipMemcpyDeviceToHost));
+    OVS_HIP_TRY_RAW(hipMemcpy(Hll, d_out + o_Hll, sizeof(double) * 9 * npt, hipMemcpyDeviceToHost));
+    OVS_HIP_TRY_RAW(hipMemcpy(bl, d_out + o_bl, sizeof(double) * 3 * npt, hipMemcpyDeviceToHost));
+    if (n_edge) OVS_HIP_TRY_RAW(hipMemcpy(Hpl, d_out + o_Hpl, sizeof(double) * 18 * ne, hipMemcpyDeviceToHost));
+    OVS_HIP_TRY_RAW(hipMemcpy(chi2, d_out + o_chi, sizeof(double) * 2, hipMemcpyDeviceToHost));
+    return OVS_OK;
 }
 
 }   // namespace

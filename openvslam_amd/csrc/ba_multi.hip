@@ -10,9 +10,11 @@
 
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "ovs_common.h"
+#include "owned_internal.inc"
 
 namespace {
 
@@ -74,6 +76,7 @@ struct Shard {
     int device = 0;
     int pose_lo = 0, pose_hi = 0;               // keyframes [pose_lo, pose_hi) belong to this shard
     ovs_ba_graph* graph = nullptr;
+    ovs::Owned res;                              // of this shard's device: released under it (~ovs_ba_multi)
     std::vector<int32_t> mono_src, stereo_src;   // shard edge -> index in the caller's arrays
     hipStream_t stream = nullptr;
     double *d_poses = nullptr, *d_points = nullptr, *d_pose_blocks = nullptr, *d_packed = nullptr, *d_hpl = nullptr;
@@ -95,30 +98,22 @@ struct ovs_ba_multi {
     double* h_pose = nullptr;     // pinned: per-shard Hpp | bp blocks
     int exchange = OVS_BA_EXCHANGE_RCCL;
     bool peer_ok = false;         // every pair of devices has peer access enabled
+    ovs::Owned res;               // the two pinned blocks
+    ~ovs_ba_multi() {
+        for (Shard& s : shards) {
+            (void)hipSetDevice(s.device);
+            if (s.stream) hipStreamSynchronize(s.stream);
+            if (s.comm && g_rccl.CommDestroy) g_rccl.CommDestroy(s.comm);
+            if (s.graph) ovs_ba_graph_destroy(s.graph);
+            s.res.clear();
+        }
+    }
 };
 
 extern "C" {
 
 ovs_status ovs_ba_multi_destroy(ovs_ba_multi* m) {
     if (!m) return OVS_OK;
-    for (Shard& s : m->shards) {
-        (void)hipSetDevice(s.device);
-        if (s.stream) hipStreamSynchronize(s.stream);
-        if (s.comm && g_rccl.CommDestroy) g_rccl.CommDestroy(s.comm);
-        if (s.graph) ovs_ba_graph_destroy(s.graph);
-        hipFree(s.d_poses);
-        hipFree(s.d_points);
-        hipFree(s.d_pose_blocks);
-        hipFree(s.d_packed);
-        hipFree(s.d_hpl);
-        hipFree(s.d_sum);
-        if (s.ev_lin) hipEventDestroy(s.ev_lin);
-        if (s.ev_sum) hipEventDestroy(s.ev_sum);
-        if (s.h_hpl) hipHostFree(s.h_hpl);
-        if (s.stream) hipStreamDestroy(s.stream);
-    }
-    if (m->h_packed) hipHostFree(m->h_packed);
-    if (m->h_pose) hipHostFree(m->h_pose);
     delete m;
     return OVS_OK;
 }
@@ -135,7 +130,8 @@ ovs_status ovs_ba_multi_create(int32_t n_gpus, int32_t n_pose, const uint8_t* po
         if (mono[i].pose_idx < 0 || mono[i].pose_idx >= n_pose) return OVS_ERR_INVALID;
     for (int i = 0; i < n_stereo; ++i)
         if (stereo[i].pose_idx < 0 || stereo[i].pose_idx >= n_pose) return OVS_ERR_INVALID;
-    ovs_ba_multi* m = new (std::nothrow) ovs_ba_multi();
+    std::unique_ptr<ovs_ba_multi> owner(new (std::nothrow) ovs_ba_multi());
+    ovs_ba_multi* const m = owner.get();
     if (!m) return OVS_ERR_INVALID;
     m->n_gpus = n_gpus;
     m->n_pose = n_pose;
@@ -144,15 +140,6 @@ ovs_status ovs_ba_multi_create(int32_t n_gpus, int32_t n_pose, const uint8_t* po
     m->n_stereo = n_stereo;
     m->shards.resize((size_t)n_gpus);
     const int per = (n_pose + n_gpus - 1) / n_gpus;   // contiguous keyframe blocks (2000 edges per keyframe at config 5: balanced)
-#define M_TRY(expr)                            \
-    do {                                       \
-        hipError_t _e = (expr);                \
-        if (_e != hipSuccess) {                \
-            set_last_error(#expr, _e);         \
-            ovs_ba_multi_destroy(m);           \
-            return OVS_ERR_HIP;                \
-        }                                      \
-    } while (0)
     for (int d = 0; d < n_gpus; ++d) {
         Shard& s = m->shards[(size_t)d];
         s.device = d;
@@ -172,29 +159,26 @@ ovs_status ovs_ba_multi_create(int32_t n_gpus, int32_t n_pose, const uint8_t* po
             }
         const ovs_status st = ovs_ba_graph_create(d, n_pose, pose_fixed, n_pt, em.data(), (int32_t)em.size(), es.data(), (int32_t)es.size(), cam,
                                                   focal_x_baseline, &s.graph);
-        if (st != OVS_OK) {
-            ovs_ba_multi_destroy(m);
-            return st;
-        }
-        M_TRY(hipSetDevice(d));
-        M_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+        if (st != OVS_OK) return st;
+        OVS_HIP_TRY_RAW(hipSetDevice(d));
+        OVS_HIP_TRY_RAW(s.res.stream(&s.stream));
         const size_t ne = std::max<size_t>(em.size() + es.size(), 1);
-        M_TRY(hipMalloc(&s.d_poses, sizeof(double) * 7 * (size_t)n_pose));
-        M_TRY(hipMalloc(&s.d_points, sizeof(double) * 3 * (size_t)n_pt));
-        M_TRY(hipMalloc(&s.d_pose_blocks, sizeof(double) * 42 * (size_t)n_pose));
-        M_TRY(hipMalloc(&s.d_packed, sizeof(double) * (12 * (size_t)n_pt + 4)));
-        M_TRY(hipMalloc(&s.d_hpl, sizeof(double) * 18 * ne));
-        M_TRY(hipHostMalloc(reinterpret_cast<void**>(&s.h_hpl), sizeof(double) * 18 * ne, hipHostMallocDefault));
+        OVS_HIP_TRY_RAW(s.res.dev(&s.d_poses, sizeof(double) * 7 * (size_t)n_pose));
+        OVS_HIP_TRY_RAW(s.res.dev(&s.d_points, sizeof(double) * 3 * (size_t)n_pt));
+        OVS_HIP_TRY_RAW(s.res.dev(&s.d_pose_blocks, sizeof(double) * 42 * (size_t)n_pose));
+        OVS_HIP_TRY_RAW(s.res.dev(&s.d_packed, sizeof(double) * (12 * (size_t)n_pt + 4)));
+        OVS_HIP_TRY_RAW(s.res.dev(&s.d_hpl, sizeof(double) * 18 * ne));
+        OVS_HIP_TRY_RAW(s.res.pinned(&s.h_hpl, sizeof(double) * 18 * ne));
         if (n_gpus > 1) {
-            M_TRY(hipMalloc(&s.d_sum, sizeof(double) * (12 * (size_t)n_pt + 4)));
-            M_TRY(hipEventCreateWithFlags(&s.ev_lin, hipEventDisableTiming));
-            M_TRY(hipEventCreateWithFlags(&s.ev_sum, hipEventDisableTiming));
+            OVS_HIP_TRY_RAW(s.res.dev(&s.d_sum, sizeof(double) * (12 * (size_t)n_pt + 4)));
+            OVS_HIP_TRY_RAW(s.res.event(&s.ev_lin, hipEventDisableTiming));
+            OVS_HIP_TRY_RAW(s.res.event(&s.ev_sum, hipEventDisableTiming));
         }
     }
     if (n_gpus > 1) {   // peer access for the direct exchange; failing to get it only disables that variant
         bool ok = true;
         for (int a = 0; a < n_gpus && ok; ++a) {
-            M_TRY(hipSetDevice(a));
+            OVS_HIP_TRY_RAW(hipSetDevice(a));
             for (int b = 0; b < n_gpus && ok; ++b) {
                 if (a == b) continue;
                 int can = 0;
@@ -209,24 +193,17 @@ ovs_status ovs_ba_multi_create(int32_t n_gpus, int32_t n_pose, const uint8_t* po
         }
         m->peer_ok = ok;
     }
-    M_TRY(hipHostMalloc(reinterpret_cast<void**>(&m->h_packed), sizeof(double) * (12 * (size_t)n_pt + 4), hipHostMallocDefault));
-    M_TRY(hipHostMalloc(reinterpret_cast<void**>(&m->h_pose), sizeof(double) * 42 * (size_t)n_pose * (size_t)n_gpus, hipHostMallocDefault));
-#undef M_TRY
+    OVS_HIP_TRY_RAW(m->res.pinned(&m->h_packed, sizeof(double) * (12 * (size_t)n_pt + 4)));
+    OVS_HIP_TRY_RAW(m->res.pinned(&m->h_pose, sizeof(double) * 42 * (size_t)n_pose * (size_t)n_gpus));
     if (n_gpus > 1) {
-        if (!g_rccl.load()) {
-            ovs_ba_multi_destroy(m);
-            return OVS_ERR_NO_DEVICE;   // no RCCL: a sharded run is impossible (ovs_last_error stays empty: not a HIP failure)
-        }
+        if (!g_rccl.load()) return OVS_ERR_NO_DEVICE;   // no RCCL: a sharded run is impossible (ovs_last_error stays empty: not a HIP failure)
         std::vector<void*> comms((size_t)n_gpus, nullptr);
         std::vector<int> devs((size_t)n_gpus);
         for (int d = 0; d < n_gpus; ++d) devs[(size_t)d] = d;
-        if (g_rccl.CommInitAll(comms.data(), n_gpus, devs.data()) != 0) {
-            ovs_ba_multi_destroy(m);
-            return OVS_ERR_HIP;
-        }
+        if (g_rccl.CommInitAll(comms.data(), n_gpus, devs.data()) != 0) return OVS_ERR_HIP;
         for (int d = 0; d < n_gpus; ++d) m->shards[(size_t)d].comm = comms[(size_t)d];
     }
-    *out = m;
+    *out = owner.release();
     return OVS_OK;
 }
 

@@ -21,6 +21,7 @@
 
 #include "ba_host_math.h"
 #include "ba_internal.h"
+#include "owned_internal.inc"
 
 namespace ovs {
 std::atomic<int> g_lba_solver{0};
@@ -85,16 +86,14 @@ struct LmScratch {
     ovs::PinnedBuffer pin;    // pin_layout
     ovs::PinnedBuffer edge;   // round 1's inlier count (4 bytes), then the final outlier flags (one byte per edge)
     ovs::PinnedBuffer pts;    // the landmarks on their way up (start of the call) and down (its end)
-    ~LmScratch() { release(); }
-    void release() {
-        if (d) (void)hipFree(d);
-        d = nullptr;
+    ovs::Owned res;           // d and stream
+    void release() {          // (the work space moves to another device)
+        (void)res.drop(&d);
         d_cap = 0;
         pin.release();
         edge.release();
         pts.release();
-        if (stream) (void)hipStreamDestroy(stream);
-        stream = nullptr;
+        (void)res.drop(&stream);
     }
 };
 
@@ -135,7 +134,7 @@ struct Lm {
             sc.release();
             sc.device = device;
         }
-        if (!sc.stream) OVS_HIP_TRY(hipStreamCreateWithFlags(&sc.stream, hipStreamNonBlocking));
+        if (!sc.stream) OVS_HIP_TRY(sc.res.stream(&sc.stream));
         stream = sc.stream;
         const size_t ne = std::max<size_t>(ne_max, 1), nd = DevBlocks::doubles(np, npt, ne_max);
         ArenaLayout lay;
@@ -146,10 +145,9 @@ struct Lm {
         const size_t o_echi = lay.place<double>(ne), o_edepth = lay.place<uint8_t>(ne), o_echi_r1 = lay.place<double>(ne), o_echi_s = lay.place<double>(ne);
         const size_t o_out1 = lay.place<uint8_t>(ne), o_outf = lay.place<uint8_t>(ne), o_nact = lay.place<int32_t>(1);
         if (sc.d_cap < lay.bytes()) {
-            if (sc.d) (void)hipFree(sc.d);
-            sc.d = nullptr;
+            (void)sc.res.drop(&sc.d);
             sc.d_cap = 0;
-            OVS_HIP_TRY(hipMalloc(&sc.d, lay.bytes()));
+            OVS_HIP_TRY(sc.res.dev(&sc.d, lay.bytes()));
             sc.d_cap = lay.bytes();
         }
         cur.carve(ArenaLayout::at<double>(sc.d, o_cur), np, npt, ne_max);

@@ -44,6 +44,7 @@
 #include <vector>
 
 #include "ba_internal.h"
+#include "owned_internal.inc"
 
 namespace ovs {
 
@@ -825,9 +826,10 @@ ovs_status ovs_ba_dense_solve(int32_t device, const double* S, const double* rhs
     for (int i = 0; i < n; ++i) std::memcpy(&h[(size_t)i * n_pad], S + (size_t)i * n, sizeof(double) * n);
     for (int i = n; i < n_pad; ++i) h[(size_t)i * n_pad + i] = 1.0;
     std::memcpy(&h[(size_t)n_pad * n_pad], rhs, sizeof(double) * n);
+    ovs::Owned tmp;
     double* d = nullptr;
     const size_t bytes = sizeof(double) * h.size();
-    OVS_HIP_TRY(hipMalloc(&d, bytes + 256));
+    OVS_HIP_TRY(tmp.dev(&d, bytes + 256));
     int32_t* d_fail = reinterpret_cast<int32_t*>(reinterpret_cast<unsigned char*>(d) + bytes);
     unsigned long long* d_t = ovs::tuning().ba_trace ? reinterpret_cast<unsigned long long*>(d_fail + 2) : nullptr;   // 8 counters behind the flag
     ovs_status st = OVS_OK;
@@ -848,7 +850,6 @@ ovs_status ovs_ba_dense_solve(int32_t device, const double* S, const double* rhs
     }
     if (e == hipSuccess && st == OVS_OK) e = hipMemcpy(x, d + (size_t)n_pad * n_pad, sizeof(double) * n, hipMemcpyDeviceToHost);
     if (e == hipSuccess && st == OVS_OK) e = hipMemcpy(&h_fail, d_fail, sizeof(int32_t), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
     if (e != hipSuccess) {
         ovs::set_last_error("ovs_ba_dense_solve", e);
         return OVS_ERR_HIP;

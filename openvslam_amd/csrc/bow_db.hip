@@ -18,12 +18,14 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <numeric>
 #include <unordered_map>
 #include <vector>
 
 #include "ovs_common.h"
+#include "owned_internal.inc"
 
 namespace {
 
@@ -45,6 +47,7 @@ struct ovs_bowdb {
     int device = 0;
     int max_keyframes = 0, max_words = 0, n_cu = 0;
     std::mutex mu;
+    ovs::Owned res;
     hipStream_t stream = nullptr;
     // database
     int32_t* d_ids = nullptr;
@@ -169,24 +172,6 @@ __global__ __launch_bounds__(256) void k_bowdb_gate(const SlotRec* __restrict__ 
 
 ovs::LdsAttrCache g_score_lds;
 
-void bowdb_free(ovs_bowdb* db) {
-    if (!db) return;
-    hipFree(db->d_ids);
-    hipFree(db->d_vals);
-    hipFree(db->d_slots);
-    hipFree(db->d_query);
-    hipFree(db->d_common);
-    hipFree(db->d_score);
-    hipFree(db->d_rejected);
-    if (db->h_query) hipHostFree(db->h_query);
-    if (db->h_out_id) hipHostFree(db->h_out_id);
-    if (db->h_out_common) hipHostFree(db->h_out_common);
-    if (db->h_out_score) hipHostFree(db->h_out_score);
-    if (db->h_head) hipHostFree(db->h_head);
-    if (db->stream) hipStreamDestroy(db->stream);
-    delete db;
-}
-
 // strictly ascending non-negative ids, finite values
 bool vector_ok(const int32_t* ids, const double* values, int32_t n) {
     if (n < 0 || (n > 0 && (!ids || !values))) return false;
@@ -257,48 +242,41 @@ ovs_status ovs_bowdb_create(int32_t device, int32_t max_keyframes, int32_t max_w
     if (12 * (size_t)max_words > ovs::kMaxLdsPerWorkgroup) return OVS_ERR_INVALID;   // the query has to fit one workgroup's LDS
     if (ovs_device_count() <= device || device < 0) return OVS_ERR_NO_DEVICE;
     OVS_HIP_TRY(hipSetDevice(device));
-    ovs_bowdb* db = new ovs_bowdb();
+    std::unique_ptr<ovs_bowdb> owner(new ovs_bowdb());
+    ovs_bowdb* const db = owner.get();
     db->device = device;
     db->max_keyframes = max_keyframes;
     db->max_words = max_words;
     db->query_cap = sizeof(QueryHead) + 12 * (size_t)max_words + sizeof(int32_t) * (size_t)max_keyframes;
     const size_t cells = (size_t)max_keyframes * (size_t)max_words;
-    hipError_t e = hipSuccess;
-#define D_TRY(expr)                                      \
-    if ((e = ovs::fault_filter(expr)) != hipSuccess) {   \
-        ovs::set_last_error(#expr, e);                   \
-        bowdb_free(db);                                  \
-        return OVS_ERR_HIP;                              \
-    }
     hipDeviceProp_t prop;
-    D_TRY(hipGetDeviceProperties(&prop, device));
+    OVS_HIP_TRY(hipGetDeviceProperties(&prop, device));
     db->n_cu = std::max(1, prop.multiProcessorCount);
-    D_TRY(hipStreamCreateWithFlags(&db->stream, hipStreamNonBlocking));
-    D_TRY(hipMalloc(&db->d_ids, sizeof(int32_t) * cells));
-    D_TRY(hipMalloc(&db->d_vals, sizeof(double) * cells));
-    D_TRY(hipMalloc(&db->d_slots, sizeof(SlotRec) * (size_t)max_keyframes));
-    D_TRY(hipMemset(db->d_slots, 0, sizeof(SlotRec) * (size_t)max_keyframes));
-    D_TRY(hipMalloc(&db->d_query, db->query_cap));
-    D_TRY(hipMalloc(&db->d_common, sizeof(int32_t) * (size_t)max_keyframes));
-    D_TRY(hipMalloc(&db->d_score, sizeof(double) * (size_t)max_keyframes));
-    D_TRY(hipMalloc(&db->d_rejected, (size_t)max_keyframes));
-    D_TRY(hipHostMalloc(reinterpret_cast<void**>(&db->h_query), db->query_cap, hipHostMallocDefault));
-    D_TRY(hipHostMalloc(reinterpret_cast<void**>(&db->h_out_id), sizeof(int32_t) * (size_t)max_keyframes, hipHostMallocMapped));
-    D_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&db->m_out_id), db->h_out_id, 0));
-    D_TRY(hipHostMalloc(reinterpret_cast<void**>(&db->h_out_common), sizeof(int32_t) * (size_t)max_keyframes, hipHostMallocMapped));
-    D_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&db->m_out_common), db->h_out_common, 0));
-    D_TRY(hipHostMalloc(reinterpret_cast<void**>(&db->h_out_score), sizeof(double) * (size_t)max_keyframes, hipHostMallocMapped));
-    D_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&db->m_out_score), db->h_out_score, 0));
-    D_TRY(hipHostMalloc(reinterpret_cast<void**>(&db->h_head), sizeof(QueryHead), hipHostMallocDefault));
-#undef D_TRY
-    *out = db;
+    OVS_HIP_TRY(db->res.stream(&db->stream));
+    OVS_HIP_TRY(db->res.dev(&db->d_ids, sizeof(int32_t) * cells));
+    OVS_HIP_TRY(db->res.dev(&db->d_vals, sizeof(double) * cells));
+    OVS_HIP_TRY(db->res.dev(&db->d_slots, sizeof(SlotRec) * (size_t)max_keyframes));
+    OVS_HIP_TRY(hipMemset(db->d_slots, 0, sizeof(SlotRec) * (size_t)max_keyframes));
+    OVS_HIP_TRY(db->res.dev(&db->d_query, db->query_cap));
+    OVS_HIP_TRY(db->res.dev(&db->d_common, sizeof(int32_t) * (size_t)max_keyframes));
+    OVS_HIP_TRY(db->res.dev(&db->d_score, sizeof(double) * (size_t)max_keyframes));
+    OVS_HIP_TRY(db->res.dev(&db->d_rejected, (size_t)max_keyframes));
+    OVS_HIP_TRY(db->res.pinned(&db->h_query, db->query_cap));
+    OVS_HIP_TRY(db->res.pinned(&db->h_out_id, sizeof(int32_t) * (size_t)max_keyframes, hipHostMallocMapped));
+    OVS_HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&db->m_out_id), db->h_out_id, 0));
+    OVS_HIP_TRY(db->res.pinned(&db->h_out_common, sizeof(int32_t) * (size_t)max_keyframes, hipHostMallocMapped));
+    OVS_HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&db->m_out_common), db->h_out_common, 0));
+    OVS_HIP_TRY(db->res.pinned(&db->h_out_score, sizeof(double) * (size_t)max_keyframes, hipHostMallocMapped));
+    OVS_HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&db->m_out_score), db->h_out_score, 0));
+    OVS_HIP_TRY(db->res.pinned(&db->h_head, sizeof(QueryHead)));
+    *out = owner.release();
     return OVS_OK;
 }
 
 ovs_status ovs_bowdb_destroy(ovs_bowdb* db) {
     if (!db) return OVS_ERR_INVALID;
     hipSetDevice(db->device);
-    bowdb_free(db);
+    delete db;
     return OVS_OK;
 }
 

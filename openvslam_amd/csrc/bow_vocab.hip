@@ -15,9 +15,11 @@
 // random 320-byte reads (1.3 MB per frame) -- the kernel is latency-bound and tiny next to the extraction.
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "ovs_common.h"
+#include "owned_internal.inc"
 
 struct ovs_vocab {
     int device = 0;
@@ -33,6 +35,7 @@ struct ovs_vocab {
     double* d_out_weight = nullptr;
     int cap = 0;
     hipStream_t stream = nullptr;
+    ovs::Owned res;
 };
 
 namespace {
@@ -86,21 +89,6 @@ __global__ __launch_bounds__(256) void k_bow_transform(const int32_t* __restrict
     }
 }
 
-void vocab_free(ovs_vocab* v) {
-    if (!v) return;
-    hipFree(v->d_child_start);
-    hipFree(v->d_children);
-    hipFree(v->d_child_desc);
-    hipFree(v->d_weight);
-    hipFree(v->d_word);
-    hipFree(v->d_desc);
-    hipFree(v->d_out_word);
-    hipFree(v->d_out_node);
-    hipFree(v->d_out_weight);
-    if (v->stream) hipStreamDestroy(v->stream);
-    delete v;
-}
-
 }   // namespace
 
 extern "C" {
@@ -121,7 +109,8 @@ ovs_status ovs_vocab_create(int32_t device, int32_t n_nodes, const int32_t* chil
         if (children[i] <= 0 || children[i] >= n_nodes) return OVS_ERR_INVALID;   // node 0 is the root and nobody's child
     if (ovs_device_count() <= device || device < 0) return OVS_ERR_NO_DEVICE;
     OVS_HIP_TRY(hipSetDevice(device));
-    ovs_vocab* v = new ovs_vocab();
+    std::unique_ptr<ovs_vocab> owner(new ovs_vocab());
+    ovs_vocab* const v = owner.get();
     v->device = device;
     v->n_nodes = n_nodes;
     v->depth = depth;
@@ -129,37 +118,29 @@ ovs_status ovs_vocab_create(int32_t device, int32_t n_nodes, const int32_t* chil
     v->cap = max_features;
     std::vector<uint8_t> cd((size_t)32 * std::max(n_edges, 1));
     for (int i = 0; i < n_edges; ++i) std::memcpy(&cd[(size_t)32 * i], node_desc + (size_t)32 * children[i], 32);
-    hipError_t e = hipSuccess;
-#define V_TRY(expr)                    \
-    if ((e = (expr)) != hipSuccess) {  \
-        ovs::set_last_error(#expr, e); \
-        vocab_free(v);                 \
-        return OVS_ERR_HIP;            \
-    }
-    V_TRY(hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking));
-    V_TRY(hipMalloc(&v->d_child_start, sizeof(int32_t) * ((size_t)n_nodes + 1)));
-    V_TRY(hipMalloc(&v->d_children, sizeof(int32_t) * (size_t)std::max(n_edges, 1)));
-    V_TRY(hipMalloc(&v->d_child_desc, cd.size()));
-    V_TRY(hipMalloc(&v->d_weight, sizeof(double) * (size_t)n_nodes));
-    V_TRY(hipMalloc(&v->d_word, sizeof(int32_t) * (size_t)n_nodes));
-    V_TRY(hipMalloc(&v->d_desc, (size_t)32 * max_features));
-    V_TRY(hipMalloc(&v->d_out_word, sizeof(int32_t) * (size_t)max_features));
-    V_TRY(hipMalloc(&v->d_out_node, sizeof(int32_t) * (size_t)max_features));
-    V_TRY(hipMalloc(&v->d_out_weight, sizeof(double) * (size_t)max_features));
-    V_TRY(hipMemcpy(v->d_child_start, child_start, sizeof(int32_t) * ((size_t)n_nodes + 1), hipMemcpyHostToDevice));
-    if (n_edges) V_TRY(hipMemcpy(v->d_children, children, sizeof(int32_t) * (size_t)n_edges, hipMemcpyHostToDevice));
-    V_TRY(hipMemcpy(v->d_child_desc, cd.data(), cd.size(), hipMemcpyHostToDevice));
-    V_TRY(hipMemcpy(v->d_weight, node_weight, sizeof(double) * (size_t)n_nodes, hipMemcpyHostToDevice));
-    V_TRY(hipMemcpy(v->d_word, node_word_id, sizeof(int32_t) * (size_t)n_nodes, hipMemcpyHostToDevice));
-#undef V_TRY
-    *out = v;
+    OVS_HIP_TRY_RAW(v->res.stream(&v->stream));
+    OVS_HIP_TRY_RAW(v->res.dev(&v->d_child_start, sizeof(int32_t) * ((size_t)n_nodes + 1)));
+    OVS_HIP_TRY_RAW(v->res.dev(&v->d_children, sizeof(int32_t) * (size_t)std::max(n_edges, 1)));
+    OVS_HIP_TRY_RAW(v->res.dev(&v->d_child_desc, cd.size()));
+    OVS_HIP_TRY_RAW(v->res.dev(&v->d_weight, sizeof(double) * (size_t)n_nodes));
+    OVS_HIP_TRY_RAW(v->res.dev(&v->d_word, sizeof(int32_t) * (size_t)n_nodes));
+    OVS_HIP_TRY_RAW(v->res.dev(&v->d_desc, (size_t)32 * max_features));
+    OVS_HIP_TRY_RAW(v->res.dev(&v->d_out_word, sizeof(int32_t) * (size_t)max_features));
+    OVS_HIP_TRY_RAW(v->res.dev(&v->d_out_node, sizeof(int32_t) * (size_t)max_features));
+    OVS_HIP_TRY_RAW(v->res.dev(&v->d_out_weight, sizeof(double) * (size_t)max_features));
+    OVS_HIP_TRY_RAW(hipMemcpy(v->d_child_start, child_start, sizeof(int32_t) * ((size_t)n_nodes + 1), hipMemcpyHostToDevice));
+    if (n_edges) OVS_HIP_TRY_RAW(hipMemcpy(v->d_children, children, sizeof(int32_t) * (size_t)n_edges, hipMemcpyHostToDevice));
+    OVS_HIP_TRY_RAW(hipMemcpy(v->d_child_desc, cd.data(), cd.size(), hipMemcpyHostToDevice));
+    OVS_HIP_TRY_RAW(hipMemcpy(v->d_weight, node_weight, sizeof(double) * (size_t)n_nodes, hipMemcpyHostToDevice));
+    OVS_HIP_TRY_RAW(hipMemcpy(v->d_word, node_word_id, sizeof(int32_t) * (size_t)n_nodes, hipMemcpyHostToDevice));
+    *out = owner.release();
     return OVS_OK;
 }
 
 ovs_status ovs_vocab_destroy(ovs_vocab* v) {
     if (!v) return OVS_ERR_INVALID;
     hipSetDevice(v->device);
-    vocab_free(v);
+    delete v;
     return OVS_OK;
 }
 

@@ -13,9 +13,11 @@
 //                              matches above 2 x median are dropped.
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <new>
 
 #include "ovs_common.h"
+#include "owned_internal.inc"
 
 namespace ovs {
 
@@ -286,6 +288,7 @@ struct ovs_stereo {
     int max_rows = 0, max_kps = 0;
     int variant = 0;   // ovs_stereo_set_variant: bit 0 outlier factor 2.1, bit 1 parabola in double
     uint32_t item_cap = 0;
+    Owned res;
     hipStream_t stream = nullptr;
     uint32_t* d_row_off = nullptr;
     uint32_t* d_row_items = nullptr;
@@ -314,7 +317,8 @@ ovs_status ovs_stereo_create(int32_t max_rows, int32_t max_keypoints, int32_t de
     if (sizeof(uint32_t) * ((size_t)max_rows + 1 + 1024) > kMaxLdsPerWorkgroup) return OVS_ERR_CAPACITY;
     *out = nullptr;
     if (ovs_device_count() <= device || device < 0) return OVS_ERR_NO_DEVICE;
-    ovs_stereo* s = new (std::nothrow) ovs_stereo();
+    std::unique_ptr<ovs_stereo> owner(new (std::nothrow) ovs_stereo());
+    ovs_stereo* const s = owner.get();
     if (!s) return OVS_ERR_INVALID;
     s->device = device;
     s->max_rows = max_rows;
@@ -322,44 +326,29 @@ ovs_status ovs_stereo_create(int32_t max_rows, int32_t max_keypoints, int32_t de
     // a right keypoint sits in at most ceil(y + 2s) - floor(y - 2s) + 1 <= 4 s_max + 3 rows; s_max = 1.2^15 would be absurd: size
     // for the largest scale factor of a 16-level x1.2 pyramid and refuse (OVS_ERR_CAPACITY) beyond it
     s->item_cap = (uint32_t)std::min<size_t>((size_t)max_keypoints * 72, (size_t)1 << 26);
-#define CREATE_TRY(expr)                       \
-    do {                                       \
-        hipError_t _e = (expr);                \
-        if (_e != hipSuccess) {                \
-            ovs::set_last_error(#expr, _e);    \
-            ovs_stereo_destroy(s);             \
-            return OVS_ERR_HIP;                \
-        }                                      \
-    } while (0)
-    CREATE_TRY(hipSetDevice(device));
-    CREATE_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+    OVS_HIP_TRY_RAW(hipSetDevice(device));
+    OVS_HIP_TRY_RAW(s->res.stream(&s->stream));
     const size_t R = (size_t)max_rows + 1, K = (size_t)max_keypoints;
-    CREATE_TRY(hipMalloc(&s->d_row_off, sizeof(uint32_t) * R));
-    CREATE_TRY(hipMalloc(&s->d_row_items, sizeof(uint32_t) * s->item_cap));
-    CREATE_TRY(hipMalloc(&s->d_best_right, sizeof(int32_t) * K));
-    CREATE_TRY(hipMalloc(&s->d_sad, sizeof(int32_t) * K));
-    CREATE_TRY(hipMalloc(&s->d_kps_l, sizeof(ovs_keypoint) * K));
-    CREATE_TRY(hipMalloc(&s->d_kps_r, sizeof(ovs_keypoint) * K));
-    CREATE_TRY(hipMalloc(&s->d_desc_l, 32 * K));
-    CREATE_TRY(hipMalloc(&s->d_desc_r, 32 * K));
-    CREATE_TRY(hipMalloc(&s->d_res, 16 + 2 * sizeof(float) * K));
-    CREATE_TRY(hipHostMalloc(&s->h_res, 16 + 2 * sizeof(float) * K, hipHostMallocDefault));
+    OVS_HIP_TRY_RAW(s->res.dev(&s->d_row_off, sizeof(uint32_t) * R));
+    OVS_HIP_TRY_RAW(s->res.dev(&s->d_row_items, sizeof(uint32_t) * s->item_cap));
+    OVS_HIP_TRY_RAW(s->res.dev(&s->d_best_right, sizeof(int32_t) * K));
+    OVS_HIP_TRY_RAW(s->res.dev(&s->d_sad, sizeof(int32_t) * K));
+    OVS_HIP_TRY_RAW(s->res.dev(&s->d_kps_l, sizeof(ovs_keypoint) * K));
+    OVS_HIP_TRY_RAW(s->res.dev(&s->d_kps_r, sizeof(ovs_keypoint) * K));
+    OVS_HIP_TRY_RAW(s->res.dev(&s->d_desc_l, 32 * K));
+    OVS_HIP_TRY_RAW(s->res.dev(&s->d_desc_r, 32 * K));
+    OVS_HIP_TRY_RAW(s->res.dev(&s->d_res, 16 + 2 * sizeof(float) * K));
+    OVS_HIP_TRY_RAW(s->res.pinned(&s->h_res, 16 + 2 * sizeof(float) * K));
     s->d_n_valid = reinterpret_cast<int32_t*>(s->d_res);
     s->d_overflow = reinterpret_cast<uint32_t*>(s->d_res + 4);
     s->d_x_right = reinterpret_cast<float*>(s->d_res + 16);
     s->d_depths = s->d_x_right + K;
-#undef CREATE_TRY
-    *out = s;
+    *out = owner.release();
     return OVS_OK;
 }
 
 ovs_status ovs_stereo_destroy(ovs_stereo* s) {
     if (!s) return OVS_OK;
-    if (s->stream) hipStreamSynchronize(s->stream);
-    void* ptrs[] = {s->d_row_off, s->d_row_items, s->d_best_right, s->d_sad, s->d_kps_l, s->d_kps_r, s->d_desc_l, s->d_desc_r, s->d_res};
-    for (void* p : ptrs) hipFree(p);
-    if (s->h_res) hipHostFree(s->h_res);
-    if (s->stream) hipStreamDestroy(s->stream);
     delete s;
     return OVS_OK;
 }

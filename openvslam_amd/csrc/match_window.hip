@@ -21,11 +21,13 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <vector>
 
 #include "ovs_common.h"
+#include "owned_internal.inc"
 
 namespace ovs {
 
@@ -966,6 +968,7 @@ struct ovs_wmatcher {
     int device = 0;
     int max_t = 0, max_q = 0;
     uint32_t max_entries = 0;
+    ovs::Owned res;
     hipStream_t stream = nullptr;
     // grid of a target frame that is uploaded per call (a resident frame carries its own)
     int32_t* d_cell_of = nullptr;
@@ -1003,6 +1006,7 @@ struct ovs_frame_dev {
     float* d_x_right = nullptr;
     int32_t *d_cell_of = nullptr, *d_cell_start = nullptr, *d_items = nullptr;
     double* d_bearings = nullptr;   // optional (ovs_frame_dev_attach_bearings): 3 doubles per keypoint, for match_for_triangulation
+    ovs::Owned res;                 // d_bearings (the arena goes back to the pool: ovs_frame_dev_destroy)
 };
 
 namespace {
@@ -1848,10 +1852,7 @@ struct FrameStage {
     size_t cap = 0;
     hipStream_t stream = nullptr;
     int device = -1;
-    ~FrameStage() {
-        if (h) (void)hipHostFree(h);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
+    ovs::Owned res;
 };
 
 }   // namespace
@@ -1863,37 +1864,29 @@ ovs_status ovs_wmatcher_create(int32_t max_targets, int32_t max_queries, int32_t
     *out = nullptr;
     if (ovs_device_count() <= device || device < 0) return OVS_ERR_NO_DEVICE;
     if (resolve_lds_bytes(max_queries, max_targets) > 150 * 1024) return OVS_ERR_CAPACITY;
-    ovs_wmatcher* w = new (std::nothrow) ovs_wmatcher();
+    std::unique_ptr<ovs_wmatcher> owner(new (std::nothrow) ovs_wmatcher());
+    ovs_wmatcher* const w = owner.get();
     if (!w) return OVS_ERR_INVALID;
     w->device = device;
     w->max_t = max_targets;
     w->max_q = max_queries;
     w->max_entries = (uint32_t)max_entries;
-#define CREATE_TRY(expr)                       \
-    do {                                       \
-        hipError_t _e = (expr);                \
-        if (_e != hipSuccess) {                \
-            ovs::set_last_error(#expr, _e);    \
-            ovs_wmatcher_destroy(w);           \
-            return OVS_ERR_HIP;                \
-        }                                      \
-    } while (0)
-    CREATE_TRY(hipSetDevice(device));
-    CREATE_TRY(hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking));
+    OVS_HIP_TRY_RAW(hipSetDevice(device));
+    OVS_HIP_TRY_RAW(w->res.stream(&w->stream));
     const size_t T = (size_t)max_targets, Q = (size_t)max_queries, M = std::max(T, Q);
-    CREATE_TRY(hipMalloc(&w->d_cell_of, sizeof(int32_t) * T));
-    CREATE_TRY(hipMalloc(&w->d_cell_start, sizeof(int32_t) * (kMaxGridCells + 1)));
-    CREATE_TRY(hipMalloc(&w->d_items, sizeof(int32_t) * T));
-    CREATE_TRY(hipMalloc(&w->d_counts, sizeof(uint32_t) * (Q + 1)));
-    CREATE_TRY(hipMalloc(&w->d_offsets, sizeof(uint32_t) * (Q + 1)));
-    CREATE_TRY(hipMalloc(&w->d_keys, sizeof(uint32_t) * (size_t)max_entries));
+    OVS_HIP_TRY_RAW(w->res.dev(&w->d_cell_of, sizeof(int32_t) * T));
+    OVS_HIP_TRY_RAW(w->res.dev(&w->d_cell_start, sizeof(int32_t) * (kMaxGridCells + 1)));
+    OVS_HIP_TRY_RAW(w->res.dev(&w->d_items, sizeof(int32_t) * T));
+    OVS_HIP_TRY_RAW(w->res.dev(&w->d_counts, sizeof(uint32_t) * (Q + 1)));
+    OVS_HIP_TRY_RAW(w->res.dev(&w->d_offsets, sizeof(uint32_t) * (Q + 1)));
+    OVS_HIP_TRY_RAW(w->res.dev(&w->d_keys, sizeof(uint32_t) * (size_t)max_entries));
     // result block: [0] overflow flag, [1..4] counts ([1] result count, [2] per-direction scratch count), [8..] assigned
-    CREATE_TRY(hipMalloc(&w->d_res_block, sizeof(int32_t) * (8 + M)));
+    OVS_HIP_TRY_RAW(w->res.dev(&w->d_res_block, sizeof(int32_t) * (8 + M)));
     w->d_overflow = w->d_res_block;
     w->d_num = reinterpret_cast<int32_t*>(w->d_res_block) + 1;
     w->d_assigned = reinterpret_cast<int32_t*>(w->d_res_block) + 8;
-    CREATE_TRY(hipMemset(w->d_res_block, 0, sizeof(int32_t) * 8));
-    CREATE_TRY(hipHostMalloc(reinterpret_cast<void**>(&w->h_res), sizeof(int32_t) * (8 + M), hipHostMallocDefault));
+    OVS_HIP_TRY_RAW(hipMemset(w->d_res_block, 0, sizeof(int32_t) * 8));
+    OVS_HIP_TRY_RAW(w->res.pinned(&w->h_res, sizeof(int32_t) * (8 + M)));
     // The staging arena holds every array of ONE call, each aligned to 256 bytes, so it is sized for the entry point that stages the most with
     // n == max_targets and m == max_queries. Which one that is depends on T : Q, hence three sums (every other entry point stages a subset of
     // the first): the host form of projection::match_frame_and_keyframe (with the stereo_x_right that match_current_and_last_frames adds),
@@ -1931,21 +1924,14 @@ ovs_status ovs_wmatcher_create(int32_t max_targets, int32_t max_queries, int32_t
                                        + sizeof(int32_t))      // the one-way result
                               + 14 * 256;
     w->stage_cap = std::max(cap_window, std::max(cap_bow, cap_mutual));
-    CREATE_TRY(hipHostMalloc(reinterpret_cast<void**>(&w->h_stage), w->stage_cap, hipHostMallocDefault));
-    CREATE_TRY(hipMalloc(&w->d_stage, w->stage_cap));
-#undef CREATE_TRY
-    *out = w;
+    OVS_HIP_TRY_RAW(w->res.pinned(&w->h_stage, w->stage_cap));
+    OVS_HIP_TRY_RAW(w->res.dev(&w->d_stage, w->stage_cap));
+    *out = owner.release();
     return OVS_OK;
 }
 
 ovs_status ovs_wmatcher_destroy(ovs_wmatcher* w) {
     if (!w) return OVS_OK;
-    if (w->stream) hipStreamSynchronize(w->stream);
-    if (w->h_res) hipHostFree(w->h_res);
-    if (w->h_stage) hipHostFree(w->h_stage);
-    void* ptrs[] = {w->d_cell_of, w->d_cell_start, w->d_items, w->d_counts, w->d_offsets, w->d_keys, w->d_res_block, w->d_stage};
-    for (void* p : ptrs) hipFree(p);
-    if (w->stream) hipStreamDestroy(w->stream);
     delete w;
     return OVS_OK;
 }
@@ -2029,7 +2015,6 @@ ovs_status ovs_assign_keypoints_to_grid(ovs_wmatcher* w, const ovs_grid_params* 
 ovs_status ovs_frame_dev_destroy(ovs_frame_dev* f) {
     if (!f) return OVS_OK;
     if (f->arena) g_frame_pool.give(f->device, f->arena_bytes, f->arena);
-    if (f->d_bearings) (void)hipFree(f->d_bearings);
     delete f;
     return OVS_OK;
 }
@@ -2041,7 +2026,8 @@ ovs_status ovs_frame_dev_create(int32_t device, const ovs_grid_params* gp, const
     if (!grid_params_ok(gp)) return OVS_ERR_INVALID;
     if (ovs_device_count() <= device || device < 0) return OVS_ERR_NO_DEVICE;
     OVS_HIP_TRY(hipSetDevice(device));
-    ovs_frame_dev* f = new (std::nothrow) ovs_frame_dev();
+    std::unique_ptr<ovs_frame_dev, decltype(&ovs_frame_dev_destroy)> owner(new (std::nothrow) ovs_frame_dev(), &ovs_frame_dev_destroy);
+    ovs_frame_dev* const f = owner.get();
     if (!f) return OVS_ERR_INVALID;
     f->device = device;
     f->n = n;
@@ -2059,7 +2045,6 @@ ovs_status ovs_frame_dev_create(int32_t device, const ovs_grid_params* gp, const
         const hipError_t e = hipMalloc(&f->arena, f->arena_bytes);
         if (e != hipSuccess) {
             ovs::set_last_error("hipMalloc(frame arena)", e);
-            delete f;
             return OVS_ERR_HIP;
         }
     }
@@ -2070,46 +2055,29 @@ ovs_status ovs_frame_dev_create(int32_t device, const ovs_grid_params* gp, const
     f->d_items = reinterpret_cast<int32_t*>(f->arena + o_items);
     f->d_cell_start = reinterpret_cast<int32_t*>(f->arena + o_start);
     static thread_local FrameStage st;
-    ovs_status rc = OVS_ERR_HIP;
-    hipError_t er = hipSuccess;
-    do {
-#define F_TRY(expr)                           \
-    if ((er = (expr)) != hipSuccess) {        \
-        ovs::set_last_error(#expr, er);       \
-        break;                                \
+    if (st.device != device) {
+        (void)st.res.drop(&st.stream);
+        st.device = device;
     }
-        if (st.device != device) {
-            if (st.stream) (void)hipStreamDestroy(st.stream);
-            st.stream = nullptr;
-            st.device = device;
-        }
-        if (!st.stream) F_TRY(hipStreamCreateWithFlags(&st.stream, hipStreamNonBlocking));
-        // the three arrays keep their arena offsets in the staging buffer, so ONE copy of [0, end of the last array) uploads them
-        const size_t up_bytes = n ? (stereo_x_right ? o_xr + 4 * (size_t)n : o_desc + 32 * (size_t)n) : 0;
-        if (st.cap < up_bytes) {
-            if (st.h) (void)hipHostFree(st.h);
-            st.h = nullptr;
-            st.cap = 0;
-            const size_t want = std::max(up_bytes, al256(o_xr + 4 * (size_t)4096 * 4));
-            F_TRY(hipHostMalloc(reinterpret_cast<void**>(&st.h), want, hipHostMallocDefault));
-            st.cap = want;
-        }
-        if (n) {
-            std::memcpy(st.h + o_kps, undist_kps, sizeof(ovs_keypoint) * (size_t)n);
-            std::memcpy(st.h + o_desc, desc, 32 * (size_t)n);
-            if (stereo_x_right) std::memcpy(st.h + o_xr, stereo_x_right, 4 * (size_t)n);
-            F_TRY(hipMemcpyAsync(f->arena, st.h, up_bytes, hipMemcpyHostToDevice, st.stream));
-        }
-        F_TRY(launch_grid_assign(f->d_kps, n, f->gp, f->d_cell_of, f->d_cell_start, f->d_items, st.stream));
-        F_TRY(hipStreamSynchronize(st.stream));   // the handle is used from other streams afterwards
-        rc = OVS_OK;
-#undef F_TRY
-    } while (0);
-    if (rc != OVS_OK) {
-        ovs_frame_dev_destroy(f);
-        return rc;
+    if (!st.stream) OVS_HIP_TRY_RAW(st.res.stream(&st.stream));
+    // the three arrays keep their arena offsets in the staging buffer, so ONE copy of [0, end of the last array) uploads them
+    const size_t up_bytes = n ? (stereo_x_right ? o_xr + 4 * (size_t)n : o_desc + 32 * (size_t)n) : 0;
+    if (st.cap < up_bytes) {
+        (void)st.res.drop(&st.h);
+        st.cap = 0;
+        const size_t want = std::max(up_bytes, al256(o_xr + 4 * (size_t)4096 * 4));
+        OVS_HIP_TRY_RAW(st.res.pinned(&st.h, want));
+        st.cap = want;
     }
-    *out = f;
+    if (n) {
+        std::memcpy(st.h + o_kps, undist_kps, sizeof(ovs_keypoint) * (size_t)n);
+        std::memcpy(st.h + o_desc, desc, 32 * (size_t)n);
+        if (stereo_x_right) std::memcpy(st.h + o_xr, stereo_x_right, 4 * (size_t)n);
+        OVS_HIP_TRY_RAW(hipMemcpyAsync(f->arena, st.h, up_bytes, hipMemcpyHostToDevice, st.stream));
+    }
+    OVS_HIP_TRY_RAW(launch_grid_assign(f->d_kps, n, f->gp, f->d_cell_of, f->d_cell_start, f->d_items, st.stream));
+    OVS_HIP_TRY_RAW(hipStreamSynchronize(st.stream));   // the handle is used from other streams afterwards
+    *out = owner.release();
     return OVS_OK;
 }
 
@@ -2121,7 +2089,7 @@ ovs_status ovs_frame_dev_attach_bearings(ovs_frame_dev* f, const double* bearing
     if (!f || (f->n > 0 && !bearings)) return OVS_ERR_INVALID;
     if (f->n == 0) return OVS_OK;
     OVS_HIP_TRY(hipSetDevice(f->device));
-    if (!f->d_bearings) OVS_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&f->d_bearings), sizeof(double) * 3 * (size_t)f->cap));
+    if (!f->d_bearings) OVS_HIP_TRY(f->res.dev(&f->d_bearings, sizeof(double) * 3 * (size_t)f->cap));
     OVS_HIP_TRY(hipMemcpy(f->d_bearings, bearings, sizeof(double) * 3 * (size_t)f->n, hipMemcpyHostToDevice));
     return OVS_OK;
 }

@@ -6,11 +6,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
 
 #include "ovs_common.h"
+#include "owned_internal.inc"
 
 namespace ovs {
 
@@ -270,6 +272,7 @@ struct ovs_orb {
     ovs_orb_params p;
     int device = 0;
     int max_rows = 0, max_cols = 0, max_batch = 0;
+    Owned res;   // every stream, event, device and pinned block below, the lazily allocated ones included
     hipStream_t stream = nullptr;
     // A0 tables
     std::vector<float> sf, isf, ls, ils;
@@ -363,6 +366,12 @@ struct ovs_orb {
     hipStream_t aux_stream = nullptr;
     hipEvent_t ev_aux_fork = nullptr, ev_aux_join = nullptr;
     StageProfiler<1> prof_aux;
+    ~ovs_orb() {
+        res.clear();   // drains the streams the profilers' events were recorded on
+        prof_aux.destroy();
+        prof.destroy();
+        for (auto& ps : prof_sub) ps.destroy();
+    }
 };
 
 namespace {
@@ -734,7 +743,8 @@ ovs_status ovs_orb_create(const ovs_orb_params* params, int32_t max_rows, int32_
         return OVS_ERR_INVALID;
     *out = nullptr;
     if (ovs_device_count() <= device || device < 0) return OVS_ERR_NO_DEVICE;
-    ovs_orb* h = new (std::nothrow) ovs_orb();
+    std::unique_ptr<ovs_orb> owner(new (std::nothrow) ovs_orb());
+    ovs_orb* const h = owner.get();
     if (!h) return OVS_ERR_INVALID;
     h->p = *params;
     h->device = device;
@@ -746,21 +756,9 @@ ovs_status ovs_orb_create(const ovs_orb_params* params, int32_t max_rows, int32_
     std::vector<ResizeTap> taps;
     std::vector<CellDesc> cells_max;
     size_t pyr_bytes, cand_entries, node_entries;
-    if (!build_geometry(h, max_rows, max_cols, geo, taps, pyr_bytes, cand_entries, node_entries, &cells_max)) {
-        delete h;
-        return OVS_ERR_INVALID;
-    }
-#define CREATE_TRY(expr)                       \
-    do {                                       \
-        hipError_t _e = (expr);                \
-        if (_e != hipSuccess) {                \
-            ovs::set_last_error(#expr, _e);    \
-            ovs_orb_destroy(h);                \
-            return OVS_ERR_HIP;                \
-        }                                      \
-    } while (0)
-    CREATE_TRY(hipSetDevice(device));
-    CREATE_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    if (!build_geometry(h, max_rows, max_cols, geo, taps, pyr_bytes, cand_entries, node_entries, &cells_max)) return OVS_ERR_INVALID;
+    OVS_HIP_TRY_RAW(hipSetDevice(device));
+    OVS_HIP_TRY_RAW(h->res.stream(&h->stream));
     const int L = params->num_levels;
     const size_t B = (size_t)max_batch;
     h->d.pyr_frame_bytes = (pyr_bytes + 255) & ~(size_t)255;
@@ -785,24 +783,24 @@ ovs_status ovs_orb_create(const ovs_orb_params* params, int32_t max_rows, int32_
     h->d.node_frame_entries = node_entries;
     h->taps_cap = taps.size() + 64;
     h->kps_cap = (size_t)h->out_cap_variant[1];
-    CREATE_TRY(hipMalloc(&h->d_geo, sizeof(FrameGeo)));
-    CREATE_TRY(hipMalloc(&h->d_taps, h->taps_cap * sizeof(ResizeTap)));
+    OVS_HIP_TRY_RAW(h->res.dev(&h->d_geo, sizeof(FrameGeo)));
+    OVS_HIP_TRY_RAW(h->res.dev(&h->d_taps, h->taps_cap * sizeof(ResizeTap)));
     h->cells_cap = cells_max.size() + 64;   // (the cell count is monotone in rows and cols: the largest image has the most cells)
-    CREATE_TRY(hipMalloc(&h->d_cells, h->cells_cap * sizeof(CellDesc)));
+    OVS_HIP_TRY_RAW(h->res.dev(&h->d_cells, h->cells_cap * sizeof(CellDesc)));
     h->chain_cap = (size_t)L * ((size_t)(max_cols + 127) / 128 + (size_t)(max_rows + 95) / 96 + 2);   // (the tile grid is monotone in rows and cols)
-    CREATE_TRY(hipMalloc(&h->d_chain, h->chain_cap * sizeof(ChainSpan)));
+    OVS_HIP_TRY_RAW(h->res.dev(&h->d_chain, h->chain_cap * sizeof(ChainSpan)));
     h->pair_cap = (size_t)L * ((size_t)(max_cols + 127) / 128 + (size_t)(max_rows + 31) / 32 + 2);
-    CREATE_TRY(hipMalloc(&h->d_pair, h->pair_cap * sizeof(PairSpan)));
+    OVS_HIP_TRY_RAW(h->res.dev(&h->d_pair, h->pair_cap * sizeof(PairSpan)));
     for (int l = 0; l < OVS_MAX_LEVELS; ++l) h->pair_off[l] = h->htab_off[l] = -1;
     h->htaps_cap = h->taps_cap;   // one record per column pair of every level: fewer than there are taps
-    CREATE_TRY(hipMalloc(&h->d_htaps, h->htaps_cap * sizeof(HTapRec)));
-    CREATE_TRY(hipMalloc(&h->d.pyr, std::max<size_t>(h->d.pyr_frame_bytes * B, 256)));
-    CREATE_TRY(hipMalloc(&h->d.cand, std::max<size_t>(cand_entries * B * sizeof(uint64_t), 256)));
-    CREATE_TRY(hipMalloc(&h->d.cand_count, sizeof(uint32_t) * B * L));
-    CREATE_TRY(hipMalloc(&h->d.nodes, std::max<size_t>(node_entries * B * 16, 256)));
-    CREATE_TRY(hipMalloc(&h->d.lvl_kps, std::max<size_t>(h->kps_cap * B * sizeof(uint64_t), 256)));
-    CREATE_TRY(hipMalloc(&h->d.lvl_count, sizeof(uint32_t) * B * L));
-    CREATE_TRY(hipMemset(h->d.lvl_count, 0, sizeof(uint32_t) * B * L));
+    OVS_HIP_TRY_RAW(h->res.dev(&h->d_htaps, h->htaps_cap * sizeof(HTapRec)));
+    OVS_HIP_TRY_RAW(h->res.dev(&h->d.pyr, std::max<size_t>(h->d.pyr_frame_bytes * B, 256)));
+    OVS_HIP_TRY_RAW(h->res.dev(&h->d.cand, std::max<size_t>(cand_entries * B * sizeof(uint64_t), 256)));
+    OVS_HIP_TRY_RAW(h->res.dev(&h->d.cand_count, sizeof(uint32_t) * B * L));
+    OVS_HIP_TRY_RAW(h->res.dev(&h->d.nodes, std::max<size_t>(node_entries * B * 16, 256)));
+    OVS_HIP_TRY_RAW(h->res.dev(&h->d.lvl_kps, std::max<size_t>(h->kps_cap * B * sizeof(uint64_t), 256)));
+    OVS_HIP_TRY_RAW(h->res.dev(&h->d.lvl_count, sizeof(uint32_t) * B * L));
+    OVS_HIP_TRY_RAW(hipMemset(h->d.lvl_count, 0, sizeof(uint32_t) * B * L));
     h->d.geo = h->d_geo;
     h->d.taps = h->d_taps;
     h->d.cells = h->d_cells;
@@ -811,26 +809,21 @@ ovs_status ovs_orb_create(const ovs_orb_params* params, int32_t max_rows, int32_
     // one contiguous device output block [counts | keypoints | descriptors] so that ONE D2H brings a frame's results back; allocated
     // for the larger of the two capacities, laid out (and copied) for the current one
     const size_t out_block_alloc = ((16 + sizeof(ovs_keypoint) * (size_t)h->out_cap_variant[1] + 31) & ~(size_t)31) + (size_t)32 * h->out_cap_variant[1];
-    {
-        uint8_t* blk = nullptr;
-        CREATE_TRY(hipMalloc(&blk, out_block_alloc));
-        h->d_out_counts = reinterpret_cast<int32_t*>(blk);
-        h->d_out_kps = reinterpret_cast<ovs_keypoint*>(blk + 16);
-    }
+    OVS_HIP_TRY_RAW(h->res.dev(&h->d_out_counts, out_block_alloc));
+    h->d_out_kps = reinterpret_cast<ovs_keypoint*>(reinterpret_cast<uint8_t*>(h->d_out_counts) + 16);
     h->set_out_layout();
-    CREATE_TRY(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-    CREATE_TRY(hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking));
-    CREATE_TRY(hipEventCreateWithFlags(&h->ev_aux_fork, hipEventDisableTiming));
-    CREATE_TRY(hipEventCreateWithFlags(&h->ev_aux_join, hipEventDisableTiming));
+    OVS_HIP_TRY_RAW(h->res.stream(&h->copy_stream));
+    OVS_HIP_TRY_RAW(h->res.stream(&h->aux_stream));
+    OVS_HIP_TRY_RAW(h->res.event(&h->ev_aux_fork, hipEventDisableTiming));
+    OVS_HIP_TRY_RAW(h->res.event(&h->ev_aux_join, hipEventDisableTiming));
     for (auto& sl : h->slot) {
-        CREATE_TRY(hipMalloc(&sl.d_img, h->img_pitch * max_rows));
-        CREATE_TRY(hipHostMalloc(&sl.h_in, h->img_pitch * max_rows, hipHostMallocDefault));
-        CREATE_TRY(hipHostMalloc(&sl.h_out, out_block_alloc, hipHostMallocDefault));
-        CREATE_TRY(hipEventCreateWithFlags(&sl.ev_h2d, hipEventDisableTiming));
-        CREATE_TRY(hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming));
+        OVS_HIP_TRY_RAW(h->res.dev(&sl.d_img, h->img_pitch * max_rows));
+        OVS_HIP_TRY_RAW(h->res.pinned(&sl.h_in, h->img_pitch * max_rows));
+        OVS_HIP_TRY_RAW(h->res.pinned(&sl.h_out, out_block_alloc));
+        OVS_HIP_TRY_RAW(h->res.event(&sl.ev_h2d, hipEventDisableTiming));
+        OVS_HIP_TRY_RAW(h->res.event(&sl.ev_done, hipEventDisableTiming));
     }
-#undef CREATE_TRY
-    *out = h;
+    *out = owner.release();
     return OVS_OK;
 }
 
@@ -838,57 +831,6 @@ int32_t ovs_orb_device(const ovs_orb* h) { return ovs::orb_device(h); }
 
 ovs_status ovs_orb_destroy(ovs_orb* h) {
     if (!h) return OVS_OK;
-    if (h->stream) hipStreamSynchronize(h->stream);
-    hipFree(h->d_geo);
-    hipFree(h->d_taps);
-    hipFree(h->d_cells);
-    hipFree(h->d_chain);
-    hipFree(h->d_pair);
-    hipFree(h->d_htaps);
-    hipFree(h->d.pyr);
-    hipFree(h->d.cand);
-    hipFree(h->d.cand_count);
-    hipFree(h->d.nodes);
-    hipFree(h->d.lvl_kps);
-    hipFree(h->d.lvl_count);
-    if (h->copy_stream) hipStreamSynchronize(h->copy_stream);
-    hipFree(h->pair.d_img);
-    hipFree(h->pair.d_mask);
-    hipFree(h->pair.d_out);
-    if (h->pair.h_out) hipHostFree(h->pair.h_out);
-    if (h->pair.ev_h2d) hipEventDestroy(h->pair.ev_h2d);
-    for (auto& sl : h->slot) {
-        hipFree(sl.d_img);
-        hipFree(sl.d_mask);
-        if (sl.h_in) hipHostFree(sl.h_in);
-        if (sl.h_mask) hipHostFree(sl.h_mask);
-        if (sl.h_out) hipHostFree(sl.h_out);
-        if (sl.h_pyr) hipHostFree(sl.h_pyr);
-        if (sl.ev_h2d) hipEventDestroy(sl.ev_h2d);
-        if (sl.ev_done) hipEventDestroy(sl.ev_done);
-        for (auto& e : sl.t)
-            if (e) hipEventDestroy(e);
-    }
-    hipFree(h->d_out_counts);   // base of the [counts | keypoints | descriptors] block
-    if (h->aux_stream) {
-        hipStreamSynchronize(h->aux_stream);
-        hipStreamDestroy(h->aux_stream);
-    }
-    if (h->ev_aux_fork) hipEventDestroy(h->ev_aux_fork);
-    if (h->ev_aux_join) hipEventDestroy(h->ev_aux_join);
-    h->prof_aux.destroy();
-    if (h->copy_stream) hipStreamDestroy(h->copy_stream);
-    h->prof.destroy();
-    for (int k = 0; k < ovs_orb::kMaxSub; ++k) {
-        h->prof_sub[k].destroy();
-        if (h->sub_stream[k]) {
-            hipStreamSynchronize(h->sub_stream[k]);
-            hipStreamDestroy(h->sub_stream[k]);
-        }
-        if (h->ev_join[k]) hipEventDestroy(h->ev_join[k]);
-    }
-    if (h->ev_fork) hipEventDestroy(h->ev_fork);
-    if (h->stream) hipStreamDestroy(h->stream);
     delete h;
     return OVS_OK;
 }
@@ -962,6 +904,8 @@ ovs_status ovs_debug_inject_hip_failures(int32_t skip_calls, int32_t n_calls) {
     return OVS_OK;
 }
 
+int64_t ovs_debug_live_resources(void) { return ovs::g_live_resources.load(std::memory_order_relaxed); }
+
 ovs_status ovs_orb_set_fast_split(ovs_orb* h, int32_t enable) {
     if (!h) return OVS_ERR_INVALID;
     h->fast_split = enable != 0;
@@ -988,10 +932,10 @@ ovs_status ovs_orb_set_pipeline(ovs_orb* h, int32_t n_sub) {
     if (!h || n_sub < 1 || n_sub > ovs_orb::kMaxSub) return OVS_ERR_INVALID;
     OVS_HIP_TRY(hipSetDevice(h->device));
     if (n_sub > 1) {
-        if (!h->ev_fork) OVS_HIP_TRY(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+        if (!h->ev_fork) OVS_HIP_TRY(h->res.event(&h->ev_fork, hipEventDisableTiming));
         for (int k = 0; k < n_sub; ++k) {
-            if (!h->sub_stream[k]) OVS_HIP_TRY(hipStreamCreateWithFlags(&h->sub_stream[k], hipStreamNonBlocking));
-            if (!h->ev_join[k]) OVS_HIP_TRY(hipEventCreateWithFlags(&h->ev_join[k], hipEventDisableTiming));
+            if (!h->sub_stream[k]) OVS_HIP_TRY(h->res.stream(&h->sub_stream[k]));
+            if (!h->ev_join[k]) OVS_HIP_TRY(h->res.event(&h->ev_join[k], hipEventDisableTiming));
             if (h->prof.enabled) OVS_HIP_TRY(h->prof_sub[k].ensure());
         }
     }
@@ -1054,7 +998,7 @@ ovs_status ovs_orb_extract_submit(ovs_orb* h, const uint8_t* image, int32_t rows
     const bool timed = h->prof.enabled;
     if (timed)
         for (auto& e : sl.t)
-            if (!e) OVS_HIP_TRY(hipEventCreate(&e));
+            if (!e) OVS_HIP_TRY(h->res.event(&e, hipEventDefault));
     // the candidate counters are cleared while the image is still on its way (a 4 us fill kernel that used to run between the upload and the pyramid)
     OVS_HIP_TRY(hipMemsetAsync(h->d.cand_count, 0, sizeof(uint32_t) * (size_t)h->geo.num_levels, s));
     h->cand_count_cleared = true;
@@ -1070,8 +1014,8 @@ ovs_status ovs_orb_extract_submit(ovs_orb* h, const uint8_t* image, int32_t rows
     st = upload_plane(h, image, stride, rows, cols, sl.h_in, sl.d_img);
     if (st != OVS_OK) return st;
     if (mask) {
-        if (!sl.d_mask) OVS_HIP_TRY(hipMalloc(&sl.d_mask, h->img_pitch * h->max_rows));
-        if (!sl.h_mask) OVS_HIP_TRY(hipHostMalloc(&sl.h_mask, h->img_pitch * h->max_rows, hipHostMallocDefault));
+        if (!sl.d_mask) OVS_HIP_TRY(h->res.dev(&sl.d_mask, h->img_pitch * h->max_rows));
+        if (!sl.h_mask) OVS_HIP_TRY(h->res.pinned(&sl.h_mask, h->img_pitch * h->max_rows));
         st = upload_plane(h, mask, mask_stride, rows, cols, sl.h_mask, sl.d_mask);
         if (st != OVS_OK) return st;
     }
@@ -1084,7 +1028,7 @@ ovs_status ovs_orb_extract_submit(ovs_orb* h, const uint8_t* image, int32_t rows
     if (timed) OVS_HIP_TRY(hipEventRecord(sl.t[2], s));
     sl.has_pyr = false;
     if (h->host_pyr && h->p.num_levels > 1) {
-        if (!sl.h_pyr) OVS_HIP_TRY(hipHostMalloc(&sl.h_pyr, h->d.pyr_frame_bytes, hipHostMallocDefault));
+        if (!sl.h_pyr) OVS_HIP_TRY(h->res.pinned(&sl.h_pyr, h->d.pyr_frame_bytes));
         const LevelGeo& gl = h->geo.lv[h->p.num_levels - 1];
         const size_t used = (size_t)gl.plane_off + (size_t)gl.pitch * gl.rows;   // levels 1 .. L-1 are contiguous in the frame block
         OVS_HIP_TRY(hipMemcpyAsync(sl.h_pyr, h->d.pyr, used, hipMemcpyDeviceToHost, s));
@@ -1155,17 +1099,16 @@ ovs_status ovs_orb_extract_pair(ovs_orb* h, const uint8_t* left, const uint8_t* 
     ovs_orb::PairBuf& pb = h->pair;
     if (!pb.d_img) {
         pb.frame_bytes = h->img_pitch * (size_t)h->max_rows;
-        OVS_HIP_TRY(hipMalloc(&pb.d_img, 2 * pb.frame_bytes));
-        OVS_HIP_TRY(hipEventCreateWithFlags(&pb.ev_h2d, hipEventDisableTiming));
+        OVS_HIP_TRY(h->res.dev(&pb.d_img, 2 * pb.frame_bytes));
+        OVS_HIP_TRY(h->res.event(&pb.ev_h2d, hipEventDisableTiming));
     }
     if (pb.cap < h->out_cap_variant[1]) {   // [counts | keypoints of both frames | descriptors of both frames], for the larger capacity
-        if (pb.d_out) (void)hipFree(pb.d_out);
-        if (pb.h_out) (void)hipHostFree(pb.h_out);
-        pb.d_out = pb.h_out = nullptr;
+        (void)h->res.drop(&pb.d_out);
+        (void)h->res.drop(&pb.h_out);
         pb.cap = h->out_cap_variant[1];
         const size_t bytes = 32 + ((2 * sizeof(ovs_keypoint) * (size_t)pb.cap + 31) & ~(size_t)31) + (size_t)64 * pb.cap;
-        OVS_HIP_TRY(hipMalloc(&pb.d_out, bytes));
-        OVS_HIP_TRY(hipHostMalloc(&pb.h_out, bytes, hipHostMallocDefault));
+        OVS_HIP_TRY(h->res.dev(&pb.d_out, bytes));
+        OVS_HIP_TRY(h->res.pinned(&pb.h_out, bytes));
     }
     const int fcap = h->out_cap;   // per frame, current variant
     pb.off_kps = 32;
@@ -1176,7 +1119,7 @@ ovs_status ovs_orb_extract_pair(ovs_orb* h, const uint8_t* left, const uint8_t* 
     if (st == OVS_OK) st = upload_plane(h, right, stride, rows, cols, nullptr, pb.d_img + pb.frame_bytes);
     if (st != OVS_OK) return st;
     if (mask_left) {
-        if (!pb.d_mask) OVS_HIP_TRY(hipMalloc(&pb.d_mask, 2 * pb.frame_bytes));
+        if (!pb.d_mask) OVS_HIP_TRY(h->res.dev(&pb.d_mask, 2 * pb.frame_bytes));
         st = upload_plane(h, mask_left, mask_stride, rows, cols, nullptr, pb.d_mask);
         if (st == OVS_OK) st = upload_plane(h, mask_right, mask_stride, rows, cols, nullptr, pb.d_mask + pb.frame_bytes);
         if (st != OVS_OK) return st;

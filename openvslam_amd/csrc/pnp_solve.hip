@@ -574,7 +574,6 @@ __global__ __launch_bounds__(64) void k_pnp_finish(const uint8_t* __restrict__ b
 
 struct ovs_pnp : ransac_handle {
     int32_t* d_inlier_idx = nullptr;   // [max_total_matches] the winner's inliers by rank, per problem at its offset
-    ~ovs_pnp() { hipFree(d_inlier_idx); }
 };
 
 extern "C" {
@@ -584,13 +583,10 @@ ovs_status ovs_pnp_create(int32_t device, int32_t max_problems, int32_t max_tota
                                         (size_t)max_problems * 64,   // 64 iterations per problem without growing
                                         kModelDoubles, out);
     if (st != OVS_OK) return st;
-    const hipError_t e = ovs::fault_filter(hipMalloc(&(*out)->d_inlier_idx, sizeof(int32_t) * (size_t)max_total_matches));
-    if (e != hipSuccess) {
-        ovs::set_last_error("hipMalloc(d_inlier_idx)", e);
-        delete *out;
-        *out = nullptr;
-        return OVS_ERR_HIP;
-    }
+    std::unique_ptr<ovs_pnp> owner(*out);
+    *out = nullptr;
+    OVS_HIP_TRY(owner->res.dev(&owner->d_inlier_idx, sizeof(int32_t) * (size_t)max_total_matches));
+    *out = owner.release();
     return OVS_OK;
 }
 

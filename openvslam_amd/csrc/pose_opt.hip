@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "ovs_common.h"
+#include "owned_internal.inc"
 
 namespace ovs {
 
@@ -811,25 +812,20 @@ static ovs_status pose_optimize_host(int model, int32_t device, const double* po
         size_t cap = 0;
         int device = -1;
         unsigned int epoch0 = 0;   // the exchange words' flags of call c are epoch0 + 1 ..: + 4096 per call, so an earlier call's words never match
-        void release() {
-            if (p) (void)hipFree(p);
-            if (h) (void)hipHostFree(h);
-            if (stream) (void)hipStreamDestroy(stream);
-            p = h = nullptr;
-            stream = nullptr;
-            cap = 0;
-            device = -1;
-        }
-        ~Scratch() { release(); }
+        ovs::Owned res;
     };
     static thread_local Scratch scratch;
     if (scratch.device != device || scratch.cap < total) {
-        scratch.release();
+        (void)scratch.res.drop(&scratch.p);
+        (void)scratch.res.drop(&scratch.h);
+        (void)scratch.res.drop(&scratch.stream);
+        scratch.cap = 0;
+        scratch.device = -1;
         const size_t want = std::max<size_t>(total, (size_t)1 << 20);
-        OVS_HIP_TRY(hipMalloc(&scratch.p, want));
+        OVS_HIP_TRY(scratch.res.dev(&scratch.p, want));
         OVS_HIP_TRY(hipMemset(scratch.p, 0, want));   // (exchange flags of a fresh block: zero, which no epoch equals)
-        OVS_HIP_TRY(hipHostMalloc(&scratch.h, want, hipHostMallocDefault));
-        OVS_HIP_TRY(hipStreamCreateWithFlags(&scratch.stream, hipStreamNonBlocking));
+        OVS_HIP_TRY(scratch.res.pinned(&scratch.h, want));
+        OVS_HIP_TRY(scratch.res.stream(&scratch.stream));
         scratch.cap = want;
         scratch.device = device;
     }

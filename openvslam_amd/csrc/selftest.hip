@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "ovs_common.h"
+#include "owned_internal.inc"
 
 namespace ovs {
 
@@ -33,19 +34,13 @@ extern "C" ovs_status ovs_detmath_eval(int32_t device, int32_t fn, const double*
     if (hipSetDevice(device) != hipSuccess) return OVS_ERR_HIP;
     double *d_a = nullptr, *d_b = nullptr, *d_o = nullptr;
     const size_t bytes = (size_t)n * sizeof(double);
-    ovs_status st = OVS_ERR_HIP;
-    do {
-        if (hipMalloc(&d_a, bytes) != hipSuccess || hipMalloc(&d_o, bytes) != hipSuccess) break;
-        if (b && hipMalloc(&d_b, bytes) != hipSuccess) break;
-        if (hipMemcpy(d_a, a, bytes, hipMemcpyHostToDevice) != hipSuccess) break;
-        if (b && hipMemcpy(d_b, b, bytes, hipMemcpyHostToDevice) != hipSuccess) break;
-        ovs::k_detmath_eval<<<(n + 255) / 256, 256>>>(fn, d_a, d_b ? d_b : d_a, d_o, n);
-        if (hipGetLastError() != hipSuccess) break;
-        if (hipMemcpy(out, d_o, bytes, hipMemcpyDeviceToHost) != hipSuccess) break;
-        st = OVS_OK;
-    } while (false);
-    hipFree(d_a);
-    hipFree(d_b);
-    hipFree(d_o);
-    return st;
+    ovs::Owned tmp;
+    if (tmp.dev(&d_a, bytes) != hipSuccess || tmp.dev(&d_o, bytes) != hipSuccess) return OVS_ERR_HIP;
+    if (b && tmp.dev(&d_b, bytes) != hipSuccess) return OVS_ERR_HIP;
+    if (hipMemcpy(d_a, a, bytes, hipMemcpyHostToDevice) != hipSuccess) return OVS_ERR_HIP;
+    if (b && hipMemcpy(d_b, b, bytes, hipMemcpyHostToDevice) != hipSuccess) return OVS_ERR_HIP;
+    ovs::k_detmath_eval<<<(n + 255) / 256, 256>>>(fn, d_a, d_b ? d_b : d_a, d_o, n);
+    if (hipGetLastError() != hipSuccess) return OVS_ERR_HIP;
+    if (hipMemcpy(out, d_o, bytes, hipMemcpyDeviceToHost) != hipSuccess) return OVS_ERR_HIP;
+    return OVS_OK;
 }

@@ -9,11 +9,13 @@
 #include <cstdint>
 #include <cstring>
 #include <initializer_list>
+#include <memory>
 #include <mutex>
 
 #include <hip/hip_runtime.h>
 
 #include "ovs_common.h"
+#include "owned_internal.inc"
 
 namespace {
 
@@ -188,6 +190,7 @@ struct ransac_handle {
     int device = 0;
     int max_problems = 0, max_total_matches = 0;
     std::mutex mu;
+    ovs::Owned res;
     hipStream_t stream = nullptr;
     uint8_t *d_block = nullptr, *h_block = nullptr;   // the staged block (the solver's Layout) and its page-locked twin
     double* d_wave_models = nullptr;                  // [problem][wave] the model of the wave's best hypothesis; grows with problems x max_num_iter
@@ -197,24 +200,12 @@ struct ransac_handle {
     ResultRec *h_result = nullptr, *m_result = nullptr;
     uint8_t *h_flags = nullptr, *m_flags = nullptr;
 
-    ransac_handle() = default;
-    ransac_handle(const ransac_handle&) = delete;
-    ~ransac_handle() {
-        hipFree(d_block);
-        hipFree(d_wave_models);
-        if (h_block) hipHostFree(h_block);
-        if (h_result) hipHostFree(h_result);
-        if (h_flags) hipHostFree(h_flags);
-        if (stream) hipStreamDestroy(stream);
-    }
-
     // room for `records` models; the stream is idle: every call ends in a synchronise
     ovs_status reserve_models(size_t records) {
         if (records <= wave_models_cap) return OVS_OK;
-        if (d_wave_models) OVS_HIP_TRY(hipFree(d_wave_models));
-        d_wave_models = nullptr;
         wave_models_cap = 0;
-        OVS_HIP_TRY(hipMalloc(&d_wave_models, sizeof(double) * model_doubles * records));
+        if (d_wave_models) OVS_HIP_TRY(res.drop(&d_wave_models));
+        OVS_HIP_TRY(res.dev(&d_wave_models, sizeof(double) * model_doubles * records));
         wave_models_cap = records;
         return OVS_OK;
     }
@@ -229,31 +220,21 @@ ovs_status ransac_create(int32_t device, int32_t max_problems, int32_t max_total
     if (max_problems > 65535) return OVS_ERR_INVALID;   // a grid's y extent
     if (ovs_device_count() <= device || device < 0) return OVS_ERR_NO_DEVICE;
     OVS_HIP_TRY(hipSetDevice(device));
-    H* s = new H();
+    std::unique_ptr<H> owner(new H());
+    H* const s = owner.get();
     s->device = device;
     s->max_problems = max_problems;
     s->max_total_matches = max_total_matches;
     s->model_doubles = model_doubles;
-    hipError_t e = hipSuccess;
-#define D_TRY(expr)                                      \
-    if ((e = ovs::fault_filter(expr)) != hipSuccess) {   \
-        ovs::set_last_error(#expr, e);                   \
-        delete s;                                        \
-        return OVS_ERR_HIP;                              \
-    }
-    D_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    D_TRY(hipMalloc(&s->d_block, block_bytes));
-    if (s->reserve_models(initial_records) != OVS_OK) {
-        delete s;
-        return OVS_ERR_HIP;
-    }
-    D_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_block), block_bytes, hipHostMallocDefault));
-    D_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_result), sizeof(ResultRec) * (size_t)max_problems, hipHostMallocMapped));
-    D_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->m_result), s->h_result, 0));
-    D_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_flags), (size_t)max_total_matches, hipHostMallocMapped));
-    D_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->m_flags), s->h_flags, 0));
-#undef D_TRY
-    *out = s;
+    OVS_HIP_TRY(s->res.stream(&s->stream));
+    OVS_HIP_TRY(s->res.dev(&s->d_block, block_bytes));
+    if (s->reserve_models(initial_records) != OVS_OK) return OVS_ERR_HIP;
+    OVS_HIP_TRY(s->res.pinned(&s->h_block, block_bytes));
+    OVS_HIP_TRY(s->res.pinned(&s->h_result, sizeof(ResultRec) * (size_t)max_problems, hipHostMallocMapped));
+    OVS_HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->m_result), s->h_result, 0));
+    OVS_HIP_TRY(s->res.pinned(&s->h_flags, (size_t)max_total_matches, hipHostMallocMapped));
+    OVS_HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->m_flags), s->h_flags, 0));
+    *out = owner.release();
     return OVS_OK;
 }
 
