@@ -78,11 +78,15 @@ constexpr int kMaxSurvivors = 1024;   // NMS survivors are pairwise non-adjacent
 // ALU ~63 % busy (the "4 cycles per instruction, 0.76-0.78 of the issue slots" of rounds 3-4 read the SQ counters' quad-cycle quantisation as a
 // busy measure). The kernel is bound by neither the vector ALU nor LDS (~47 % busy, a third of it bank conflicts) nor HBM (0.9-1.2 TB/s) alone but
 // by the latency chain of a cell -- six LDS-only barriers, dependent LDS gathers of the exact scoring / NMS with 3-4x bank conflicts -- at the 28
-// waves per CU that 21 KB of LDS leave. Halving the pre-test's cycles, an eight-diameter pre-test (-22 %
+// waves per CU that 22 KB of LDS leave. Halving the pre-test's cycles, an eight-diameter pre-test (-22 %
 // candidates), 8 workgroups per CU (aliased LDS, 64 VGPRs) each moved the launch by < 3 %; the grouping + prefetch + single reservation
 // are worth ~6 % together (0.50 -> 0.47 ms per 64 frames).
-// LDS: raw tile 5.6 KB + R tile 5.6 KB + score map 4.75 KB + pooled list 4 KB + group buffer 1 KB = 21.1 KB -> 7 workgroups per CU (until late in
-// round 3: an 8 KB list for all 4096 pixels of a cell and a 2 KB buffer, 26.2 KB, six workgroups; see kListCap).
+// LDS: raw tile 5.6 KB + R tile 5.6 KB + score map 4.75 KB + pooled list 4 KB + flag words 1 KB + group buffer 1 KB = 22.1 KB -> 7 workgroups per
+// CU (until late in round 3: an 8 KB list for all 4096 pixels of a cell and a 2 KB buffer, 26.2 KB, six workgroups; see kListCap).
+// The list loop runs as often as a wave's fullest lane has candidates (8 times per wave on video with 11 of 64 lanes active,
+// tools/fast_list_model.py), so it only writes (thread << 5) | mask bit; the scoring pass, whose lanes are dense, turns an entry into position
+// and polarity flags with the owning thread's flag word (cflag) and writes it back for the NMS pass: 19 -> 6 VALU per loop iteration, + 16 per
+// scoring wave-pass, 14 % fewer VALU wave-instructions per launch.
 __device__ __forceinline__ uint32_t wave_prefix_incl(uint32_t v) {
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);    // row_shr:1
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);    // row_shr:2
@@ -204,8 +208,8 @@ __device__ __forceinline__ void glds4(const uint8_t* base, uint32_t voff, uint32
 __device__ __forceinline__ void wait_tile() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ uint32_t lds_addr(const void* p) { return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p; }
 
-// LDS per workgroup: raw tile 5.6 KB + R tile 5.6 KB + score map 4.75 KB + pooled list 4 KB + group buffer 1 KB = 21.1 KB, seven workgroups
-// per CU, 72 VGPRs. The next cell's tile is requested when the current cell's last tile read (the exact scoring; the NMS survivor list aliases
+// LDS per workgroup: raw tile 5.6 KB + R tile 5.6 KB + score map 4.75 KB + pooled list 4 KB + flag words 1 KB + group buffer 1 KB = 22.1 KB,
+// seven workgroups per CU (limit 23 405 B), 72 VGPRs. The next cell's tile is requested when the current cell's last tile read (the exact scoring; the NMS survivor list aliases
 // the R tile) is behind every wave, and lands under the cell's tail and the other six workgroups. (A second raw-tile buffer, requested a whole
 // cell ahead -- 26.7 KB, six workgroups per CU -- measured 5-10 % slower in round 4 and is gone.)
 // kTiming: wave 0 accumulates shader cycles per phase into tstats (tuning aid, OVS_FAST_TIMING).
@@ -217,7 +221,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) voi
     __shared__ __attribute__((aligned(16))) uint32_t tiles[1][kTileRowsMax][kTileWords];
     __shared__ __attribute__((aligned(16))) uint32_t smap[kSmapRows][kSmapWords];
     __shared__ __attribute__((aligned(16))) uint32_t rtile[kTileRowsMax][kTileWords];
-    __shared__ uint16_t clist[kListCap];                // pixels that passed the diameter test, (y << 8) | x, all four waves
+    __shared__ uint16_t clist[kListCap];                // pixels that passed the diameter test, all four waves: (thread << 5) | mask bit from
+                                                        // the list loop to the scoring pass, which rewrites it as (y << 8) | x | flags
+    __shared__ uint32_t cflag[256];                     // every thread's flag word (dmask after the fix-up) for the scoring pass's decode
     __shared__ uint32_t wgbuf[kWgSurvivors];            // (slot << 26) | (score << 12) | (y << 6) | x of the group's survivors not yet written out
     __shared__ uint32_t n_cand_wg, n_out, list_base;
 
@@ -446,12 +452,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) voi
                     uint32_t pos = wave_base + incl - n_mine;
                     // a wave whose range does not fit the list writes nothing: the cell then holds more than kListCap candidates in total and
                     // takes the exhaustive path below, which does not read the list (no per-entry bound check in the common case)
+                    // The loop runs as often as the wave's fullest lane has candidates (8 times per wave on video, 11 of 64 lanes active), so it
+                    // writes RAW entries, (thread << 5) | bit: position and flags are functions of (thread, bit, the thread's flag word) and are
+                    // worked out by the scoring pass, whose lanes are dense.
+                    cflag[tid] = dmask;
                     if (wave_base + wave_total <= (uint32_t)kListCap) {
+                        uint32_t tid5 = (uint32_t)tid << 5;
+                        asm volatile("" : "+v"(tid5));   // no instruction: keeps the shift out of the loop (hipcc rematerialises it per iteration)
                         while (cmask) {
-                            const int b = __ffs(cmask) - 1;
+                            const uint32_t b = (uint32_t)__builtin_ctz(cmask);
                             cmask &= cmask - 1;
-                            const uint32_t fl = (((dmask >> b) & 1u) << 6) | (((dmask >> (b + 4)) & 1u) << 7);
-                            clist[pos++] = (uint16_t)(((row0 + ((b >> 1) & 1)) << 8) | (c0 + 4 * (b & 1) + (b >> 3)) | fl);
+                            clist[pos++] = (uint16_t)(tid5 | b);
                         }
                     }
                 }
@@ -494,11 +505,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) voi
                 }
                 // ---- 3. exact S for the candidates, one per lane, into the score map: one polarity per candidate (both where both tests passed)
                 for (int i = tid; i < n_cand; i += 256) {
-                    const uint32_t e = clist[i];
-                    const int x = e & 63, y = e >> 8;
+                    // raw entry -> (y << 8) | x | flags, written back for the NMS pass (same i, behind barrier 3)
+                    const uint32_t raw = clist[i];
+                    const uint32_t pt = raw >> 5, b = raw & 31u;
+                    const uint32_t fw = cflag[pt] >> b;
+                    const int x = (int)(8u * (pt & 7u) + 4u * (b & 1u) + (b >> 3)), y = (int)(2u * (pt >> 3) + ((b >> 1) & 1u));
+                    const uint32_t e = ((uint32_t)y << 8) | (uint32_t)x | ((fw & 1u) << 6) | ((fw & 0x10u) << 3);
+                    clist[i] = (uint16_t)e;
                     uint32_t r[16], c;
                     load_ring(tbytes + y * (kTileWords * 4) + x + 3, r, c);
-                    const uint32_t flip = (e & 0x40u) ? 0xffu : 0u;
+                    uint32_t flip = (e & 0x40u) ? 0xffu : 0u;
+                    asm volatile("" : "+v"(flip));   // no instruction: with the value opaque the 17 flips are v_xor_b32, not 3-operand v_bitop3_b32
 #pragma unroll
                     for (int q = 0; q < 16; ++q) r[q] ^= flip;
                     c ^= flip;

@@ -1,6 +1,8 @@
 #!/bin/bash
 # PMC passes (SQ issue mix, SQ stalls, FETCH_SIZE) over the FAST kernel alone: tools/ab_extract.py's child (64 frames, 3 repetitions) under
 # rocprofv3, once per variant. Usage (GPU box, repo root): tools/gpu_fast_pmc.sh <tag> "<VAR=VAL,VAR=VAL>" ...
+# One counter group per run, kernel trace only. A pass that fails or runs into its time limit ends the script with that status: nothing more is
+# started on a card after a fault or a hang (the log of the failing pass is v<i>p<pass>.log in the output directory).
 tag=$1; shift
 export TMPDIR=/tmp
 out=$PWD/gpurun_out/$tag
@@ -15,7 +17,13 @@ for v in "$@"; do
       2) ctr="SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR GRBM_GUI_ACTIVE" ;;
       3) ctr="FETCH_SIZE" ;;
     esac
-    ( cd /tmp && env $envs OVS_AB_CHILD=1 timeout 300 rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $out/v${i}p${pass} -o p -- python $OLDPWD/tools/ab_extract.py 64 3 > $out/v${i}p${pass}.log 2>&1 )
+    ( cd /tmp && env $envs OVS_AB_CHILD=1 timeout -k 10 300 rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $out/v${i}p${pass} -o p -- python $OLDPWD/tools/ab_extract.py 64 3 > $out/v${i}p${pass}.log 2>&1 )
+    rc=$?
+    if [ $rc -ne 0 ]; then
+      echo "variant $i ($v) pass $pass: exit status $rc, stopping" | tee -a $out/summary.txt
+      tail -n 20 $out/v${i}p${pass}.log
+      exit $rc
+    fi
   done
   echo "== variant $i: $v" | tee -a $out/summary.txt
   python - $out $i <<'PY' | tee -a $out/summary.txt
