@@ -731,6 +731,39 @@ ovs_status ovs_pnp_solve_batch(ovs_pnp* s, int32_t n_problems, const int32_t* of
                                int32_t* out_valid, int32_t* out_best_iter, int32_t* out_num_inliers, double* out_rot_cw, double* out_trans_cw,
                                uint8_t* out_inlier_flags);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Sim3 transform optimiser for loop-candidate verification.  replaces: optimize::transform_optimizer::optimize(keyfrm_1, keyfrm_2,
+ *   matched_lms_in_keyfrm_2, Sim3_12, chi_sq) (src/openvslam/optimize/transform_optimizer.{h,cc}): the g2o graph of one Sim3 vertex and two
+ *   reprojection edges per match, two Levenberg-Marquardt rounds with Huber kernels and the chi-square classification between and after
+ *   them, for a BATCH of (keyframe 1, candidate keyframe 2) problems in ONE launch (rules 1 to 8).
+ * ovs_sim3opt_create: a handle for up to max_problems problems of max_total_matches matches together; one internal mutex serialises the
+ *   calls on a handle.
+ * ovs_sim3opt_optimize_batch: problem p owns matches [offsets[p], offsets[p + 1]) (offsets[0] = 0, non-decreasing). p1 / p2: 3 doubles per
+ *   match, the landmark in camera-1 / camera-2 coordinates (collected as sim3_solver's constructor does); obs1 / obs2: 2 doubles per match,
+ *   the undistorted keypoint of the landmark in keyframe 1 / 2; inv_sigma_sq_1 / _2: inv_level_sigma_sq[octave] of those keypoints, as
+ *   floats; cams_1 / cams_2: one camera per problem and side (model 0 reads fx fy cx cy, model 1 cols rows); rot_12_in (9, row-major),
+ *   trans_12_in (3), scale_12_in: the initial Sim3_12 per problem. fix_scale, chi_sq (upstream's caller passes 10) and num_iter (upstream's
+ *   constructor argument, default 10) hold for the whole call. Outputs per problem: num_inliers (optimize's return value), rot_12, trans_12,
+ *   scale_12 (the estimate; the input when fewer than 10 matches survive round 1, with num_inliers 0); outlier_flags: one byte per match,
+ *   1 where upstream nulls matched_lms_in_keyfrm_2. out_info: NULL, or 8 doubles per problem that localise a mismatch: iterations and trials
+ *   of round 1, the robust chi-square after it, the outliers after it, iterations, trials and robust chi-square of round 2, the last lambda.
+ *   Results are bit-exact functions of the inputs, whatever the problem's position in the batch. A problem without matches is not an error:
+ *   its result is 0 inliers. A match with a NaN or Inf in it is not an error either, and the call returns: the match is flagged, but its
+ *   terms make the sums of the problem's first round NaN, so that round accepts no step and classifies every match at the INPUT transform;
+ *   unless the input is already close, fewer than 10 survive and the problem's result is 0 inliers with the input returned (DESIGN.md 3.11
+ *   rule 8). Other problems of the batch are not affected. A caller that can meet such values filters them before the call.
+ * OVS_ERR_INVALID: a NULL required pointer (out_info may be NULL), offsets not starting at 0 or decreasing, an unknown camera model, non-finite
+ *   fx fy cx cy (model 0) or cols / rows < 1 (model 1), chi_sq not finite and positive, num_iter < 1. OVS_ERR_CAPACITY: more problems or
+ *   matches than the handle was created for (nothing is truncated, no output is written). Both are decided before any launch. */
+typedef struct ovs_sim3opt ovs_sim3opt;
+ovs_status ovs_sim3opt_create(int32_t device, int32_t max_problems, int32_t max_total_matches, ovs_sim3opt** out);
+ovs_status ovs_sim3opt_destroy(ovs_sim3opt* s);
+ovs_status ovs_sim3opt_optimize_batch(ovs_sim3opt* s, int32_t n_problems, const int32_t* offsets, const double* p1, const double* p2, const double* obs1,
+                                      const double* obs2, const float* inv_sigma_sq_1, const float* inv_sigma_sq_2, const ovs_camera* cams_1,
+                                      const ovs_camera* cams_2, const double* rot_12_in, const double* trans_12_in, const double* scale_12_in,
+                                      int32_t fix_scale, float chi_sq, int32_t num_iter, int32_t* out_num_inliers, double* out_rot_12, double* out_trans_12,
+                                      double* out_scale_12, uint8_t* out_outlier_flags, double* out_info);
+
 /* replaces: the optimisation inside  void optimize::local_bundle_adjuster::optimize(data::keyframe* curr_keyfrm, bool* const
  *               force_stop_flag) const  (src/openvslam/optimize/local_bundle_adjuster.{h,cc}): everything between the graph build and the
  * write-back, i.e. optimizer.optimize(num_first_iter) with Huber kernels (ONE delta per rig: setup_type 0 = Monocular -> sqrtf(5.99146f),
@@ -873,6 +906,9 @@ ovs_status ovs_projection_match_keyframes_mutually_f(ovs_wmatcher* w, const ovs_
 #define OVS_DETMATH_ATAN2 3   /* atan2(a, b) */
 #define OVS_DETMATH_SINF 4    /* float in, float out (widened): the OVS_VARIANT_TRIG = 1 steering */
 #define OVS_DETMATH_COSF 5
+#define OVS_DETMATH_SIN 6     /* double: the transform optimiser's exponential map (DESIGN.md 3.11 rule 3) */
+#define OVS_DETMATH_COS 7
+#define OVS_DETMATH_EXP 8
 ovs_status ovs_detmath_eval(int32_t device, int32_t fn, const double* a, const double* b, double* out, int32_t n);
 
 #ifdef __cplusplus

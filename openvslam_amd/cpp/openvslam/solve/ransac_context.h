@@ -1,5 +1,6 @@
-// What solve::sim3_solver and solve::pnp_solver share around their one ABI call: the process's device handle (created on first use,
-// enlarged when a batch outgrows it, dropped after a device failure) and the part of a solver's result that every RANSAC has.
+// What solve::sim3_solver, solve::pnp_solver and optimize::transform_optimizer share around their one ABI call: the process's device handle
+// (ransac_context: created on first use, enlarged when a batch outgrows it, dropped after a device failure) and, for the two RANSAC
+// solvers, the part of a result that every RANSAC has.
 // Failure policy: util/device_policy.h.
 #pragma once
 #include <ovslam_hip.h>

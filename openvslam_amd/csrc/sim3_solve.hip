@@ -269,26 +269,6 @@ __global__ __launch_bounds__(kFinishThreads) void k_sim3_finish(const uint8_t* _
 
 struct ovs_sim3 : ransac_handle {};
 
-namespace {
-
-bool camera_ok(const ovs_camera& c, CamRec* rec) {
-    rec->pad = 0;
-    rec->model = c.model;
-    if (c.model == 0) {
-        if (!std::isfinite(c.fx) || !std::isfinite(c.fy) || !std::isfinite(c.cx) || !std::isfinite(c.cy)) return false;
-        rec->a = c.fx, rec->b = c.fy, rec->c = c.cx, rec->d = c.cy;
-        return true;
-    }
-    if (c.model == 1) {
-        if (c.cols < 1 || c.rows < 1) return false;
-        rec->a = (double)c.cols, rec->b = (double)c.rows, rec->c = 0.0, rec->d = 0.0;
-        return true;
-    }
-    return false;
-}
-
-}   // namespace
-
 extern "C" {
 
 ovs_status ovs_sim3_create(int32_t device, int32_t max_problems, int32_t max_total_matches, ovs_sim3** out) {

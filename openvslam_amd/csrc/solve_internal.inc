@@ -2,8 +2,10 @@
 // the hypothesis key, the result record and its invalid form, the cyclic Jacobi rotation and Horn's quaternion form of the absolute
 // orientation. DESIGN.md 3.9 rule 2 fixes every operation; the units are built with -ffp-contract=off. On the host: ransac_handle, the
 // batch scaffold under both C ABIs (create, reserve_models, run_batch). A solver supplies its model, its two kernels, the Layout of its
-// staged block, and to run_batch what stages its arrays and what launches its kernels. (An .inc, not an .h: bench.py fingerprints every
-// .h of this directory into the committed counters of the extractor and matcher stages, which include none of this.)
+// staged block, and to run_batch what stages its arrays and what launches its kernels. run_batch is run_staged with the RANSAC's two
+// launches; the Sim3 transform optimiser (sim3_opt.hip), a one-launch solver over the same handle, calls run_staged itself. (An .inc, not
+// an .h: bench.py fingerprints every .h of this directory into the committed counters of the extractor and matcher stages, which include
+// none of this.)
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -211,10 +213,11 @@ struct ransac_handle {
     }
 };
 
-// H: ovs_sim3 or ovs_pnp. block_bytes: the solver's Layout at full capacity; initial_records: the models that fit without growing
+// H: ovs_sim3, ovs_pnp or ovs_sim3opt. block_bytes: the solver's Layout at full capacity; initial_records: the models that fit without
+// growing; result_bytes: the solver's record per problem in the mapped result block where it is not ResultRec
 template <class H>
 ovs_status ransac_create(int32_t device, int32_t max_problems, int32_t max_total_matches, size_t block_bytes, size_t initial_records,
-                         int model_doubles, H** out) {
+                         int model_doubles, H** out, size_t result_bytes = sizeof(ResultRec)) {
     if (!out || max_problems < 1 || max_total_matches < 1) return OVS_ERR_INVALID;
     *out = nullptr;
     if (max_problems > 65535) return OVS_ERR_INVALID;   // a grid's y extent
@@ -230,7 +233,7 @@ ovs_status ransac_create(int32_t device, int32_t max_problems, int32_t max_total
     OVS_HIP_TRY(s->res.dev(&s->d_block, block_bytes));
     if (s->reserve_models(initial_records) != OVS_OK) return OVS_ERR_HIP;
     OVS_HIP_TRY(s->res.pinned(&s->h_block, block_bytes));
-    OVS_HIP_TRY(s->res.pinned(&s->h_result, sizeof(ResultRec) * (size_t)max_problems, hipHostMallocMapped));
+    OVS_HIP_TRY(s->res.pinned(&s->h_result, result_bytes * (size_t)max_problems, hipHostMallocMapped));
     OVS_HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->m_result), s->h_result, 0));
     OVS_HIP_TRY(s->res.pinned(&s->h_flags, (size_t)max_total_matches, hipHostMallocMapped));
     OVS_HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->m_flags), s->h_flags, 0));
@@ -246,6 +249,25 @@ ovs_status ransac_destroy(H* s) {
     return OVS_OK;
 }
 
+// an ovs_camera as the kernels read it (Rec: a, b, c, d, model, pad): perspective (fx, fy, cx, cy) or equirectangular ((double)cols,
+// (double)rows, -, -); false for an unknown model or intrinsics a kernel cannot use
+template <class Rec>
+bool camera_ok(const ovs_camera& c, Rec* rec) {
+    rec->pad = 0;
+    rec->model = c.model;
+    if (c.model == 0) {
+        if (!std::isfinite(c.fx) || !std::isfinite(c.fy) || !std::isfinite(c.cx) || !std::isfinite(c.cy)) return false;
+        rec->a = c.fx, rec->b = c.fy, rec->c = c.cx, rec->d = c.cy;
+        return true;
+    }
+    if (c.model == 1) {
+        if (c.cols < 1 || c.rows < 1) return false;
+        rec->a = (double)c.cols, rec->b = (double)c.rows, rec->c = 0.0, rec->d = 0.0;
+        return true;
+    }
+    return false;
+}
+
 // where a call's results go: the caller's arrays of the C ABI (scale: nullptr for a solver that has none)
 struct BatchOut {
     int32_t *valid, *best_iter, *num_inliers;
@@ -259,50 +281,78 @@ inline bool all_set(std::initializer_list<const void*> pointers) {
     return true;
 }
 
-// One solve_batch call. `required`: the solver's own pointers that every call needs; `per_match`: its match arrays, needed once there is a
-// match. stage(h_block, layout, T) copies the solver's arrays into the page-locked block and may refuse them (OVS_ERR_INVALID);
-// hypotheses(stream, waves_per_problem, T) and finish(stream, waves_per_problem, T) launch the solver's two kernels. The order of decisions is the
-// ABI's: argument errors before the lock, OVS_ERR_CAPACITY before anything is staged, and no output is touched on any error.
-template <class Layout, class Stage, class Hypotheses, class Finish>
-ovs_status run_batch(ransac_handle* s, int32_t n_problems, const int32_t* offsets, std::initializer_list<const void*> required,
-                     std::initializer_list<const void*> per_match, int32_t min_num_inliers, int32_t max_num_iter, int hyp_per_wave,
-                     Layout (*layout_of)(int, int), const BatchOut& o, Stage stage, Hypotheses hypotheses, Finish finish) {
+// One batch call of any solver of this file's shape, whatever it launches. `required`: the pointers every call needs; `per_match`: the
+// arrays needed once there is a match, as is the per-match output. stage(h_block, layout, T) copies the solver's arrays into the
+// page-locked block and may refuse them (OVS_ERR_INVALID); reserve() grows what the launch needs while the stream is idle; launch(stream, T) enqueues the solver's kernels
+// behind the block's upload; collect(T) copies the mapped results out after the stream has drained. The order of decisions is the ABI's:
+// argument errors before the lock, OVS_ERR_CAPACITY before anything is staged, and no output is touched on any error.
+template <class Layout, class Stage, class Reserve, class Launch, class Collect>
+ovs_status run_staged(ransac_handle* s, int32_t n_problems, const int32_t* offsets, std::initializer_list<const void*> required,
+                      std::initializer_list<const void*> per_match, const void* per_match_out, Layout (*layout_of)(int, int), Stage stage,
+                      Reserve reserve, Launch launch, Collect collect) {
     // every argument error is decided here, before the device is touched
-    if (!s || n_problems < 0 || max_num_iter < 1 || max_num_iter > kMaxIter || min_num_inliers < 0) return OVS_ERR_INVALID;
+    if (!s || n_problems < 0) return OVS_ERR_INVALID;
     if (n_problems == 0) return OVS_OK;
-    if (!offsets || !o.valid || !o.best_iter || !o.num_inliers || !o.rot || !o.trans || !all_set(required)) return OVS_ERR_INVALID;
+    if (!offsets || !all_set(required)) return OVS_ERR_INVALID;
     if (offsets[0] != 0) return OVS_ERR_INVALID;
     for (int32_t p = 0; p < n_problems; ++p)
         if (offsets[p + 1] < offsets[p]) return OVS_ERR_INVALID;
     const int32_t T = offsets[n_problems];
-    if (T > 0 && (!o.flags || !all_set(per_match))) return OVS_ERR_INVALID;
+    if (T > 0 && (!per_match_out || !all_set(per_match))) return OVS_ERR_INVALID;
     std::lock_guard<std::mutex> lock(s->mu);
     if (n_problems > s->max_problems || T > s->max_total_matches) return OVS_ERR_CAPACITY;   // nothing is truncated
     const Layout lay = layout_of(n_problems, T);
     const ovs_status staged = stage(s->h_block, lay, T);
     if (staged != OVS_OK) return staged;
-    std::memset(s->h_block + lay.keys, 0, 8 * (size_t)n_problems);
     std::memcpy(s->h_block + lay.offsets, offsets, 4 * ((size_t)n_problems + 1));
     OVS_HIP_TRY(hipSetDevice(s->device));
-    const int waves = (max_num_iter + hyp_per_wave - 1) / hyp_per_wave;
-    if (s->reserve_models((size_t)n_problems * (size_t)waves) != OVS_OK) return OVS_ERR_HIP;
+    const ovs_status reserved = reserve();
+    if (reserved != OVS_OK) return reserved;
     OVS_HIP_TRY(hipMemcpyAsync(s->d_block, s->h_block, lay.bytes, hipMemcpyHostToDevice, s->stream));
-    hypotheses(s->stream, waves, T);
-    OVS_HIP_TRY(hipGetLastError());
-    finish(s->stream, waves, T);
-    OVS_HIP_TRY(hipGetLastError());
+    const ovs_status launched = launch(s->stream, T);
+    if (launched != OVS_OK) return launched;
     OVS_HIP_TRY(hipStreamSynchronize(s->stream));
-    for (int32_t p = 0; p < n_problems; ++p) {
-        const ResultRec& r = s->h_result[p];
-        o.valid[p] = r.valid;
-        o.best_iter[p] = r.best_iter;
-        o.num_inliers[p] = r.num_inliers;
-        std::memcpy(o.rot + 9 * (size_t)p, r.rot, sizeof(r.rot));
-        std::memcpy(o.trans + 3 * (size_t)p, r.trans, sizeof(r.trans));
-        if (o.scale) o.scale[p] = r.scale;
-    }
-    if (T > 0) std::memcpy(o.flags, s->h_flags, (size_t)T);
+    collect(T);
     return OVS_OK;
+}
+
+// One solve_batch call of a RANSAC solver: run_staged with the two launches, the keys and the result record both solvers have.
+// hypotheses(stream, waves_per_problem, T) and finish(stream, waves_per_problem, T) launch the solver's two kernels.
+template <class Layout, class Stage, class Hypotheses, class Finish>
+ovs_status run_batch(ransac_handle* s, int32_t n_problems, const int32_t* offsets, std::initializer_list<const void*> required,
+                     std::initializer_list<const void*> per_match, int32_t min_num_inliers, int32_t max_num_iter, int hyp_per_wave,
+                     Layout (*layout_of)(int, int), const BatchOut& o, Stage stage, Hypotheses hypotheses, Finish finish) {
+    if (!s || n_problems < 0 || max_num_iter < 1 || max_num_iter > kMaxIter || min_num_inliers < 0) return OVS_ERR_INVALID;
+    if (n_problems > 0 && (!o.valid || !o.best_iter || !o.num_inliers || !o.rot || !o.trans)) return OVS_ERR_INVALID;
+    if (n_problems > 0 && !all_set(required)) return OVS_ERR_INVALID;
+    const int waves = (max_num_iter + hyp_per_wave - 1) / hyp_per_wave;
+    return run_staged(
+        s, n_problems, offsets, required, per_match, o.flags, layout_of,
+        [&](uint8_t* h_block, const Layout& lay, int32_t T) {
+            const ovs_status staged = stage(h_block, lay, T);
+            if (staged == OVS_OK) std::memset(h_block + lay.keys, 0, 8 * (size_t)n_problems);
+            return staged;
+        },
+        [&] { return s->reserve_models((size_t)n_problems * (size_t)waves) != OVS_OK ? OVS_ERR_HIP : OVS_OK; },
+        [&](hipStream_t stream, int32_t T) {
+            hypotheses(stream, waves, T);
+            OVS_HIP_TRY(hipGetLastError());
+            finish(stream, waves, T);
+            OVS_HIP_TRY(hipGetLastError());
+            return OVS_OK;
+        },
+        [&](int32_t T) {
+            for (int32_t p = 0; p < n_problems; ++p) {
+                const ResultRec& r = s->h_result[p];
+                o.valid[p] = r.valid;
+                o.best_iter[p] = r.best_iter;
+                o.num_inliers[p] = r.num_inliers;
+                std::memcpy(o.rot + 9 * (size_t)p, r.rot, sizeof(r.rot));
+                std::memcpy(o.trans + 3 * (size_t)p, r.trans, sizeof(r.trans));
+                if (o.scale) o.scale[p] = r.scale;
+            }
+            if (T > 0) std::memcpy(o.flags, s->h_flags, (size_t)T);
+        });
 }
 
 }   // namespace

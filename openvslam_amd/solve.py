@@ -1,4 +1,4 @@
-"""solve/ on the MI355X: the two RANSAC solvers whose candidates come in batches.
+"""solve/ on the MI355X: the two RANSAC solvers whose candidates come in batches, and the Sim3 optimiser that follows the first.
 
 solve::sim3_solver (expected: src/openvslam/solve/sim3_solver.{h,cc}) on the MI355X: the RANSAC the loop detector runs on every loop
 candidate between bow_tree::match_keyframes and projection::match_by_Sim3_transform. All candidates of a keyframe go to the device in ONE
@@ -7,7 +7,12 @@ bit-exact functions of (inputs, seed, position in the batch).
 
 solve::pnp_solver (expected: src/openvslam/solve/pnp_solver.{h,cc}): the EPnP RANSAC the relocaliser runs on every candidate keyframe between
 bow_tree::match_frame_and_keyframe and the pose optimiser. All candidates go to the device in ONE call (ovs_pnp_solve_batch,
-csrc/pnp_solve.hip): two launches whatever their number. DESIGN.md 3.10 has the rules; bit-exact in the same sense."""
+csrc/pnp_solve.hip): two launches whatever their number. DESIGN.md 3.10 has the rules; bit-exact in the same sense.
+
+optimize::transform_optimizer (expected: src/openvslam/optimize/transform_optimizer.{h,cc}): the Sim3 refinement the loop detector runs on
+every candidate after projection::match_by_Sim3_transform. It lives here, beside the handle and packing code it shares with the solvers.
+All candidates go to the device in ONE call and ONE launch (ovs_sim3opt_optimize_batch, csrc/sim3_opt.hip). DESIGN.md 3.11 has the rules;
+the results are bit-exact functions of the inputs."""
 import ctypes as C
 import math
 
@@ -216,3 +221,64 @@ class pnp_solver(_ransac_solver):
         T = np.eye(4)
         T[:3, :3], T[:3, 3] = self._get("rot_cw"), self._get("trans_cw")
         return T
+
+
+# ---- optimize::transform_optimizer
+def transform_problem_from_keyframes(pose_cw_1, pose_cw_2, pos_w_1, pos_w_2, keypts_1, keypts_2, octaves_1, octaves_2, inv_level_sigma_sq_1,
+                                     inv_level_sigma_sq_2, cam_1, cam_2, rot_12, trans_12, scale_12):
+    """What transform_optimizer collects for the matched landmark pairs (lm_1[i], lm_2[i]): each landmark in its own keyframe's camera (as
+    problem_from_keyframes does), the two undistorted keypoints widened to double and inv_level_sigma_sq[octave] of each, with the initial
+    Sim3_12. keypts_*: (n, 2) float32; the other arguments as problem_from_keyframes takes them."""
+    w1 = np.asarray(inv_level_sigma_sq_1, np.float32)[np.asarray(octaves_1, np.int64)]
+    w2 = np.asarray(inv_level_sigma_sq_2, np.float32)[np.asarray(octaves_2, np.int64)]
+    return dict(p1=_transform(pose_cw_1, pos_w_1), p2=_transform(pose_cw_2, pos_w_2), obs1=np.asarray(keypts_1, np.float32).reshape(-1, 2).astype(np.float64),
+                obs2=np.asarray(keypts_2, np.float32).reshape(-1, 2).astype(np.float64), w1=w1, w2=w2, cam_1=cam_1, cam_2=cam_2,
+                R=np.asarray(rot_12, np.float64).reshape(3, 3), t=np.asarray(trans_12, np.float64).reshape(3), s=float(scale_12))
+
+
+class _transform_handle(_ransac_handle):
+    """ovs_sim3opt with its capacity."""
+    _abi = "ovs_sim3opt"
+
+
+def optimize_transform_batch(problems, fix_scale, chi_sq=10.0, num_iter=10, handle=None, device=0, with_info=True):
+    """transform_optimizer::optimize for every problem (dicts as transform_problem_from_keyframes returns them) in one call: a list of dicts
+    num_inliers, rot_12 (3 x 3), trans_12 (3), scale_12, outlier_flags (n, bool) and info (8 doubles: iterations and trials of round 1, its
+    robust chi-square, its outliers, the same three of round 2, the last lambda). `handle`: a _transform_handle to reuse."""
+    P = len(problems)
+    if P == 0:
+        return []
+    offsets = np.zeros(P + 1, np.int32)
+    offsets[1:] = np.cumsum([len(np.asarray(q["w1"])) for q in problems])
+    T = int(offsets[-1])
+    cat = lambda key, dt, w: np.ascontiguousarray(np.concatenate([np.asarray(q[key], dt).reshape(-1, w) for q in problems]) if T else np.zeros((0, w), dt))
+    packed = [cat(*a) for a in (("p1", np.float64, 3), ("p2", np.float64, 3), ("obs1", np.float64, 2), ("obs2", np.float64, 2), ("w1", np.float32, 1),
+                                ("w2", np.float32, 1))]
+    if any(len(a) != T for a in packed):
+        raise ValueError("p1, p2, obs1, obs2, w1 and w2 of a problem must have one entry per match")
+    cams_1 = (_lib.Camera * P)(*[q["cam_1"] for q in problems])
+    cams_2 = (_lib.Camera * P)(*[q["cam_2"] for q in problems])
+    rot_in = np.ascontiguousarray([np.asarray(q["R"], np.float64).reshape(3, 3) for q in problems])
+    trans_in = np.ascontiguousarray([np.asarray(q["t"], np.float64).reshape(3) for q in problems])
+    scale_in = np.ascontiguousarray([float(q["s"]) for q in problems])
+    if handle is None:
+        handle = _transform_handle(P, max(T, 1), device)
+    num, rot, trans, scale = np.zeros(P, np.int32), np.zeros((P, 3, 3)), np.zeros((P, 3)), np.zeros(P)
+    flags, info = np.zeros(max(T, 1), np.uint8), np.zeros((P, 8)) if with_info else None
+    _lib.check(handle._L.ovs_sim3opt_optimize_batch(handle._h, P, _p(offsets), *map(_p, packed), cams_1, cams_2, _p(rot_in), _p(trans_in), _p(scale_in),
+                                                    1 if fix_scale else 0, float(chi_sq), int(num_iter), _p(num), _p(rot), _p(trans), _p(scale), _p(flags),
+                                                    _p(info)), "ovs_sim3opt_optimize_batch")
+    return [dict(num_inliers=int(num[i]), rot_12=rot[i].copy(), trans_12=trans[i].copy(), scale_12=float(scale[i]),
+                 outlier_flags=flags[offsets[i]:offsets[i + 1]].astype(bool), info=None if info is None else info[i].copy()) for i in range(P)]
+
+
+class transform_optimizer:
+    """optimize::transform_optimizer: the constructor is upstream's (fix_scale, num_iter); optimize takes what the C++ class collects from the
+    two keyframes (see transform_problem_from_keyframes) and returns (num_inliers, rot_12, trans_12, scale_12, outlier_flags)."""
+
+    def __init__(self, fix_scale, num_iter=10, device=0):
+        self._fix_scale, self._num_iter, self._device = bool(fix_scale), int(num_iter), device
+
+    def optimize(self, problem, chi_sq=10.0):
+        r = optimize_transform_batch([problem], self._fix_scale, chi_sq, self._num_iter, device=self._device)[0]
+        return r["num_inliers"], r["rot_12"], r["trans_12"], r["scale_12"], r["outlier_flags"]
