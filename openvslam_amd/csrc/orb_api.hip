@@ -50,6 +50,7 @@ const Tuning& tuning() {
         v.pose_threads = num("OVS_POSE_THREADS", 0);
         v.pose_groups = std::max(0, num("OVS_POSE_GROUPS", 0));
         v.resolve_wide_from = num("OVS_RESOLVE_WIDE_FROM", 1024);
+        v.pyr_strip = std::max(0, num("OVS_PYR_STRIP", 0));
         v.pyr_chain = std::max(0, num("OVS_PYR_CHAIN", 2));
         return v;
     }();

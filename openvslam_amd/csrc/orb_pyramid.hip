@@ -433,27 +433,33 @@ __device__ __forceinline__ uint32_t vgroup_packed(const uint2 h0, const uint2 h1
     return __builtin_amdgcn_perm(p23, p01, 0x06040200u);
 }
 
-// One tile's scalars (workgroup-uniform) ...
-struct PairTile {
-    int x0, y0, sx_lo, sy_lo, bx0, nG, nrB, own_g, own_r, ax_lo, nwordsA, ay_lo, nrA, cx_hi;
-    const uint8_t* s;
-    uint8_t *d1, *d2;
-};
-// ... and what a thread fetches for it ahead of time: its three staging chunks, its three column-pair records, its y-tap record
-struct PairFetch {
-    uint4 v[3];
-    uint4 r1, r2, r3;
-    uint32_t w1, w2, w3;
-    ResizeTap ty;
-};
-
+// Column strips: a workgroup walks `strip` vertically consecutive tiles of ONE tile column of one frame. About 40 % of the kernel's vector
+// instructions per tile were not resize arithmetic but set-up, and nearly all of that depends only on the tile column and the thread: the
+// three HTapRec records, the staging column and its predicates, the group / row-phase split of both vertical passes with their column
+// predicates, every LDS pointer and the column part of every global address. All of it is computed once, ahead of the loop, and lives in
+// registers (the kernel's occupancy is set by its LDS: five workgroups per CU leave ~100 VGPRs). Per tile there remain the row span (fetched one
+// tile ahead), the two y-tap tables, the row predicates, and the global addresses -- a workgroup-uniform row base (scalar registers) plus the
+// thread's hoisted 32-bit offset. Work order: item = (frame, strip row, tile column), column fastest, so strips of neighbouring columns are
+// neighbours in the XCD's contiguous eighth and their halo columns meet in one L2; strip = 1 is exactly the tile-per-workgroup order. A strip
+// never crosses a frame; the last strip of a column may be shorter.
+// (A multi-tile form measured in round 6 walked consecutive tile ids, i.e. along x, where nothing is shared between tiles, and spent 121 VGPRs
+// on prefetching the next tile to hide a memory latency the kernel does not wait for: profiles/r06z_pyr_pair.txt. This one removes instructions.)
+//
+// Barriers of one tile, and what each orders (bufA / bufH / s_tyA / s_tyB are re-used by the next tile of the strip):
+//   B1  staging writes of bufA and s_tyA  ->  stage A's horizontal reads of bufA. It also ends the PREVIOUS tile for every thread: its stage B
+//       vertical reads of bufH and s_tyB are done, so bufH may be overwritten (stage A horizontal) and s_tyB is written right AFTER B1 -- its
+//       readers are behind B4, and writing it with the staging, ahead of B1, would race with the previous tile's vertical pass.
+//   B2  stage A's horizontal writes of bufH  ->  stage A's vertical reads of bufH (and of s_tyA).
+//   B3  stage A's vertical writes of bufA (the middle region; bufA's lower rectangle was last read before B2)  ->  stage B's horizontal reads.
+//   B4  stage B's horizontal writes of bufH (last read before B3)  ->  stage B's vertical reads of bufH and s_tyB. bufA's and s_tyA's last readers
+//       are behind B4 / B3, so the next tile's staging starts without a further barrier.
 __global__ __launch_bounds__(256) void k_resize_pair_u8(const uint8_t* __restrict__ src, size_t src_frame_stride, int src_pitch,
                                                        uint8_t* __restrict__ dst1, int pitch1, int rows1, int cols1, uint8_t* __restrict__ dst2,
                                                        int pitch2, int rows2, int cols2, size_t dst_frame_stride,
                                                        const ResizeTap* __restrict__ yt1, const ResizeTap* __restrict__ yt2,
                                                        const HTapRec* __restrict__ ht1, const HTapRec* __restrict__ ht2,
-                                                       const PairSpan* __restrict__ plan, int tiles_x, int tiles_frame, int batch,
-                                                       uint32_t tiles_x_magic, uint32_t tiles_frame_magic) {
+                                                       const PairSpan* __restrict__ plan, int tiles_x, int tiles_y, int strip, int strips_frame,
+                                                       int batch, uint32_t tiles_x_magic, uint32_t strips_frame_magic) {
     __shared__ __attribute__((aligned(16))) uint32_t bufA[kPairSrcRows * kPairSrcWords + 4];
     __shared__ __attribute__((aligned(8))) uint32_t bufH[kPairSrcRows * 2 * kPairGroups];
     // y taps as LDS records {byte offset of source row o0 in bufH | that of o1 << 16, a0 | a1 << 16}: the vertical passes read them with immediate offsets
@@ -461,193 +467,210 @@ __global__ __launch_bounds__(256) void k_resize_pair_u8(const uint8_t* __restric
     static_assert(kPairSrcRows * kPairSrcWords >= kSrcRows * kSrcWords && kPairSrcRows * 2 * kPairGroups >= kSrcRows * (kTileW / 2), "stage B reuses both buffers");
     const int tid = threadIdx.x;
     const int xp = tid & 63, q = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // XCD-aware order: XCD k owns the k-th contiguous eighth of the tile sequence. (A form in which a workgroup took 2 - 8 consecutive tiles and fetched
-    // tile i + 1 into registers under tile i's arithmetic was measured: 121 VGPRs, 0.70 / 0.75 / 0.78 ms at 2 / 4 / 8 tiles against 0.705 for one tile
-    // per workgroup -- the kernel waits for its vector ALU, not for memory: profiles/r06z_pyr_pair.txt.)
+    // XCD-aware order: XCD k owns the k-th contiguous eighth of the item sequence (frame, strip row, tile column)
     const int per_xcd = gridDim.x >> 3;
-    const int first = ((int)blockIdx.x & 7) * per_xcd + ((int)blockIdx.x >> 3);
-    if (first >= tiles_frame * batch) return;
-    // staging split: thread = (16-byte chunk column c, row phase sph), rows sph, sph + 18, sph + 36
+    const int item = ((int)blockIdx.x & 7) * per_xcd + ((int)blockIdx.x >> 3);
+    if (item >= strips_frame * batch) return;
+    const int frame = (int)udiv_magic((uint32_t)item, (uint32_t)strips_frame, strips_frame_magic);
+    const int irem = item - frame * strips_frame;
+    const int si = (int)udiv_magic((uint32_t)irem, (uint32_t)tiles_x, tiles_x_magic), txi = irem - si * tiles_x;
+    const int ty_first = si * strip, ty_end = min(ty_first + strip, tiles_y);
+
+    // ================= per column and thread: once per strip =================
+    // stage B's tile origin sx_lo, the middle region's columns [bx0, bx0 + 4 nG), the lower rectangle's columns [ax_lo, ax_lo + 4 nwordsA)
+    const PairSpan PX = plan[txi];
+    const int x0 = txi * kTileW, sx_lo = PX.s_lo, bx0 = PX.b0, nG = PX.n, own_g = PX.own, ax_lo = PX.a0, nwordsA = PX.an;
+    const int cx_hi = min(bx0 + 4 * nG - 1, cols1 - 1);   // last middle column that exists
+    const uint8_t* const s = src + (size_t)frame * src_frame_stride;
+    uint8_t* const d1 = dst1 + (size_t)frame * dst_frame_stride;
+    uint8_t* const d2 = dst2 + (size_t)frame * dst_frame_stride;
+    // the x taps of this thread's column pairs (host-built records: selectors, coefficients, first source word). stage A: phase 1 = column pairs
+    // 0 .. 63 of the region (lane = pair, wave q takes rows q, q + 4, ..), phase 2 = pairs 64 .. 79 (16 lanes per row group, 16 row groups);
+    // stage B: pair xp of the tile. Pairs outside the region take the last pair's record: values nobody reads.
+    const int p2 = 64 + (tid & 15);
+    HTaps t1, t2, t3;
+    {
+        const int jmax1 = cx_hi >> 1;
+        const HTapRec* const r1 = ht1 + min((bx0 >> 1) + xp, jmax1);
+        const HTapRec* const r2 = ht1 + min((bx0 >> 1) + p2, jmax1);
+        const HTapRec* const r3 = ht2 + min((x0 >> 1) + xp, (cols2 - 1) >> 1);
+        const uint4 v1 = *reinterpret_cast<const uint4*>(r1), v2 = *reinterpret_cast<const uint4*>(r2), v3 = *reinterpret_cast<const uint4*>(r3);
+        t1 = HTaps{v1.x, v1.y, v1.z, v1.w, (int)r1->wa - (ax_lo >> 2)};
+        t2 = HTaps{v2.x, v2.y, v2.z, v2.w, (int)r2->wa - (ax_lo >> 2)};
+        t3 = HTaps{v3.x, v3.y, v3.z, v3.w, (int)r3->wa - (sx_lo >> 2)};
+    }
+    // staging split: thread = (16-byte chunk column sc, row phase sph), rows sph, sph + 18, sph + 36
     const int sph = (tid * 4682) >> 16, sc = tid - sph * kPairRowChunks;   // tid / 14, tid % 14
     static_assert(kPairRowChunks == 14 && 18 * kPairRowChunks <= 256 && 3 * 18 >= kPairSrcRows, "staging split");
-    const int p2 = 64 + (tid & 15);
+    const int gx = ax_lo + 16 * sc;
+    const bool col_in = sph < 18 && 4 * sc < nwordsA, whole = gx + 16 <= src_pitch;
+    const uint32_t st_off = (uint32_t)(sph * src_pitch + gx);   // from the rectangle's first row; the row base is workgroup-uniform
+    uint4* const st_w = reinterpret_cast<uint4*>(&bufA[0]) + sph * kPairRowChunks + sc;
+    // stage A, horizontal pass
+    const uint32_t* const a_Ts = &bufA[q * kPairSrcWords + t1.wa];
+    uint32_t* const a_H = &bufH[q * (2 * kPairGroups) + xp];
+    const int a_r0 = tid >> 4;
+    const uint32_t* const a_T2 = &bufA[a_r0 * kPairSrcWords + t2.wa];
+    uint32_t* const a_H2 = &bufH[a_r0 * (2 * kPairGroups) + p2];
+    // stage A, vertical pass: thread = (4-pixel group grp, row phase ph), rows ph, ph + 6, ..: constant strides
+    const int ph = (tid * 1639) >> 16, grp = tid - ph * kPairGroups;   // tid / 40, tid % 40
+    static_assert(kPairGroups == 40 && 6 * kPairGroups <= 256 && 6 * 8 >= kSrcRows, "vertical split of stage A");
+    const bool gvalid = ph < 6 && grp < nG;
+    const int x4 = bx0 + 4 * grp;
+    const bool own_ok = gvalid && grp < own_g && x4 < cols1;
+    const uint32_t v1_off = (uint32_t)(ph * pitch1 + x4);   // from the region's first row
+    uint32_t* const v1_tb = &bufA[ph * kSrcWords + ((bx0 - sx_lo) >> 2) + grp];
+    const uint8_t* const v1_hb = reinterpret_cast<const uint8_t*>(&bufH[0]) + 8 * grp;
+    const uint2* const v1_ty = &s_tyA[ph];
+    // stage B, horizontal pass
+    const uint32_t* const b_Ts = &bufA[q * kSrcWords + t3.wa];
+    uint32_t* const b_H = &bufH[q * (kTileW / 2) + xp];
+    // stage B, vertical pass: thread = (group xg, row phase ph2), rows ph2, ph2 + 8, ..
+    const int xg = tid & 31, ph2 = tid >> 5, x4b = x0 + 4 * xg;
+    const bool xok = x4b < cols2;
+    const uint32_t v2_off = (uint32_t)(ph2 * pitch2 + x4b);   // from the tile's first row
+    const uint8_t* const v2_hb = reinterpret_cast<const uint8_t*>(&bufH[0]) + 8 * xg;
+    const uint2* const v2_ty = &s_tyB[ph2];
 
-    auto decode = [&](int tile_id) -> PairTile {
-        PairTile t;
-        const int frame = (int)udiv_magic((uint32_t)tile_id, (uint32_t)tiles_frame, tiles_frame_magic);
-        const int trem = tile_id - frame * tiles_frame;
-        const int tyi = (int)udiv_magic((uint32_t)trem, (uint32_t)tiles_x, tiles_x_magic), txi = trem - tyi * tiles_x;
-        const PairSpan PX = plan[txi], PY = plan[tiles_x + tyi];
-        t.x0 = txi * kTileW;
-        t.y0 = tyi * kTileH;
-        t.s = src + (size_t)frame * src_frame_stride;
-        t.d1 = dst1 + (size_t)frame * dst_frame_stride;
-        t.d2 = dst2 + (size_t)frame * dst_frame_stride;
-        // stage B's tile origin (v4's sx_lo, sy_lo), the middle region [bx0, bx0 + 4 nG) x [sy_lo, sy_lo + nrB), the lower rectangle
-        t.sx_lo = PX.s_lo; t.sy_lo = PY.s_lo; t.bx0 = PX.b0; t.nG = PX.n; t.nrB = PY.n; t.own_g = PX.own; t.own_r = PY.own;
-        t.ax_lo = PX.a0; t.nwordsA = PX.an; t.ay_lo = PY.a0; t.nrA = PY.an;
-        t.cx_hi = min(t.bx0 + 4 * t.nG - 1, cols1 - 1);   // last middle column that exists
-        return t;
-    };
-    auto fetch = [&](const PairTile& t) -> PairFetch {
-        PairFetch f;
-        // the x taps of this thread's column pairs (host-built records: selectors, coefficients, first source word). stage A: phase 1 = column pairs
-        // 0 .. 63 of the region (lane = pair, wave q takes rows q, q + 4, ..), phase 2 = pairs 64 .. 79 (16 lanes per row group, 16 row groups);
-        // stage B: pair xp of the tile. Pairs outside the region take the last pair's record: values nobody reads.
-        const int jmax1 = t.cx_hi >> 1;
-        const HTapRec* const r1 = ht1 + min((t.bx0 >> 1) + xp, jmax1);
-        const HTapRec* const r2 = ht1 + min((t.bx0 >> 1) + p2, jmax1);
-        const HTapRec* const r3 = ht2 + min((t.x0 >> 1) + xp, (cols2 - 1) >> 1);
-        f.r1 = *reinterpret_cast<const uint4*>(r1);
-        f.r2 = *reinterpret_cast<const uint4*>(r2);
-        f.r3 = *reinterpret_cast<const uint4*>(r3);
-        f.w1 = r1->wa;
-        f.w2 = r2->wa;
-        f.w3 = r3->wa;
+    // ================= per tile =================
+    // The row span of tile tyi + 1 is fetched under tile tyi and moved to scalar registers once the staging data (issued after it) has arrived: inside
+    // the loop the compiler reads `plan` with a vector load (stores to the planes lie between the iterations), and every row bound derived from a
+    // vector register would turn the uniform address and predicate arithmetic below into per-lane instructions.
+    const uint32_t* const plan_w = reinterpret_cast<const uint32_t*>(plan + tiles_x);   // row spans: {s_lo | b0 << 16, n | own << 16, a0 | an << 16, pad}
+    uint32_t py0 = __builtin_amdgcn_readfirstlane(plan_w[4 * ty_first]), py1 = __builtin_amdgcn_readfirstlane(plan_w[4 * ty_first + 1]),
+             py2 = __builtin_amdgcn_readfirstlane(plan_w[4 * ty_first + 2]);
+#pragma unroll 1
+    for (int tyi = ty_first; tyi < ty_end; ++tyi) {
+        // the middle region's rows [sy_lo, sy_lo + nrB) (sy_lo = origin of stage B's LDS tile), the lower rectangle's rows [ay_lo, ay_lo + nrA)
+        const int y0 = tyi * kTileH, sy_lo = (int16_t)(py0 & 0xffffu), nrB = (int16_t)(py1 & 0xffffu), own_r = (int16_t)(py1 >> 16),
+                  ay_lo = (int16_t)(py2 & 0xffffu), nrA = (int16_t)(py2 >> 16);
+        const uint32_t* const pn = plan_w + 4 * min(tyi + 1, tiles_y - 1);
+        const uint32_t n0 = pn[0], n1 = pn[1], n2 = pn[2];
         // the y tap of one row of the middle region (threads 0 .. 47) or of the tile (64 .. 95)
-        f.ty = ResizeTap{0, 0, 0, 0};
-        if (tid < 48) f.ty = yt1[min(t.sy_lo + tid, rows1 - 1)];
-        else if (tid >= 64 && tid < 64 + kTileH) f.ty = yt2[min(t.y0 + tid - 64, rows2 - 1)];
-        // the lower rectangle: one address, two strides
-        const int gx = t.ax_lo + 16 * sc;
-        const bool col_in = sph < 18 && 4 * sc < t.nwordsA, whole = gx + 16 <= src_pitch;
-        const uint8_t* p = t.s + (size_t)(t.ay_lo + sph) * src_pitch + gx;
+        ResizeTap ty = ResizeTap{0, 0, 0, 0};
+        if (tid < 48) ty = yt1[min(sy_lo + tid, rows1 - 1)];
+        else if (tid >= 64 && tid < 64 + kTileH) ty = yt2[min(y0 + tid - 64, rows2 - 1)];
+        // ---- the lower rectangle -> LDS
+        {
+            const uint8_t* const srow = s + (size_t)ay_lo * src_pitch;
+            uint4 v[3];
 #pragma unroll
-        for (int k = 0; k < 3; ++k, p += (size_t)18 * src_pitch) {
-            f.v[k] = uint4{0u, 0u, 0u, 0u};
-            if (col_in && sph + 18 * k < t.nrA) {
-                if (whole) {
-                    f.v[k] = *reinterpret_cast<const uint4*>(p);
-                } else {   // row tail
-                    const uint32_t* p4 = reinterpret_cast<const uint32_t*>(p);
-                    if (gx + 4 <= src_pitch) f.v[k].x = p4[0];
-                    if (gx + 8 <= src_pitch) f.v[k].y = p4[1];
-                    if (gx + 12 <= src_pitch) f.v[k].z = p4[2];
+            for (int k = 0; k < 3; ++k) {
+                if (col_in && sph + 18 * k < nrA) {   // (v[k] is read below under the same condition only)
+                    const uint8_t* const p = srow + (size_t)(18 * k) * src_pitch + st_off;
+                    if (whole) {
+                        v[k] = *reinterpret_cast<const uint4*>(p);
+                    } else {   // row tail
+                        v[k] = uint4{0u, 0u, 0u, 0u};
+                        const uint32_t* p4 = reinterpret_cast<const uint32_t*>(p);
+                        if (gx + 4 <= src_pitch) v[k].x = p4[0];
+                        if (gx + 8 <= src_pitch) v[k].y = p4[1];
+                        if (gx + 12 <= src_pitch) v[k].z = p4[2];
+                    }
                 }
             }
-        }
-        return f;
-    };
-
-    const PairTile T = decode(first);
-    const PairFetch F = fetch(T);
-    {
-        // ---- this tile's fetched data -> LDS
-        {
-            const bool col_in = sph < 18 && 4 * sc < T.nwordsA;
-            uint4* const w = reinterpret_cast<uint4*>(&bufA[0]) + sph * kPairRowChunks + sc;
 #pragma unroll
             for (int k = 0; k < 3; ++k)
-                if (col_in && sph + 18 * k < T.nrA) w[k * 18 * kPairRowChunks] = F.v[k];
+                if (col_in && sph + 18 * k < nrA) st_w[k * 18 * kPairRowChunks] = v[k];
             if (tid < 48)
-                s_tyA[tid] = uint2{(uint32_t)((F.ty.o0 - T.ay_lo) * (8 * kPairGroups)) | ((uint32_t)((F.ty.o1 - T.ay_lo) * (8 * kPairGroups)) << 16),
-                                   (uint32_t)(uint16_t)F.ty.a0 | ((uint32_t)(uint16_t)F.ty.a1 << 16)};
-            else if (tid >= 64 && tid < 64 + kTileH)
-                s_tyB[tid - 64] = uint2{(uint32_t)((F.ty.o0 - T.sy_lo) * (2 * kTileW)) | ((uint32_t)((F.ty.o1 - T.sy_lo) * (2 * kTileW)) << 16),
-                                        (uint32_t)(uint16_t)F.ty.a0 | ((uint32_t)(uint16_t)F.ty.a1 << 16)};
+                s_tyA[tid] = uint2{(uint32_t)((ty.o0 - ay_lo) * (8 * kPairGroups)) | ((uint32_t)((ty.o1 - ay_lo) * (8 * kPairGroups)) << 16),
+                                   (uint32_t)(uint16_t)ty.a0 | ((uint32_t)(uint16_t)ty.a1 << 16)};
         }
-        const HTaps t1 = HTaps{F.r1.x, F.r1.y, F.r1.z, F.r1.w, (int)F.w1 - (T.ax_lo >> 2)};
-        const HTaps t2 = HTaps{F.r2.x, F.r2.y, F.r2.z, F.r2.w, (int)F.w2 - (T.ax_lo >> 2)};
-        const HTaps t3 = HTaps{F.r3.x, F.r3.y, F.r3.z, F.r3.w, (int)F.w3 - (T.sx_lo >> 2)};
-        const PairTile& C = T;
-        __syncthreads();
+        __syncthreads();   // B1
+        py0 = __builtin_amdgcn_readfirstlane(n0);
+        py1 = __builtin_amdgcn_readfirstlane(n1);
+        py2 = __builtin_amdgcn_readfirstlane(n2);
+        if (tid >= 64 && tid < 64 + kTileH)
+            s_tyB[tid - 64] = uint2{(uint32_t)((ty.o0 - sy_lo) * (2 * kTileW)) | ((uint32_t)((ty.o1 - sy_lo) * (2 * kTileW)) << 16),
+                                    (uint32_t)(uint16_t)ty.a0 | ((uint32_t)(uint16_t)ty.a1 << 16)};
         // ---- stage A, horizontal pass: bufH[r][pair] for the 52 rows of the rectangle (rows >= nrA hold stale bytes nobody reads)
         {
-            const uint32_t* Ts = &bufA[q * kPairSrcWords + t1.wa];
-            uint32_t* H = &bufH[q * (2 * kPairGroups) + xp];
             static_assert(kPairSrcRows == 52, "thirteen steps of four rows, four steps of sixteen");
             uint32_t lo[13], hi[13];
 #pragma unroll
             for (int k = 0; k < 13; ++k) {
-                lo[k] = Ts[4 * k * kPairSrcWords];
-                hi[k] = Ts[4 * k * kPairSrcWords + 1];
+                lo[k] = a_Ts[4 * k * kPairSrcWords];
+                hi[k] = a_Ts[4 * k * kPairSrcWords + 1];
             }
 #pragma unroll
-            for (int k = 0; k < 13; ++k) H[4 * k * (2 * kPairGroups)] = hpair(lo[k], hi[k], t1);
-            const int r0 = tid >> 4;
-            const uint32_t* T2 = &bufA[r0 * kPairSrcWords + t2.wa];
-            uint32_t* H2 = &bufH[r0 * (2 * kPairGroups) + p2];
+            for (int k = 0; k < 13; ++k) a_H[4 * k * (2 * kPairGroups)] = hpair(lo[k], hi[k], t1);
             uint32_t lo2[4], hi2[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const bool in = r0 + 16 * k < kPairSrcRows;
-                lo2[k] = in ? T2[16 * k * kPairSrcWords] : 0u;
-                hi2[k] = in ? T2[16 * k * kPairSrcWords + 1] : 0u;
+                const bool in = a_r0 + 16 * k < kPairSrcRows;
+                lo2[k] = in ? a_T2[16 * k * kPairSrcWords] : 0u;
+                hi2[k] = in ? a_T2[16 * k * kPairSrcWords + 1] : 0u;
             }
 #pragma unroll
             for (int k = 0; k < 4; ++k)
-                if (r0 + 16 * k < kPairSrcRows) H2[16 * k * (2 * kPairGroups)] = hpair(lo2[k], hi2[k], t2);
+                if (a_r0 + 16 * k < kPairSrcRows) a_H2[16 * k * (2 * kPairGroups)] = hpair(lo2[k], hi2[k], t2);
         }
-        __syncthreads();
+        __syncthreads();   // B2
         // ---- stage A, vertical pass: the middle region into bufA (laid out as v4's staged tile: pitch kSrcWords, origin (sx_lo, sy_lo)) and, where
-        // this tile owns it, into the middle level's plane. Thread = (4-pixel group grp, row phase ph), rows ph, ph + 6, ..: constant strides.
+        // this tile owns it, into the middle level's plane
         {
-            const int ph = (tid * 1639) >> 16, grp = tid - ph * kPairGroups;   // tid / 40, tid % 40
-            static_assert(kPairGroups == 40 && 6 * kPairGroups <= 256 && 6 * 8 >= kSrcRows, "vertical split of stage A");
-            const bool gvalid = ph < 6 && grp < C.nG;
-            const int x4 = C.bx0 + 4 * grp;
-            const bool own_ok = grp < C.own_g && x4 < cols1;
-            uint8_t* gp = C.d1 + (size_t)(C.sy_lo + ph) * pitch1 + x4;
-            uint32_t* const tb = &bufA[ph * kSrcWords + ((C.bx0 - C.sx_lo) >> 2) + grp];
-            const uint8_t* const hb = reinterpret_cast<const uint8_t*>(&bufH[0]) + 8 * grp;
-            const uint2* const ty = &s_tyA[ph];
+            uint8_t* const drow = d1 + (size_t)sy_lo * pitch1;
 #pragma unroll
-            for (int k = 0; k < 8; ++k, gp += (size_t)6 * pitch1) {
-                const int row = ph + 6 * k;
-                if (gvalid && row < C.nrB) {
-                    const uint2 t = ty[6 * k];
-                    const uint2 h0 = *reinterpret_cast<const uint2*>(hb + (t.x & 0xffffu));
-                    const uint2 h1 = *reinterpret_cast<const uint2*>(hb + (t.x >> 16));
+            for (int k = 0; k < 8; ++k) {
+                if (gvalid && ph < nrB - 6 * k) {   // row ph + 6 k of the region (the bound is a scalar)
+                    const uint2 t = v1_ty[6 * k];
+                    const uint2 h0 = *reinterpret_cast<const uint2*>(v1_hb + (t.x & 0xffffu));
+                    const uint2 h1 = *reinterpret_cast<const uint2*>(v1_hb + (t.x >> 16));
                     const uint32_t out = vgroup_packed(h0, h1, t.y);
-                    tb[6 * k * kSrcWords] = out;
-                    if (own_ok && row < C.own_r) *reinterpret_cast<uint32_t*>(gp) = out;
+                    v1_tb[6 * k * kSrcWords] = out;
+                    if (own_ok && ph < own_r - 6 * k) *reinterpret_cast<uint32_t*>(drow + (size_t)(6 * k) * pitch1 + v1_off) = out;
                 }
             }
         }
-        __syncthreads();
+        __syncthreads();   // B3
         // ---- stage B = v4 on the LDS tile: horizontal pass
         {
-            const uint32_t* Ts = &bufA[q * kSrcWords + t3.wa];
-            uint32_t* H = &bufH[q * (kTileW / 2) + xp];
             uint32_t lo[11], hi[11];
 #pragma unroll
             for (int k = 0; k < 11; ++k) {
-                lo[k] = Ts[4 * k * kSrcWords];
-                hi[k] = Ts[4 * k * kSrcWords + 1];
+                lo[k] = b_Ts[4 * k * kSrcWords];
+                hi[k] = b_Ts[4 * k * kSrcWords + 1];
             }
 #pragma unroll
-            for (int k = 0; k < 11; ++k) H[4 * k * (kTileW / 2)] = hpair(lo[k], hi[k], t3);
+            for (int k = 0; k < 11; ++k) b_H[4 * k * (kTileW / 2)] = hpair(lo[k], hi[k], t3);
         }
-        __syncthreads();
-        // ---- stage B: vertical pass + store (thread = (group, row phase), rows ph, ph + 8, ..)
+        __syncthreads();   // B4
+        // ---- stage B: vertical pass + store
         {
-            const int xg = tid & 31, ph = tid >> 5, x4 = C.x0 + 4 * xg;
-            const bool xok = x4 < cols2;
-            uint8_t* gp = C.d2 + (size_t)(C.y0 + ph) * pitch2 + x4;
-            const uint8_t* const hb = reinterpret_cast<const uint8_t*>(&bufH[0]) + 8 * xg;
-            const uint2* const ty = &s_tyB[ph];
+            uint8_t* const drow = d2 + (size_t)y0 * pitch2;
 #pragma unroll
-            for (int g = 0; g < kGroups; ++g, gp += (size_t)8 * pitch2) {
-                if (xok && C.y0 + ph + 8 * g < rows2) {
-                    const uint2 t = ty[8 * g];
-                    const uint2 h0 = *reinterpret_cast<const uint2*>(hb + (t.x & 0xffffu));
-                    const uint2 h1 = *reinterpret_cast<const uint2*>(hb + (t.x >> 16));
-                    *reinterpret_cast<uint32_t*>(gp) = vgroup_packed(h0, h1, t.y);
+            for (int g = 0; g < kGroups; ++g) {
+                if (xok && ph2 < rows2 - y0 - 8 * g) {
+                    const uint2 t = v2_ty[8 * g];
+                    const uint2 h0 = *reinterpret_cast<const uint2*>(v2_hb + (t.x & 0xffffu));
+                    const uint2 h1 = *reinterpret_cast<const uint2*>(v2_hb + (t.x >> 16));
+                    *reinterpret_cast<uint32_t*>(drow + (size_t)(8 * g) * pitch2 + v2_off) = vgroup_packed(h0, h1, t.y);
                 }
             }
         }
     }
 }
 
+// Tiles per strip by launch size (OVS_PYR_STRIP forces it). A strip's set-up is paid once, but a workgroup lives `strip` times as long, so the
+// launch needs enough strips to keep the tail -- the last, partly filled round of workgroups -- small against the whole. Measured per launch at
+// 256 frames of 1920 x 1080 (67584 / 34816 / 18432 tiles; profiles/r08_pyr_strips.txt), strip = 2 / 4 / 6: 329 / 310 / 311, 181 / 173 / 175 and
+// 98.5 / 94 / 100 us (one tile per workgroup: 98 us for the smallest): four everywhere. Launches of a few frames keep one tile per workgroup:
+// 1280 workgroups are resident at a time, and nothing below 16 k tiles was measured.
+static int pair_strip_auto(long long launch_tiles) {
+    return launch_tiles >= 16384 ? 4 : 1;
+}
+
 hipError_t launch_resize_pair(const uint8_t* src, size_t src_frame_stride, int src_pitch, uint8_t* dst1, int pitch1, int rows1, int cols1,
                               uint8_t* dst2, int pitch2, int rows2, int cols2, size_t dst_frame_stride, const ResizeTap* yt1, const ResizeTap* yt2,
                               const HTapRec* ht1, const HTapRec* ht2, const PairSpan* plan, int batch, hipStream_t s) {
     const int tiles_x = (cols2 + kTileW - 1) / kTileW, tiles_y = (rows2 + kTileH - 1) / kTileH;
-    const int tiles_frame = tiles_x * tiles_y;
-    dim3 grid(((tiles_frame * batch + 7) / 8) * 8);
+    const Tuning& tn = tuning();
+    const int strip = std::min(tn.pyr_strip > 0 ? tn.pyr_strip : pair_strip_auto((long long)tiles_x * tiles_y * batch), tiles_y);
+    const int strips_frame = tiles_x * ((tiles_y + strip - 1) / strip);   // <= tiles_frame: resize_pair_launchable's bound covers the divisions
+    dim3 grid(((strips_frame * batch + 7) / 8) * 8);
     auto magic = [](int d) { return d > 1 ? (uint32_t)(((1ull << 32) + (uint64_t)d - 1) / (uint64_t)d) : 0u; };
     hipLaunchKernelGGL(k_resize_pair_u8, grid, dim3(256), 0, s, src, src_frame_stride, src_pitch, dst1, pitch1, rows1, cols1, dst2, pitch2, rows2, cols2,
-                       dst_frame_stride, yt1, yt2, ht1, ht2, plan, tiles_x, tiles_frame, batch, magic(tiles_x), magic(tiles_frame));
+                       dst_frame_stride, yt1, yt2, ht1, ht2, plan, tiles_x, tiles_y, strip, strips_frame, batch, magic(tiles_x), magic(strips_frame));
     return hipGetLastError();
 }
 // the conditions launch_resize_pair adds to those of the plan (pair_ok): what v4 asks of its source and of the tile count

@@ -173,6 +173,7 @@ struct Tuning {
     int pose_threads;      // OVS_POSE_THREADS: 256 / 512 (0 = by problem size)
     int pose_groups;       // OVS_POSE_GROUPS: workgroups a single frame's pose optimisation is spread over (0 = by observation count, 1 = one)
     int resolve_wide_from; // OVS_RESOLVE_WIDE_FROM: queries from which a resolver round takes 512 of them
+    int pyr_strip;         // OVS_PYR_STRIP: vertically consecutive tiles per k_resize_pair_u8 workgroup (0 = by launch size, 1 = one tile per workgroup)
     int pyr_chain;         // OVS_PYR_CHAIN: frames per launch up to which the pyramid is ONE k_pyramid_chain launch (default 2: measured 24 vs 37 us for one frame, 33.5 vs 35.7 for two, 73 vs 46 for eight; 0 = never)
 };
 const Tuning& tuning();
