@@ -163,12 +163,16 @@ def _util_cos(v):
     return np.where(v < half_pi, poly(v), np.where(v < pi, -poly(pi - v), np.where(v < three_half_pi, -poly(v - pi), poly(two_pi - v)))).astype(_F)
 
 
-def orb_descriptors(blurred, xs, ys, angles_deg, pattern):
-    """compute_orb_descriptor for keypoints (xs, ys) of one blurred level; pattern = the 256 x 4 int8 rBRIEF table."""
+def orb_descriptors(blurred, xs, ys, angles_deg, pattern, trig_variant=0):
+    """compute_orb_descriptor for keypoints (xs, ys) of one blurred level; pattern = the 256 x 4 int8 rBRIEF table.
+    trig_variant = 1 (rule 11's variant): libm's cosf / sinf of the float radian -- here numpy's float32 cos / sin -- instead of util::cos / sin."""
     B = np.asarray(blurred, np.uint8)
     xs, ys = np.asarray(xs, np.int64), np.asarray(ys, np.int64)
     rad = (np.asarray(angles_deg, _F).astype(np.float64) * np.pi / 180.0).astype(_F)   # double product and quotient, ONE rounding to float
-    c, s = _util_cos(rad), _util_cos(_F(1.57079632679489661923) - rad)
+    if trig_variant:
+        c, s = np.cos(rad, dtype=_F), np.sin(rad, dtype=_F)
+    else:
+        c, s = _util_cos(rad), _util_cos(_F(1.57079632679489661923) - rad)
     pat = np.asarray(pattern, np.int64).reshape(256, 4).astype(_F)
 
     def sample(px, py):   # (256,) pattern coordinates against (n,) keypoints -> (n, 256) intensities
