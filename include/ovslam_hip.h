@@ -764,6 +764,39 @@ ovs_status ovs_sim3opt_optimize_batch(ovs_sim3opt* s, int32_t n_problems, const 
                                       int32_t fix_scale, float chi_sq, int32_t num_iter, int32_t* out_num_inliers, double* out_rot_12, double* out_trans_12,
                                       double* out_scale_12, uint8_t* out_outlier_flags, double* out_info);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Two-view triangulation of a keyframe's new landmarks.  replaces: bool module::two_view_triangulator::triangulate(const unsigned idx_1,
+ *   const unsigned idx_2, Vec3_t& pos_w) const (src/openvslam/module/two_view_triangulator.{h,cc}) with solve::triangulator::triangulate
+ *   (src/openvslam/solve/triangulator.h) under it: the choice between the two-view solution and a stereo back-projection by parallax, the
+ *   positive-depth, reprojection and scale-consistency gates, for EVERY matched pair of a BATCH of (keyframe 1, keyframe 2) problems in ONE
+ *   launch (rules T1 to T9) -- local_map_updater's create_new_landmarks hands over all neighbours of a new keyframe at once.
+ * ovs_triangulate_create: a handle for up to max_problems problems of max_total_matches matches together; one internal mutex serialises the
+ *   calls on a handle.
+ * ovs_triangulate_batch: problem p owns matches [offsets[p], offsets[p + 1]) (offsets[0] = 0, non-decreasing). Per match and side: bearings
+ *   (3 doubles: bearings_[idx]), keypts (2 floats: undist_keypts_[idx].pt), x_right (stereo_x_right_[idx]; below 0: no stereo observation),
+ *   depths (depths_[idx]; read only where the side is stereo), sigma_sq (level_sigma_sq_[octave]) and scale_factors (scale_factors_[octave]).
+ *   Per problem and side: cams (model 0 reads fx fy cx cy focal_x_baseline true_baseline, model 1 cols rows) and poses_cw (12 doubles: the
+ *   rotation row-major, then the translation). cos_rays_parallax_thr: the cosine of the constructor's rays_parallax_deg_thr (the class shims
+ *   pass ovs_det_cos(1.0 * pi / 180)); ratio_factor: the caller's 1.5f * scale_factor. Both hold for the whole call.
+ *   Outputs per match: out_pos_w (3 doubles: the point, whatever its status; three zeros under status 1), out_status (0 accepted: upstream
+ *   returns true; 1 no method by parallax, 2 / 3 not in front of camera 1 / 2, 4 / 5 reprojection error in keyframe 1 / 2, 6 scale
+ *   consistency: the first that fails in this order), out_method (0 none, 1 two-view, 2 / 3 back-projection of keyframe 1's / 2's stereo
+ *   observation). Per problem: out_num_accepted. Results are bit-exact functions of a match's own inputs and its problem's, whatever its
+ *   position in the batch. A problem without matches is not an error. A match with a NaN or Inf in it is not an error either: it is rejected
+ *   by the first gate it reaches, and no other match is affected.
+ * OVS_ERR_INVALID: a NULL required pointer, offsets not starting at 0 or decreasing, an unknown camera model, non-finite fx fy cx cy or a zero
+ *   fx / fy (model 0), cols / rows < 1 (model 1), cos_rays_parallax_thr or ratio_factor not finite. OVS_ERR_CAPACITY: more problems or matches
+ *   than the handle was created for (nothing is truncated). Both are decided before any launch, and no output is written. */
+typedef struct ovs_triangulate ovs_triangulate;
+ovs_status ovs_triangulate_create(int32_t device, int32_t max_problems, int32_t max_total_matches, ovs_triangulate** out);
+ovs_status ovs_triangulate_destroy(ovs_triangulate* s);
+ovs_status ovs_triangulate_batch(ovs_triangulate* s, int32_t n_problems, const int32_t* offsets, const double* bearings_1, const double* bearings_2,
+                                 const float* keypts_1, const float* keypts_2, const float* x_right_1, const float* x_right_2, const float* depths_1,
+                                 const float* depths_2, const float* sigma_sq_1, const float* sigma_sq_2, const float* scale_factors_1,
+                                 const float* scale_factors_2, const ovs_camera* cams_1, const ovs_camera* cams_2, const double* poses_cw_1,
+                                 const double* poses_cw_2, double cos_rays_parallax_thr, float ratio_factor, double* out_pos_w, uint8_t* out_status,
+                                 uint8_t* out_method, int32_t* out_num_accepted);
+
 /* replaces: the optimisation inside  void optimize::local_bundle_adjuster::optimize(data::keyframe* curr_keyfrm, bool* const
  *               force_stop_flag) const  (src/openvslam/optimize/local_bundle_adjuster.{h,cc}): everything between the graph build and the
  * write-back, i.e. optimizer.optimize(num_first_iter) with Huber kernels (ONE delta per rig: setup_type 0 = Monocular -> sqrtf(5.99146f),

@@ -128,7 +128,10 @@ SYMBOLS = {
     "ovs_sim3opt_destroy": (_i32, [_vp]),
     "ovs_sim3opt_optimize_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _f, _i32, _vp, _vp, _vp, _vp, _vp,
                                           _vp]),
-    "ovs_local_ba_optimize": (_i32, [_i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, C.c_double, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "ovs_triangulate_create": (_i32, [_i32, _i32, _i32, C.POINTER(_vp)]),
+    "ovs_triangulate_destroy": (_i32, [_vp]),
+    "ovs_triangulate_batch": (_i32, [_vp, _i32, _vp] + [_vp] * 16 + [C.c_double, _f, _vp, _vp, _vp, _vp]),
+    "ovs_local_ba_optimize":(_i32, [_i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, C.c_double, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ovs_local_ba_optimize_equirect": (_i32, [_i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ovs_ba_linearize_stereo": (_i32, [_i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ovs_ba_linearize_stereo_dev": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, C.c_double, C.c_double, _i32, _vp, _vp, _vp, _vp, _vp,

@@ -152,6 +152,7 @@ public:
     std::vector<cv::KeyPoint> keypts_;
     std::vector<cv::KeyPoint> undist_keypts_;
     std::vector<float> stereo_x_right_;
+    std::vector<float> depths_;   // per keypoint, read only where stereo_x_right_ is not negative (module::two_view_triangulator)
     std::vector<Vec3_t> bearings_;
     cv::Mat descriptors_;
     std::vector<landmark*> landmarks_;
@@ -160,6 +161,7 @@ public:
     std::vector<float> level_sigma_sq_;
     std::vector<float> inv_level_sigma_sq_;
     float log_scale_factor_ = 0;
+    float scale_factor_ = 1.2f;
     camera::base* camera_ = nullptr;
     unsigned int id_ = 0;
     bow_vector bow_vec_;
@@ -189,7 +191,8 @@ public:
         : device_cache_(frm.device_cache_), num_keypts_(frm.num_keypts_), keypts_(frm.keypts_), undist_keypts_(frm.undist_keypts_),
           stereo_x_right_(frm.stereo_x_right_), bearings_(frm.bearings_), descriptors_(frm.descriptors_), landmarks_(frm.landmarks_),
           scale_factors_(frm.scale_factors_), level_sigma_sq_(frm.level_sigma_sq_), inv_level_sigma_sq_(frm.inv_level_sigma_sq_), log_scale_factor_(frm.log_scale_factor_),
-          camera_(frm.camera_), bow_vec_(frm.bow_vec_), bow_feat_vec_(frm.bow_feat_vec_), cam_pose_cw_(frm.cam_pose_cw_) {}
+          camera_(frm.camera_), bow_vec_(frm.bow_vec_), bow_feat_vec_(frm.bow_feat_vec_), cam_pose_cw_(frm.cam_pose_cw_), depths_(frm.depths_),
+          scale_factor_(frm.scale_factor_) {}
     std::shared_ptr<frame_device_cache> device_cache_ = std::make_shared<frame_device_cache>();
     unsigned int id_ = 0;
     bool will_be_erased() const { return will_be_erased_; }
@@ -216,6 +219,8 @@ public:
     bow_vector bow_vec_;
     bow_feature_vector bow_feat_vec_;
     Mat44_t cam_pose_cw_;
+    std::vector<float> depths_;   // per keypoint, read only where stereo_x_right_ is not negative (module::two_view_triangulator)
+    float scale_factor_ = 1.2f;
     Mat44_t get_cam_pose() const { return cam_pose_cw_; }
     std::vector<landmark*> get_landmarks() const { return landmarks_; }
     landmark* get_landmark(unsigned int idx) const { return landmarks_.at(idx); }

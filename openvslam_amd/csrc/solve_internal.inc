@@ -1,5 +1,5 @@
 // solve_internal.inc -- what the RANSAC solvers of solve/ share (sim3_solve.hip, pnp_solve.hip). On the device: the counter-based sampler,
-// the hypothesis key, the result record and its invalid form, the cyclic Jacobi rotation and Horn's quaternion form of the absolute
+// the hypothesis key, the result record and its invalid form, the cyclic Jacobi rotation (jacobi_math.inc) and Horn's quaternion form of the absolute
 // orientation. DESIGN.md 3.9 rule 2 fixes every operation; the units are built with -ffp-contract=off. On the host: ransac_handle, the
 // batch scaffold under both C ABIs (create, reserve_models, run_batch). A solver supplies its model, its two kernels, the Layout of its
 // staged block, and to run_batch what stages its arrays and what launches its kernels. run_batch is run_staged with the RANSAC's two
@@ -16,6 +16,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "jacobi_math.inc"
 #include "ovs_common.h"
 #include "owned_internal.inc"
 
@@ -95,41 +96,9 @@ __device__ __forceinline__ void write_invalid(uint8_t* __restrict__ flags, int n
     }
 }
 
-// the rotation (c, s) that zeroes the off-diagonal entry apq != 0 of a symmetric matrix with the diagonal entries app, aqq
-__device__ __forceinline__ void jacobi_angle(double app, double aqq, double apq, double& c, double& s) {
-    const double theta = (aqq - app) / (2.0 * apq);
-    const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-    c = 1.0 / sqrt(t * t + 1.0);
-    s = t * c;
-}
-
-// one Jacobi rotation on the pair (P, Q) of an N x N symmetric matrix held in registers, the operations of
-// essential_solver.h::compute_E_21: columns, then rows, then V
-template <int N, int P, int Q>
-__device__ __forceinline__ void jacobi_rotate(double (&A)[N][N], double (&V)[N][N]) {
-    const double apq = A[P][Q];
-    if (apq == 0.0) return;
-    double c, s;
-    jacobi_angle(A[P][P], A[Q][Q], apq, c, s);
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        const double akp = A[k][P], akq = A[k][Q];
-        A[k][P] = c * akp - s * akq;
-        A[k][Q] = s * akp + c * akq;
-    }
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        const double apk = A[P][k], aqk = A[Q][k];
-        A[P][k] = c * apk - s * aqk;
-        A[Q][k] = s * apk + c * aqk;
-    }
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        const double vkp = V[k][P], vkq = V[k][Q];
-        V[k][P] = c * vkp - s * vkq;
-        V[k][Q] = s * vkp + c * vkq;
-    }
-}
+// the cyclic Jacobi rotation (jacobi_math.inc: shared with triangulate_math.inc, which a plain host compiler builds too)
+using ovs_jacobi::jacobi_angle;
+using ovs_jacobi::jacobi_rotate;
 
 __device__ __forceinline__ double dot3(double a0, double a1, double a2, double b0, double b1, double b2) { return (a0 * b0 + a1 * b1) + a2 * b2; }
 

@@ -12,7 +12,11 @@ csrc/pnp_solve.hip): two launches whatever their number. DESIGN.md 3.10 has the 
 optimize::transform_optimizer (expected: src/openvslam/optimize/transform_optimizer.{h,cc}): the Sim3 refinement the loop detector runs on
 every candidate after projection::match_by_Sim3_transform. It lives here, beside the handle and packing code it shares with the solvers.
 All candidates go to the device in ONE call and ONE launch (ovs_sim3opt_optimize_batch, csrc/sim3_opt.hip). DESIGN.md 3.11 has the rules;
-the results are bit-exact functions of the inputs."""
+the results are bit-exact functions of the inputs.
+
+module::two_view_triangulator (expected: src/openvslam/module/two_view_triangulator.{h,cc}): the triangulation local mapping runs on every
+pair robust::match_for_triangulation returns. All pairs of all neighbours of a new keyframe go to the device in ONE call and ONE launch
+(ovs_triangulate_batch, csrc/triangulate.hip). DESIGN.md 3.12 has the rules; bit-exact in the same sense."""
 import ctypes as C
 import math
 
@@ -282,3 +286,144 @@ class transform_optimizer:
     def optimize(self, problem, chi_sq=10.0):
         r = optimize_transform_batch([problem], self._fix_scale, chi_sq, self._num_iter, device=self._device)[0]
         return r["num_inliers"], r["rot_12"], r["trans_12"], r["scale_12"], r["outlier_flags"]
+
+
+# ---- module::two_view_triangulator
+def _det_cos(x):
+    """ovs_det_cos of include/ovs_detmath.h (DESIGN.md 3.11 rule 3), operation for operation: a Python float is an IEEE f64 and every
+    operation rounds once. The class shims of both languages turn rays_parallax_deg_thr into cos_rays_parallax_thr with it."""
+    if not abs(x) <= 1048576.0:
+        return float("nan")
+    m = 0
+    while abs(x) > _PI_O_4:
+        x = x * 0.5
+        m += 1
+    z = x * x
+    p = _SIN_K[0]
+    for k in _SIN_K[1:]:
+        p = k + z * p
+    s = x + x * (z * p)
+    p = _COS_K[0]
+    for k in _COS_K[1:]:
+        p = k + z * p
+    c = (1.0 - 0.5 * z) + z * (z * p)
+    for _ in range(m):
+        s, c = 2.0 * (s * c), 1.0 - 2.0 * (s * s)
+    return c
+
+
+_PI_O_4 = float.fromhex("0x1.921fb54442d18p-1")
+_SIN_K = [float.fromhex(h) for h in ("0x1.952c77030ad4ap-49", "-0x1.ae7f3e733b81fp-41", "0x1.6124613a86d09p-33", "-0x1.ae64567f544e4p-26",
+                                     "0x1.71de3a556c734p-19", "-0x1.a01a01a01a01ap-13", "0x1.1111111111111p-7", "-0x1.5555555555555p-3")]
+_COS_K = [float.fromhex(h) for h in ("0x1.ae7f3e733b81fp-45", "-0x1.93974a8c07c9dp-37", "0x1.1eed8eff8d898p-29", "-0x1.27e4fb7789f5cp-22",
+                                     "0x1.a01a01a01a01ap-16", "-0x1.6c16c16c16c17p-10", "0x1.5555555555555p-5")]
+
+
+def cos_rays_parallax_thr(rays_parallax_deg_thr=1.0):
+    """two_view_triangulator's cos_rays_parallax_thr_ for the constructor's rays_parallax_deg_thr."""
+    return _det_cos(float(rays_parallax_deg_thr) * math.pi / 180.0)
+
+
+_TRI_ARRAYS = (("bearings_1", np.float64, 3), ("bearings_2", np.float64, 3), ("keypts_1", np.float32, 2), ("keypts_2", np.float32, 2),
+               ("x_right_1", np.float32, 1), ("x_right_2", np.float32, 1), ("depths_1", np.float32, 1), ("depths_2", np.float32, 1),
+               ("sigma_sq_1", np.float32, 1), ("sigma_sq_2", np.float32, 1), ("scale_factors_1", np.float32, 1), ("scale_factors_2", np.float32, 1))
+
+
+def _pose12(pose_cw):
+    """rotation row-major, then translation, of a 4 x 4 or 3 x 4 world -> camera pose (12 doubles pass through)."""
+    T = np.asarray(pose_cw, np.float64)
+    if T.size == 12 and T.ndim == 1:
+        return T.copy()
+    return np.concatenate([T[:3, :3].ravel(), T[:3, 3]])
+
+
+def triangulation_problem_from_keyframes(matches, keypts_1, keypts_2, stereo_x_right_1, stereo_x_right_2, depths_1, depths_2, bearings_1, bearings_2,
+                                         octaves_1, octaves_2, scale_factors, level_sigma_sq, pose_cw_1, pose_cw_2, cam_1, cam_2):
+    """What two_view_triangulator reads of two keyframes for the matched pairs. matches: (m, 2) pairs (idx_1, idx_2), or a 1-D matched_2_in_1
+    array exactly as match_for_triangulation returns it (entry idx_1 holds idx_2, or -1). keypts_*: (n, 2) undistorted keypoints;
+    stereo_x_right_* / depths_*: (n,), or None for a keyframe without stereo observations; bearings_*: (n, 3); octaves_*: (n,);
+    scale_factors / level_sigma_sq: per level; pose_cw_*: 4 x 4 (or 3 x 4) world -> camera. The problem keeps the pairs as idx_1 / idx_2."""
+    m = np.asarray(matches)
+    if m.ndim == 1:
+        idx_1 = np.nonzero(m >= 0)[0].astype(np.int64)
+        idx_2 = m[idx_1].astype(np.int64)
+    else:
+        m = m.reshape(-1, 2).astype(np.int64)
+        idx_1, idx_2 = m[:, 0], m[:, 1]
+    sf, sig = np.asarray(scale_factors, np.float32), np.asarray(level_sigma_sq, np.float32)
+    take = lambda a, idx, n: np.full(len(idx), -1.0, np.float32) if a is None else np.asarray(a, np.float32).reshape(n)[idx]
+    q = dict(idx_1=idx_1, idx_2=idx_2, cam_1=cam_1, cam_2=cam_2, pose_cw_1=_pose12(pose_cw_1), pose_cw_2=_pose12(pose_cw_2))
+    for side, idx, kp, xr, dep, b, octv in (("1", idx_1, keypts_1, stereo_x_right_1, depths_1, bearings_1, octaves_1),
+                                             ("2", idx_2, keypts_2, stereo_x_right_2, depths_2, bearings_2, octaves_2)):
+        n = len(np.asarray(octv).ravel())
+        o = np.asarray(octv, np.int64).ravel()[idx]
+        q["bearings_" + side] = np.asarray(b, np.float64).reshape(n, 3)[idx]
+        q["keypts_" + side] = np.asarray(kp, np.float32).reshape(n, 2)[idx]
+        q["x_right_" + side] = take(xr, idx, n)
+        q["depths_" + side] = take(dep, idx, n)
+        q["sigma_sq_" + side] = sig[o]
+        q["scale_factors_" + side] = sf[o]
+    return q
+
+
+class _triangulate_handle(_ransac_handle):
+    """ovs_triangulate with its capacity."""
+    _abi = "ovs_triangulate"
+
+
+def triangulate_batch(problems, ratio_factor, cos_rays_parallax_thr=cos_rays_parallax_thr(1.0), handle=None, device=0):
+    """two_view_triangulator::triangulate for every match of every problem (dicts as triangulation_problem_from_keyframes returns them) in one
+    call: a list of dicts pos_w (n, 3), status (n, uint8: 0 accepted, else the gate that rejected, DESIGN.md 3.12 rule T9), method (n, uint8),
+    accepted (n, bool) and num_accepted. ratio_factor: the caller's 1.5f * scale_factor. `handle`: a _triangulate_handle to reuse (the mapping
+    thread keeps one)."""
+    P = len(problems)
+    if P == 0:
+        return []
+    offsets = np.zeros(P + 1, np.int32)
+    offsets[1:] = np.cumsum([len(np.asarray(q["x_right_1"]).ravel()) for q in problems])
+    T = int(offsets[-1])
+    cat = lambda key, dt, w: np.ascontiguousarray(np.concatenate([np.asarray(q[key], dt).reshape(-1, w) for q in problems]) if T else np.zeros((0, w), dt))
+    packed = [cat(*a) for a in _TRI_ARRAYS]
+    if any(len(a) != T for a in packed):
+        raise ValueError("every per-match array of a problem must have one entry per match")
+    cams_1 = (_lib.Camera * P)(*[q["cam_1"] for q in problems])
+    cams_2 = (_lib.Camera * P)(*[q["cam_2"] for q in problems])
+    poses_1 = np.ascontiguousarray([_pose12(q["pose_cw_1"]) for q in problems])
+    poses_2 = np.ascontiguousarray([_pose12(q["pose_cw_2"]) for q in problems])
+    if handle is None:
+        handle = _triangulate_handle(P, max(T, 1), device)
+    pos, status, method, num = np.zeros((max(T, 1), 3)), np.zeros(max(T, 1), np.uint8), np.zeros(max(T, 1), np.uint8), np.zeros(P, np.int32)
+    _lib.check(handle._L.ovs_triangulate_batch(handle._h, P, _p(offsets), *map(_p, packed), cams_1, cams_2, _p(poses_1), _p(poses_2),
+                                               float(cos_rays_parallax_thr), float(ratio_factor), _p(pos), _p(status), _p(method), _p(num)),
+               "ovs_triangulate_batch")
+    return [dict(pos_w=pos[offsets[i]:offsets[i + 1]].copy(), status=status[offsets[i]:offsets[i + 1]].copy(), method=method[offsets[i]:offsets[i + 1]].copy(),
+                 accepted=status[offsets[i]:offsets[i + 1]] == 0, num_accepted=int(num[i])) for i in range(P)]
+
+
+class two_view_triangulator:
+    """module::two_view_triangulator: upstream's constructor (keyfrm_1, keyfrm_2, rays_parallax_deg_thr) and triangulate(idx_1, idx_2), which
+    returns (accepted, pos_w); triangulate_matches(pairs) hands every pair of the two keyframes to one device call. A keyframe is a dict:
+    undist_keypts (n, 2), stereo_x_right and depths ((n,) or None), bearings (n, 3), octaves (n,), scale_factors and level_sigma_sq (per
+    level), scale_factor, pose_cw (4 x 4) and camera (solve.camera)."""
+
+    def __init__(self, keyfrm_1, keyfrm_2, rays_parallax_deg_thr=1.0, device=0):
+        self._k1, self._k2, self._device = keyfrm_1, keyfrm_2, device
+        self._cos_thr = cos_rays_parallax_thr(rays_parallax_deg_thr)
+        self._ratio_factor = np.float32(1.5) * np.float32(max(keyfrm_1["scale_factor"], keyfrm_2["scale_factor"]))
+
+    def problem(self, pairs):
+        a, b = self._k1, self._k2
+        if np.asarray(a["scale_factors"], np.float32).tolist() != np.asarray(b["scale_factors"], np.float32).tolist():
+            raise ValueError("both keyframes must share their scale pyramid")
+        return triangulation_problem_from_keyframes(np.asarray(pairs, np.int64).reshape(-1, 2), a["undist_keypts"], b["undist_keypts"], a.get("stereo_x_right"),
+                                                    b.get("stereo_x_right"), a.get("depths"), b.get("depths"), a["bearings"], b["bearings"], a["octaves"],
+                                                    b["octaves"], a["scale_factors"], a["level_sigma_sq"], a["pose_cw"], b["pose_cw"], a["camera"], b["camera"])
+
+    def triangulate_matches(self, pairs, handle=None):
+        """(accepted (m, bool), pos_w (m, 3)) for the pairs (idx_1, idx_2)."""
+        r = triangulate_batch([self.problem(pairs)], float(self._ratio_factor), self._cos_thr, handle=handle, device=self._device)[0]
+        return r["accepted"], r["pos_w"]
+
+    def triangulate(self, idx_1, idx_2):
+        accepted, pos_w = self.triangulate_matches([(idx_1, idx_2)])
+        return bool(accepted[0]), pos_w[0]
