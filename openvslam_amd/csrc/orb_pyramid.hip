@@ -1,7 +1,7 @@
 // orb_pyramid.hip -- A1: orb_extractor::compute_image_pyramid (expected: src/openvslam/feature/orb_extractor.cc), i.e.
 // cv::resize(prev_level, level, size, 0, 0, INTER_LINEAR) for CV_8UC1 in OpenCV's 11-bit fixed point.
 // Integer-only on the device: the float/double part of OpenCV (source coordinate, coefficient rounding) is evaluated
-// once per geometry on the host into ResizeTap tables (orb_api.hip: build_taps) so no device float can change a pixel.
+// once per geometry on the host into ResizeTap tables (orb_plan.inc: build_taps) so no device float can change a pixel.
 //
 // HBM-bound streaming kernel. A 256-thread workgroup produces a 128 x 32 output tile: the source rectangle its taps
 // touch (<= 160 x 41 bytes at scale 1.2) is staged in LDS with coalesced, aligned u32 loads -- v1 gathered 16 single bytes
@@ -16,14 +16,14 @@
 
 namespace ovs {
 
-constexpr int kTileW = 128, kTileH = 32;
+// kTileW x kTileH output tile, kSrcWords x kSrcRows staged source rectangle: orb_geometry.h, where the planner (orb_plan.inc) reads them too
 constexpr int kGroups = kTileW * kTileH / 4 / 256;   // 4-pixel groups per thread
 constexpr int kSlots = 8;                            // u32 staging loads per thread in flight (generic-alignment path)
-constexpr int kSrcWords = 48;    // 192-byte LDS pitch: source span of 128 output px is <= 128*src/dst + 2 <= 160 at scale <= 1.25, + 15
-                                 // bytes so that the staged rectangle starts on a 16-byte boundary (16-byte staging loads)
 constexpr int kRowChunks = kSrcWords / 4;   // 16-byte chunks per staged row
 constexpr int kChunkSlots = 3;              // 44 rows x 12 chunks <= 3 * 256
-constexpr int kSrcRows = 44;    // 32 output rows span <= 32 * 1.25 + 2 source rows (16-row tiles: 0.167 ms, 32: 0.142, 64: 0.165)
+// what resize_windows_ok (orb_plan.inc) admits must be what the kernels below index: the tile, its staged rectangle, the 16-byte staging chunks
+static_assert(kTileW == 128 && kTileH == 32 && kSrcWords == 48 && kSrcRows == 44 && kSrcWords % 4 == 0 && kSrcRows * kRowChunks <= kChunkSlots * 256,
+              "v4 tile and LDS rectangle");
 
 // high 32 bits of the 48-bit product of two 24-bit operands (full-rate VOP3; hipcc has no builtin for it)
 __device__ __forceinline__ uint32_t mulhi_u24(uint32_t a, uint32_t b) {
@@ -369,12 +369,13 @@ hipError_t launch_resize(const uint8_t* src, size_t src_frame_stride, int src_pi
 // tiles overlap by a halo of 1-6 columns / 1-2 rows that both compute (identical integers) and only one stores. Stage B is v4's code on that
 // LDS tile. Same integers as two v4 launches (tests: planes byte-equal; the oracle's resize is the reference for both).
 // LDS: bufA = lower rectangle, later the middle region; bufH = stage A's horizontal pass, later stage B's: 28.3 KB, five workgroups per CU.
-// The regions (PairSpan per tile column / tile row) are computed on the host from the tap tables (orb_api.hip build_pair_plan), which also checks
+// The regions (PairSpan per tile column / tile row) are computed on the host from the tap tables (orb_plan.inc build_pair_plan), which also checks
 // that everything fits (pair_ok); a level pair that does not fit runs as two v4 / generic launches.
-constexpr int kPairSrcWords = 56;     // 224-byte pitch of the lower rectangle: 160 middle columns x 1.25 + 2 + 15 <= 217
-constexpr int kPairSrcRows = 52;      // 44 middle rows x 1.2 + 2 (host-checked)
+// kPairSrcWords x kPairSrcRows lower rectangle, kPairGroups groups per middle row: orb_geometry.h
 constexpr int kPairRowChunks = kPairSrcWords / 4;   // 52 rows x 14 sixteen-byte chunks
-constexpr int kPairGroups = 40;       // 4-pixel groups per row of the middle region (160 columns)
+// build_pair_plan bounds the middle region by v4's tile (stage B runs v4's code on it, at v4's pitch): 48 words x 44 rows, at most 40 groups computed
+static_assert(kSrcWords == 48 && kSrcRows == 44 && kPairGroups <= kSrcWords && kPairSrcWords == 56 && kPairSrcRows == 52 && kPairSrcWords % 4 == 0,
+              "pair kernel: stage B's tile is the v4 tile");
 
 struct HTaps {
     uint32_t sel_a, sel_b, ca, cb;
@@ -689,7 +690,7 @@ bool resize_pair_launchable(const uint8_t* src, size_t src_frame_stride, int src
 // level's region needs of level l (the tap footprint: a halo of 1-2 pixels per level and side, recomputed redundantly by the neighbours --
 // identical integers, and only the OWNED pixels are stored to the level's plane). No workgroup waits for another one, so there are no
 // flags, no grid barrier and no ordering between launches: one launch, L - 1 workgroup barriers. The regions (ChainSpan, per level and tile
-// column / row) are computed on the host with the tap tables (orb_api.hip build_chain_plan); the arithmetic is the generic kernel's
+// column / row) are computed on the host with the tap tables (orb_plan.inc build_chain_plan); the arithmetic is the generic kernel's
 // (the same integers as v4): h = (S[o0] a0 + S[o1] a1) >> 4 per source row, out = (((b0 h0) >> 16) + ((b1 h1) >> 16) + 2) >> 2.
 // Throughput is NOT the point (about 1.2x the pixels, byte-wise LDS reads): the batch path keeps the per-level kernels above.
 constexpr int kChainThreads = 1024;
@@ -823,11 +824,10 @@ __global__ __launch_bounds__(kChainThreads) void k_pyramid_chain(const uint8_t* 
     }
 }
 
-size_t chain_lds_bytes(int bufA_bytes, int bufB_bytes, int tap_cap) {
-    return (size_t)bufA_bytes + bufB_bytes + sizeof(ChainSpan) * 2 * OVS_MAX_LEVELS + sizeof(int4) * OVS_MAX_LEVELS + sizeof(ResizeTap) * (size_t)tap_cap;
-}
+// what build_chain_plan (orb_plan.inc) bounds the regions by: s_lv's records in chain_lds_bytes (orb_geometry.h), the level-0 staging, the column chunks
+static_assert(sizeof(int4) == 16 && kChainMaxH0 == 16 * kChainRowsPerThread && kChainMaxW0 == 4 * 64 && kChainMaxW == 3 * 64, "chain regions");
 
-// plan: L x (TX + TY) spans in device memory (orb_api.hip build_chain_plan, uploaded by ensure_geometry); lds = bufA + bufB + spans + taps
+// plan: L x (TX + TY) spans in device memory (orb_plan.inc build_chain_plan, uploaded by ensure_geometry); lds = bufA + bufB + spans + taps
 hipError_t launch_pyramid_chain(const uint8_t* img0, size_t frame_stride0, int pitch0, uint8_t* pyr, size_t pyr_frame_bytes, const FrameGeo* d_geo,
                                 const ResizeTap* d_taps, const ChainSpan* d_plan, int TX, int TY, int bufA_bytes, int bufB_bytes, int tap_cap,
                                 int batch, hipStream_t s) {

@@ -782,7 +782,7 @@ static int tree_root_cap(const FrameGeo& hgeo) {
     return (r + 3) & ~3;
 }
 
-// LDS the quad-tree kernel needs for this geometry (its per-node arrays are sized by the largest level); build_geometry refuses
+// LDS the quad-tree kernel needs for this geometry (its per-node arrays are sized by the largest level); orb_api.hip's plan_for refuses
 // parameter sets that exceed the 160 KB a workgroup can have (about 2100 keypoints on ONE level, e.g. 9 600 features over 8 levels)
 size_t tree_lds_bytes_for(const FrameGeo& hgeo) {
     int NCmax = 0;

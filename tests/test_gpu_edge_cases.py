@@ -164,6 +164,42 @@ def test_refused_geometry_leaves_the_handle_usable(oracle):
     assert np.array_equal(k3.view(np.uint8), wk.view(np.uint8)) and np.array_equal(d3, wd)
 
 
+def test_failed_geometry_switch_commits_nothing():
+    """ensure_geometry commits the new plan only after its last upload: the k-th checked call of an extract at a new size reported as failed
+    (ovs_debug_inject_hip_failures: the call itself still runs), for every k up to the switch's own calls -- hipSetDevice, the synchronisation
+    and the six uploads. Each attempt returns OVS_ERR_HIP or succeeds, and afterwards the new size and then the previous one give what a fresh
+    handle gives, byte for byte."""
+    import torch
+    from openvslam_amd import _lib, feature
+    L = _lib.lib()
+    rng = np.random.default_rng(7)
+    img64, img45 = rng.integers(0, 256, (64, 64), np.uint8), rng.integers(0, 64, (45, 45), np.uint8)
+    img45[22, 22] = 255   # level 0 of 45 x 45 has one testable pixel: make it a corner
+    make = lambda: feature.orb_extractor(feature.orb_params(max_num_keypts=300, scale_factor=1.2, num_levels=8), max_rows=64, max_cols=64)
+    want64, want45 = make().extract(img64), make().extract(img45)
+    assert len(want64[0]) > 0 and len(want45[0]) > 0
+    ex = make()
+    first = ex.extract(img64)
+    assert np.array_equal(first[0].view(np.uint8), want64[0].view(np.uint8)) and np.array_equal(first[1], want64[1])
+    failed = 0
+    try:
+        for skip in range(8):
+            L.ovs_debug_inject_hip_failures(skip, 1)
+            try:
+                ex.extract(img45)
+            except _lib.OvsError as e:
+                assert e.status == -3, (skip, e.status)
+                failed += 1
+            L.ovs_debug_inject_hip_failures(0, 0)
+    finally:
+        L.ovs_debug_inject_hip_failures(0, 0)
+    assert failed >= 7   # every call of the switch is a checked one
+    torch.cuda.synchronize()
+    for img, want in ((img45, want45), (img64, want64)):
+        k, d = ex.extract(img)
+        assert len(k) == len(want[0]) and np.array_equal(k.view(np.uint8), want[0].view(np.uint8)) and np.array_equal(d, want[1]), img.shape
+
+
 def test_more_than_64_root_patches(oracle):
     """VERDICT round 5, missing #5: aspect ratios above ~64:1 were refused (the quad-tree's root tables held 64 patches); upstream's
     initialize_nodes has no such limit. A handle created for the strip runs it, bit for bit against the oracle: 60 x 1920 (85 root patches on
