@@ -20,6 +20,7 @@
 
 #include "ovs_common.h"
 #include "owned_internal.inc"
+#include "pose_plan.inc"
 
 namespace ovs {
 
@@ -259,8 +260,8 @@ __device__ __forceinline__ double pose_edge_impl(const double* R, const double* 
     return c2;
 }
 
-constexpr int kPoseMaxObs = 8192;   // <= 32 observations per thread: the inlier flags of a thread fit one register
-// one workgroup per frame, kPoseThreads threads (template parameter: 256 / 512 / 1024, chosen per launch)
+static_assert(sizeof(ovs_pose_obs) == kPoseObsBytes, "pose_plan.inc lays the records out");
+// one workgroup per frame (or G of them), kPoseThreads threads (template parameter: 256 / 512, chosen per launch by pose_plan.inc)
 
 // KREG (round 6): 2 = the launcher knows that no thread owns more than two observations (n <= 2 G kPoseThreads: every tracked frame on the
 // G > 1 path): a thread then loads ITS two 64-byte records once, before the first round, and every one of the ~50 passes of a call reads
@@ -285,7 +286,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_optimize(const double* __
     __shared__ PoseD s_T, s_Tn;
     __shared__ PoseD s_Tq[9];              // trial poses of an iteration's retries 1 .. 9 (evaluated together, see below)
     __shared__ double s_okq[9], s_scq[9];  // ... whether the solve succeeded, and the gain ratio's denominator
-    __shared__ double s_ctl[4];   // [0] = continue trials of this iteration, [1] = continue iterations of this round
+    __shared__ double s_ctl[2];   // of the trial thread 0 solved alone: [0] = the solve succeeded, [1] = the gain ratio's denominator
     __shared__ int s_cnt[kPoseWaves];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     // G > 1 is launched for ONE frame with 8 G workgroups of which every eighth works: consecutive workgroups are dealt round-robin to the
@@ -341,8 +342,11 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_optimize(const double* __
         __syncthreads();
         return true;
     };
-#define POSE_EXCHANGE(nv)                                        \
-    if (!exchange(nv)) {                                         \
+// the one way to leave on an abandoned barrier, at every exchange site: met = what exchange() (or linearise_at(), which ends in one) returned.
+// (A macro, not a lambda: a lambda alone moved hipcc's block placement and schedule of the whole kernel, and every such move measured 1-5 %
+// slower; see docs/HISTORY.md, "the pose optimiser's launch plan leaves pose_opt.hip".)
+#define POSE_LEAVE_UNLESS(met)                                   \
+    if (!(met)) {                                                \
         if (tid == 0 && grp == 0) num_valid[p] = -2;             \
         return;                                                  \
     }
@@ -472,10 +476,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_optimize(const double* __
             };
             for (int it = 0; it < 10; ++it) {
                 err_at_trial = false;    // solve() starts with computeActiveErrors() at the current estimate
-                if (!have_lin && !linearise_at(false)) {
-                    if (tid == 0 && grp == 0) num_valid[p] = -2;
-                    return;
-                }
+                POSE_LEAVE_UNLESS(have_lin || linearise_at(false))
                 have_lin = false;
                 // the system stays in LDS (s_sys: H upper triangle row-major, b, chi2): only thread 0 needs it, for the solve, and 42 doubles
                 // held by every thread across the trial's linearisation would not fit the register file of a 512-thread workgroup
@@ -558,7 +559,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_optimize(const double* __
                             for (int u = 0; u < 9; ++u) part[u] = u == q ? pq : part[u];   // (no dynamic index into the register array)
                         }
                         reduce(part, 9);
-                        POSE_EXCHANGE(9)
+                        POSE_LEAVE_UNLESS(exchange(9))
                         double lam = lambda, nn = ni;
                         int last_ok = -1;
                         bool accepted = false;
@@ -628,10 +629,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_optimize(const double* __
                     double temp_chi = 1.7976931348623157e308;
                     const bool full = ok && qmax == 0;   // (workgroup-uniform)
                     if (full) {
-                        if (!linearise_at(true)) {
-                            if (tid == 0 && grp == 0) num_valid[p] = -2;
-                            return;
-                        }
+                        POSE_LEAVE_UNLESS(linearise_at(true))
                         temp_chi = s_sum[27];
                         err_at_trial = true;
                     } else if (ok) {
@@ -653,7 +651,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_optimize(const double* __
                         if (has_stereo) sweep(std::true_type{});
                         else sweep(std::false_type{});
                         reduce(&part, 1);
-                        POSE_EXCHANGE(1)
+                        POSE_LEAVE_UNLESS(exchange(1))
                         temp_chi = s_sum[0];
                         err_at_trial = true;
                     }
@@ -661,7 +659,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_optimize(const double* __
                     rho = (current_chi - temp_chi) / scale;
                     if (rho > 0 && isfinite(temp_chi)) {
                         const double tr = 2 * rho - 1;
-                                double alpha = 1. - tr * tr * tr;   // (g2o: pow(2 rho - 1, 3); the library pow was ~150 instructions per lane for a cube)
+                        double alpha = 1. - tr * tr * tr;   // (g2o: pow(2 rho - 1, 3); the library pow was ~150 instructions per lane for a cube)
                         alpha = fmin(alpha, 2.0 / 3.0);
                         lambda *= fmax(1.0 / 3.0, alpha);
                         ni = 2;
@@ -708,7 +706,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_optimize(const double* __
                 if (G > 1) {   // (counts below 2^53 are exact as doubles)
                     if (tid == 0) s_sum[0] = (double)num_bad;
                     __syncthreads();
-                    POSE_EXCHANGE(1)
+                    POSE_LEAVE_UNLESS(exchange(1))
                     num_bad = (int)s_sum[0];
                     __syncthreads();
                 }
@@ -721,7 +719,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_optimize(const double* __
         if (tid < 3) poses_out[12 * (size_t)p + 9 + tid] = s_T.t[tid];
         if (tid == 0) num_valid[p] = n >= 5 ? n - num_bad : 0;
     }
-#undef POSE_EXCHANGE
+#undef POSE_LEAVE_UNLESS
 }
 
 }   // namespace ovs
@@ -731,41 +729,60 @@ using namespace ovs;
 // ovs_pose_set_variant(OVS_POSE_VARIANT_RESET_EACH_ROUND, 0 | 1): process-wide, read at every launch
 static std::atomic<int> g_pose_reset_each_round{0};
 
-extern "C" {
+namespace {
 
-static ovs_status pose_optimize_batch_dev(int model, const double* d_poses_in, const ovs_pose_obs* d_obs, const int32_t* d_obs_offsets, int32_t batch,
-                                          const ovs_ba_cam& cam, double focal_x_baseline, int32_t setup_type, double* d_poses_out,
-                                          uint8_t* d_outlier, int32_t* d_num_valid, void* stream, int threads_default = 256, int groups = 1,
-                                          unsigned long long* d_gpart = nullptr, unsigned int epoch0 = 0, int batch_retries_auto = 0, bool obs_in_regs = false, int stereo_hint = -1) {
-    if (!d_poses_in || !d_obs || !d_obs_offsets || !d_poses_out || !d_outlier || !d_num_valid || batch < 1) return OVS_ERR_INVALID;
-    // workgroup size: the kernel is one latency-bound workgroup per frame; more waves hide the f64 latency of the per-observation work
-    // but pay in barriers (measured per 2000-observation frame in DESIGN.md section 3.6)
-    const int threads_env = tuning().pose_threads;
-    const int T = threads_env == 256 || threads_env == 512 ? threads_env : threads_default;
-    const size_t lds = sizeof(double) * 28 * (size_t)(T + 8);
-#define OVS_POSE_LAUNCH(MODEL, TT, KR, BF, ST)                                                                                              \
-    do {                                                                                                                              \
-        static LdsAttrCache configured; /* per device: a second device needs the attribute too (116 KB of dynamic LDS at 512 threads) */  \
-        OVS_HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(k_pose_optimize<MODEL, TT, KR>), sizeof(double) * 28 * (TT + 8), configured)); \
-        hipLaunchKernelGGL((k_pose_optimize<MODEL, TT, KR>), dim3(batch, groups > 1 ? 8 * groups : 1), dim3(TT), lds, (hipStream_t)stream, d_poses_in, d_obs, d_obs_offsets, \
-                           cam, BF, ST, d_poses_out, d_outlier, d_num_valid, g_pose_reset_each_round.load(std::memory_order_relaxed), groups, d_gpart, \
-                           epoch0, tuning().pose_batch_retries < 0 ? batch_retries_auto : tuning().pose_batch_retries, stereo_hint);      \
-    } while (0)
-    // obs_in_regs: the caller knows every frame of the launch has at most 2 * groups * 256 observations (KREG = 2, 256-thread workgroups only)
-    const bool kreg = obs_in_regs && T == 256 && tuning().pose_obs_regs;
-    if (model == 1) {
-        if (T == 512) OVS_POSE_LAUNCH(1, 512, 0, 0.0, 0);
-        else if (kreg) OVS_POSE_LAUNCH(1, 256, 2, 0.0, 0);
-        else OVS_POSE_LAUNCH(1, 256, 0, 0.0, 0);
-    } else {
-        if (T == 512) OVS_POSE_LAUNCH(0, 512, 0, focal_x_baseline, (int)setup_type);
-        else if (kreg) OVS_POSE_LAUNCH(0, 256, 2, focal_x_baseline, (int)setup_type);
-        else OVS_POSE_LAUNCH(0, 256, 0, focal_x_baseline, (int)setup_type);
-    }
-#undef OVS_POSE_LAUNCH
+PoseSwitches pose_switches() {
+    const Tuning& t = tuning();
+    return {t.pose_threads, t.pose_groups, t.pose_batch_retries, t.pose_obs_regs, t.pose_zero_copy};
+}
+
+// what a launch works on: `batch` frames, frame p with the observations [offsets[p], offsets[p + 1])
+struct PoseArgs {
+    const double* poses_in;
+    const ovs_pose_obs* obs;
+    const int32_t* offsets;
+    int32_t batch;
+    ovs_ba_cam cam;
+    double bf;
+    int32_t setup_type;
+    double* poses_out;
+    uint8_t* outlier;
+    int32_t* num_valid;
+    unsigned long long* gpart = nullptr;   // exchange words of the grouped form (one frame, PoseLaunch::groups > 1)
+    unsigned int epoch0 = 0;
+    int stereo_hint = -1;                  // -1: the kernel finds out whether a frame holds a stereo observation
+};
+
+template <int MODEL, int TT, int KR>
+ovs_status launch_pose(const PoseArgs& a, const PoseLaunch& l, hipStream_t stream) {
+    static LdsAttrCache configured;   // per device: a second device needs the attribute too (116 KB of dynamic LDS at 512 threads)
+    constexpr size_t lds = sizeof(double) * 28 * (TT + 8);
+    OVS_HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(k_pose_optimize<MODEL, TT, KR>), lds, configured));
+    hipLaunchKernelGGL((k_pose_optimize<MODEL, TT, KR>), dim3(a.batch, l.groups > 1 ? 8 * l.groups : 1), dim3(TT), lds, stream, a.poses_in, a.obs, a.offsets,
+                       a.cam, a.bf, (int)a.setup_type, a.poses_out, a.outlier, a.num_valid, g_pose_reset_each_round.load(std::memory_order_relaxed), l.groups,
+                       a.gpart, a.epoch0, l.batch_retries, a.stereo_hint);
     OVS_HIP_TRY(hipGetLastError());
     return OVS_OK;
 }
+
+ovs_status pose_launch(int model, const PoseArgs& a, const PoseLaunch& l, void* stream) {
+    if (!a.poses_in || !a.obs || !a.offsets || !a.poses_out || !a.outlier || !a.num_valid || a.batch < 1) return OVS_ERR_INVALID;
+    ovs_status (*launch)(const PoseArgs&, const PoseLaunch&, hipStream_t);
+    if (model == 1) {
+        if (l.threads == 512) launch = launch_pose<1, 512, 0>;
+        else if (l.kreg) launch = launch_pose<1, 256, 2>;
+        else launch = launch_pose<1, 256, 0>;
+    } else {
+        if (l.threads == 512) launch = launch_pose<0, 512, 0>;
+        else if (l.kreg) launch = launch_pose<0, 256, 2>;
+        else launch = launch_pose<0, 256, 0>;
+    }
+    return launch(a, l, (hipStream_t)stream);
+}
+
+}   // namespace
+
+extern "C" {
 
 ovs_status ovs_pose_set_variant(int32_t which, int32_t value) {
     if (which != OVS_POSE_VARIANT_RESET_EACH_ROUND || (value != 0 && value != 1)) return OVS_ERR_INVALID;
@@ -777,16 +794,16 @@ ovs_status ovs_pose_optimize_batch_dev(const double* d_poses_in, const ovs_pose_
                                        const ovs_ba_cam* cam, double focal_x_baseline, int32_t setup_type, double* d_poses_out,
                                        uint8_t* d_outlier, int32_t* d_num_valid, void* stream) {
     if (!cam) return OVS_ERR_INVALID;
-    return pose_optimize_batch_dev(0, d_poses_in, d_obs, d_obs_offsets, batch, *cam, focal_x_baseline, setup_type, d_poses_out, d_outlier, d_num_valid,
-                                   stream);
+    return pose_launch(0, {d_poses_in, d_obs, d_obs_offsets, batch, *cam, focal_x_baseline, setup_type, d_poses_out, d_outlier, d_num_valid},
+                       pose_plan_batch(pose_switches()), stream);
 }
 
 ovs_status ovs_pose_optimize_equirect_batch_dev(const double* d_poses_in, const ovs_pose_obs* d_obs, const int32_t* d_obs_offsets, int32_t batch,
                                                 int32_t cols, int32_t rows, double* d_poses_out, uint8_t* d_outlier, int32_t* d_num_valid,
                                                 void* stream) {
     if (cols < 1 || rows < 1) return OVS_ERR_INVALID;
-    const ovs_ba_cam cam = {(double)cols, (double)rows, 0.0, 0.0};
-    return pose_optimize_batch_dev(1, d_poses_in, d_obs, d_obs_offsets, batch, cam, 0.0, 0, d_poses_out, d_outlier, d_num_valid, stream);
+    return pose_launch(1, {d_poses_in, d_obs, d_obs_offsets, batch, {(double)cols, (double)rows, 0.0, 0.0}, 0.0, 0, d_poses_out, d_outlier, d_num_valid},
+                       pose_plan_batch(pose_switches()), stream);
 }
 
 static ovs_status pose_optimize_host(int model, int32_t device, const double* pose_cw_in, const ovs_pose_obs* obs, int32_t n_obs,
@@ -796,14 +813,7 @@ static ovs_status pose_optimize_host(int model, int32_t device, const double* po
     if (n_obs > kPoseMaxObs) return OVS_ERR_CAPACITY;
     if (ovs_device_count() <= device || device < 0) return OVS_ERR_NO_DEVICE;
     OVS_HIP_TRY(hipSetDevice(device));
-    const size_t no = (size_t)std::max(n_obs, 1);
-    // one device block and its pinned host mirror: inputs [pose 12 f64 | offsets 2 i32 | pad | observations] go up in ONE copy, outputs
-    // [pose 12 f64 | num_valid | pad | outlier flags] come back in ONE copy, one wait (was three synchronous copies each way: ~60 us of a
-    // 0.7 ms call)
-    const size_t off_off = 96, off_sync = 112, off_obs = 128, in_bytes = off_obs + sizeof(ovs_pose_obs) * no;
-    const size_t off_out = (in_bytes + 255) & ~(size_t)255, off_nv = off_out + 96, off_fl = off_out + 128, out_bytes = 128 + no;
-    constexpr int kMaxGroups = 8;
-    const size_t off_part = (off_out + out_bytes + 255) & ~(size_t)255, total = off_part + sizeof(unsigned long long) * 2 * kMaxGroups * 56;
+    const PoseBlock blk = pose_block_of(n_obs);
     // per-thread, per-device staging that only grows: this runs once per tracked frame, an allocation per call would cost more than
     // the optimisation itself
     struct Scratch {
@@ -815,13 +825,13 @@ static ovs_status pose_optimize_host(int model, int32_t device, const double* po
         ovs::Owned res;
     };
     static thread_local Scratch scratch;
-    if (scratch.device != device || scratch.cap < total) {
+    if (scratch.device != device || scratch.cap < blk.total) {
         (void)scratch.res.drop(&scratch.p);
         (void)scratch.res.drop(&scratch.h);
         (void)scratch.res.drop(&scratch.stream);
         scratch.cap = 0;
         scratch.device = -1;
-        const size_t want = std::max<size_t>(total, (size_t)1 << 20);
+        const size_t want = std::max<size_t>(blk.total, (size_t)1 << 20);
         OVS_HIP_TRY(scratch.res.dev(&scratch.p, want));
         OVS_HIP_TRY(hipMemset(scratch.p, 0, want));   // (exchange flags of a fresh block: zero, which no epoch equals)
         OVS_HIP_TRY(scratch.res.pinned(&scratch.h, want));
@@ -832,65 +842,38 @@ static ovs_status pose_optimize_host(int model, int32_t device, const double* po
     unsigned char *d = scratch.p, *h = scratch.h;
     const int32_t offs[2] = {0, n_obs};
     std::memcpy(h, pose_cw_in, sizeof(double) * 12);
-    std::memcpy(h + off_off, offs, sizeof(offs));
-    std::memset(h + off_sync, 0, 16);   // (unused since round 6: the exchange has no arrival counter)
-    if (n_obs) std::memcpy(h + off_obs, obs, sizeof(ovs_pose_obs) * (size_t)n_obs);
-    // one latency-bound workgroup: 512 threads hide the f64 latency of the per-observation work when there is enough of it; measured,
-    // 256 / 512 threads: perspective 2000 observations 0.509 / 0.512 ms, 1000: 0.438 / 0.422, 500: 0.286 / 0.293; equirectangular
-    // 2000: 1.39 / 1.15, 1000: 0.759 / 0.786, 500: 0.427 / 0.588
-    // Round 4: a frame with 1200 or more observations is spread over four workgroups of 256 threads on one XCD: the per-iteration pass over
-    // the observations shrinks to a quarter, at the price of one grid-wide barrier per pass (~1.5 us: arrival counter + partial sums through
-    // that XCD's L2). Means over 8 synthetic frames, 1 / 4 workgroups (profiles/r04w_pose_groups.txt; r04u_pose_groups.txt has 2 and 8
-    // too): 300 observations 0.253 / 0.345 ms, 700: 0.280 / 0.327, 1000: 0.392 / 0.397, 1300: 0.408 / 0.367, 2000: 0.452 / 0.381,
-    // 4000: 0.614 / 0.378. A frame's time also depends on how many rejected trials its converged rounds end on (+-20 % between frames of
-    // one size), hence means, and hence a threshold a little above the crossover (tracked 1080p frames carry ~1300 matches: mean of four frame pairs 0.400 -> 0.376 ms). OVS_POSE_GROUPS=g forces g; the one-workgroup form is also the
-    // fallback if a barrier is ever abandoned (num_valid == -2).
-    const int groups_env = tuning().pose_groups;
-    // round 5 (after the fused multiply-add accumulation made the per-observation work a third lighter; profiles/r05s_pose_groups.txt, means over 8
-    // frames, 1 / 2 / 4 / 8 workgroups): 300 observations 0.235 / 0.259 / 0.267 / 0.285 ms, 700: 0.275 / 0.283 / 0.285 / 0.302, 1000: 0.320 / 0.322 /
-    // 0.277 / 0.297, 1300: 0.335 / 0.323 / 0.298 / 0.288, 2000: 0.373 / 0.382 / 0.324 / 0.301, 4000: 0.541 / 0.466 / 0.378 / 0.325
-    // round 6 (observations in registers, exchange without an arrival counter; profiles/r06w_pose_groups.txt, 1 / 2 / 4 / 8 workgroups): 300 observations
-    // 0.222 / 0.234 / 0.238 / 0.251 ms, 700: 0.284 / 0.251 / 0.257 / 0.264, 1000: 0.332 / 0.284 / 0.249 / 0.258, 1300: 0.345 / 0.312 / 0.255 / 0.251,
-    // 2000: 0.383 / 0.370 / 0.280 / 0.262, 4000: 0.553 / 0.461 / 0.363 / 0.277
-    int groups = groups_env > 0 ? std::min(groups_env, kMaxGroups) : (n_obs >= 1600 ? 8 : (n_obs >= 850 ? 4 : (n_obs >= 500 ? 2 : 1)));
-    int stereo_hint = 0;
+    std::memcpy(h + blk.off_off, offs, sizeof(offs));
+    if (n_obs) std::memcpy(h + blk.off_obs, obs, sizeof(ovs_pose_obs) * (size_t)n_obs);
+    int stereo_hint = 0;   // looked up here: with the records in host memory G scans of them by the kernel would cross PCIe
     if (model == 0)
         for (int32_t i = 0; i < n_obs; ++i) stereo_hint |= obs[i].is_stereo != 0;
-    // Round 6, zero copy: when the kernel reads every record exactly once (KREG form), it reads them -- and the pose -- straight from the pinned block
-    // and writes pose, count and flags straight into it: no H2D copy before the launch, no D2H copy after it (two runtime copy commands and their
-    // dependencies, ~20 us of a ~0.25 ms call). The exchange words stay in device memory. OVS_POSE_ZERO_COPY=0: the copies of rounds 3-5.
-    bool first = true;
-    for (;;) {
-        // retries 1 .. 9 of an iteration in ONE pass (k_pose_optimize): nine trial poses per observation pay where a thread holds few
-        // observations -- means over 8 frames, one pass / one by one (profiles/r04aj_pose_batched_retries.txt): four workgroups 1300
-        // observations 0.322 / 0.347 ms, 2000: 0.337 / 0.370, 300: 0.271 / 0.322; one workgroup 300: 0.245 / 0.256 but 1300: 0.408 / 0.394,
-        // 2000: 0.478 / 0.439 (a sequence that accepts its second or third trial has then evaluated seven poses for nothing). Same bits.
-        const int batch_retries = (groups > 1 || n_obs <= 512) ? 1 : 0;
-        const int threads = groups > 1 ? 256 : ((model == 1 ? n_obs >= 1500 : n_obs >= 768) ? 512 : 256);
-        const bool in_regs = n_obs <= 2 * groups * 256 && threads == 256 && tuning().pose_obs_regs && tuning().pose_threads != 512;
-        const bool zero_copy = in_regs && tuning().pose_zero_copy && first;
-        unsigned char* const io = zero_copy ? h : d;   // where the kernel finds its inputs and leaves its outputs
-        if (!zero_copy) OVS_HIP_TRY(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, scratch.stream));
-        const ovs_status st = pose_optimize_batch_dev(model, reinterpret_cast<double*>(io), reinterpret_cast<ovs_pose_obs*>(io + off_obs),
-                                                      reinterpret_cast<int32_t*>(io + off_off), 1, *cam, focal_x_baseline, setup_type,
-                                                      reinterpret_cast<double*>(io + off_out), io + off_fl, reinterpret_cast<int32_t*>(io + off_nv),
-                                                      scratch.stream, threads, groups, reinterpret_cast<unsigned long long*>(d + off_part),
-                                                      (scratch.epoch0 += 4096u), batch_retries, in_regs, stereo_hint);
+    const PoseSwitches sw = pose_switches();
+    for (bool first = true;; first = false) {
+        const PoseLaunch l = pose_plan_frame(model, n_obs, sw, first);
+        // Zero copy: the kernel reads every record exactly once (KREG form), so it reads them -- and the pose -- straight from the pinned block and
+        // writes pose, count and flags straight into it: no H2D copy before the launch, no D2H copy after it (two runtime copy commands and their
+        // dependencies, ~20 us of a ~0.25 ms call). The exchange words stay in device memory.
+        unsigned char* const io = l.zero_copy ? h : d;   // where the kernel finds its inputs and leaves its outputs
+        if (!l.zero_copy) OVS_HIP_TRY(hipMemcpyAsync(d, h, blk.in_bytes, hipMemcpyHostToDevice, scratch.stream));
+        PoseArgs a = {reinterpret_cast<double*>(io), reinterpret_cast<ovs_pose_obs*>(io + blk.off_obs), reinterpret_cast<int32_t*>(io + blk.off_off), 1, *cam,
+                      focal_x_baseline, setup_type, reinterpret_cast<double*>(io + blk.off_out), io + blk.off_fl, reinterpret_cast<int32_t*>(io + blk.off_nv)};
+        a.gpart = reinterpret_cast<unsigned long long*>(d + blk.off_part);
+        a.epoch0 = (scratch.epoch0 += 4096u);
+        a.stereo_hint = stereo_hint;
+        const ovs_status st = pose_launch(model, a, l, scratch.stream);
         if (st != OVS_OK) {
             (void)hipStreamSynchronize(scratch.stream);   // the upload may still be reading the pinned block the next call overwrites
             return st;
         }
-        if (!zero_copy) OVS_HIP_TRY(hipMemcpyAsync(h + off_out, d + off_out, out_bytes, hipMemcpyDeviceToHost, scratch.stream));
+        if (!l.zero_copy) OVS_HIP_TRY(hipMemcpyAsync(h + blk.off_out, d + blk.off_out, blk.out_bytes, hipMemcpyDeviceToHost, scratch.stream));
         OVS_HIP_TRY(hipStreamSynchronize(scratch.stream));
         int32_t nv = 0;
-        std::memcpy(&nv, h + off_nv, sizeof(nv));
-        if (nv != -2 || groups == 1) break;
-        groups = 1;   // a workgroup of the frame was not scheduled within 50 ms: run the frame in one workgroup (inputs through device memory)
-        first = false;
+        std::memcpy(&nv, h + blk.off_nv, sizeof(nv));
+        if (nv != -2 || l.groups == 1) break;   // -2: a workgroup of the frame was not scheduled within 50 ms; the plan's next attempt is one workgroup
     }
-    std::memcpy(pose_cw_out, h + off_out, sizeof(double) * 12);
-    std::memcpy(num_valid, h + off_nv, sizeof(int32_t));
-    if (n_obs) std::memcpy(outlier_flags, h + off_fl, (size_t)n_obs);
+    std::memcpy(pose_cw_out, h + blk.off_out, sizeof(double) * 12);
+    std::memcpy(num_valid, h + blk.off_nv, sizeof(int32_t));
+    if (n_obs) std::memcpy(outlier_flags, h + blk.off_fl, (size_t)n_obs);
     return OVS_OK;
 }
 

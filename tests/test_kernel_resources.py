@@ -39,16 +39,16 @@ def ba_kernels():
 def test_optimiser_kernels_keep_their_register_budgets(ba_kernels):
     """Round 4's kernels of the optimisers: the one-workgroup Cholesky holds its in-flight trailing tiles in registers (512 threads: two waves
     per SIMD, 256 registers each) and must not spill; the pair kernel of the reduced camera system keeps three waves per SIMD; the
-    256-thread pose optimiser (the form a frame spread over several workgroups uses) stays free of scratch."""
+    pose optimiser stays free of scratch in all six forms, within the 256 registers per lane a 512-thread workgroup has."""
     solve = [v for k, v in ba_kernels.items() if k.startswith("ovs::k_chol_solve")]
     assert len(solve) == 1 and solve[0]["scratch"] == 0 and solve[0]["vgpr"] + solve[0]["agpr"] <= 256
     pairs = [v for k, v in ba_kernels.items() if k == "ovs::k_schur"]   # pair blocks + right-hand side rows in one launch (round 5)
     assert len(pairs) == 1 and pairs[0]["scratch"] == 0 and pairs[0]["vgpr"] + pairs[0]["agpr"] <= 168     # 512 / 3 waves per SIMD
     pose = {k: v for k, v in ba_kernels.items() if k.startswith("ovs::k_pose_optimize<")}
     # (third template argument, round 6: 2 = a thread's at most two observations held in registers, 0 = re-read from memory per pass)
-    for name in ("ovs::k_pose_optimize<0, 256, 0>", "ovs::k_pose_optimize<1, 256, 0>", "ovs::k_pose_optimize<0, 256, 2>", "ovs::k_pose_optimize<1, 256, 2>"):
+    for name in ("ovs::k_pose_optimize<0, 256, 0>", "ovs::k_pose_optimize<1, 256, 0>", "ovs::k_pose_optimize<0, 256, 2>", "ovs::k_pose_optimize<1, 256, 2>",
+                 "ovs::k_pose_optimize<0, 512, 0>", "ovs::k_pose_optimize<1, 512, 0>"):
         assert pose[name]["scratch"] == 0 and pose[name]["vgpr"] + pose[name]["agpr"] <= 256, name   # two waves per SIMD or more
-
 
 def test_no_kernel_touches_scratch_memory():
     """Every kernel of the library, read from the code objects: none uses scratch (private memory spilled to HBM). Until round 5 the 512-thread
