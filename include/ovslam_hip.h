@@ -765,6 +765,31 @@ ovs_status ovs_sim3opt_optimize_batch(ovs_sim3opt* s, int32_t n_problems, const 
                                       double* out_scale_12, uint8_t* out_outlier_flags, double* out_info);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Homography and fundamental-matrix RANSAC for the monocular initialiser.  replaces: solve::homography_solver::find_via_ransac and
+ *   solve::fundamental_solver::find_via_ransac (src/openvslam/solve/{homography,fundamental}_solver.{h,cc}), which
+ *   initialize::perspective::initialize runs on two threads, and its choice between the two models, for a BATCH of (reference frame,
+ *   current frame) problems in two launches (rules 1 to 9).
+ * ovs_twoview_create: a handle for up to max_problems problems of max_total_matches matches together; one internal mutex serialises the
+ *   calls on a handle.
+ * ovs_twoview_solve_batch: problem p owns matches [offsets[p], offsets[p + 1]) (offsets[0] = 0, non-decreasing). x1 / x2: 2 doubles per
+ *   match, the undistorted keypoint of the reference / current frame. sigma, max_num_iter and recompute are upstream's; models: bit 0 asks
+ *   for H, bit 1 for F (1, 2 or 3). seed: upstream draws from random_device; here hypothesis h of problem p is a function of (seed, p, h)
+ *   and serves both models. Outputs per problem: H_21 and F_21 (9 each, row-major); scores, valid, best_iter and num_inliers (2 each: H,
+ *   then F); selected (1: H, 2: F, 0: neither; with one model asked for, that model or 0). Per match: one flag byte per model. An invalid
+ *   or unrequested model returns identity, score 0, best_iter -1, flags 0. Results are bit-exact functions of (inputs, seed, p): problem
+ *   p of a batch, solved alone under the seed `seed + 0x9E3779B97F4A7C15 * (p << 24)`, gives the same result.
+ * OVS_ERR_INVALID: a NULL required pointer, offsets not starting at 0 or decreasing, max_num_iter < 1 or > 2^20, models outside 1 .. 3,
+ *   sigma not finite and positive. OVS_ERR_CAPACITY: more problems or matches than the handle was created for (nothing is truncated, no
+ *   output is written). Both are decided before any launch. A problem with fewer than 8 matches is not an error: it is invalid. */
+typedef struct ovs_twoview ovs_twoview;
+ovs_status ovs_twoview_create(int32_t device, int32_t max_problems, int32_t max_total_matches, ovs_twoview** out);
+ovs_status ovs_twoview_destroy(ovs_twoview* s);
+ovs_status ovs_twoview_solve_batch(ovs_twoview* s, int32_t n_problems, const int32_t* offsets, const double* x1, const double* x2, double sigma,
+                                   int32_t max_num_iter, int32_t recompute, uint64_t seed, int32_t models, double* out_H_21, double* out_F_21,
+                                   double* out_scores, int32_t* out_valid, int32_t* out_best_iter, int32_t* out_num_inliers, int32_t* out_selected,
+                                   uint8_t* out_inlier_flags_H, uint8_t* out_inlier_flags_F);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Two-view triangulation of a keyframe's new landmarks.  replaces: bool module::two_view_triangulator::triangulate(const unsigned idx_1,
  *   const unsigned idx_2, Vec3_t& pos_w) const (src/openvslam/module/two_view_triangulator.{h,cc}) with solve::triangulator::triangulate
  *   (src/openvslam/solve/triangulator.h) under it: the choice between the two-view solution and a stereo back-projection by parallax, the

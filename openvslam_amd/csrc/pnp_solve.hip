@@ -108,39 +108,6 @@ __device__ __forceinline__ void alphas_of(const Control& k, const double (&d)[3]
     a[0] = ((1.0 - a[1]) - a[2]) - a[3];
 }
 
-// the cyclic Jacobi iteration on sh.A / sh.V: row-major pair order, kSweeps sweeps, the rotation of jacobi_rotate. Lane k < 12 rotates
-// column pair k, then row pair k; lane 16 + k the vectors' pair k (which no entry of A depends on).
-__device__ __forceinline__ void jacobi12(Lds& sh, int lane) {
-#pragma unroll 1
-    for (int sweep = 0; sweep < kSweeps; ++sweep)
-#pragma unroll 1
-        for (int p = 0; p < 11; ++p)
-#pragma unroll 1
-            for (int q = p + 1; q < 12; ++q) {
-                const double apq = sh.A[p * 12 + q];
-                const bool rot = apq != 0.0;   // wave-uniform
-                double c = 1.0, s = 0.0;
-                if (rot) jacobi_angle(sh.A[p * 12 + p], sh.A[q * 12 + q], apq, c, s);
-                if (rot && lane < 12) {
-                    const double akp = sh.A[lane * 12 + p], akq = sh.A[lane * 12 + q];
-                    sh.A[lane * 12 + p] = c * akp - s * akq;
-                    sh.A[lane * 12 + q] = s * akp + c * akq;
-                } else if (rot && lane >= 16 && lane < 28) {
-                    const int k = lane - 16;
-                    const double vkp = sh.V[k * 12 + p], vkq = sh.V[k * 12 + q];
-                    sh.V[k * 12 + p] = c * vkp - s * vkq;
-                    sh.V[k * 12 + q] = s * vkp + c * vkq;
-                }
-                __syncthreads();
-                if (rot && lane < 12) {
-                    const double apk = sh.A[p * 12 + lane], aqk = sh.A[q * 12 + lane];
-                    sh.A[p * 12 + lane] = c * apk - s * aqk;
-                    sh.A[q * 12 + lane] = s * apk + c * aqk;
-                }
-                __syncthreads();
-            }
-}
-
 __device__ __forceinline__ double select3(int which, double a, double b, double c) { return which == 0 ? a : which == 1 ? b : c; }
 
 // rule 2: EPnP over the n matches idx[0 .. n) of a problem (bearings / pos_w: the problem's first match), by one wavefront. Every lane
@@ -269,7 +236,7 @@ __device__ __forceinline__ void epnp_wave(const double* __restrict__ bearings, c
         __syncthreads();
     }
     // 4. the eigenvectors of the four smallest eigenvalues, the smallest first, the lowest index first on a tie
-    jacobi12(sh, lane);
+    jacobi_lds<12, kSweeps>(sh.A, sh.V, lane);
     {
         double diag[12];
 #pragma unroll

@@ -1,5 +1,6 @@
-// solve_internal.inc -- what the RANSAC solvers of solve/ share (sim3_solve.hip, pnp_solve.hip). On the device: the counter-based sampler,
-// the hypothesis key, the result record and its invalid form, the cyclic Jacobi rotation (jacobi_math.inc) and Horn's quaternion form of the absolute
+// solve_internal.inc -- what the RANSAC solvers of solve/ share (sim3_solve.hip, pnp_solve.hip, two_view_solve.hip). On the device: the
+// counter-based sampler, the hypothesis key, the result record and its invalid form, the cyclic Jacobi rotation (jacobi_math.inc), its
+// sweeps over a matrix in LDS and Horn's quaternion form of the absolute
 // orientation. DESIGN.md 3.9 rule 2 fixes every operation; the units are built with -ffp-contract=off. On the host: ransac_handle, the
 // batch scaffold under both C ABIs (create, reserve_models, run_batch). A solver supplies its model, its two kernels, the Layout of its
 // staged block, and to run_batch what stages its arrays and what launches its kernels. run_batch is run_staged with the RANSAC's two
@@ -100,6 +101,41 @@ __device__ __forceinline__ void write_invalid(uint8_t* __restrict__ flags, int n
 using ovs_jacobi::jacobi_angle;
 using ovs_jacobi::jacobi_rotate;
 
+// the cyclic Jacobi iteration by one wavefront on an N x N matrix A and its vectors V in LDS (row-major, N <= 16): row-major pair order,
+// SWEEPS sweeps, the rotation of jacobi_rotate. Lane k < N rotates column pair k, then row pair k; lane 16 + k the vectors' pair k (which no entry of A
+// depends on). `lane` is the lane's number among the 32 that share A and V: the halves of a wavefront may sweep two matrices side by side.
+template <int N, int SWEEPS>
+__device__ __forceinline__ void jacobi_lds(double* A, double* V, int lane) {
+#pragma unroll 1
+    for (int sweep = 0; sweep < SWEEPS; ++sweep)
+#pragma unroll 1
+        for (int p = 0; p < N - 1; ++p)
+#pragma unroll 1
+            for (int q = p + 1; q < N; ++q) {
+                const double apq = A[p * N + q];
+                const bool rot = apq != 0.0;   // the same in every lane of one matrix
+                double c = 1.0, s = 0.0;
+                if (rot) jacobi_angle(A[p * N + p], A[q * N + q], apq, c, s);
+                if (rot && lane < N) {
+                    const double akp = A[lane * N + p], akq = A[lane * N + q];
+                    A[lane * N + p] = c * akp - s * akq;
+                    A[lane * N + q] = s * akp + c * akq;
+                } else if (rot && lane >= 16 && lane < 16 + N) {
+                    const int k = lane - 16;
+                    const double vkp = V[k * N + p], vkq = V[k * N + q];
+                    V[k * N + p] = c * vkp - s * vkq;
+                    V[k * N + q] = s * vkp + c * vkq;
+                }
+                __syncthreads();
+                if (rot && lane < N) {
+                    const double apk = A[p * N + lane], aqk = A[q * N + lane];
+                    A[p * N + lane] = c * apk - s * aqk;
+                    A[q * N + lane] = s * apk + c * aqk;
+                }
+                __syncthreads();
+            }
+}
+
 __device__ __forceinline__ double dot3(double a0, double a1, double a2, double b0, double b1, double b2) { return (a0 * b0 + a1 * b1) + a2 * b2; }
 
 // Horn's closed form with the scale left out: M[r][c] = sum over the centred pairs of b[r] * a[c]; R (row-major) is the rotation with
@@ -156,7 +192,7 @@ __device__ __forceinline__ void horn_rotation(const double (&M)[3][3], double (&
     R[8] = 1.0 - 2.0 * (x * x + y * y);
 }
 
-// ---- the host side: one handle and one batch call under ovs_sim3_* and ovs_pnp_*
+// ---- the host side: one handle and one batch call under ovs_sim3_*, ovs_pnp_*, ovs_sim3opt_* and ovs_twoview_*
 struct ransac_handle {
     int device = 0;
     int max_problems = 0, max_total_matches = 0;
@@ -182,7 +218,7 @@ struct ransac_handle {
     }
 };
 
-// H: ovs_sim3, ovs_pnp or ovs_sim3opt. block_bytes: the solver's Layout at full capacity; initial_records: the models that fit without
+// H: ovs_sim3, ovs_pnp, ovs_sim3opt or ovs_twoview. block_bytes: the solver's Layout at full capacity; initial_records: the models that fit without
 // growing; result_bytes: the solver's record per problem in the mapped result block where it is not ResultRec
 template <class H>
 ovs_status ransac_create(int32_t device, int32_t max_problems, int32_t max_total_matches, size_t block_bytes, size_t initial_records,

@@ -16,7 +16,12 @@ the results are bit-exact functions of the inputs.
 
 module::two_view_triangulator (expected: src/openvslam/module/two_view_triangulator.{h,cc}): the triangulation local mapping runs on every
 pair robust::match_for_triangulation returns. All pairs of all neighbours of a new keyframe go to the device in ONE call and ONE launch
-(ovs_triangulate_batch, csrc/triangulate.hip). DESIGN.md 3.12 has the rules; bit-exact in the same sense."""
+(ovs_triangulate_batch, csrc/triangulate.hip). DESIGN.md 3.12 has the rules; bit-exact in the same sense.
+
+solve::homography_solver and solve::fundamental_solver (expected: src/openvslam/solve/{homography,fundamental}_solver.{h,cc}): the two RANSACs
+initialize::perspective::initialize runs on two threads for every frame until the map exists. Both models of all problems go to the device in
+ONE call (ovs_twoview_solve_batch, csrc/two_view_solve.hip): two launches, with upstream's choice between the models. DESIGN.md 3.13 has
+the rules; bit-exact in the same sense."""
 import ctypes as C
 import math
 
@@ -64,7 +69,7 @@ def problem_from_keyframes(pose_cw_1, pose_cw_2, pos_w_1, pos_w_2, octaves_1, oc
 
 
 class _ransac_handle:
-    """A solver's device handle (ovs_sim3 or ovs_pnp: `_abi` is the prefix of its create / destroy / solve_batch) with its capacity."""
+    """A solver's device handle (ovs_sim3, ovs_pnp, ...: `_abi` is the prefix of its create / destroy / solve_batch) with its capacity."""
     _abi = None
 
     def __init__(self, max_problems, max_total_matches, device=0):
@@ -427,3 +432,92 @@ class two_view_triangulator:
     def triangulate(self, idx_1, idx_2):
         accepted, pos_w = self.triangulate_matches([(idx_1, idx_2)])
         return bool(accepted[0]), pos_w[0]
+
+
+# ---- solve::homography_solver and solve::fundamental_solver
+TWO_VIEW_DEFAULT_SEED = 0x48462D32   # upstream draws from random_device; here a run is reproducible
+MODEL_H, MODEL_F = 1, 2              # the bits of `models`, and the values of `selected`
+
+
+def two_view_problem_seed(seed, p):
+    """The seed under which problem p of a batch, solved ALONE (as problem 0), draws the samples it draws in the batch (3.13 rule 2)."""
+    return (seed + _G * (p << 24)) & _MASK
+
+
+def two_view_problem(undist_keypts_1, undist_keypts_2, matches_12):
+    """What the two solvers' constructors keep: the undistorted keypoints of the matched pairs (idx_1, idx_2), widened to double. keypts:
+    (n, 2); matches_12: (m, 2) pairs."""
+    m = np.asarray(matches_12, np.int64).reshape(-1, 2)
+    return dict(x1=np.asarray(undist_keypts_1, np.float64).reshape(-1, 2)[m[:, 0]], x2=np.asarray(undist_keypts_2, np.float64).reshape(-1, 2)[m[:, 1]])
+
+
+class _two_view_handle(_ransac_handle):
+    """ovs_twoview with its capacity."""
+    _abi = "ovs_twoview"
+
+
+def solve_two_view_batch(problems, sigma=1.0, max_num_iter=100, recompute=True, seed=TWO_VIEW_DEFAULT_SEED, models=3, handle=None, device=0):
+    """Both find_via_ransac of the monocular initialiser for every problem (dicts with x1, x2: (n, 2)) in one call: a list of dicts H and F
+    (each valid, best_iter, num_inliers, score, the matrix H_21 / F_21 (3 x 3) and inlier_flags (n, bool); the invalid form for a model
+    `models` leaves out) and selected (1: H, 2: F, 0: neither). `handle`: a _two_view_handle to reuse (the initialiser keeps one)."""
+    P = len(problems)
+    if P == 0:
+        return []
+    offsets = np.zeros(P + 1, np.int32)
+    offsets[1:] = np.cumsum([len(np.asarray(q["x1"]).reshape(-1, 2)) for q in problems])
+    T = int(offsets[-1])
+    cat = lambda key: np.ascontiguousarray(np.concatenate([np.asarray(q[key], np.float64).reshape(-1, 2) for q in problems]) if T else np.zeros((0, 2)))
+    x1, x2 = cat("x1"), cat("x2")
+    if len(x1) != T or len(x2) != T:
+        raise ValueError("x1 and x2 of a problem must have one entry per match")
+    if handle is None:
+        handle = _two_view_handle(P, max(T, 1), device)
+    mats = [np.zeros((P, 3, 3)), np.zeros((P, 3, 3))]
+    scores, valid, best_iter, num = np.zeros((P, 2)), np.zeros((P, 2), np.int32), np.zeros((P, 2), np.int32), np.zeros((P, 2), np.int32)
+    selected, flags = np.zeros(P, np.int32), [np.zeros(max(T, 1), np.uint8), np.zeros(max(T, 1), np.uint8)]
+    _lib.check(handle._L.ovs_twoview_solve_batch(handle._h, P, _p(offsets), _p(x1), _p(x2), float(sigma), int(max_num_iter), 1 if recompute else 0,
+                                                 int(seed) & _MASK, int(models), _p(mats[0]), _p(mats[1]), _p(scores), _p(valid), _p(best_iter), _p(num),
+                                                 _p(selected), _p(flags[0]), _p(flags[1])), "ovs_twoview_solve_batch")
+    out = []
+    for i in range(P):
+        r = {"selected": int(selected[i])}
+        for m, (name, key) in enumerate((("H", "H_21"), ("F", "F_21"))):
+            r[name] = {"valid": bool(valid[i, m]), "best_iter": int(best_iter[i, m]), "num_inliers": int(num[i, m]), "score": float(scores[i, m]),
+                       key: mats[m][i].copy(), "inlier_flags": flags[m][offsets[i]:offsets[i + 1]].astype(bool)}
+        out.append(r)
+    return out
+
+
+class _two_view_solver(_ransac_solver):
+    """What homography_solver and fundamental_solver share: upstream's constructor (undist_keypts_1, undist_keypts_2, matches_12, sigma),
+    find_via_ransac and the getters both have."""
+    _model, _name = None, None
+
+    def __init__(self, undist_keypts_1, undist_keypts_2, matches_12, sigma, device=0):
+        self._matches = [tuple(int(v) for v in m) for m in np.asarray(matches_12, np.int64).reshape(-1, 2)]
+        self._problem, self._sigma, self._device = two_view_problem(undist_keypts_1, undist_keypts_2, matches_12), float(sigma), device
+
+    def find_via_ransac(self, max_num_iter, recompute=True, seed=TWO_VIEW_DEFAULT_SEED):
+        self._result = solve_two_view_batch([self._problem], self._sigma, max_num_iter, recompute, seed, self._model, device=self._device)[0][self._name]
+
+    def get_best_score(self):
+        return self._get("score")
+
+    def get_inlier_matches(self):
+        return self._get("inlier_flags")
+
+
+class homography_solver(_two_view_solver):
+    """solve::homography_solver over one problem."""
+    _model, _name = MODEL_H, "H"
+
+    def get_best_H_21(self):
+        return self._get("H_21")
+
+
+class fundamental_solver(_two_view_solver):
+    """solve::fundamental_solver over one problem."""
+    _model, _name = MODEL_F, "F"
+
+    def get_best_F_21(self):
+        return self._get("F_21")
