@@ -822,6 +822,44 @@ ovs_status ovs_triangulate_batch(ovs_triangulate* s, int32_t n_problems, const i
                                  const double* poses_cw_2, double cos_rays_parallax_thr, float ratio_factor, double* out_pos_w, uint8_t* out_status,
                                  uint8_t* out_method, int32_t* out_num_accepted);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Landmark upkeep.  replaces: void data::landmark::update_normal_and_depth() and void data::landmark::compute_descriptor()
+ *   (src/openvslam/data/landmark.{h,cc}) for MANY landmarks in ONE call (rules L1 to L9): the mean viewing normal, the raw
+ *   valid distance range and the representative descriptor every matcher that takes landmarks reads.
+ * ovs_landmarks_create: a handle for up to max_landmarks landmarks (at most 65535) of max_total_observations observations together, in up to
+ *   max_keyframes keyframes; one internal mutex serialises the calls on a handle.
+ * ovs_landmarks_update_batch: what: bit 0 the geometry (L1 to L5), bit 1 the descriptor (L6 to L9). Landmark p owns observations
+ *   [offsets[p], offsets[p + 1]) (offsets[0] = 0, non-decreasing), in the order the results are reproduced for. Per landmark: pos_w (3 doubles),
+ *   ref_keyfrm (the slot of its reference keyframe), ref_level (the octave of its keypoint there). Per observation: obs_keyfrm (the slot of
+ *   its keyframe), obs_desc (32 bytes), obs_use (0: the keyframe will be erased, it takes no part in the descriptor; NULL: all take part).
+ *   Per slot: cam_centers (3 doubles). scale_factors: the pyramid's table of num_levels floats, one for the whole call.
+ *   Outputs per landmark: out_mean_normal (3 doubles), out_min_max_dist (min_valid_dist_, max_valid_dist_: the raw members, before the
+ *   getters' 0.7 / 1.3), out_best_obs (the position of the chosen observation in the landmark's list, -1 where none takes part), out_desc
+ *   (its 32 bytes), out_status (0; 1: no observations, nothing to do). A landmark without observations leaves its other outputs untouched;
+ *   one of which none takes part leaves out_desc untouched. The arrays of a part that is not asked for may be NULL (obs_keyfrm belongs to
+ *   the geometry, and to the descriptor in the _f form) and are never written.
+ * ovs_landmarks_update_batch_f: the same with the descriptors gathered on the device from resident keyframes: keyfrms[slot] is the
+ *   keyframe's handle, obs_keypoint[t] the observation's keypoint index in it.
+ * OVS_ERR_INVALID: a NULL required pointer, offsets not starting at 0 or decreasing, `what` outside 1..3, num_levels outside 1..OVS_MAX_LEVELS
+ *   or n_keyframes < 0 (geometry), a slot outside [0, n_keyframes), a ref_level outside [0, num_levels), a landmark of 2^22 observations or
+ *   more, a NULL handle, a handle on another device or a keypoint index outside its handle (_f). OVS_ERR_CAPACITY: more landmarks,
+ *   observations or keyframes than the handle was created for (nothing is truncated). Both are decided before any launch, and no output is
+ *   written. n_landmarks == 0 is OVS_OK. */
+typedef struct ovs_landmarks ovs_landmarks;
+ovs_status ovs_landmarks_create(int32_t device, int32_t max_landmarks, int32_t max_total_observations, int32_t max_keyframes, ovs_landmarks** out);
+ovs_status ovs_landmarks_destroy(ovs_landmarks* s);
+ovs_status ovs_landmarks_update_batch(ovs_landmarks* s, int32_t what, int32_t n_landmarks, const int32_t* offsets, const double* pos_w,
+                                      const int32_t* ref_keyfrm, const int32_t* ref_level, const int32_t* obs_keyfrm, const uint8_t* obs_desc,
+                                      const uint8_t* obs_use, const double* cam_centers, int32_t n_keyframes, const float* scale_factors,
+                                      int32_t num_levels, double* out_mean_normal, float* out_min_max_dist, int32_t* out_best_obs, uint8_t* out_desc,
+                                      uint8_t* out_status);
+ovs_status ovs_landmarks_update_batch_f(ovs_landmarks* s, int32_t what, int32_t n_landmarks, const int32_t* offsets, const double* pos_w,
+                                        const int32_t* ref_keyfrm, const int32_t* ref_level, const int32_t* obs_keyfrm,
+                                        const ovs_frame_dev* const* keyfrms, const int32_t* obs_keypoint, const uint8_t* obs_use,
+                                        const double* cam_centers, int32_t n_keyframes, const float* scale_factors, int32_t num_levels,
+                                        double* out_mean_normal, float* out_min_max_dist, int32_t* out_best_obs, uint8_t* out_desc,
+                                        uint8_t* out_status);
+
 /* replaces: the optimisation inside  void optimize::local_bundle_adjuster::optimize(data::keyframe* curr_keyfrm, bool* const
  *               force_stop_flag) const  (src/openvslam/optimize/local_bundle_adjuster.{h,cc}): everything between the graph build and the
  * write-back, i.e. optimizer.optimize(num_first_iter) with Huber kernels (ONE delta per rig: setup_type 0 = Monocular -> sqrtf(5.99146f),

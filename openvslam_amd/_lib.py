@@ -134,6 +134,10 @@ SYMBOLS = {
     "ovs_triangulate_create": (_i32, [_i32, _i32, _i32, C.POINTER(_vp)]),
     "ovs_triangulate_destroy": (_i32, [_vp]),
     "ovs_triangulate_batch": (_i32, [_vp, _i32, _vp] + [_vp] * 16 + [C.c_double, _f, _vp, _vp, _vp, _vp]),
+    "ovs_landmarks_create": (_i32, [_i32, _i32, _i32, _i32, C.POINTER(_vp)]),
+    "ovs_landmarks_destroy": (_i32, [_vp]),
+    "ovs_landmarks_update_batch": (_i32, [_vp, _i32, _i32] + [_vp] * 8 + [_i32, _vp, _i32] + [_vp] * 5),
+    "ovs_landmarks_update_batch_f": (_i32, [_vp, _i32, _i32] + [_vp] * 9 + [_i32, _vp, _i32] + [_vp] * 5),
     "ovs_local_ba_optimize":(_i32, [_i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, C.c_double, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ovs_local_ba_optimize_equirect": (_i32, [_i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "ovs_ba_linearize_stereo": (_i32, [_i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),

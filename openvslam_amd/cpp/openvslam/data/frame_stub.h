@@ -97,6 +97,7 @@ public:
     Vec3_t pos_w_, mean_normal_;
     float min_valid_dist_ = 0, max_valid_dist_ = 0;
     std::map<keyframe*, unsigned int> observations_;
+    keyframe* ref_keyfrm_ = nullptr;   // upstream: the keyframe whose keypoint gives the valid distance range its scale level (data::update_landmarks)
     bool will_be_erased_ = false;
     unsigned int num_observations_ = 1;
     cv::Mat descriptor_;

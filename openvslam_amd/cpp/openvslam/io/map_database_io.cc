@@ -150,6 +150,12 @@ loaded_map map_database_io::load_message_pack(const std::string& path) {
     for (auto& kf : m.keyframes)
         for (size_t i = 0; i < kf.second->landmarks_.size(); ++i)
             if (kf.second->landmarks_[i]) kf.second->landmarks_[i]->add_observation(kf.second.get(), (unsigned int)i);
+    // landmark::ref_keyfrm_ (data::update_landmarks reads it): the file's ref_keyfrm, where the file holds that keyframe
+    for (const auto& kv : root.at("landmarks").o) {
+        if (!kv.second.has("ref_keyfrm")) continue;
+        const auto it = m.keyframes.find((unsigned int)kv.second.at("ref_keyfrm").integer_value());
+        if (it != m.keyframes.end()) m.landmarks.at((unsigned int)std::stoul(kv.first))->ref_keyfrm_ = it->second.get();
+    }
 
     // graph_node::update_connections: weight = shared landmarks; keep >= 15 (the best one if none), strongest first
     for (auto& kf : m.keyframes) {

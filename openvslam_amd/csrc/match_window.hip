@@ -26,6 +26,7 @@
 #include <new>
 #include <vector>
 
+#include "frame_dev_internal.inc"
 #include "ovs_common.h"
 #include "owned_internal.inc"
 
@@ -1008,6 +1009,9 @@ struct ovs_frame_dev {
     double* d_bearings = nullptr;   // optional (ovs_frame_dev_attach_bearings): 3 doubles per keypoint, for match_for_triangulation
     ovs::Owned res;                 // d_bearings (the arena goes back to the pool: ovs_frame_dev_destroy)
 };
+
+// frame_dev_internal.inc: the landmark upkeep (landmark_update.hip) gathers descriptors from resident keyframes
+ovs::FrameDescriptors ovs::frame_descriptors(const ovs_frame_dev* f) { return {f->device, f->n, f->d_desc}; }
 
 namespace {
 

@@ -57,6 +57,11 @@ class landmark:
     ref_keyfrm: int
     n_vis: int = 1
     n_fnd: int = 1
+    # not stored in the file: openvslam_amd.landmarks.landmark_updater.update_map computes them from the observations
+    descriptor: np.ndarray = None      # (32,) uint8
+    mean_normal: np.ndarray = None     # (3,) float64
+    min_valid_dist: float = None       # the raw members, before the getters' 0.7 / 1.3
+    max_valid_dist: float = None
 
 
 class map_database:
