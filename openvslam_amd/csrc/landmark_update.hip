@@ -237,12 +237,11 @@ ovs_status update_batch(ovs_landmarks* s, const Inputs& a) {
             const uint8_t** ptrs = reinterpret_cast<const uint8_t**>(s->h_table + ptrs_at);
             for (int32_t k = 0; k < K; ++k) {
                 if (!a.keyfrms[k]) return OVS_ERR_INVALID;
-                const ovs::FrameDescriptors f = ovs::frame_descriptors(a.keyfrms[k]);
-                if (f.device != s->device) return OVS_ERR_INVALID;
-                ptrs[k] = f.d_desc;
+                if (a.keyfrms[k]->device != s->device) return OVS_ERR_INVALID;
+                ptrs[k] = a.keyfrms[k]->d_desc;
             }
             for (int32_t t = 0; t < T; ++t)
-                if (a.obs_keypoint[t] < 0 || a.obs_keypoint[t] >= ovs::frame_descriptors(a.keyfrms[a.obs_keyfrm[t]]).n) return OVS_ERR_INVALID;
+                if (a.obs_keypoint[t] < 0 || a.obs_keypoint[t] >= a.keyfrms[a.obs_keyfrm[t]]->n) return OVS_ERR_INVALID;
             if (T > 0) std::memcpy(h_block + lay.obs_kp, a.obs_keypoint, 4 * (size_t)T);
         }
         if (slots && T > 0) std::memcpy(h_block + lay.obs_slot, a.obs_keyfrm, 4 * (size_t)T);

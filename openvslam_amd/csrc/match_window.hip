@@ -22,24 +22,17 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
-#include <mutex>
 #include <new>
 #include <vector>
 
-#include "frame_dev_internal.inc"
+#include "frame_dev_internal.inc"      // ovs_frame_dev, launch_grid_assign
+#include "match_window_plan.inc"       // every size, threshold and offset the host side decides; the kernels' argument structs
 #include "ovs_common.h"
 #include "owned_internal.inc"
 
 namespace ovs {
 
-struct GridP {
-    float min_x, min_y;
-    float inv_w, inv_h;
-    int32_t cols, rows;
-};
-
 constexpr uint32_t kNone = 0xFFFFFFFFu;
-constexpr int kMarkSize = 4096;   // hashed stamp table of the resolver (collisions only cost an extra round)
 
 __device__ __forceinline__ uint32_t hamming256_g(const uint32_t (&a)[8], const uint32_t* __restrict__ b) {
     uint32_t d = 0;
@@ -52,7 +45,6 @@ __device__ __forceinline__ uint32_t hamming256_g(const uint32_t (&a)[8], const u
 // Round 6: the scan of the cell histogram by wave shuffles (two barriers; the 1024-wide Hillis-Steele loop had twenty) and, when the keypoints fit
 // (items_in_lds: n <= kGridItemsLds), the member lists built and sorted in LDS and written once, coalesced -- the per-cell insertion sort used to walk
 // `items` in global memory, a chain of dependent round trips per cell: 17 -> ~8 us per 2000-keypoint frame, once per tracked frame.
-constexpr int kGridItemsLds = 8192;
 __global__ __launch_bounds__(1024) void k_grid_assign(const ovs_keypoint* __restrict__ kps, int n, GridP gp, int32_t* __restrict__ cell_of,
                                                      int32_t* __restrict__ cell_start, int32_t* __restrict__ items, int items_in_lds) {
     extern __shared__ int32_t s_grid[];
@@ -138,37 +130,6 @@ __global__ __launch_bounds__(1024) void k_grid_assign(const ovs_keypoint* __rest
 
 // ---- 2. candidate lists ---------------------------------------------------------------------------------------------------
 enum { kModeProjection = 0, kModeArea = 1, kModeGeneric = 2 };
-
-struct WinArgs {
-    // targets: the frame whose grid is searched
-    const ovs_keypoint* t_kps;
-    const uint8_t* t_desc;
-    const uint8_t* t_occupied;   // projection: keypoint already holds a landmark with observations (NULL = none)
-    const float* t_x_right;      // projection: frm.stereo_x_right_ (NULL = monocular)
-    const int32_t* cell_start;
-    const int32_t* items;
-    GridP gp;
-    // queries
-    int n_q;
-    const float* q_xy;           // projection: reproj_in_tracking_; area: prev_matched_pts
-    const float* q_x_right;      // projection: x_right_in_tracking_
-    const int32_t* q_level;      // projection: scale_level_in_tracking_
-    const uint8_t* q_valid;      // projection: is_observable_in_tracking_ && !will_be_erased()
-    const ovs_keypoint* q_kps;   // area: frame-1 undistorted keypoints
-    const float* q_radius;       // generic: search radius, level window (filled by k_reproject_queries)
-    const int32_t* q_minl;
-    const int32_t* q_maxl;
-    const uint8_t* q_desc;
-    float margin;
-    float sf[OVS_MAX_LEVELS];
-    int mode;
-    // Candidates whose Hamming distance can neither win (d > the rule's acceptance threshold) nor make a ratio test fail (fl(d * ratio) >= that
-    // threshold) are left out of the lists altogether: every candidate with d >= dead_from (0: no filter; set per rule by dead_from_*() below).
-    // The sequential rule decides the same with or without them (a dropped best is a reject either way, a dropped second accepts either way, and
-    // so does every later second), but the resolver's rounds are bounded by the chains of queries sharing LIVE candidates and its lists only fit
-    // LDS when they are short: with a 100-px margin (BASELINE config 0) a query has ~110 candidates of which ~1 is alive.
-    uint32_t dead_from;
-};
 
 // One WAVE per query: the lanes take the cells of the query's window (a 100-px margin covers ~340 of the 64 x 48 cells -- a single
 // lane walking them was ~0.7 ms of dependent loads per pass), count their members that pass the filters, and an exclusive scan over
@@ -271,16 +232,7 @@ __global__ __launch_bounds__(256) void k_window_lists(WinArgs a, uint32_t* __res
     if (!FILL && lane == 0) counts[q] = total;
 }
 
-// camera::perspective / camera::equirectangular ::reproject_to_image in double precision, one rounding per operation (the library
-// is built with -ffp-contract=off), same operation order as the oracle.
-struct CamP {
-    int32_t model, setup;
-    double fx, fy, cx, cy, fxb;
-    int32_t cols, rows;
-    float min_x, min_y, max_x, max_y;
-    double P[12];   // rot_cw row-major, trans_cw
-};
-
+// camera::perspective / camera::equirectangular ::reproject_to_image (CamP: match_window_plan.inc)
 __device__ __forceinline__ bool reproject_to_image(const CamP& c, const double* __restrict__ X, double& u, double& v, float& x_right) {
     const double pcx = (c.P[0] * X[0] + c.P[1] * X[1]) + c.P[2] * X[2] + c.P[9];
     const double pcy = (c.P[3] * X[0] + c.P[4] * X[1]) + c.P[5] * X[2] + c.P[10];
@@ -354,29 +306,7 @@ __global__ __launch_bounds__(256) void k_reproject_queries(CamP cam, const ovs_k
     q_valid[i] = valid ? 1 : 0;
 }
 
-// fuse::replace_duplication, candidate search: landmarks are independent (the write-back that follows is host-side graph surgery)
-struct FuseArgs {
-    const ovs_keypoint* t_kps;
-    const uint8_t* t_desc;
-    const float* t_x_right;
-    const int32_t* cell_start;
-    const int32_t* items;
-    GridP gp;
-    CamP cam;
-    double cc[3];                 // camera centre
-    const double* lm_pos_w;
-    const float* lm_dist;         // (min, max) valid distance
-    const double* lm_normal;
-    const uint8_t* lm_desc;
-    const uint8_t* lm_valid;
-    int m, num_levels;
-    float log_scale_factor, margin;
-    float sf[OVS_MAX_LEVELS], ils[OVS_MAX_LEVELS];
-    int variant;                  // kFuseReplace / kFuseDetect / kFuseMutual
-    uint32_t max_dist;            // acceptance threshold on the best Hamming distance
-    double P1[12];                // kFuseMutual: pose of the landmark's own keyframe (pos_1 = R_1w X + t_1w, then cam.P = [s R_21 | t_21])
-};
-
+// fuse::replace_duplication, candidate search (FuseArgs: match_window_plan.inc).
 // kFuseReplace: fuse::replace_duplication (chi-square gate); kFuseDetect: fuse::detect_duplication (no chi-square gate);
 // kFuseMutual: one direction of projection::match_keyframes_mutually (no viewing-angle gate, distance = |pos in the other keyframe|)
 enum { kFuseReplace = 0, kFuseDetect = 1, kFuseMutual = 2 };
@@ -506,33 +436,7 @@ __global__ __launch_bounds__(256) void k_cross_check(const int32_t* __restrict__
     if ((threadIdx.x & 63) == 0 && any) atomicAdd(num, (int32_t)__popcll(any));
 }
 
-// bow_tree: queries = the keyframe's feature-vector entries in walk order; the list of a query is its node's frame bucket
-struct BowArgs {
-    const uint8_t* kf_desc;
-    const uint8_t* kf_valid;
-    const int32_t* kf_node_ids;
-    const int32_t* kf_node_start;
-    const int32_t* kf_items;
-    int kf_nodes, n_q;           // n_q = kf_node_start[kf_nodes]
-    const uint8_t* frm_desc;
-    const uint8_t* frm_valid;    // match_keyframes: the target keypoint must hold a live landmark too (NULL = all)
-    // robust::match_for_triangulation (tri != 0): pair filters d <= THR_LOW, epipole proximity, epipolar constraint; candidates are
-    // listed in REVERSE bucket order because upstream lets a later equal distance replace an earlier one
-    int tri;
-    uint32_t dead_from;   // as WinArgs::dead_from (bow rule; the triangulation filter d <= THR_LOW is part of its pair test)
-    const ovs_keypoint* kf_kps;  // octave of keypoint 1 (threshold scale)
-    const float* kf_x_right;
-    const float* frm_x_right;
-    const double* kf_bearings;
-    const double* frm_bearings;
-    double E[9], epipole[3];
-    float sf[OVS_MAX_LEVELS];
-    const int32_t* frm_node_ids;
-    const int32_t* frm_node_start;
-    const int32_t* frm_items;
-    int frm_nodes;
-};
-
+// bow_tree (BowArgs: match_window_plan.inc)
 template <bool FILL>
 __global__ __launch_bounds__(256) void k_bow_lists(BowArgs a, uint32_t* __restrict__ counts, const uint32_t* __restrict__ offsets,
                                                   uint32_t* __restrict__ keys, uint32_t key_cap, uint32_t* __restrict__ overflow) {
@@ -653,27 +557,6 @@ __global__ __launch_bounds__(1024) void k_scan_counts(const uint32_t* __restrict
 
 // ---- 3. sequential-claim resolver ---------------------------------------------------------------------------------------
 enum { kRuleProjection = 0, kRuleArea = 1, kRuleBow = 2, kRuleBestOnly = 3, kRuleTriang = 4 };   // Triang = BestOnly accept, Bow output
-
-struct ResolveArgs {
-    const uint32_t* offsets;   // n_q + 1
-    const uint32_t* keys;
-    int n_q, n_t;
-    float lowe_ratio;
-    int check_orientation;
-    int angle_keep_rule;   // ovs_match_set_variant(OVS_MATCH_VARIANT_ANGLE_KEEP_RULE): filled in by launch_resolve
-    int angle_tie_order;   // ovs_match_set_variant(OVS_MATCH_VARIANT_ANGLE_TIE_ORDER): 0 equal sizes -> lower bin first, 1 higher bin first
-    const ovs_keypoint* q_kps;    // area: frame-1 keypoints (angle); bow: keyframe keypoints (angle), indexed through q_items
-    const int32_t* q_items;       // bow: query -> keyframe keypoint index (NULL: identity)
-    const ovs_keypoint* t_kps;    // area / bow: target keypoints (angle, pt)
-    float* prev_matched_xy;       // area: updated for the final matches
-    int32_t* assigned;            // projection / area: [n_q] target or -1; bow: [n_t] keyframe keypoint index or -1
-    uint32_t key_pool;            // LDS words available for a copy of the key CSR
-    int offsets_in_lds;           // the list bounds are staged in LDS (room for n_q + 1 words before the key pool)
-    uint32_t best_only_thr;       // BestOnly: accept iff best <= this (match_current_and_last_frames: THR_HIGH)
-    int bow_by_query;             // bow (match_keyframes): output [n_out_q] indexed by q_items[q] = target or -1
-    int n_out_q;
-    int32_t* num_matches;
-};
 
 template <int RULE>
 __device__ __forceinline__ bool rule_accepts(uint32_t best, uint32_t second, float ratio, uint32_t best_only_thr) {
@@ -993,94 +876,42 @@ struct ovs_wmatcher {
     size_t stage_cap = 0;
 };
 
-// a frame / keyframe resident in HBM (created by ovs_frame_dev_create below)
-struct ovs_frame_dev {
-    int device = 0;
-    int n = 0, cap = 0, n_cells = 0;
-    bool has_stereo = false;
-    GridP gp{};
-    ovs_grid_params gpp{};
-    unsigned char* arena = nullptr;
-    size_t arena_bytes = 0;
-    ovs_keypoint* d_kps = nullptr;
-    uint8_t* d_desc = nullptr;
-    float* d_x_right = nullptr;
-    int32_t *d_cell_of = nullptr, *d_cell_start = nullptr, *d_items = nullptr;
-    double* d_bearings = nullptr;   // optional (ovs_frame_dev_attach_bearings): 3 doubles per keypoint, for match_for_triangulation
-    ovs::Owned res;                 // d_bearings (the arena goes back to the pool: ovs_frame_dev_destroy)
-};
-
-// frame_dev_internal.inc: the landmark upkeep (landmark_update.hip) gathers descriptors from resident keyframes
-ovs::FrameDescriptors ovs::frame_descriptors(const ovs_frame_dev* f) { return {f->device, f->n, f->d_desc}; }
+// k_grid_assign over `n` device keypoints (frame_dev_internal.inc: the resident frame handle indexes its keypoints with it too)
+hipError_t ovs::launch_grid_assign(const ovs_keypoint* d_kps, int n, const GridP& g, int32_t* cell_of, int32_t* cell_start, int32_t* items, hipStream_t s) {
+    const GridLaunch l = grid_launch_plan(n, g.cols * g.rows);
+    if (l.raise_attr) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_grid_assign), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds_bytes);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_grid_assign, dim3(1), dim3(1024), l.lds_bytes, s, d_kps, n, g, cell_of, cell_start, items, l.items_in_lds);
+    return hipGetLastError();
+}
 
 namespace {
-
-constexpr int kMaxGridCells = 16384;
-
-GridP make_gridp(const ovs_grid_params& p) {
-    GridP g;
-    g.min_x = p.min_x;
-    g.min_y = p.min_y;
-    g.inv_w = (float)((double)p.cols / (double)(p.max_x - p.min_x));   // camera::base: double division, float member
-    g.inv_h = (float)((double)p.rows / (double)(p.max_y - p.min_y));
-    g.cols = p.cols;
-    g.rows = p.rows;
-    return g;
-}
-
-bool grid_params_ok(const ovs_grid_params* gp) {
-    return gp && gp->cols >= 1 && gp->rows >= 1 && gp->cols * gp->rows <= kMaxGridCells && gp->max_x > gp->min_x && gp->max_y > gp->min_y;
-}
-
-size_t resolve_lds_bytes(int n_q, int n_t) {
-    return (size_t)kMarkSize * 4 + 32 * 4 + (size_t)2 * 2 * ((n_t + 1) & ~1) + (size_t)2 * 2 * ((n_q + 1) & ~1);
-}
 
 template <int RULE>
 ovs_status launch_resolve(const ResolveArgs& ra_in, hipStream_t s) {
     ResolveArgs ra = ra_in;
     ra.angle_keep_rule = g_angle_keep_rule.load(std::memory_order_relaxed);
     ra.angle_tie_order = g_angle_tie_order.load(std::memory_order_relaxed);
-    size_t fixed = resolve_lds_bytes(ra.n_q, ra.n_t);
-    if (fixed > 150 * 1024) return OVS_ERR_CAPACITY;
-    // the queries' list bounds are staged in LDS too unless the problem is so large that they would take the room of everything else
-    const size_t off_bytes = (size_t)4 * ((ra.n_q + 4) & ~3);
-    ra.offsets_in_lds = fixed + off_bytes <= (size_t)120 * 1024 ? 1 : 0;
-    if (ra.offsets_in_lds) fixed += off_bytes;
-    // the rest of the allocation (96 KiB, or 24 KiB beyond the fixed part for the largest problems) holds a copy of the key CSR when it
-    // fits (checked on the device: the size is only known there)
-    const size_t lds = std::min((size_t)150 * 1024, std::max((size_t)96 * 1024, fixed + (size_t)24 * 1024));
-    ra.key_pool = (uint32_t)((lds - fixed) / 4);
-    // 1 / 4 / 8 waves (64 / 256 / 512 queries per round) by problem size: up to 256, up to 1024, beyond
-    const int wide_from = tuning().resolve_wide_from;   // 1024 (2048 until the commit rule changed: tracked frame, 2008 queries: 0.158 -> 0.147 ms, area 0.123 -> 0.094)
-    const int width = ra.n_q > wide_from ? 2 : (ra.n_q > 256 ? 1 : 0);
+    const ResolveLaunch l = resolve_plan(ra.n_q, ra.n_t, tuning().resolve_wide_from);
+    if (!l.ok) return OVS_ERR_CAPACITY;
+    ra.offsets_in_lds = l.offsets_in_lds;
+    ra.key_pool = l.key_pool;
     {
         static LdsAttrCache configured[3];   // per (RULE: this instantiation, width), per device
-        const void* fn = width == 2 ? reinterpret_cast<const void*>(k_list_resolve<RULE, 8>)
-                                    : (width == 1 ? reinterpret_cast<const void*>(k_list_resolve<RULE, 4>) : reinterpret_cast<const void*>(k_list_resolve<RULE, 1>));
-        OVS_HIP_TRY(ensure_dynamic_lds(fn, lds, configured[width]));
+        const void* fn = l.width == 2 ? reinterpret_cast<const void*>(k_list_resolve<RULE, 8>)
+                                      : (l.width == 1 ? reinterpret_cast<const void*>(k_list_resolve<RULE, 4>) : reinterpret_cast<const void*>(k_list_resolve<RULE, 1>));
+        OVS_HIP_TRY(ensure_dynamic_lds(fn, l.lds_bytes, configured[l.width]));
     }
-    if (width == 2)
-        hipLaunchKernelGGL((k_list_resolve<RULE, 8>), dim3(1), dim3(512), lds, s, ra);
-    else if (width == 1)
-        hipLaunchKernelGGL((k_list_resolve<RULE, 4>), dim3(1), dim3(256), lds, s, ra);
+    if (l.width == 2)
+        hipLaunchKernelGGL((k_list_resolve<RULE, 8>), dim3(1), dim3(512), l.lds_bytes, s, ra);
+    else if (l.width == 1)
+        hipLaunchKernelGGL((k_list_resolve<RULE, 4>), dim3(1), dim3(256), l.lds_bytes, s, ra);
     else
-        hipLaunchKernelGGL((k_list_resolve<RULE, 1>), dim3(1), dim3(64), lds, s, ra);
+        hipLaunchKernelGGL((k_list_resolve<RULE, 1>), dim3(1), dim3(64), l.lds_bytes, s, ra);
     OVS_HIP_TRY(hipGetLastError());
     return OVS_OK;
-}
-
-// k_grid_assign over `n` device keypoints: one workgroup, the member lists in LDS when they fit
-hipError_t launch_grid_assign(const ovs_keypoint* d_kps, int n, const GridP& g, int32_t* cell_of, int32_t* cell_start, int32_t* items, hipStream_t s) {
-    const int nc = g.cols * g.rows;
-    const int in_lds = (n <= kGridItemsLds && (size_t)(2 * nc + 1 + n) * sizeof(int32_t) <= 144 * 1024) ? 1 : 0;
-    const size_t lds = (size_t)(2 * nc + 1 + (in_lds ? n : 0)) * sizeof(int32_t);
-    if (lds > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_grid_assign), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k_grid_assign, dim3(1), dim3(1024), lds, s, d_kps, n, g, cell_of, cell_start, items, in_lds);
-    return hipGetLastError();
 }
 
 // the context's own grid over device keypoints
@@ -1092,41 +923,14 @@ ovs_status grid_assign(ovs_wmatcher* w, const ovs_grid_params* gp, const ovs_key
     return OVS_OK;
 }
 
-size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// per-call staging of host arrays: memcpy into the context's pinned buffer, ONE copy up for all of them
-struct Stager {
-    ovs_wmatcher* w;
-    size_t used = 0;
-    bool overflow = false;
-    explicit Stager(ovs_wmatcher* w_) : w(w_) {}
-    template <typename T>
-    const T* put(const T* src, size_t count) {   // nullptr in -> nullptr out
-        if (!src) return nullptr;
-        const size_t bytes = sizeof(T) * count, off = al256(used);
-        if (off + bytes > w->stage_cap) {
-            overflow = true;
-            return nullptr;
-        }
-        std::memcpy(w->h_stage + off, src, bytes);
-        used = off + bytes;
-        return reinterpret_cast<const T*>(w->d_stage + off);
-    }
-    template <typename T>
-    T* reserve(size_t count) {   // device-only scratch in the same arena (filled by a kernel)
-        const size_t bytes = sizeof(T) * count, off = al256(used);
-        if (off + bytes > w->stage_cap) {
-            overflow = true;
-            return nullptr;
-        }
-        used = off + bytes;
-        return reinterpret_cast<T*>(w->d_stage + off);
-    }
+// per-call staging of host arrays: StageWriter (match_window_plan.inc) places them in the context's pinned buffer, ONE copy up for all of them
+struct Stager : StageWriter {
+    explicit Stager(ovs_wmatcher* w) : StageWriter(w->h_stage, w->d_stage, w->stage_cap) {}
     ovs_status flush(hipStream_t s) {   // behind the call's last put / reserve
         if (overflow) return OVS_ERR_CAPACITY;
         flushed_on = s;
         flushed = true;
-        if (used) OVS_HIP_TRY(hipMemcpyAsync(w->d_stage, w->h_stage, used, hipMemcpyHostToDevice, s));
+        if (used) OVS_HIP_TRY(hipMemcpyAsync(d, h, used, hipMemcpyHostToDevice, s));
         return OVS_OK;
     }
     // A call returns with its stream idle, on EVERY path: the next call (or the shim's immediate retry) memcpy's into the same pinned buffer, and
@@ -1139,34 +943,12 @@ struct Stager {
     }
 };
 
-// One SIDE of a call -- the keypoints that are searched through the grid (the target of a windowed matcher), or either side of a BoW matcher:
-// host arrays, staged per call, or a frame / keyframe RESIDENT in HBM (ovs_frame_dev: uploaded and indexed once, when the handle was
-// created). Keyframes are the long-lived, immutable objects of the map: mapping_module matches every new keyframe against ~20 covisible
-// ones (fuse::replace_duplication), loop closing against more; with the handle none of those calls moves keypoints or descriptors.
-struct TargetRef {
-    const ovs_keypoint* kps;
-    const uint8_t* desc;
-    const float* x_right;
-    const double* bearings;
-    const int32_t* cell_start;   // nullptr: staged, not indexed yet (index_target)
-    const int32_t* items;
-    GridP gp;
-};
-// the one place that decides resident or uploaded; issues no device work (a staged side travels with the Stager's flush)
-ovs_status stage_target(ovs_wmatcher* w, Stager& stg, const ovs_frame_dev* res, const ovs_keypoint* kps, const uint8_t* desc, const float* x_right,
-                        const double* bearings, int n, TargetRef* t) {
-    if (res) {
-        if (res->device != w->device || res->n != n) return OVS_ERR_INVALID;
-        // bearings: the handle's when it carries them (ovs_frame_dev_attach_bearings), else the caller's
-        *t = TargetRef{res->d_kps, res->d_desc, res->has_stereo ? res->d_x_right : nullptr, res->d_bearings ? res->d_bearings : stg.put(bearings, (size_t)3 * n),
-                       res->d_cell_start, res->d_items, res->gp};
-        return OVS_OK;
-    }
-    *t = TargetRef{};
-    t->kps = stg.put(kps, (size_t)n);
-    t->desc = stg.put(desc, (size_t)32 * n);
-    t->x_right = stg.put(x_right, (size_t)n);
-    t->bearings = stg.put(bearings, (size_t)3 * n);
+// A side of a call that is a resident frame / keyframe: checked against the context, then its arrays as stage_target (match_window_plan.inc) takes
+// them (the callers pass `res ? &r : nullptr` on). Nothing to do for a side that comes as host arrays.
+ovs_status resident_side(const ovs_wmatcher* w, const ovs_frame_dev* res, int n, TargetRef* r) {
+    if (!res) return OVS_OK;
+    if (res->device != w->device || res->n != n) return OVS_ERR_INVALID;
+    *r = TargetRef{res->d_kps, res->d_desc, res->has_stereo ? res->d_x_right : nullptr, res->d_bearings, res->d_cell_start, res->d_items, res->gp};
     return OVS_OK;
 }
 // behind the flush: the grid of a staged target (a resident one brings its own)
@@ -1179,17 +961,6 @@ ovs_status index_target(ovs_wmatcher* w, const ovs_grid_params* gp, int n, Targe
     t->gp = w->gp;
     return OVS_OK;
 }
-
-// WinArgs::dead_from for a rule that accepts iff best <= thr and (ratio rules) !(fl(second * ratio) < best): the smallest distance d > thr with
-// fl(d * ratio) >= thr -- from there on a candidate can neither be an accepted best nor make the ratio test fail (the float product is monotone
-// in d, and "no second at all" counts as distance 256, which then accepts too). 257: nothing is dead; 0 would switch the filter off.
-uint32_t dead_from_ratio(uint32_t thr, float ratio) {
-    if (!(ratio > 0.0f)) return 257u;
-    for (uint32_t d = thr + 1u; d <= 256u; ++d)
-        if ((float)d * ratio >= (float)thr) return d;
-    return 257u;
-}
-uint32_t dead_from_thr(uint32_t thr) { return thr + 1u; }   // rules without a ratio test: best <= thr or nothing
 
 template <typename ARGS, typename KCOUNT, typename KFILL>
 ovs_status build_lists(ovs_wmatcher* w, const ARGS& args, int n_q, KCOUNT kcount, KFILL kfill, hipStream_t s, int q_per_block = 4) {
@@ -1246,33 +1017,6 @@ void fill_cam(CamP& cp, const ovs_camera* cam, const ovs_grid_params* gp, const 
     cp.max_y = gp->max_y;
     std::memcpy(cp.P, P, sizeof(double) * 12);
 }
-// camera centre -R^T t of the pose P = [R | t] (9 + 3 doubles, row-major R)
-void camera_centre(const double* P, double* cc) {
-    cc[0] = -((P[0] * P[9] + P[3] * P[10]) + P[6] * P[11]);
-    cc[1] = -((P[1] * P[9] + P[4] * P[10]) + P[7] * P[11]);
-    cc[2] = -((P[2] * P[9] + P[5] * P[10]) + P[8] * P[11]);
-}
-// Sim3_cw = [s R | t'] -> scale s = |first row of sR|, rot_cw = sR / s, trans_cw = t' / s, camera centre -R^T t (upstream decomposes the
-// 4x4 the same way in fuse::detect_duplication / projection::match_by_Sim3_transform)
-void decompose_sim3(const double* S, double* P, double* cc) {
-    const double sc = std::sqrt((S[0] * S[0] + S[1] * S[1]) + S[2] * S[2]);
-    for (int i = 0; i < 9; ++i) P[i] = S[i] / sc;
-    for (int i = 0; i < 3; ++i) P[9 + i] = S[9 + i] / sc;
-    camera_centre(P, cc);
-}
-// the per-level tables the kernels index up to OVS_MAX_LEVELS: `src` (nullptr: none) for the levels in use, `fill` beyond
-void pad_levels(float* dst, const float* src, int num_levels, float fill) {
-    for (int l = 0; l < OVS_MAX_LEVELS; ++l) dst[l] = (src && l < num_levels) ? src[l] : fill;
-}
-// match_current_and_last_frames (stereo / RGBD only): trans_wc = -rot_cw^T trans_cw; trans_lc = rot_lw trans_wc + trans_lw; its z against the baseline
-void motion_direction(const ovs_camera* cam, const double* pose_cw_curr, const double* pose_cw_last, int* forward, int* backward) {
-    double twc[3];
-    camera_centre(pose_cw_curr, twc);
-    const double* Rl = pose_cw_last;
-    const double tlc_z = ((Rl[6] * twc[0] + Rl[7] * twc[1]) + Rl[8] * twc[2]) + pose_cw_last[11];
-    *forward = cam->setup == 0 ? 0 : (tlc_z > cam->true_baseline);
-    *backward = cam->setup == 0 ? 0 : (-tlc_z > cam->true_baseline);
-}
 // robust::match_for_triangulation: "valid" for the bow kernels = the keypoint has NO landmark yet
 std::vector<uint8_t> no_landmark_mask(const uint8_t* has_lm, int n) {
     std::vector<uint8_t> v((size_t)std::max(n, 1), 1);
@@ -1281,24 +1025,6 @@ std::vector<uint8_t> no_landmark_mask(const uint8_t* has_lm, int n) {
     return v;
 }
 
-// what k_reproject_queries writes per query, in the staging arena
-struct QueryScratch {
-    const uint8_t* valid_in;   // the caller's flags (nullptr: every query), read ...
-    uint8_t* valid;            // ... and written in place: same index, read-then-write by one lane
-    float *xy, *x_right, *radius;
-    int32_t *minl, *maxl;
-};
-QueryScratch reserve_queries(Stager& stg, const uint8_t* valid, int n) {
-    QueryScratch q{};
-    q.valid = valid ? const_cast<uint8_t*>(stg.put(valid, (size_t)n)) : stg.reserve<uint8_t>((size_t)n);
-    q.valid_in = valid ? q.valid : nullptr;
-    q.xy = stg.reserve<float>((size_t)2 * n);
-    q.x_right = stg.reserve<float>((size_t)n);
-    q.radius = stg.reserve<float>((size_t)n);
-    q.minl = stg.reserve<int32_t>((size_t)n);
-    q.maxl = stg.reserve<int32_t>((size_t)n);
-    return q;
-}
 // kModeGeneric: reprojected queries with their own radius and level window against a target's grid
 WinArgs generic_window_args(const TargetRef& t, bool stereo, const uint8_t* d_occupied, const QueryScratch& q, const uint8_t* d_q_desc, int n_q, float margin,
                             uint32_t dead_from) {
@@ -1421,21 +1147,17 @@ ovs_status projection_match_frame_and_landmarks_impl(ovs_wmatcher* w, const ovs_
     const bool stereo = res ? res->has_stereo : stereo_x_right != nullptr;
     if ((!res && (!kps || !desc)) || !lm_xy || !lm_level || !lm_desc || (stereo && !lm_x_right)) return OVS_ERR_INVALID;
     Stager stg(w);
-    TargetRef tg;
-    ovs_status st = stage_target(w, stg, res, kps, desc, stereo_x_right, nullptr, n, &tg);
+    TargetRef r;
+    ovs_status st = resident_side(w, res, n, &r);
     if (st != OVS_OK) return st;
+    TargetRef tg = stage_target(stg, res ? &r : nullptr, kps, desc, stereo_x_right, nullptr, n);
     if (n > w->max_t || m > w->max_q) return OVS_ERR_CAPACITY;
     OVS_HIP_TRY(hipSetDevice(w->device));
     hipStream_t s = w->stream;
-    const uint8_t* d_occupied = stg.put(occupied, (size_t)n);
-    const float* d_lm_xy = stg.put(lm_xy, (size_t)2 * m);
-    const float* d_lm_x_right = stereo ? stg.put(lm_x_right, (size_t)m) : nullptr;
-    const int32_t* d_lm_level = stg.put(lm_level, (size_t)m);
-    const uint8_t* d_lm_valid = stg.put(lm_valid, (size_t)m);
-    const uint8_t* d_lm_desc = stg.put(lm_desc, (size_t)32 * m);
+    const LandmarkQueries q = stage_landmark_queries(stg, occupied, n, lm_xy, stereo ? lm_x_right : nullptr, lm_level, lm_valid, lm_desc, m);
     if ((st = stg.flush(s)) != OVS_OK || (st = index_target(w, gp, n, &tg, s)) != OVS_OK) return st;
-    st = frame_and_landmarks_on_device(w, tg, d_occupied, n, d_lm_xy, d_lm_x_right, d_lm_level, d_lm_desc, d_lm_valid, m, scale_factors, num_levels, margin,
-                                       lowe_ratio, w->d_assigned, w->d_num, s);
+    st = frame_and_landmarks_on_device(w, tg, q.occupied, n, q.xy, q.x_right, q.level, q.desc, q.valid, m, scale_factors, num_levels, margin, lowe_ratio,
+                                       w->d_assigned, w->d_num, s);
     if (st != OVS_OK) return st;
     return fetch_results(w, m, assigned, num_matches, s);
 }
@@ -1454,19 +1176,18 @@ ovs_status area_match_in_consistent_area_impl(ovs_wmatcher* w, const ovs_frame_d
     }
     if (!res_2 && (!kps_2 || !desc_2)) return OVS_ERR_INVALID;
     Stager stg(w);
-    // prev_matched_pts are read AND updated by the resolver: they live in the staging arena (first: offset 0) and come back with their own copy
-    float* d_prev = const_cast<float*>(stg.put(prev_matched_xy, (size_t)2 * n1));
-    TargetRef f1, f2;
-    ovs_status st = stage_target(w, stg, res_1, kps_1, desc_1, nullptr, nullptr, n1, &f1);
-    if (st == OVS_OK) st = stage_target(w, stg, res_2, kps_2, desc_2, nullptr, nullptr, n2, &f2);
+    TargetRef r1, r2;
+    ovs_status st = resident_side(w, res_1, n1, &r1);
+    if (st == OVS_OK) st = resident_side(w, res_2, n2, &r2);
     if (st != OVS_OK) return st;
+    AreaStaged a = stage_area(stg, prev_matched_xy, res_1 ? &r1 : nullptr, kps_1, desc_1, n1, res_2 ? &r2 : nullptr, kps_2, desc_2, n2);
     if (n2 > w->max_t || n1 > w->max_q) return OVS_ERR_CAPACITY;
     OVS_HIP_TRY(hipSetDevice(w->device));
     hipStream_t s = w->stream;
-    if ((st = stg.flush(s)) != OVS_OK || (st = index_target(w, gp, n2, &f2, s)) != OVS_OK) return st;
-    st = area_on_device(w, f1.kps, f1.desc, n1, f2, n2, d_prev, w->d_assigned, margin, lowe_ratio, check_orientation, w->d_num, s);
+    if ((st = stg.flush(s)) != OVS_OK || (st = index_target(w, gp, n2, &a.f2, s)) != OVS_OK) return st;
+    st = area_on_device(w, a.f1.kps, a.f1.desc, n1, a.f2, n2, a.prev, w->d_assigned, margin, lowe_ratio, check_orientation, w->d_num, s);
     if (st != OVS_OK) return st;
-    OVS_HIP_TRY(hipMemcpyAsync(w->h_stage, d_prev, sizeof(float) * 2 * (size_t)n1, hipMemcpyDeviceToHost, s));
+    OVS_HIP_TRY(hipMemcpyAsync(w->h_stage, a.prev, sizeof(float) * 2 * (size_t)n1, hipMemcpyDeviceToHost, s));
     st = fetch_results(w, n1, matched_2_in_1, num_matches, s);
     if (st != OVS_ERR_HIP) std::memcpy(prev_matched_xy, w->h_stage, sizeof(float) * 2 * (size_t)n1);   // only behind fetch_results' synchronisation
     return st;
@@ -1488,9 +1209,10 @@ ovs_status projection_match_current_and_last_frames_impl(ovs_wmatcher* w, const 
     if (n_curr == 0) return OVS_OK;
     if ((!res && (!curr_kps || !curr_desc)) || !last_kps || !last_pos_w || !last_lm_desc) return OVS_ERR_INVALID;
     Stager stg(w);
-    TargetRef tg;
-    ovs_status st = stage_target(w, stg, res, curr_kps, curr_desc, curr_stereo_x_right, nullptr, n_curr, &tg);
+    TargetRef r;
+    ovs_status st = resident_side(w, res, n_curr, &r);
     if (st != OVS_OK) return st;
+    TargetRef tg = stage_target(stg, res ? &r : nullptr, curr_kps, curr_desc, curr_stereo_x_right, nullptr, n_curr);
     if (n_curr > w->max_t || n_last > w->max_q) return OVS_ERR_CAPACITY;
     OVS_HIP_TRY(hipSetDevice(w->device));
     hipStream_t s = w->stream;
@@ -1500,18 +1222,14 @@ ovs_status projection_match_current_and_last_frames_impl(ovs_wmatcher* w, const 
     fill_cam(cp, cam, gp, pose_cw_curr);
     float sf16[OVS_MAX_LEVELS];
     pad_levels(sf16, scale_factors, num_levels, 1.0f);
-    const uint8_t* d_occupied = stg.put(curr_occupied, (size_t)n_curr);
-    const ovs_keypoint* d_query_kps = stg.put(last_kps, (size_t)n_last);
-    const double* d_q_pos = stg.put(last_pos_w, (size_t)3 * n_last);
-    const uint8_t* d_q_desc = stg.put(last_lm_desc, (size_t)32 * n_last);
-    const float* d_scale = stg.put(sf16, (size_t)OVS_MAX_LEVELS);
-    const QueryScratch q = reserve_queries(stg, last_valid, n_last);
+    const ReprojectedQueries rq = stage_reprojected_queries(stg, curr_occupied, n_curr, last_kps, last_pos_w, nullptr, nullptr, last_lm_desc, sf16, last_valid, n_last);
+    const QueryScratch& q = rq.q;
     if ((st = stg.flush(s)) != OVS_OK || (st = index_target(w, gp, n_curr, &tg, s)) != OVS_OK) return st;
-    hipLaunchKernelGGL(k_reproject_queries, dim3((n_last + 255) / 256), dim3(256), 0, s, cp, d_query_kps, d_q_pos, q.valid_in, n_last, margin, d_scale, num_levels, forward,
+    hipLaunchKernelGGL(k_reproject_queries, dim3((n_last + 255) / 256), dim3(256), 0, s, cp, rq.kps, rq.pos, q.valid_in, n_last, margin, rq.scale, num_levels, forward,
                        backward, (const float*)nullptr, 0.0, 0.0, 0.0, 0.0f, q.xy, q.x_right, q.radius, q.minl, q.maxl, q.valid);
     OVS_HIP_TRY(hipGetLastError());
-    const WinArgs a = generic_window_args(tg, true, d_occupied, q, d_q_desc, n_last, margin, dead_from_thr(OVS_HAMMING_DIST_THR_HIGH));
-    return generic_match(w, a, n_curr, d_query_kps, check_orientation, OVS_HAMMING_DIST_THR_HIGH, assigned, num_matches, s);
+    const WinArgs a = generic_window_args(tg, true, rq.occupied, q, rq.desc, n_last, margin, dead_from_thr(OVS_HAMMING_DIST_THR_HIGH));
+    return generic_match(w, a, n_curr, rq.kps, check_orientation, OVS_HAMMING_DIST_THR_HIGH, assigned, num_matches, s);
 }
 
 ovs_status projection_match_frame_and_keyframe_impl(ovs_wmatcher* w, const ovs_frame_dev* res, const ovs_camera* cam, const ovs_grid_params* gp,
@@ -1539,21 +1257,18 @@ ovs_status projection_match_frame_and_keyframe_impl(ovs_wmatcher* w, const ovs_f
     float sf16[OVS_MAX_LEVELS];
     pad_levels(sf16, scale_factors, num_levels, 1.0f);
     Stager stg(w);
-    const uint8_t* d_occupied = stg.put(curr_occupied, (size_t)n_curr);
-    const ovs_keypoint* d_query_kps = stg.put(kf_kps, (size_t)n_kf);
-    const double* d_q_pos = stg.put(kf_pos_w, (size_t)3 * n_kf);
-    const float* d_q_dist = stg.put(kf_dist_min_max, (size_t)2 * n_kf);
-    const uint8_t* d_q_desc = stg.put(kf_lm_desc, (size_t)32 * n_kf);
-    const float* d_scale = stg.put(sf16, (size_t)OVS_MAX_LEVELS);
-    const QueryScratch q = reserve_queries(stg, kf_valid, n_kf);
-    TargetRef tg;
-    ovs_status st = stage_target(w, stg, res, curr_kps, curr_desc, nullptr, nullptr, n_curr, &tg);
-    if (st != OVS_OK || (st = stg.flush(s)) != OVS_OK || (st = index_target(w, gp, n_curr, &tg, s)) != OVS_OK) return st;
-    hipLaunchKernelGGL(k_reproject_queries, dim3((n_kf + 255) / 256), dim3(256), 0, s, cp, d_query_kps, d_q_pos, q.valid_in, n_kf, margin, d_scale, num_levels, 0, 0,
-                       d_q_dist, cc[0], cc[1], cc[2], log_scale_factor, q.xy, q.x_right, q.radius, q.minl, q.maxl, q.valid);
+    TargetRef r;
+    ovs_status st = resident_side(w, res, n_curr, &r);
+    if (st != OVS_OK) return st;
+    const ReprojectedQueries rq = stage_reprojected_queries(stg, curr_occupied, n_curr, kf_kps, kf_pos_w, kf_dist_min_max, nullptr, kf_lm_desc, sf16, kf_valid, n_kf);
+    const QueryScratch& q = rq.q;
+    TargetRef tg = stage_target(stg, res ? &r : nullptr, curr_kps, curr_desc, nullptr, nullptr, n_curr);
+    if ((st = stg.flush(s)) != OVS_OK || (st = index_target(w, gp, n_curr, &tg, s)) != OVS_OK) return st;
+    hipLaunchKernelGGL(k_reproject_queries, dim3((n_kf + 255) / 256), dim3(256), 0, s, cp, rq.kps, rq.pos, q.valid_in, n_kf, margin, rq.scale, num_levels, 0, 0,
+                       rq.dist, cc[0], cc[1], cc[2], log_scale_factor, q.xy, q.x_right, q.radius, q.minl, q.maxl, q.valid);
     OVS_HIP_TRY(hipGetLastError());
-    const WinArgs a = generic_window_args(tg, false, d_occupied, q, d_q_desc, n_kf, margin, dead_from_thr(hamm_dist_thr));
-    return generic_match(w, a, n_curr, d_query_kps, check_orientation, hamm_dist_thr, assigned, num_matches, s);
+    const WinArgs a = generic_window_args(tg, false, rq.occupied, q, rq.desc, n_kf, margin, dead_from_thr(hamm_dist_thr));
+    return generic_match(w, a, n_curr, rq.kps, check_orientation, hamm_dist_thr, assigned, num_matches, s);
 }
 
 ovs_status projection_match_by_sim3_transform_impl(ovs_wmatcher* w, const ovs_frame_dev* res, const ovs_camera* cam, const ovs_grid_params* gp,
@@ -1580,33 +1295,20 @@ ovs_status projection_match_by_sim3_transform_impl(ovs_wmatcher* w, const ovs_fr
     float sf16[OVS_MAX_LEVELS];
     pad_levels(sf16, scale_factors, num_levels, 1.0f);
     Stager stg(w);
-    const uint8_t* d_occupied = stg.put(occupied, (size_t)n);
-    const double* d_q_pos = stg.put(lm_pos_w, (size_t)3 * m);
-    const float* d_q_dist = stg.put(lm_dist_min_max, (size_t)2 * m);
-    const double* d_q_normal = stg.put(lm_normal, (size_t)3 * m);
-    const uint8_t* d_q_desc = stg.put(lm_desc, (size_t)32 * m);
-    const float* d_scale = stg.put(sf16, (size_t)OVS_MAX_LEVELS);
-    const QueryScratch q = reserve_queries(stg, lm_valid, m);
-    TargetRef tg;
-    ovs_status st = stage_target(w, stg, res, kps, desc, nullptr, nullptr, n, &tg);
-    if (st != OVS_OK || (st = stg.flush(s)) != OVS_OK || (st = index_target(w, gp, n, &tg, s)) != OVS_OK) return st;
-    hipLaunchKernelGGL(k_reproject_queries, dim3((m + 255) / 256), dim3(256), 0, s, cp, (const ovs_keypoint*)nullptr, d_q_pos, q.valid_in, m, margin, d_scale,
-                       num_levels, 0, 0, d_q_dist, cc[0], cc[1], cc[2], log_scale_factor, q.xy, q.x_right, q.radius, q.minl, q.maxl, q.valid, d_q_normal, 0);
+    TargetRef r;
+    ovs_status st = resident_side(w, res, n, &r);
+    if (st != OVS_OK) return st;
+    const ReprojectedQueries rq = stage_reprojected_queries(stg, occupied, n, nullptr, lm_pos_w, lm_dist_min_max, lm_normal, lm_desc, sf16, lm_valid, m);
+    const QueryScratch& q = rq.q;
+    TargetRef tg = stage_target(stg, res ? &r : nullptr, kps, desc, nullptr, nullptr, n);
+    if ((st = stg.flush(s)) != OVS_OK || (st = index_target(w, gp, n, &tg, s)) != OVS_OK) return st;
+    hipLaunchKernelGGL(k_reproject_queries, dim3((m + 255) / 256), dim3(256), 0, s, cp, rq.kps, rq.pos, q.valid_in, m, margin, rq.scale, num_levels, 0, 0, rq.dist,
+                       cc[0], cc[1], cc[2], log_scale_factor, q.xy, q.x_right, q.radius, q.minl, q.maxl, q.valid, rq.normal, 0);
     OVS_HIP_TRY(hipGetLastError());
-    const WinArgs a = generic_window_args(tg, false, d_occupied, q, d_q_desc, m, margin, dead_from_thr(OVS_HAMMING_DIST_THR_LOW));
+    const WinArgs a = generic_window_args(tg, false, rq.occupied, q, rq.desc, m, margin, dead_from_thr(OVS_HAMMING_DIST_THR_LOW));
     return generic_match(w, a, n, nullptr, 0, OVS_HAMMING_DIST_THR_LOW, assigned, num_matches, s);
 }
 
-// the landmark side of a k_fuse_best launch: host arrays through the Stager
-void stage_fuse_landmarks(Stager& stg, FuseArgs& a, const double* lm_pos_w, const double* lm_normal, const float* lm_dist_min_max, const uint8_t* lm_desc,
-                          const uint8_t* lm_valid, int m) {
-    a.m = m;
-    a.lm_pos_w = stg.put(lm_pos_w, (size_t)3 * m);
-    a.lm_normal = stg.put(lm_normal, (size_t)3 * m);
-    a.lm_dist = stg.put(lm_dist_min_max, (size_t)2 * m);
-    a.lm_desc = stg.put(lm_desc, (size_t)32 * m);
-    a.lm_valid = stg.put(lm_valid, (size_t)m);
-}
 // k_fuse_best of `a.m` landmarks against an indexed target
 ovs_status launch_fuse_best(FuseArgs& a, const TargetRef& t, bool stereo, int32_t* d_best, int32_t* d_num, hipStream_t s) {
     a.t_kps = t.kps;
@@ -1657,10 +1359,12 @@ ovs_status fuse_duplication_impl(ovs_wmatcher* w, const ovs_frame_dev* res, int 
     a.variant = variant;
     a.max_dist = OVS_HAMMING_DIST_THR_LOW;
     Stager stg(w);
+    TargetRef r;
+    ovs_status st = resident_side(w, res, n, &r);
+    if (st != OVS_OK) return st;
     stage_fuse_landmarks(stg, a, lm_pos_w, lm_normal, lm_dist_min_max, lm_desc, lm_valid, m);
-    TargetRef tg;
-    ovs_status st = stage_target(w, stg, res, kps, desc, stereo_x_right, nullptr, n, &tg);
-    if (st != OVS_OK || (st = stg.flush(s)) != OVS_OK || (st = index_target(w, gp, n, &tg, s)) != OVS_OK) return st;
+    TargetRef tg = stage_target(stg, res ? &r : nullptr, kps, desc, stereo_x_right, nullptr, n);
+    if ((st = stg.flush(s)) != OVS_OK || (st = index_target(w, gp, n, &tg, s)) != OVS_OK) return st;
     OVS_HIP_TRY(hipMemsetAsync(w->d_num, 0, sizeof(int32_t), s));
     st = launch_fuse_best(a, tg, replace, w->d_assigned, w->d_num, s);
     if (st != OVS_OK) return st;
@@ -1690,14 +1394,8 @@ ovs_status projection_match_keyframes_mutually_impl(ovs_wmatcher* w, const ovs_f
     if (nmax > w->max_t || nmax > w->max_q) return OVS_ERR_CAPACITY;
     OVS_HIP_TRY(hipSetDevice(w->device));
     hipStream_t s = w->stream;
-    // Sim3 in both directions: [s_12 R_12 | t_12] takes keyframe-2 coordinates to keyframe 1; [R_12^T / s_12 | -(R_12^T / s_12) t_12] back
     double S12[12], S21[12];
-    for (int i = 0; i < 9; ++i) S12[i] = s_12 * rot_12[i];
-    for (int i = 0; i < 3; ++i) S12[9 + i] = trans_12[i];
-    const double inv_s = 1.0 / s_12;
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) S21[3 * r + c] = inv_s * rot_12[3 * c + r];
-    for (int r = 0; r < 3; ++r) S21[9 + r] = -((S21[3 * r] * trans_12[0] + S21[3 * r + 1] * trans_12[1]) + S21[3 * r + 2] * trans_12[2]);
+    sim3_both_ways(s_12, rot_12, trans_12, S12, S21);
     // two one-way searches, then the cross check. a21: the landmarks of keyframe 1 (pose 1, then S21) against the keypoints of keyframe 2; a12: the reverse
     FuseArgs a21{}, a12{};
     fill_cam(a21.cam, cam_2, gp_2, S21);
@@ -1714,20 +1412,19 @@ ovs_status projection_match_keyframes_mutually_impl(ovs_wmatcher* w, const ovs_f
         a->max_dist = OVS_HAMMING_DIST_THR_HIGH;
     }
     Stager stg(w);   // both directions in one arena: one copy up
-    stage_fuse_landmarks(stg, a21, lm_pos_w_1, nullptr, lm_dist_1, lm_desc_1, lm_valid_1, n1);
-    stage_fuse_landmarks(stg, a12, lm_pos_w_2, nullptr, lm_dist_2, lm_desc_2, lm_valid_2, n2);
-    int32_t* d_2_in_1 = stg.reserve<int32_t>((size_t)n1);
-    int32_t* d_1_in_2 = stg.reserve<int32_t>((size_t)n2);
-    TargetRef t1, t2;
-    ovs_status st = stage_target(w, stg, res_1, kps_1, desc_1, nullptr, nullptr, n1, &t1);
-    if (st == OVS_OK) st = stage_target(w, stg, res_2, kps_2, desc_2, nullptr, nullptr, n2, &t2);
-    if (st != OVS_OK || (st = stg.flush(s)) != OVS_OK) return st;
+    TargetRef r1, r2;
+    ovs_status st = resident_side(w, res_1, n1, &r1);
+    if (st == OVS_OK) st = resident_side(w, res_2, n2, &r2);
+    if (st != OVS_OK) return st;
+    MutualStaged m = stage_mutual(stg, a21, a12, res_1 ? &r1 : nullptr, kps_1, desc_1, n1, lm_pos_w_1, lm_dist_1, lm_desc_1, lm_valid_1, res_2 ? &r2 : nullptr, kps_2,
+                                  desc_2, n2, lm_pos_w_2, lm_dist_2, lm_desc_2, lm_valid_2);
+    if ((st = stg.flush(s)) != OVS_OK) return st;
     // staged targets share the context's one grid: the second is indexed behind the first direction's kernel, in stream order.
     // d_num[1] takes the per-direction counts: scratch
-    if ((st = index_target(w, gp_2, n2, &t2, s)) != OVS_OK || (st = launch_fuse_best(a21, t2, false, d_2_in_1, w->d_num + 1, s)) != OVS_OK) return st;
-    if ((st = index_target(w, gp_1, n1, &t1, s)) != OVS_OK || (st = launch_fuse_best(a12, t1, false, d_1_in_2, w->d_num + 1, s)) != OVS_OK) return st;
+    if ((st = index_target(w, gp_2, n2, &m.t2, s)) != OVS_OK || (st = launch_fuse_best(a21, m.t2, false, m.d_2_in_1, w->d_num + 1, s)) != OVS_OK) return st;
+    if ((st = index_target(w, gp_1, n1, &m.t1, s)) != OVS_OK || (st = launch_fuse_best(a12, m.t1, false, m.d_1_in_2, w->d_num + 1, s)) != OVS_OK) return st;
     OVS_HIP_TRY(hipMemsetAsync(w->d_num, 0, sizeof(int32_t), s));
-    hipLaunchKernelGGL(k_cross_check, dim3((n1 + 255) / 256), dim3(256), 0, s, (const int32_t*)d_2_in_1, (const int32_t*)d_1_in_2, n1, n2, w->d_assigned, w->d_num);
+    hipLaunchKernelGGL(k_cross_check, dim3((n1 + 255) / 256), dim3(256), 0, s, (const int32_t*)m.d_2_in_1, (const int32_t*)m.d_1_in_2, n1, n2, w->d_assigned, w->d_num);
     OVS_HIP_TRY(hipGetLastError());
     return fetch_results(w, n1, matched_2_in_1, num_matches, s, false);
 }
@@ -1763,28 +1460,32 @@ ovs_status bow_match_impl(ovs_wmatcher* w, const ovs_frame_dev* res_kf, const ov
         return OVS_ERR_INVALID;
     // keypoints (angle, octave), descriptors and for the triangulation matcher stereo_x_right and bearings of either side
     Stager stg(w);
-    TargetRef kf, frm;
-    ovs_status st = stage_target(w, stg, res_kf, kf_kps, kf_desc, tri ? tri->x_right_1 : nullptr, tri ? tri->bearings_1 : nullptr, n_kf, &kf);
-    if (st == OVS_OK) st = stage_target(w, stg, res_frm, frm_kps, frm_desc, tri ? tri->x_right_2 : nullptr, tri ? tri->bearings_2 : nullptr, n_frm, &frm);
+    TargetRef r_kf, r_frm;
+    ovs_status st = resident_side(w, res_kf, n_kf, &r_kf);
+    if (st == OVS_OK) st = resident_side(w, res_frm, n_frm, &r_frm);
     if (st != OVS_OK) return st;
     const int nq = kf_node_start[kf_nodes], nfi = frm_node_start[frm_nodes];
     if (nq == 0 || nfi == 0) return OVS_OK;
     if (n_frm > w->max_t || n_kf > w->max_q || nq > w->max_q || (by_query && n_kf > std::max(w->max_t, w->max_q))) return OVS_ERR_CAPACITY;
     OVS_HIP_TRY(hipSetDevice(w->device));
     hipStream_t s = w->stream;
+    const BowStaged b = stage_bow(stg, res_kf ? &r_kf : nullptr, kf_kps, kf_desc, tri ? tri->x_right_1 : nullptr, tri ? tri->bearings_1 : nullptr, kf_valid, n_kf,
+                                  kf_node_ids, kf_node_start, kf_items, kf_nodes, nq, res_frm ? &r_frm : nullptr, frm_kps, frm_desc, tri ? tri->x_right_2 : nullptr,
+                                  tri ? tri->bearings_2 : nullptr, frm_valid, n_frm, frm_node_ids, frm_node_start, frm_items, frm_nodes, nfi);
+    const TargetRef &kf = b.kf, &frm = b.frm;
     BowArgs a{};
     a.kf_desc = kf.desc;
-    a.kf_valid = stg.put(kf_valid, (size_t)n_kf);
-    a.kf_node_ids = stg.put(kf_node_ids, (size_t)kf_nodes);
-    a.kf_node_start = stg.put(kf_node_start, (size_t)kf_nodes + 1);
-    a.kf_items = stg.put(kf_items, (size_t)nq);
+    a.kf_valid = b.kf_fv.valid;
+    a.kf_node_ids = b.kf_fv.node_ids;
+    a.kf_node_start = b.kf_fv.node_start;
+    a.kf_items = b.kf_fv.items;
     a.kf_nodes = kf_nodes;
     a.n_q = nq;
     a.frm_desc = frm.desc;
-    a.frm_valid = stg.put(frm_valid, (size_t)n_frm);
-    a.frm_node_ids = stg.put(frm_node_ids, (size_t)frm_nodes);
-    a.frm_node_start = stg.put(frm_node_start, (size_t)frm_nodes + 1);
-    a.frm_items = stg.put(frm_items, (size_t)nfi);
+    a.frm_valid = b.frm_fv.valid;
+    a.frm_node_ids = b.frm_fv.node_ids;
+    a.frm_node_start = b.frm_fv.node_start;
+    a.frm_items = b.frm_fv.items;
     a.frm_nodes = frm_nodes;
     if ((st = stg.flush(s)) != OVS_OK) return st;   // (a feature vector beyond the arena's CSR budget: OVS_ERR_CAPACITY)
     if (tri) {
@@ -1816,49 +1517,6 @@ ovs_status bow_match_impl(ovs_wmatcher* w, const ovs_frame_dev* res_kf, const ov
     return fetch_results(w, n_out, matched_kf_in_frm, num_matches, s);
 }
 
-// device arenas of destroyed frame handles, kept for the next frame (a tracker creates one handle per frame: a hipMalloc / hipFree pair
-// per frame would cost more than the upload). Bounded; keyed by device and size.
-struct FrameArenaPool {
-    struct Item {
-        int device;
-        size_t bytes;
-        unsigned char* p;
-    };
-    std::mutex mu;
-    std::vector<Item> free_list;
-    unsigned char* take(int device, size_t bytes) {
-        std::lock_guard<std::mutex> lk(mu);
-        for (size_t i = 0; i < free_list.size(); ++i)
-            if (free_list[i].device == device && free_list[i].bytes == bytes) {
-                unsigned char* p = free_list[i].p;
-                free_list.erase(free_list.begin() + (long)i);
-                return p;
-            }
-        return nullptr;
-    }
-    void give(int device, size_t bytes, unsigned char* p) {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            if (free_list.size() < 8) {
-                free_list.push_back(Item{device, bytes, p});
-                return;
-            }
-        }
-        (void)hipSetDevice(device);
-        (void)hipFree(p);
-    }
-};
-FrameArenaPool g_frame_pool;
-
-// pinned staging for the once-per-frame upload, per thread (frames are created by the tracking thread; stereo rigs by two)
-struct FrameStage {
-    unsigned char* h = nullptr;
-    size_t cap = 0;
-    hipStream_t stream = nullptr;
-    int device = -1;
-    ovs::Owned res;
-};
-
 }   // namespace
 
 extern "C" {
@@ -1867,7 +1525,7 @@ ovs_status ovs_wmatcher_create(int32_t max_targets, int32_t max_queries, int32_t
     if (!out || max_targets < 1 || max_queries < 1 || max_entries < 1 || max_targets > 65534 || max_queries > 65534) return OVS_ERR_INVALID;
     *out = nullptr;
     if (ovs_device_count() <= device || device < 0) return OVS_ERR_NO_DEVICE;
-    if (resolve_lds_bytes(max_queries, max_targets) > 150 * 1024) return OVS_ERR_CAPACITY;
+    if (!resolve_plan(max_queries, max_targets, 0).ok) return OVS_ERR_CAPACITY;   // the resolver could not hold the largest call in LDS
     std::unique_ptr<ovs_wmatcher> owner(new (std::nothrow) ovs_wmatcher());
     ovs_wmatcher* const w = owner.get();
     if (!w) return OVS_ERR_INVALID;
@@ -1891,43 +1549,7 @@ ovs_status ovs_wmatcher_create(int32_t max_targets, int32_t max_queries, int32_t
     w->d_assigned = reinterpret_cast<int32_t*>(w->d_res_block) + 8;
     OVS_HIP_TRY_RAW(hipMemset(w->d_res_block, 0, sizeof(int32_t) * 8));
     OVS_HIP_TRY_RAW(w->res.pinned(&w->h_res, sizeof(int32_t) * (8 + M)));
-    // The staging arena holds every array of ONE call, each aligned to 256 bytes, so it is sized for the entry point that stages the most with
-    // n == max_targets and m == max_queries. Which one that is depends on T : Q, hence three sums (every other entry point stages a subset of
-    // the first): the host form of projection::match_frame_and_keyframe (with the stereo_x_right that match_current_and_last_frames adds),
-    // the host form of robust::match_for_triangulation, and the host form of projection::match_keyframes_mutually (n1, n2 <= min(T, Q)).
-    const size_t N = std::min(T, Q);
-    const size_t cap_window = T * (sizeof(ovs_keypoint)    // target keypoints
-                                   + 32                    // target descriptors
-                                   + sizeof(float)         // target stereo_x_right
-                                   + 1)                    // occupied flags
-                              + Q * (sizeof(ovs_keypoint)  // query keypoints
-                                     + 3 * sizeof(double)  // world positions
-                                     + 3 * sizeof(double)  // mean normals (match_by_Sim3_transform, fuse; those stage no query keypoints: slack)
-                                     + 2 * sizeof(float)   // valid distance range
-                                     + 32                  // landmark descriptors
-                                     + 1                   // valid flags
-                                     + 2 * sizeof(float)   // k_reproject_queries: reprojection
-                                     + sizeof(float)       //   x_right
-                                     + sizeof(float)       //   search radius
-                                     + 2 * sizeof(int32_t))   //   level window
-                              + sizeof(float) * OVS_MAX_LEVELS   // padded scale factors
-                              + 15 * 256;
-    const size_t cap_bow = (T + Q) * (sizeof(ovs_keypoint)    // keypoints of either side
-                                      + 32                    // descriptors
-                                      + 1                     // valid / has-no-landmark flags
-                                      + sizeof(float)         // stereo_x_right
-                                      + 3 * sizeof(double))   // bearings
-                           + sizeof(int32_t) * (4 * (T + Q) + 16)   // the two feature vectors: ids | start | items (<= 3 n + 1 each with no empty node)
-                           + 16 * 256;
-    const size_t cap_mutual = 2 * N * (sizeof(ovs_keypoint)    // keypoints of either keyframe
-                                       + 32                    // descriptors
-                                       + 3 * sizeof(double)    // landmark positions
-                                       + 2 * sizeof(float)     // valid distance range
-                                       + 32                    // landmark descriptors
-                                       + 1                     // valid flags
-                                       + sizeof(int32_t))      // the one-way result
-                              + 14 * 256;
-    w->stage_cap = std::max(cap_window, std::max(cap_bow, cap_mutual));
+    w->stage_cap = stage_capacity(T, Q);   // room for every array of the call that stages the most at n == max_targets, m == max_queries
     OVS_HIP_TRY_RAW(w->res.pinned(&w->h_stage, w->stage_cap));
     OVS_HIP_TRY_RAW(w->res.dev(&w->d_stage, w->stage_cap));
     *out = owner.release();
@@ -2011,90 +1633,6 @@ ovs_status ovs_assign_keypoints_to_grid(ovs_wmatcher* w, const ovs_grid_params* 
         OVS_HIP_TRY(hipMemcpyAsync(items, w->d_items, sizeof(int32_t) * *n_items, hipMemcpyDeviceToHost, s));
         OVS_HIP_TRY(hipStreamSynchronize(s));
     }
-    return OVS_OK;
-}
-
-// ---- frame / keyframe handles ----
-
-ovs_status ovs_frame_dev_destroy(ovs_frame_dev* f) {
-    if (!f) return OVS_OK;
-    if (f->arena) g_frame_pool.give(f->device, f->arena_bytes, f->arena);
-    delete f;
-    return OVS_OK;
-}
-
-ovs_status ovs_frame_dev_create(int32_t device, const ovs_grid_params* gp, const ovs_keypoint* undist_kps, const uint8_t* desc,
-                                const float* stereo_x_right, int32_t n, ovs_frame_dev** out) {
-    if (!out || !gp || n < 0 || n > 65534 || (n > 0 && (!undist_kps || !desc))) return OVS_ERR_INVALID;
-    *out = nullptr;
-    if (!grid_params_ok(gp)) return OVS_ERR_INVALID;
-    if (ovs_device_count() <= device || device < 0) return OVS_ERR_NO_DEVICE;
-    OVS_HIP_TRY(hipSetDevice(device));
-    std::unique_ptr<ovs_frame_dev, decltype(&ovs_frame_dev_destroy)> owner(new (std::nothrow) ovs_frame_dev(), &ovs_frame_dev_destroy);
-    ovs_frame_dev* const f = owner.get();
-    if (!f) return OVS_ERR_INVALID;
-    f->device = device;
-    f->n = n;
-    f->cap = std::max((n + 4095) & ~4095, 4096);   // capacity classes of 4096 keypoints: pooled arenas fit the next frame
-    f->n_cells = gp->cols * gp->rows;
-    f->has_stereo = stereo_x_right != nullptr;
-    f->gpp = *gp;
-    f->gp = make_gridp(*gp);
-    const size_t C = (size_t)f->cap;
-    const size_t o_kps = 0, o_desc = al256(o_kps + sizeof(ovs_keypoint) * C), o_xr = al256(o_desc + 32 * C), o_cellof = al256(o_xr + 4 * C),
-                 o_items = al256(o_cellof + 4 * C), o_start = al256(o_items + 4 * C);
-    f->arena_bytes = al256(o_start + sizeof(int32_t) * (kMaxGridCells + 1));
-    f->arena = g_frame_pool.take(device, f->arena_bytes);
-    if (!f->arena) {
-        const hipError_t e = hipMalloc(&f->arena, f->arena_bytes);
-        if (e != hipSuccess) {
-            ovs::set_last_error("hipMalloc(frame arena)", e);
-            return OVS_ERR_HIP;
-        }
-    }
-    f->d_kps = reinterpret_cast<ovs_keypoint*>(f->arena + o_kps);
-    f->d_desc = f->arena + o_desc;
-    f->d_x_right = reinterpret_cast<float*>(f->arena + o_xr);
-    f->d_cell_of = reinterpret_cast<int32_t*>(f->arena + o_cellof);
-    f->d_items = reinterpret_cast<int32_t*>(f->arena + o_items);
-    f->d_cell_start = reinterpret_cast<int32_t*>(f->arena + o_start);
-    static thread_local FrameStage st;
-    if (st.device != device) {
-        (void)st.res.drop(&st.stream);
-        st.device = device;
-    }
-    if (!st.stream) OVS_HIP_TRY_RAW(st.res.stream(&st.stream));
-    // the three arrays keep their arena offsets in the staging buffer, so ONE copy of [0, end of the last array) uploads them
-    const size_t up_bytes = n ? (stereo_x_right ? o_xr + 4 * (size_t)n : o_desc + 32 * (size_t)n) : 0;
-    if (st.cap < up_bytes) {
-        (void)st.res.drop(&st.h);
-        st.cap = 0;
-        const size_t want = std::max(up_bytes, al256(o_xr + 4 * (size_t)4096 * 4));
-        OVS_HIP_TRY_RAW(st.res.pinned(&st.h, want));
-        st.cap = want;
-    }
-    if (n) {
-        std::memcpy(st.h + o_kps, undist_kps, sizeof(ovs_keypoint) * (size_t)n);
-        std::memcpy(st.h + o_desc, desc, 32 * (size_t)n);
-        if (stereo_x_right) std::memcpy(st.h + o_xr, stereo_x_right, 4 * (size_t)n);
-        OVS_HIP_TRY_RAW(hipMemcpyAsync(f->arena, st.h, up_bytes, hipMemcpyHostToDevice, st.stream));
-    }
-    OVS_HIP_TRY_RAW(launch_grid_assign(f->d_kps, n, f->gp, f->d_cell_of, f->d_cell_start, f->d_items, st.stream));
-    OVS_HIP_TRY_RAW(hipStreamSynchronize(st.stream));   // the handle is used from other streams afterwards
-    *out = owner.release();
-    return OVS_OK;
-}
-
-int32_t ovs_frame_dev_num_keypoints(const ovs_frame_dev* f) { return f ? f->n : -1; }
-int32_t ovs_frame_dev_device(const ovs_frame_dev* f) { return f ? f->device : -1; }
-
-// 3 doubles per keypoint (data::keyframe::bearings_), uploaded once. Call it before the handle is shared between threads.
-ovs_status ovs_frame_dev_attach_bearings(ovs_frame_dev* f, const double* bearings) {
-    if (!f || (f->n > 0 && !bearings)) return OVS_ERR_INVALID;
-    if (f->n == 0) return OVS_OK;
-    OVS_HIP_TRY(hipSetDevice(f->device));
-    if (!f->d_bearings) OVS_HIP_TRY(f->res.dev(&f->d_bearings, sizeof(double) * 3 * (size_t)f->cap));
-    OVS_HIP_TRY(hipMemcpy(f->d_bearings, bearings, sizeof(double) * 3 * (size_t)f->n, hipMemcpyHostToDevice));
     return OVS_OK;
 }
 
