@@ -790,6 +790,40 @@ ovs_status ovs_twoview_solve_batch(ovs_twoview* s, int32_t n_problems, const int
                                    uint8_t* out_inlier_flags_H, uint8_t* out_inlier_flags_F);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Pose recovery for the monocular initialiser.  replaces: initialize::perspective::reconstruct_with_H and reconstruct_with_F with
+ *   initialize::base::check_pose and find_most_plausible_pose under them (src/openvslam/initialize/{base,perspective}.{h,cc}): the
+ *   decomposition of the chosen model into 8 (H) or 4 (F) pose hypotheses, the triangulation and the parallax, depth and reprojection gates
+ *   of every inlier match under every hypothesis, and the choice of the one plausible pose, for a BATCH of (reference frame, current frame)
+ *   problems in two launches (rules R1 to R12). It takes what ovs_twoview_solve_batch returns for the selected model.
+ * ovs_reconstruct_create: a handle for up to max_problems problems of max_total_matches matches together; one internal mutex serialises
+ *   the calls on a handle.
+ * ovs_reconstruct_batch: problem p owns matches [offsets[p], offsets[p + 1]) (offsets[0] = 0, non-decreasing). Per problem: models (1: H_21,
+ *   2: F_21), mats (9 doubles, row-major, as ovs_twoview_solve_batch writes them), cams (perspective: model 0, fx fy cx cy are read). Per
+ *   match: inlier_flags (the chosen model's flag byte; a match with 0 is skipped), keypts_ref / keypts_cur (2 doubles: the undistorted
+ *   keypoint of the reference / current frame), bearings_ref / bearings_cur (3 doubles each). reproj_err_thr, parallax_deg_thr and
+ *   min_num_triangulated are upstream's (4.0, 1.0, 50) and hold for the whole call.
+ *   Outputs per problem: out_success (1 or 0), out_best (the winning hypothesis, -1 on failure), out_rot_ref_to_cur (9, row-major) and
+ *   out_trans_ref_to_cur (3): zeros on failure; out_counts and out_parallax_deg (8 each: every hypothesis's number of triangulated matches
+ *   and its parallax in degrees; 0 for a hypothesis that does not exist). Per match: out_triangulated_pts (3 doubles in the reference
+ *   camera's frame; zeros where the match did not survive the winner's gates, and everywhere on failure) and out_is_triangulated (1 where
+ *   it survived with enough parallax). Results are bit-exact functions of a problem's own inputs, whatever its position in the batch.
+ *   A problem without matches or without inliers is not an error: it fails. Neither is a NaN or Inf in a match or a matrix: the match is
+ *   an outlier, the problem fails, nothing traps or loops.
+ * OVS_ERR_INVALID: a NULL required pointer, offsets not starting at 0 or decreasing, a model outside 1 .. 2, reproj_err_thr or
+ *   parallax_deg_thr not finite and positive, a camera that is not perspective or whose fx fy cx cy are not finite or whose fx / fy is zero.
+ *   OVS_ERR_CAPACITY: more problems or matches than the handle was created for (nothing is truncated). Both are decided before any launch,
+ *   and no output is written. */
+typedef struct ovs_reconstruct ovs_reconstruct;
+ovs_status ovs_reconstruct_create(int32_t device, int32_t max_problems, int32_t max_total_matches, ovs_reconstruct** out);
+ovs_status ovs_reconstruct_destroy(ovs_reconstruct* s);
+ovs_status ovs_reconstruct_batch(ovs_reconstruct* s, int32_t n_problems, const int32_t* offsets, const int32_t* models, const double* mats,
+                                 const ovs_camera* cams, const uint8_t* inlier_flags, const double* keypts_ref, const double* keypts_cur,
+                                 const double* bearings_ref, const double* bearings_cur, float reproj_err_thr, float parallax_deg_thr,
+                                 int32_t min_num_triangulated, int32_t* out_success, int32_t* out_best, double* out_rot_ref_to_cur,
+                                 double* out_trans_ref_to_cur, int32_t* out_counts, float* out_parallax_deg, double* out_triangulated_pts,
+                                 uint8_t* out_is_triangulated);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Two-view triangulation of a keyframe's new landmarks.  replaces: bool module::two_view_triangulator::triangulate(const unsigned idx_1,
  *   const unsigned idx_2, Vec3_t& pos_w) const (src/openvslam/module/two_view_triangulator.{h,cc}) with solve::triangulator::triangulate
  *   (src/openvslam/solve/triangulator.h) under it: the choice between the two-view solution and a stereo back-projection by parallax, the

@@ -21,7 +21,11 @@ pair robust::match_for_triangulation returns. All pairs of all neighbours of a n
 solve::homography_solver and solve::fundamental_solver (expected: src/openvslam/solve/{homography,fundamental}_solver.{h,cc}): the two RANSACs
 initialize::perspective::initialize runs on two threads for every frame until the map exists. Both models of all problems go to the device in
 ONE call (ovs_twoview_solve_batch, csrc/two_view_solve.hip): two launches, with upstream's choice between the models. DESIGN.md 3.13 has
-the rules; bit-exact in the same sense."""
+the rules; bit-exact in the same sense.
+
+initialize::perspective's reconstruct_with_H / reconstruct_with_F (expected: src/openvslam/initialize/{base,perspective}.{h,cc}): the pose
+hypotheses of the chosen model, check_pose over every inlier match and find_most_plausible_pose. All problems go to the device in ONE call
+(ovs_reconstruct_batch, csrc/two_view_reconstruct.hip): two launches. DESIGN.md 3.15 has the rules; bit-exact in the same sense."""
 import ctypes as C
 import math
 
@@ -521,3 +525,69 @@ class fundamental_solver(_two_view_solver):
 
     def get_best_F_21(self):
         return self._get("F_21")
+
+
+# ---- initialize::perspective's reconstruct_with_H / reconstruct_with_F, check_pose and find_most_plausible_pose
+def bearings_of(undist_keypts, cam):
+    """camera::perspective::convert_keypoints_to_bearings: ((u - cx) / fx, (v - cy) / fy, 1) normalised, per undistorted keypoint, in f64."""
+    kp = np.asarray(undist_keypts, np.float64).reshape(-1, 2)
+    x, y = (kp[:, 0] - cam.cx) / cam.fx, (kp[:, 1] - cam.cy) / cam.fy
+    l = np.sqrt((x * x + y * y) + 1.0)
+    return np.stack([x / l, y / l, 1.0 / l], axis=1)
+
+
+def reconstruct_problem(model, mat, cam, inlier_flags, keypts_ref, keypts_cur, bearings_ref, bearings_cur):
+    """One (reference frame, current frame) problem of the pose recovery: model (MODEL_H or MODEL_F) with its matrix H_21 / F_21 (3 x 3),
+    the perspective camera (solve.camera), and per match the model's inlier flag, the two undistorted keypoints (n, 2) and the two bearings
+    (n, 3)."""
+    return dict(model=int(model), mat=np.ascontiguousarray(mat, np.float64).reshape(3, 3), cam=cam, inlier=np.ascontiguousarray(inlier_flags, np.uint8).ravel(),
+                kp_ref=np.ascontiguousarray(keypts_ref, np.float64).reshape(-1, 2), kp_cur=np.ascontiguousarray(keypts_cur, np.float64).reshape(-1, 2),
+                b_ref=np.ascontiguousarray(bearings_ref, np.float64).reshape(-1, 3), b_cur=np.ascontiguousarray(bearings_cur, np.float64).reshape(-1, 3))
+
+
+def reconstruct_problem_from_solution(solution, two_view, cam, bearings_ref=None, bearings_cur=None):
+    """The problem of the model one result of solve_two_view_batch selected (None where it selected neither). two_view: the problem that
+    call solved (x1, x2: the matched undistorted keypoints); the bearings default to bearings_of the keypoints."""
+    if solution["selected"] not in (MODEL_H, MODEL_F):
+        return None
+    name, key = ("H", "H_21") if solution["selected"] == MODEL_H else ("F", "F_21")
+    x1, x2 = np.asarray(two_view["x1"], np.float64).reshape(-1, 2), np.asarray(two_view["x2"], np.float64).reshape(-1, 2)
+    return reconstruct_problem(solution["selected"], solution[name][key], cam, solution[name]["inlier_flags"], x1, x2,
+                               bearings_of(x1, cam) if bearings_ref is None else bearings_ref, bearings_of(x2, cam) if bearings_cur is None else bearings_cur)
+
+
+class _reconstruct_handle(_ransac_handle):
+    """ovs_reconstruct with its capacity."""
+    _abi = "ovs_reconstruct"
+
+
+_REC_ARRAYS = (("inlier", np.uint8, 1), ("kp_ref", np.float64, 2), ("kp_cur", np.float64, 2), ("b_ref", np.float64, 3), ("b_cur", np.float64, 3))
+
+
+def reconstruct_two_view_batch(problems, reproj_err_thr=4.0, parallax_deg_thr=1.0, min_num_triangulated=50, handle=None, device=0):
+    """reconstruct_with_H / reconstruct_with_F for every problem (dicts as reconstruct_problem returns them) in one call: a list of dicts
+    success, best (the winning hypothesis, -1), rot_ref_to_cur (3 x 3), trans_ref_to_cur (3), triangulated_pts (n, 3), is_triangulated
+    (n, bool), counts (8) and parallax_deg (8, float32) per hypothesis. `handle`: a _reconstruct_handle to reuse (the initialiser keeps one)."""
+    P = len(problems)
+    if P == 0:
+        return []
+    offsets = np.zeros(P + 1, np.int32)
+    offsets[1:] = np.cumsum([len(q["inlier"]) for q in problems])
+    T = int(offsets[-1])
+    cat = lambda key, dt, w: np.ascontiguousarray(np.concatenate([np.asarray(q[key], dt).reshape(-1, w) for q in problems]) if T else np.zeros((0, w), dt))
+    packed = [cat(*a) for a in _REC_ARRAYS]
+    if any(len(a) != T for a in packed):
+        raise ValueError("every per-match array of a problem must have one entry per match")
+    models = np.ascontiguousarray([q["model"] for q in problems], np.int32)
+    mats = np.ascontiguousarray([np.asarray(q["mat"], np.float64).reshape(3, 3) for q in problems])
+    cams = (_lib.Camera * P)(*[q["cam"] for q in problems])
+    if handle is None:
+        handle = _reconstruct_handle(P, max(T, 1), device)
+    success, best, rot, trans = np.zeros(P, np.int32), np.zeros(P, np.int32), np.zeros((P, 3, 3)), np.zeros((P, 3))
+    counts, parallax, pts, flags = np.zeros((P, 8), np.int32), np.zeros((P, 8), np.float32), np.zeros((max(T, 1), 3)), np.zeros(max(T, 1), np.uint8)
+    _lib.check(handle._L.ovs_reconstruct_batch(handle._h, P, _p(offsets), _p(models), _p(mats), cams, *map(_p, packed), float(reproj_err_thr),
+                                               float(parallax_deg_thr), int(min_num_triangulated), _p(success), _p(best), _p(rot), _p(trans), _p(counts),
+                                               _p(parallax), _p(pts), _p(flags)), "ovs_reconstruct_batch")
+    return [dict(success=bool(success[i]), best=int(best[i]), rot_ref_to_cur=rot[i].copy(), trans_ref_to_cur=trans[i].copy(),
+                 triangulated_pts=pts[offsets[i]:offsets[i + 1]].copy(), is_triangulated=flags[offsets[i]:offsets[i + 1]].astype(bool),
+                 counts=counts[i].copy(), parallax_deg=parallax[i].copy()) for i in range(P)]
