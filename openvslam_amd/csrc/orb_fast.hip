@@ -27,6 +27,7 @@
 // (frame, level) candidate list with ONE global atomic per workgroup. List order is irrelevant downstream (the quad-tree
 // kernel uses counts and an explicit emission-order key).
 #include "ovs_common.h"
+#include "fast_order.inc"
 
 #include <algorithm>
 #include <cstdio>
@@ -212,12 +213,16 @@ __device__ __forceinline__ uint32_t lds_addr(const void* p) { return (uint32_t)(
 // seven workgroups per CU (limit 23 405 B), 72 VGPRs. The next cell's tile is requested when the current cell's last tile read (the exact scoring; the NMS survivor list aliases
 // the R tile) is behind every wave, and lands under the cell's tail and the other six workgroups. (A second raw-tile buffer, requested a whole
 // cell ahead -- 26.7 KB, six workgroups per CU -- measured 5-10 % slower in round 4 and is gone.)
+// Set-up kept off the vector ALU (profiles/r16_fast_setup.txt): the work order (frame and group of a workgroup) is
+// scalar arithmetic on host-built values (fast_order.inc), the score-map clear is two stores at a held address, a clipped cell's pixel mask is two
+// shifts, and a wave without a testable row in a bottom-clipped cell skips pre-test, prefix and list loop on a scalar branch (same barriers).
 // kTiming: wave 0 accumulates shader cycles per phase into tstats (tuning aid, OVS_FAST_TIMING).
 template <bool kTiming>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) void k_fast_cells(
     const FrameGeo* __restrict__ geo, const CellDesc* __restrict__ cell_tab, const uint8_t* __restrict__ img0, size_t stride0, size_t frame_stride0,
     const uint8_t* __restrict__ pyr, size_t pyr_frame_bytes, uint64_t* __restrict__ cand, size_t cand_frame_entries, uint32_t* __restrict__ cand_count,
-    const uint8_t* __restrict__ mask, int batch, int cell_lo, int n_cells, int cells_per_wg, unsigned long long* __restrict__ tstats) {
+    const uint8_t* __restrict__ mask, int cell_lo, int n_cells, int cells_per_wg, uint32_t n_groups, uint32_t share, uint32_t total, uint32_t groups_magic,
+    unsigned long long* __restrict__ tstats) {
     __shared__ __attribute__((aligned(16))) uint32_t tiles[1][kTileRowsMax][kTileWords];
     __shared__ __attribute__((aligned(16))) uint32_t smap[kSmapRows][kSmapWords];
     __shared__ __attribute__((aligned(16))) uint32_t rtile[kTileRowsMax][kTileWords];
@@ -245,13 +250,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) voi
     // first tile's load latency are paid once per group, not once per cell). Group-major and XCD-aware: XCD k takes the k-th contiguous
     // eighth of the (frame, group) sequence, groups fastest, so the workgroups an XCD runs together read neighbouring 64-byte pieces of the
     // same image rows (DRAM pages, L2 lines): 13 % faster than the frames-fastest order of rounds 3-5 (round 6).
-    const int n_groups = (n_cells + cells_per_wg - 1) / cells_per_wg;
-    const int xcd = (int)blockIdx.x & 7, idx = (int)blockIdx.x >> 3;
-    const int share = (n_groups * batch + 7) >> 3;
-    const int gid = xcd * share + idx;
-    if (idx >= share || gid >= n_groups * batch) return;
-    const int frame = gid / n_groups;
-    const int group = gid - frame * n_groups;
+    // n_groups, share, total = n_groups * batch and the division's magic come from the host (fast_order.inc): the two run-time divisions this
+    // prologue had went through the vector unit's float reciprocal; now the whole work order is scalar.
+    const uint32_t gid = fast_order_gid(blockIdx.x, share, total);
+    if (gid >= total) return;
+    const int frame = (int)fast_order_frame(gid, n_groups, groups_magic);
+    const int group = (int)(gid - (uint32_t)frame * n_groups);
     const int cell_first = cell_lo + group * cells_per_wg;
     const int n_here = min(cells_per_wg, cell_lo + n_cells - cell_first);
 
@@ -300,10 +304,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) voi
             for (int j = 0; j < 6; ++j) {
                 int lane = tid & 63;
                 asm volatile("" : "+v"(lane));   // keeps the per-lane (row, word) of this rare path out of registers that live across the cell loop
-                const int i = 64 * (wave + 4 * j) + lane;
+                int wv = wave;
+                asm volatile("" : "+s"(wv));     // ... and its six LDS destinations out of scalar registers: hoisted, they were spilled to vector lanes
+                                                 // in every workgroup's prologue (six v_writelane) and read back here
+                const int i = 64 * (wv + 4 * j) + lane;
                 const int r = (i * 0x0ccd) >> 16, c4 = i - 20 * r;   // i / 20 for i < 1536
                 if (i < kTileRowsMax * kTileWords && r < ch && gx + 4 * c4 + 4 <= lv.pitch)
-                    glds4(base, (uint32_t)(r * lv.pitch + 4 * c4), lds_tile + 256u * (uint32_t)(wave + 4 * j));
+                    glds4(base, (uint32_t)(r * lv.pitch + 4 * c4), lds_tile + 256u * (uint32_t)(wv + 4 * j));
             }
         }
     };
@@ -312,6 +319,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) voi
     uint32_t* const smap_flat = &smap[0][0];
     uint8_t* const sbytes = reinterpret_cast<uint8_t*>(smap_flat);
     static_assert((kSmapRows * kSmapWords) % 4 == 0, "score map is cleared with 16-byte stores");
+    constexpr int kSmapChunks = kSmapRows * kSmapWords / 4;   // 297: one 16-byte store per thread + a second one for threads 0..40
+    static_assert(kSmapChunks > 256 && kSmapChunks <= 512, "score-map clear: one store per thread and one predicated store");
+    uint4* const clr = reinterpret_cast<uint4*>(smap_flat) + tid;   // address and predicate live across the cells (no counted loop)
+    const bool clr_b = tid + 256 < kSmapChunks;
+    auto clear_smap = [&]() {
+        clr[0] = uint4{0u, 0u, 0u, 0u};
+        if (clr_b) clr[256] = uint4{0u, 0u, 0u, 0u};
+    };
     const uint8_t* const fmask = mask ? mask + (size_t)frame * frame_stride0 : nullptr;   // same layout as the level-0 frames
     const int ini_thr = geo->ini_thr, min_thr = geo->min_thr;
     const uint32_t lds_tile0 = lds_addr(&tiles[0][0][0]);
@@ -374,7 +389,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) voi
                 *reinterpret_cast<uint4*>(&rtile[rb][4 * qb]) = uint4{to_r6(vb.x), to_r6(vb.y), to_r6(vb.z), to_r6(vb.w)};
             }
         }
-        for (int i = tid; i < kSmapRows * kSmapWords / 4; i += 256) reinterpret_cast<uint4*>(smap_flat)[i] = uint4{0u, 0u, 0u, 0u};
+        clear_smap();
         if (tid == 0) {
             n_out = 0;
             n_cand_wg = 0;
@@ -400,71 +415,71 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) voi
             uint32_t valid = 0x0f0f0f0fu;
             if (iw < kCellSize || ih < kCellSize) {
                 asm volatile("" ::: "memory");
-                valid = 0;
-#pragma unroll
-                for (int b = 0; b < 4; ++b)
-#pragma unroll
-                    for (int G = 0; G < 2; ++G) {
-                        const uint32_t colok = (c0 + 4 * G + b < iw) ? 1u : 0u;
-                        valid |= ((row0 < ih ? colok : 0u) << (8 * b + G)) | ((row0 + 1 < ih ? colok : 0u) << (8 * b + 2 + G));
-                    }
+                valid = fast_valid_mask(c0, row0, iw, ih);   // fast_order.inc: two shifts instead of sixteen compare / select pairs
             }
+            // Wave w pre-tests rows 16 w .. 16 w + 15: where the cell's testable area ends above them (bottom-clipped cells) its `valid` is zero in
+            // every lane and the pre-test cannot produce a candidate. Wave-uniform on scalar values: such a wave goes straight to barrier 2.
+            const bool wave_live = ih > 16 * wave;
 
             int thr = ini_thr;
             for (;;) {
-                // ---- 1. four-diameter test, four pixels per register, on the R tile: candidate mask + "dark end" mask
-                uint32_t cmask, dmask;
-                {
-                    uint32_t w[8][5];
+                if (wave_live) {
+                    // ---- 1. four-diameter test, four pixels per register, on the R tile: candidate mask + "dark end" mask
+                    uint32_t cmask, dmask;
+                    {
+                        uint32_t w[8][5];
 #pragma unroll
-                    for (int r = 0; r < 8; ++r) {
-                        const uint2 b = *reinterpret_cast<const uint2*>(&rtile[row0 + r][2 * run + 2]);
-                        w[r][1] = rtile[row0 + r][2 * run + 1];
-                        w[r][2] = b.x;
-                        w[r][3] = b.y;
-                        if (r == 3 || r == 4) {
-                            w[r][0] = rtile[row0 + r][2 * run];
-                            w[r][4] = rtile[row0 + r][2 * run + 4];
+                        for (int r = 0; r < 8; ++r) {
+                            const uint2 b = *reinterpret_cast<const uint2*>(&rtile[row0 + r][2 * run + 2]);
+                            w[r][1] = rtile[row0 + r][2 * run + 1];
+                            w[r][2] = b.x;
+                            w[r][3] = b.y;
+                            if (r == 3 || r == 4) {
+                                w[r][0] = rtile[row0 + r][2 * run];
+                                w[r][4] = rtile[row0 + r][2 * run + 4];
+                            }
+                        }
+                        const uint32_t kk = 0x80808080u - (uint32_t)((thr + 1) >> 2) * 0x01010101u;
+                        uint32_t b00, d00, b10, d10, b01, d01, b11, d11;
+                        swar_diameter_test<0, 0>(w, kk, b00, d00);
+                        swar_diameter_test<1, 0>(w, kk, b10, d10);
+                        swar_diameter_test<0, 1>(w, kk, b01, d01);
+                        swar_diameter_test<1, 1>(w, kk, b11, d11);
+                        constexpr uint32_t kM = 0x80808080u;
+                        const uint32_t bm = ((b00 & kM) >> 7) | ((b10 & kM) >> 6) | ((b01 & kM) >> 5) | ((b11 & kM) >> 4);
+                        dmask = (((d00 & kM) >> 7) | ((d10 & kM) >> 6) | ((d01 & kM) >> 5) | ((d11 & kM) >> 4)) & valid;
+                        cmask = (bm & valid) | dmask;
+                        // entry flags: 0x40 = evaluate the dark polarity (the bright test failed), 0x80 = both tests passed (evaluate both)
+                        dmask = (dmask & ~bm) | ((dmask & bm) << 4);   // bits 4..7 of every byte are free in the mask layout
+                    }
+                    FAST_MARK(4)   // diameter test
+                    // ---- 2. pool the candidates of the four waves: exclusive prefix inside the wave, one LDS atomic per wave for its base
+                    {
+                        const uint32_t n_mine = (uint32_t)__popc(cmask);
+                        const uint32_t incl = wave_prefix_incl(n_mine);
+                        const uint32_t wave_total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+                        uint32_t base = 0;
+                        if ((tid & 63) == 0 && wave_total) base = atomicAdd(&n_cand_wg, wave_total);
+                        const uint32_t wave_base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+                        uint32_t pos = wave_base + incl - n_mine;
+                        // a wave whose range does not fit the list writes nothing: the cell then holds more than kListCap candidates in total and
+                        // takes the exhaustive path below, which does not read the list (no per-entry bound check in the common case)
+                        // The loop runs as often as the wave's fullest lane has candidates (8 times per wave on video, 11 of 64 lanes active), so it
+                        // writes RAW entries, (thread << 5) | bit: position and flags are functions of (thread, bit, the thread's flag word) and are
+                        // worked out by the scoring pass, whose lanes are dense.
+                        cflag[tid] = dmask;
+                        if (wave_base + wave_total <= (uint32_t)kListCap) {
+                            uint32_t tid5 = (uint32_t)tid << 5;
+                            asm volatile("" : "+v"(tid5));   // no instruction: keeps the shift out of the loop (hipcc rematerialises it per iteration)
+                            while (cmask) {
+                                const uint32_t b = (uint32_t)__builtin_ctz(cmask);
+                                cmask &= cmask - 1;
+                                clist[pos++] = (uint16_t)(tid5 | b);
+                            }
                         }
                     }
-                    const uint32_t kk = 0x80808080u - (uint32_t)((thr + 1) >> 2) * 0x01010101u;
-                    uint32_t b00, d00, b10, d10, b01, d01, b11, d11;
-                    swar_diameter_test<0, 0>(w, kk, b00, d00);
-                    swar_diameter_test<1, 0>(w, kk, b10, d10);
-                    swar_diameter_test<0, 1>(w, kk, b01, d01);
-                    swar_diameter_test<1, 1>(w, kk, b11, d11);
-                    constexpr uint32_t kM = 0x80808080u;
-                    const uint32_t bm = ((b00 & kM) >> 7) | ((b10 & kM) >> 6) | ((b01 & kM) >> 5) | ((b11 & kM) >> 4);
-                    dmask = (((d00 & kM) >> 7) | ((d10 & kM) >> 6) | ((d01 & kM) >> 5) | ((d11 & kM) >> 4)) & valid;
-                    cmask = (bm & valid) | dmask;
-                    // entry flags: 0x40 = evaluate the dark polarity (the bright test failed), 0x80 = both tests passed (evaluate both)
-                    dmask = (dmask & ~bm) | ((dmask & bm) << 4);   // bits 4..7 of every byte are free in the mask layout
-                }
-                FAST_MARK(4)   // diameter test
-                // ---- 2. pool the candidates of the four waves: exclusive prefix inside the wave, one LDS atomic per wave for its base
-                {
-                    const uint32_t n_mine = (uint32_t)__popc(cmask);
-                    const uint32_t incl = wave_prefix_incl(n_mine);
-                    const uint32_t wave_total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-                    uint32_t base = 0;
-                    if ((tid & 63) == 0 && wave_total) base = atomicAdd(&n_cand_wg, wave_total);
-                    const uint32_t wave_base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-                    uint32_t pos = wave_base + incl - n_mine;
-                    // a wave whose range does not fit the list writes nothing: the cell then holds more than kListCap candidates in total and
-                    // takes the exhaustive path below, which does not read the list (no per-entry bound check in the common case)
-                    // The loop runs as often as the wave's fullest lane has candidates (8 times per wave on video, 11 of 64 lanes active), so it
-                    // writes RAW entries, (thread << 5) | bit: position and flags are functions of (thread, bit, the thread's flag word) and are
-                    // worked out by the scoring pass, whose lanes are dense.
-                    cflag[tid] = dmask;
-                    if (wave_base + wave_total <= (uint32_t)kListCap) {
-                        uint32_t tid5 = (uint32_t)tid << 5;
-                        asm volatile("" : "+v"(tid5));   // no instruction: keeps the shift out of the loop (hipcc rematerialises it per iteration)
-                        while (cmask) {
-                            const uint32_t b = (uint32_t)__builtin_ctz(cmask);
-                            cmask &= cmask - 1;
-                            clist[pos++] = (uint16_t)(tid5 | b);
-                        }
-                    }
+                } else {
+                    cflag[tid] = 0;   // no candidate of this thread's: nothing reads the word, it only keeps the flag words defined
                 }
                 FAST_MARK(5)   // prefix + list writes
                 lds_barrier();
@@ -555,7 +570,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) voi
                 if (n_out != 0 || thr <= min_thr) break;
                 // "if keypts_in_cell.empty()": again with min_fast_thr (rare: flat cells). No survivor was written, so the R tile is intact.
                 thr = min_thr;
-                for (int i = tid; i < kSmapRows * kSmapWords / 4; i += 256) reinterpret_cast<uint4*>(smap_flat)[i] = uint4{0u, 0u, 0u, 0u};
+                clear_smap();
                 if (tid == 0) n_cand_wg = 0;
                 lds_barrier();
             }
@@ -635,9 +650,8 @@ hipError_t launch_fast(const FrameGeo& hgeo, const DevBuffers& d, const uint8_t*
     if (n_cells < 0) n_cells = hgeo.total_cells - cell_lo;
     if (n_cells <= 0 || batch <= 0) return hipSuccess;
     const Tuning& tn = tuning();
-    const unsigned per_xcd = (unsigned)(n_cells + 7) / 8u;
-    // launch-size bound (per_xcd * batch * batch < 2^32): keeps the kernel's int work-order arithmetic (n_groups * batch) far from overflow
-    if ((uint64_t)per_xcd * (uint64_t)batch * (uint64_t)batch >= (1ull << 32)) return hipErrorInvalidValue;
+    // launch-size bound (per_xcd * batch * batch < 2^32): keeps the work-order arithmetic (n_groups * batch) far from overflow
+    if (!fast_launch_admitted(n_cells, batch)) return hipErrorInvalidValue;
     const long long launch_cells = (long long)n_cells * batch;
     // Cells per group: consecutive cells amortise a group's set-up and let the next tile's copy overlap the current cell's tail; with the
     // group-major work order (round 6) short groups are best, because the waves in flight then cover a compact run of cell rows whose image
@@ -645,8 +659,8 @@ hipError_t launch_fast(const FrameGeo& hgeo, const DevBuffers& d, const uint8_t*
     // 26.4 with one).
     const int cells_auto = launch_cells >= 65536 ? 3 : 2;
     const int cells_per_wg = tn.fast_cells > 0 ? std::min(tn.fast_cells, kMaxCellsPerWg) : cells_auto;
-    const unsigned n_groups = ((unsigned)n_cells + (unsigned)cells_per_wg - 1) / (unsigned)cells_per_wg, gper = (n_groups + 7) / 8u;
-    const dim3 grid(8u * gper * (unsigned)batch), block(256);
+    const FastOrder fo = fast_order(n_cells, cells_per_wg, batch);
+    const dim3 grid(fo.grid), block(256);
     const size_t pad_lds = (size_t)tn.fast_pad_lds;   // occupancy probe: extra dynamic LDS per workgroup (0 in production)
     if (tn.fast_timing) {   // tuning aid: per-phase shader cycles of wave 0 of every workgroup, printed per launch
         int dev = 0;
@@ -657,7 +671,7 @@ hipError_t launch_fast(const FrameGeo& hgeo, const DevBuffers& d, const uint8_t*
         if (!d_t[dev] && hipMalloc(&d_t[dev], 16 * sizeof(unsigned long long)) != hipSuccess) return hipErrorOutOfMemory;
         (void)hipMemsetAsync(d_t[dev], 0, 16 * sizeof(unsigned long long), s);
         hipLaunchKernelGGL((k_fast_cells<true>), grid, block, pad_lds, s, d.geo, d.cells, img0, stride0, frame_stride0, d.pyr, d.pyr_frame_bytes, d.cand,
-                           d.cand_frame_entries, d.cand_count, mask, batch, cell_lo, n_cells, cells_per_wg, d_t[dev]);
+                           d.cand_frame_entries, d.cand_count, mask, cell_lo, n_cells, cells_per_wg, fo.n_groups, fo.share, fo.total, fo.magic, d_t[dev]);
         unsigned long long h_t[16];
         (void)hipStreamSynchronize(s);
         (void)hipMemcpy(h_t, d_t[dev], sizeof(h_t), hipMemcpyDeviceToHost);
@@ -671,7 +685,8 @@ hipError_t launch_fast(const FrameGeo& hgeo, const DevBuffers& d, const uint8_t*
         return hipGetLastError();
     }
     hipLaunchKernelGGL((k_fast_cells<false>), grid, block, pad_lds, s, d.geo, d.cells, img0, stride0, frame_stride0, d.pyr, d.pyr_frame_bytes, d.cand,
-                       d.cand_frame_entries, d.cand_count, mask, batch, cell_lo, n_cells, cells_per_wg, (unsigned long long*)nullptr);
+                       d.cand_frame_entries, d.cand_count, mask, cell_lo, n_cells, cells_per_wg, fo.n_groups, fo.share, fo.total, fo.magic,
+                       (unsigned long long*)nullptr);
     return hipGetLastError();
 }
 
