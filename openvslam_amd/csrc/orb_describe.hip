@@ -2,15 +2,15 @@
 // compute_orb_descriptor and correct_keypoint_scale (expected: src/openvslam/feature/orb_extractor.cc,
 // util/trigonometric.h; OpenCV fastAtan2, GaussianBlur, cvRound).
 //
-// One WAVE (a 64-thread workgroup) per selected keypoint -- no workgroup barriers, 30 keypoints in flight per CU.
+// One WAVE (a 64-thread workgroup) per selected keypoint -- no workgroup barriers, 32 keypoints in flight per CU (its wave slots).
 // Everything a keypoint needs lies in the 43x43 patch around it (rBRIEF reaches +-18 px after rotation, the blur adds 3):
-//   * the patch is staged in LDS as 43 aligned 64-byte row segments (three 16-byte loads per lane),
+//   * the patch is staged in LDS as 43 aligned 64-byte row segments (three 16-byte loads per lane), 80 bytes apart,
 //   * the intensity-centroid moments are exact integer sums over the radius-15 disc (two lanes per disc row + wave reduce),
 //   * the angle is cv::fastAtan2's float polynomial evaluated with explicit non-fused IEEE ops (__fmul_rn/__fadd_rn/
 //     __fdiv_rn) in the oracle's order, so the float result is bit-identical to the CPU; every lane evaluates it (uniform),
 //   * the blur is evaluated ONLY where it is sampled: row pass in 8.8 fixed point over 43x37 (four outputs per lane-step from
-//     word reads, v_alignbyte_b32 + v_dot4_u32_u8), column pass at the 512 sample points (instead of blurring 6.4 MP per
-//     frame, upstream's cv::GaussianBlur of every level),
+//     word reads, v_alignbyte_b32 + v_dot4_u32_u8; every blurred row written over the pixels it was made from), column pass at the
+//     512 sample points (instead of blurring 6.4 MP per frame, upstream's cv::GaussianBlur of every level),
 //   * lane l evaluates tests l, l+64, l+128, l+192; each ballot is 8 descriptor bytes (bit i of byte j = test 8j+i).
 // Keypoints are written level-major at their final position: frame offset = sum of lower levels' counts.
 #include <cstdlib>
@@ -69,9 +69,13 @@ constexpr int kPatch = 43;       // 2*(18+3)+1
 constexpr int kPatchR = 21;
 constexpr int kBlurW = 37;       // 2*18+1 (columns of the row-blurred patch that are read)
 constexpr int kBlurR = 18;
-constexpr int kPatchPitch = 64;   // bytes: one aligned 64-byte window of each image row
+constexpr int kSegBytes = 64;     // one aligned 64-byte window of each image row holds the patch's 43 pixels at any offset 0 .. 15
 constexpr int kHbPitch = 40;      // u16 per row of the row-blurred patch (37 used)
+constexpr int kPatchPitch = 80;   // bytes from one staged row segment to the next: the blurred row's pitch, so that row r is blurred over its own pixels
+constexpr int kBandRows = 6;      // rows of the patch one step of the blur's row pass covers (ten lanes per row)
 static_assert(kBlurW <= kHbPitch && kBlurW + 6 == kPatch, "blur window geometry");
+static_assert(kPatchPitch == kHbPitch * 2 && kSegBytes <= kPatchPitch && kPatchPitch % 16 == 0,
+              "the blurred rows take the patch's place, row for row from the same base: see the row pass in k_describe");
 
 // cv::fastAtan2 (scalar form), degrees in [0, 360). Every operation individually rounded (no FMA contraction).
 __device__ __forceinline__ float fast_atan2_deg(float y, float x) {
@@ -142,8 +146,13 @@ __global__ __launch_bounds__(64) void k_describe(const FrameGeo* __restrict__ ge
                                                 uint8_t* __restrict__ desc_m, int32_t* __restrict__ counts_m) {
     // kps_m / desc_m / counts_m (round 6, one-frame host calls): a second copy of every output, written straight into the caller-side pinned
     // block -- the frame's results then need no D2H copy command after the kernel (nullptr: batches, device-resident callers)
-    __shared__ __attribute__((aligned(16))) uint8_t patch[kPatch * kPatchPitch];
+    // ONE block of LDS, 3 440 B, holds first the patch (row r: the 64 bytes from byte 80 r) and then the row-blurred patch (row r: the 40 u16
+    // from byte 80 r). After ic_angle the patch is read by the blur's row pass alone, and the row pass makes row r of the blurred patch from
+    // row r of the patch, so the blurred rows take the patch's place (see the row pass for why no pixel is overwritten unread). With two
+    // blocks (2 752 + 3 440 B) the LDS held 25 of these one-wave workgroups per CU; with one the CU's 32 wave slots are the limit.
     __shared__ __attribute__((aligned(16))) uint16_t hblur[kPatch * kHbPitch];
+    uint8_t* const patch = reinterpret_cast<uint8_t*>(hblur);
+    static_assert((kPatch - 1) * kPatchPitch + kSegBytes <= (int)sizeof(hblur), "the patch fits the blurred patch's block");
 
     const int lane = threadIdx.x;
     // Workgroup -> (frame, keypoint slot). Workgroups are handed to the eight XCDs round-robin in launch order, and each XCD has its own
@@ -151,8 +160,9 @@ __global__ __launch_bounds__(64) void k_describe(const FrameGeo* __restrict__ ge
     // lines = 14 MB of line fetches over a 6.8 MB pyramid -- are spread over all eight L2s and every line comes in from the fabric again
     // (13.8 MB per 1080p frame measured). Mapped so that XCD x walks the slots of frame 8 g + x in order, a level's plane (<= 2 MB)
     // stays in that XCD's L2 while its keypoints are described: 5.7 MB per frame, 2.4x less (profiles/r03_describe_pmc.txt).
-    // The kernel's TIME does not move with it: it is bound by the vector ALU (637 VALU instructions per keypoint-wave x 4 cycles x 253
-    // waves per SIMD = the 0.33 ms per 128 frames), see DESIGN.md section 3.4 for what was tried against that.
+    // The kernel's TIME does not move with it, and it is not the vector ALU's either (494 VALU instructions per keypoint-wave are 0.35 ms
+    // per 256 frames of the 0.56): the counters show the LDS array active for about nine tenths of the kernel's cycles, three fifths of
+    // them bank-conflict cycles (the steered tests' u16 gathers), see DESIGN.md section 3.4 and profiles/r17_describe_inplace.txt.
     const int total_cap = geo->total_kp_cap;
     const uint32_t xcd = blockIdx.x & 7u, idx = blockIdx.x >> 3;
     const uint32_t grp = idx / (uint32_t)total_cap;
@@ -264,25 +274,61 @@ __global__ __launch_bounds__(64) void k_describe(const FrameGeo* __restrict__ ge
     // lane -> (row r0 = lane / 10 of a six-row band, column group q = lane % 10), lanes 60 .. 63 idle; band it covers rows 6 it + r0. Every
     // address is the lane's base plus a compile-time constant (no per-step index arithmetic: the 64-lane stride over the 430 steps cost
     // twelve instructions per step for the division by ten)
+    //
+    // The blurred rows are written over the patch, row r over row r: both have the pitch of 80 bytes from the block's byte 0 (static_assert
+    // above), so row r's pixels (bytes [80 r, 80 r + 64)) and its forty blurred values (bytes [80 r, 80 r + 80)) share a range that holds
+    // nothing of another row.
+    //   * Between rows, and so between bands: no write can reach a pixel of a row other than its own. Band it (rows 6 it .. 6 it + 5) reads and
+    //     writes bytes [480 it, 480 it + 480) and nothing else; the order of the bands is free.
+    //   * Inside a row: the ten lanes of row r read the words at bytes 80 r + ((off + 4 q) & ~3) .. + 15 and write the two words at
+    //     80 r + 8 q, q = 0 .. 9 -- lane q's words land on pixels that other lanes of the row read (off <= 15). Every lane's four reads of
+    //     a band precede its two writes in program order and a wave's DS operations execute in order, so all 64 lanes' reads are done
+    //     before the first write. wave_handover states that order to the compiler (wavefront-scope release / acquire and a wave barrier:
+    //     no instruction), instead of leaving it to the fact that it cannot prove the indices distinct; the first one also keeps
+    //     ic_angle's reads of the patch ahead of every write.
+    // The bands are walked from the last to the first, and the reads of band it - 1 (bytes below 480 it: nothing band it writes) are issued
+    // ahead of band it's writes: the LDS round trip of the next band runs under the dot products and stores of this one (measured against
+    // reading after the writes, and against a 64-byte patch pitch with the same walk: profiles/r17_describe_inplace.txt).
+    auto wave_handover = [&]() __attribute__((always_inline)) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    };
     if (lane < 60) {
         const int r0 = (lane * 0x199a) >> 16, q = lane - 10 * r0;   // lane / 10 for lane < 64
         const uint32_t* const pw0 = reinterpret_cast<const uint32_t*>(patch + r0 * kPatchPitch + ((off + 4 * q) & ~3));
         uint32_t* const hb0 = hb32 + r0 * (kHbPitch / 2) + 2 * q;
+        auto read_band = [&](int it, uint32_t (&w)[4]) __attribute__((always_inline)) {
+            const uint32_t* pw = pw0 + it * kBandRows * (kPatchPitch / 4);
 #pragma unroll
-        for (int it = 0; it < 8; ++it) {
-            if (it == 7 && r0 != 0) break;   // rows 42 .. 47: only row 42 exists
-            const uint32_t* pw = pw0 + it * 6 * (kPatchPitch / 4);
-            const uint32_t w0 = pw[0], w1 = pw[1], w2 = pw[2], w3 = pw[3];
-            const uint32_t n0 = __builtin_amdgcn_alignbyte(w1, w0, sh), n1 = __builtin_amdgcn_alignbyte(w2, w1, sh),
-                           n2 = __builtin_amdgcn_alignbyte(w3, w2, sh);
+            for (int k = 0; k < 4; ++k) w[k] = pw[k];
+        };
+        auto blur_band = [&](int it, const uint32_t (&w)[4]) __attribute__((always_inline)) {
+            const uint32_t n0 = __builtin_amdgcn_alignbyte(w[1], w[0], sh), n1 = __builtin_amdgcn_alignbyte(w[2], w[1], sh),
+                           n2 = __builtin_amdgcn_alignbyte(w[3], w[2], sh);
             // every sum <= 255 * 257 = 65535
             const uint32_t o0 = __builtin_amdgcn_udot4(n0, g0123, __builtin_amdgcn_udot4(n1, g456, 0u, false), false);
             const uint32_t o1 = __builtin_amdgcn_udot4(n0, t1a, __builtin_amdgcn_udot4(n1, t1b, 0u, false), false);
             const uint32_t o2 = __builtin_amdgcn_udot4(n0, t2a, __builtin_amdgcn_udot4(n1, t2b, __builtin_amdgcn_udot4(n2, t2c, 0u, false), false), false);
             const uint32_t o3 = __builtin_amdgcn_udot4(n0, t3a, __builtin_amdgcn_udot4(n1, t3b, __builtin_amdgcn_udot4(n2, t3c, 0u, false), false), false);
-            uint32_t* hb = hb0 + it * 6 * (kHbPitch / 2);
+            wave_handover();   // all lanes' reads of this band (and of the next one) -> the writes over them
+            uint32_t* hb = hb0 + it * kBandRows * (kHbPitch / 2);
             hb[0] = o0 | (o1 << 16);
             hb[1] = o2 | (o3 << 16);
+        };
+        uint32_t w[4], wn[4];
+        if (r0 == 0) {   // band 7 = rows 42 .. 47: only row 42 exists
+            read_band(7, w);
+            blur_band(7, w);
+        }
+        read_band(6, w);
+#pragma unroll
+        for (int it = 6; it >= 0; --it) {
+            if (it > 0) read_band(it - 1, wn);
+            blur_band(it, w);
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (it > 0) w[k] = wn[k];
         }
     }
     __syncthreads();
