@@ -790,6 +790,30 @@ ovs_status ovs_twoview_solve_batch(ovs_twoview* s, int32_t n_problems, const int
                                    uint8_t* out_inlier_flags_H, uint8_t* out_inlier_flags_F);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Essential-matrix RANSAC on bearing vectors.  replaces: solve::essential_solver::find_via_ransac
+ *   (src/openvslam/solve/essential_solver.{h,cc}), which match::robust::match_frame_and_keyframe runs on the host after its brute-force
+ *   match: 50 eight-point hypotheses, each a 9 x 9 null-vector problem and a pass over every match, for a BATCH of (frame 1, frame 2)
+ *   problems in two launches (rules E1 to E8).
+ * ovs_essential_create: a handle for up to max_problems problems of max_total_matches matches together; one internal mutex serialises the
+ *   calls on a handle.
+ * ovs_essential_solve_batch: problem p owns matches [offsets[p], offsets[p + 1]) (offsets[0] = 0, non-decreasing). bearings_1 /
+ *   bearings_2: 3 doubles per match, the unit bearing of the match's keypoint in frame 1 / frame 2. residual_cos_thr: a direction passes
+ *   while |cos| of the angle between a bearing and the normal of its partner's epipolar plane is at most this (upstream: the float
+ *   0.01745240643f, one degree); max_num_iter and recompute are upstream's. seed: upstream draws from random_device; here hypothesis h of
+ *   problem p is a function of (seed, p, h). Outputs per problem: E_21 (9, row-major), score, valid, best_iter, num_inliers; per match one
+ *   flag byte. An invalid problem returns identity, score 0, best_iter -1, flags 0. Results are bit-exact functions of (inputs, seed, p):
+ *   problem p of a batch, solved alone under the seed `seed + 0x9E3779B97F4A7C15 * (p << 24)`, gives the same result.
+ * OVS_ERR_INVALID: a NULL required pointer, offsets not starting at 0 or decreasing, max_num_iter < 1 or > 2^20, residual_cos_thr not
+ *   finite or outside (0, 1]. OVS_ERR_CAPACITY: more problems or matches than the handle was created for (nothing is truncated, no output
+ *   is written). Both are decided before any launch. A problem with fewer than 8 matches is not an error: it is invalid. */
+typedef struct ovs_essential ovs_essential;
+ovs_status ovs_essential_create(int32_t device, int32_t max_problems, int32_t max_total_matches, ovs_essential** out);
+ovs_status ovs_essential_destroy(ovs_essential* s);
+ovs_status ovs_essential_solve_batch(ovs_essential* s, int32_t n_problems, const int32_t* offsets, const double* bearings_1, const double* bearings_2,
+                                     double residual_cos_thr, int32_t max_num_iter, int32_t recompute, uint64_t seed, double* out_E_21, double* out_scores,
+                                     int32_t* out_valid, int32_t* out_best_iter, int32_t* out_num_inliers, uint8_t* out_inlier_flags);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Pose recovery for the monocular initialiser.  replaces: initialize::perspective::reconstruct_with_H and reconstruct_with_F with
  *   initialize::base::check_pose and find_most_plausible_pose under them (src/openvslam/initialize/{base,perspective}.{h,cc}): the
  *   decomposition of the chosen model into 8 (H) or 4 (F) pose hypotheses, the triangulation and the parallax, depth and reprojection gates

@@ -131,6 +131,9 @@ SYMBOLS = {
     "ovs_twoview_create": (_i32, [_i32, _i32, _i32, C.POINTER(_vp)]),
     "ovs_twoview_destroy": (_i32, [_vp]),
     "ovs_twoview_solve_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, C.c_double, _i32, _i32, C.c_uint64, _i32] + [_vp] * 9),
+    "ovs_essential_create": (_i32, [_i32, _i32, _i32, C.POINTER(_vp)]),
+    "ovs_essential_destroy": (_i32, [_vp]),
+    "ovs_essential_solve_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, C.c_double, _i32, _i32, C.c_uint64] + [_vp] * 6),
     "ovs_reconstruct_create": (_i32, [_i32, _i32, _i32, C.POINTER(_vp)]),
     "ovs_reconstruct_destroy": (_i32, [_vp]),
     "ovs_reconstruct_batch": (_i32, [_vp, _i32] + [_vp] * 9 + [_f, _f, _i32] + [_vp] * 8),

@@ -1,5 +1,5 @@
 // match::robust (expected: src/openvslam/match/robust.h). brute_force_match and match_for_triangulation (incl.
-// check_epipolar_constraint) run on the MI355X; match_frame_and_keyframe = brute_force_match + upstream's host-side essential-matrix RANSAC.
+// check_epipolar_constraint) run on the MI355X; match_frame_and_keyframe = brute_force_match + the essential-matrix RANSAC on the device (solve::essential_solver).
 #pragma once
 #include <utility>
 #include <vector>
@@ -15,7 +15,7 @@ public:
     explicit robust(const float lowe_ratio, const bool check_orientation) : base(lowe_ratio, check_orientation) {}
     ~robust() final = default;
 
-    //! brute-force match + upstream's host-side essential-matrix RANSAC (solve::essential_solver); only the inliers are written to
+    //! brute-force match + the essential-matrix RANSAC (solve::essential_solver, on the device); only the inliers are written to
     //! matched_lms_in_frm (indexed by frame keypoint)
     unsigned int match_frame_and_keyframe(data::frame& frm, data::keyframe* keyfrm, std::vector<data::landmark*>& matched_lms_in_frm);
 

@@ -1,155 +1,107 @@
-// Stand-in for solve::essential_solver (expected: src/openvslam/solve/essential_solver.{h,cc}) -- HOST code that is NOT part of the
-// MI355X hot path: robust::match_frame_and_keyframe calls it after the device brute-force match, exactly as upstream does, and in an
-// OpenVSLAM checkout upstream's own solver is used unchanged. This header only exists so the shim tree compiles and can be tested
-// without Eigen: same interface (ctor from two bearing vectors + matches, find_via_ransac, solution_is_valid, get_inlier_matches,
-// get_best_E_21), eight-point estimate by a cyclic-Jacobi eigen-decomposition, upstream's inlier rule (angle between a bearing and
-// the epipolar plane of its partner below 1 degree, both directions), a deterministic sampler instead of upstream's random_device.
+// solve::essential_solver (expected: src/openvslam/solve/essential_solver.{h,cc}): the bearing-vector eight-point RANSAC
+// match::robust::match_frame_and_keyframe runs after its brute-force match. Upstream's constructor (two bearing vectors and the matches),
+// find_via_ransac and getters; the RANSAC itself -- sampling, the eight-point null vector with the rank-two step, the epipolar-plane test
+// of every match under every hypothesis, the winner, the refit over its inliers -- runs on the device (ovs_essential_solve_batch,
+// csrc/essential_solve.hip). Upstream draws its samples from random_device; here they are a function of (seed, position
+// in the batch, hypothesis), so a run is reproducible; set_seed changes it. find_via_ransac_batch solves several solvers in ONE call.
+// Failure policy (util/device_policy.h): a device failure means one retry on a rebuilt handle, then solution_is_valid() == false -- the
+// caller sees zero inlier matches, a state upstream handles. A match that points past its bearing vector throws (std::out_of_range).
 #pragma once
-#include <array>
-#include <cmath>
+#include <ovslam_hip.h>
+
+#include <algorithm>
 #include <cstdint>
 #include <utility>
 #include <vector>
 
 #include "../data/frame_stub.h"
+#include "ransac_context.h"
 
 namespace openvslam {
 namespace solve {
 
-class essential_solver {
+class essential_solver : protected ransac_result {
 public:
+    //! upstream keeps references to the bearings and the matches; here the matched bearings are gathered once
     essential_solver(const std::vector<Vec3_t>& bearings_1, const std::vector<Vec3_t>& bearings_2, const std::vector<std::pair<int, int>>& matches_12)
-        : bearings_1_(bearings_1), bearings_2_(bearings_2), matches_12_(matches_12) {}
-
-    void find_via_ransac(const unsigned int max_num_iter, const bool recompute = true) {
-        const unsigned int num_matches = (unsigned int)matches_12_.size();
-        solution_is_valid_ = false;
-        is_inlier_match_.assign(num_matches, false);
-        if (num_matches < min_set_size_) return;
-        best_score_ = 0.0;
-        uint64_t rng = 0x9E3779B97F4A7C15ull;
-        for (unsigned int iter = 0; iter < max_num_iter; ++iter) {
-            std::vector<unsigned int> pick;
-            while (pick.size() < min_set_size_) {   // sample without replacement (splitmix-style generator: reproducible)
-                rng += 0x9E3779B97F4A7C15ull;
-                uint64_t z = rng;
-                z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-                z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-                const unsigned int k = (unsigned int)((z ^ (z >> 31)) % num_matches);
-                bool dup = false;
-                for (auto p : pick) dup |= p == k;
-                if (!dup) pick.push_back(k);
-            }
-            const Mat33_t E_21 = compute_E_21(pick);
-            std::vector<bool> inl;
-            const double score = check_inliers(E_21, inl);
-            if (best_score_ < score) {
-                best_score_ = score;
-                best_E_21_ = E_21;
-                is_inlier_match_ = inl;
+        : num_matches_((unsigned int)matches_12.size()) {
+        b1_.reserve(3 * matches_12.size());
+        b2_.reserve(3 * matches_12.size());
+        for (const auto& m : matches_12) {
+            const Vec3_t& a = bearings_1.at((size_t)m.first);
+            const Vec3_t& b = bearings_2.at((size_t)m.second);
+            for (int k = 0; k < 3; ++k) {
+                b1_.push_back(a(k));
+                b2_.push_back(b(k));
             }
         }
-        unsigned int num_inliers = 0;
-        for (const bool b : is_inlier_match_) num_inliers += b;
-        solution_is_valid_ = best_score_ > 0.0 && num_inliers >= min_set_size_;
-        if (!solution_is_valid_ || !recompute) return;
-        std::vector<unsigned int> all;
-        for (unsigned int i = 0; i < num_matches; ++i)
-            if (is_inlier_match_[i]) all.push_back(i);
-        best_E_21_ = compute_E_21(all);
-        best_score_ = check_inliers(best_E_21_, is_inlier_match_);
+        is_inlier_match_.assign(num_matches_, false);
+    }
+
+    void set_seed(const uint64_t seed) { seed_ = seed; }
+    //! upstream's constant (the float 0.01745240643f: one degree) unless set
+    void set_residual_cos_thr(const double thr) { residual_cos_thr_ = thr; }
+    //! the HIP device the solvers run on (process-wide; 0 unless an integration places the tracker elsewhere)
+    static void set_device(const int device) { ctx().set_device(device); }
+
+    void find_via_ransac(const unsigned int max_num_iter, const bool recompute = true) { find_via_ransac_batch({this}, max_num_iter, recompute); }
+
+    //! every solver's RANSAC in ONE device call; solver i takes its samples as problem i under the FIRST solver's seed and threshold
+    static void find_via_ransac_batch(const std::vector<essential_solver*>& solvers, const unsigned int max_num_iter, const bool recompute = true) {
+        if (solvers.empty()) return;
+        std::vector<int32_t> offsets(1, 0);
+        std::vector<double> b1, b2;
+        for (essential_solver* s : solvers) {
+            s->reset();
+            b1.insert(b1.end(), s->b1_.begin(), s->b1_.end());
+            b2.insert(b2.end(), s->b2_.begin(), s->b2_.end());
+            offsets.push_back(offsets.back() + (int32_t)s->num_matches_);
+        }
+        const int32_t P = (int32_t)solvers.size(), T = offsets.back();
+        ransac_batch_out out(P, T);
+        std::vector<double> E(9 * (size_t)P), scores((size_t)P);
+        const essential_solver& first = *solvers.front();
+        if (!ctx().run("ovs_essential_solve_batch", P, T, [&](ovs_essential* handle) {
+                return ovs_essential_solve_batch(handle, P, offsets.data(), b1.data(), b2.data(), first.residual_cos_thr_,
+                                                 (int32_t)std::min<unsigned int>(max_num_iter, 1u << 30), recompute ? 1 : 0, first.seed_, E.data(),
+                                                 scores.data(), out.valid.data(), out.best_iter.data(), out.num_inliers.data(), out.flags.data());
+            }))
+            return;   // as reset() left them: solution_is_valid() == false
+        for (int32_t p = 0; p < P; ++p) {
+            essential_solver& s = *solvers[(size_t)p];
+            s.take(out, p, offsets[(size_t)p]);
+            s.best_score_ = scores[(size_t)p];
+            for (int i = 0; i < 9; ++i) s.best_E_21_.m[i] = E[9 * (size_t)p + (size_t)i];
+        }
     }
 
     bool solution_is_valid() const { return solution_is_valid_; }
     double get_best_score() const { return best_score_; }
     Mat33_t get_best_E_21() const { return best_E_21_; }
+    //! per match, in the constructor's order
     std::vector<bool> get_inlier_matches() const { return is_inlier_match_; }
+    unsigned int get_num_inliers() const { return num_inliers_; }
+    int get_best_iter() const { return best_iter_; }   // the winning hypothesis, -1 without a valid solution
 
 private:
-    // null vector of the stacked epipolar constraints b2^T E b1 = 0 (smallest eigenvector of A^T A, cyclic Jacobi)
-    Mat33_t compute_E_21(const std::vector<unsigned int>& idx) const {
-        double M[81] = {0};
-        for (const unsigned int k : idx) {
-            const Vec3_t& b1 = bearings_1_.at((size_t)matches_12_[k].first);
-            const Vec3_t& b2 = bearings_2_.at((size_t)matches_12_[k].second);
-            double a[9];
-            for (int r = 0; r < 3; ++r)
-                for (int c = 0; c < 3; ++c) a[3 * r + c] = b2(r) * b1(c);
-            for (int i = 0; i < 9; ++i)
-                for (int j = 0; j < 9; ++j) M[9 * i + j] += a[i] * a[j];
-        }
-        double V[81] = {0};
-        for (int i = 0; i < 9; ++i) V[10 * i] = 1.0;
-        for (int sweep = 0; sweep < 60; ++sweep) {
-            double off = 0;
-            for (int p = 0; p < 9; ++p)
-                for (int q = p + 1; q < 9; ++q) off += M[9 * p + q] * M[9 * p + q];
-            if (off < 1e-30) break;
-            for (int p = 0; p < 9; ++p)
-                for (int q = p + 1; q < 9; ++q) {
-                    if (std::fabs(M[9 * p + q]) < 1e-300) continue;
-                    const double theta = (M[9 * q + q] - M[9 * p + p]) / (2.0 * M[9 * p + q]);
-                    const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-                    const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
-                    for (int k = 0; k < 9; ++k) {
-                        const double mkp = M[9 * k + p], mkq = M[9 * k + q];
-                        M[9 * k + p] = c * mkp - s * mkq;
-                        M[9 * k + q] = s * mkp + c * mkq;
-                    }
-                    for (int k = 0; k < 9; ++k) {
-                        const double mpk = M[9 * p + k], mqk = M[9 * q + k];
-                        M[9 * p + k] = c * mpk - s * mqk;
-                        M[9 * q + k] = s * mpk + c * mqk;
-                    }
-                    for (int k = 0; k < 9; ++k) {
-                        const double vkp = V[9 * k + p], vkq = V[9 * k + q];
-                        V[9 * k + p] = c * vkp - s * vkq;
-                        V[9 * k + q] = s * vkp + c * vkq;
-                    }
-                }
-        }
-        int best = 0;
-        for (int i = 1; i < 9; ++i)
-            if (M[10 * i] < M[10 * best]) best = i;
-        Mat33_t E;
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c) E(r, c) = V[9 * (3 * r + c) + best];
-        return E;
+    void reset() {
+        ransac_result::reset(num_matches_);
+        best_score_ = 0.0;
+        best_E_21_ = Mat33_t();
     }
 
-    double check_inliers(const Mat33_t& E_21, std::vector<bool>& is_inlier) const {
-        const unsigned int num_matches = (unsigned int)matches_12_.size();
-        is_inlier.assign(num_matches, false);
-        const double residual_cos_thr = std::cos(M_PI / 2.0 - 0.01745240643728351);   // 1 degree
-        double score = 0.0;
-        for (unsigned int i = 0; i < num_matches; ++i) {
-            const Vec3_t& b1 = bearings_1_.at((size_t)matches_12_[i].first);
-            const Vec3_t& b2 = bearings_2_.at((size_t)matches_12_[i].second);
-            double plane_2[3], plane_1[3];   // E_21 b1 and E_21^T b2
-            for (int r = 0; r < 3; ++r) {
-                plane_2[r] = (E_21(r, 0) * b1(0) + E_21(r, 1) * b1(1)) + E_21(r, 2) * b1(2);
-                plane_1[r] = (E_21(0, r) * b2(0) + E_21(1, r) * b2(1)) + E_21(2, r) * b2(2);
-            }
-            const double n2 = std::sqrt((plane_2[0] * plane_2[0] + plane_2[1] * plane_2[1]) + plane_2[2] * plane_2[2]);
-            const double n1 = std::sqrt((plane_1[0] * plane_1[0] + plane_1[1] * plane_1[1]) + plane_1[2] * plane_1[2]);
-            if (!(n1 > 0) || !(n2 > 0)) continue;
-            const double r2 = std::fabs(((plane_2[0] * b2(0) + plane_2[1] * b2(1)) + plane_2[2] * b2(2)) / n2);
-            const double r1 = std::fabs(((plane_1[0] * b1(0) + plane_1[1] * b1(1)) + plane_1[2] * b1(2)) / n1);
-            if (residual_cos_thr < r2 || residual_cos_thr < r1) continue;
-            is_inlier[i] = true;
-            score += (residual_cos_thr - r2) * (residual_cos_thr - r2) + (residual_cos_thr - r1) * (residual_cos_thr - r1);
-        }
-        return score;
+    using context = ransac_context<ovs_essential, ovs_essential_create, ovs_essential_destroy>;
+    static context& ctx() {
+        static context c;
+        return c;
     }
 
-    const std::vector<Vec3_t>& bearings_1_;
-    const std::vector<Vec3_t>& bearings_2_;
-    const std::vector<std::pair<int, int>>& matches_12_;
-    static constexpr unsigned int min_set_size_ = 8;
-    bool solution_is_valid_ = false;
+    const unsigned int num_matches_;
+    uint64_t seed_ = 0x45737365ull;
+    double residual_cos_thr_ = (double)0.01745240643f;
     double best_score_ = 0.0;
     Mat33_t best_E_21_;
-    std::vector<bool> is_inlier_match_;
+    std::vector<double> b1_, b2_;   // 3 per match
 };
 
 }   // namespace solve

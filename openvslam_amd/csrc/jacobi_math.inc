@@ -1,6 +1,6 @@
 // jacobi_math.inc -- the cyclic Jacobi rotation on a symmetric matrix held in registers, for the device and for a plain host compiler alike:
 // solve_internal.inc (Horn's quaternion form under Sim3, EPnP and the transform optimiser's callers) and triangulate_math.inc (the null vector
-// of the two-view system) share it. The operations are those of essential_solver.h::compute_E_21, every one rounded on its own (the units
+// of the two-view system) share it. The operations are those of jacobi_angle and jacobi_rotate below, every one rounded on its own (the units
 // are built with -ffp-contract=off); sqrt and fabs are correctly rounded on both sides. (An .inc, not an .h: see solve_internal.inc.)
 #pragma once
 #include <cmath>

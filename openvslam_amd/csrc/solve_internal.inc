@@ -1,4 +1,4 @@
-// solve_internal.inc -- what the RANSAC solvers of solve/ share (sim3_solve.hip, pnp_solve.hip, two_view_solve.hip). On the device: the
+// solve_internal.inc -- what the RANSAC solvers of solve/ share (sim3_solve.hip, pnp_solve.hip, two_view_solve.hip, essential_solve.hip). On the device: the
 // counter-based sampler, the hypothesis key, the result record and its invalid form, the cyclic Jacobi rotation (jacobi_math.inc), its
 // sweeps over a matrix in LDS and Horn's quaternion form of the absolute
 // orientation. DESIGN.md 3.9 rule 2 fixes every operation; the units are built with -ffp-contract=off. On the host: ransac_handle, the
@@ -17,6 +17,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "essential_math.inc"
 #include "jacobi_math.inc"
 #include "ovs_common.h"
 #include "owned_internal.inc"
@@ -136,6 +137,49 @@ __device__ __forceinline__ void jacobi_lds(double* A, double* V, int lane) {
             }
 }
 
+// the same iteration in the parallel ordering of DESIGN.md 3.16 rule E3 (essential_math.inc's round_pair): a sweep is N rounds of (N - 1) / 2
+// disjoint pairs, so a round's rotations, its column updates and its row updates are each independent lane work: N dependent steps a sweep
+// in place of N (N - 1) / 2. Sixteen lanes serve a pair, all computing its rotation from the matrix as the round finds it: lane i < N of the
+// sixteen rotates row i of the pair's columns, then (after a barrier) column i of its rows; lanes N .. 15 rotate the vectors' rows
+// 0 .. 15 - N beside the columns and the rest beside the rows. A pair whose entry is 0.0 does not rotate. Precondition: the 64 lanes are ONE
+// wavefront. A round reads its pairs' three entries and then writes their columns with no barrier in between, which is right only because a
+// wavefront's LDS operations execute in program order (jacobi_lds above rests on the same); a workgroup of several wavefronts sharing A
+// would need a barrier after the reads.
+template <int N, int SWEEPS>
+__device__ __forceinline__ void jacobi_lds_rounds(double* A, double* V, int lane) {
+    static_assert(N == ess::kRounds && (N - 1) / 2 == ess::kRoundPairs && 2 * (16 - N) >= N, "the lane layout is that of the 9 x 9 problem");
+    const int k = (lane >> 4) + 1, i = lane & 15;
+#pragma unroll 1
+    for (int sweep = 0; sweep < SWEEPS; ++sweep)
+#pragma unroll 1
+        for (int r = 0; r < N; ++r) {
+            int p, q;
+            ess::round_pair(r, k, p, q);
+            const double apq = A[p * N + q];
+            const bool rot = apq != 0.0;   // the same in the sixteen lanes of a pair
+            double c = 1.0, s = 0.0;
+            if (rot) jacobi_angle(A[p * N + p], A[q * N + q], apq, c, s);
+            if (rot) {
+                double* M = i < N ? A + i * N : V + (i - N) * N;
+                const double mp = M[p], mq = M[q];
+                M[p] = c * mp - s * mq;
+                M[q] = s * mp + c * mq;
+            }
+            __syncthreads();
+            if (rot && i < N) {
+                const double apk = A[p * N + i], aqk = A[q * N + i];
+                A[p * N + i] = c * apk - s * aqk;
+                A[q * N + i] = s * apk + c * aqk;
+            } else if (rot && i < 3 * N - 16) {   // the vectors' rows 16 - N .. N - 1
+                double* M = V + (i + 16 - 2 * N) * N;
+                const double mp = M[p], mq = M[q];
+                M[p] = c * mp - s * mq;
+                M[q] = s * mp + c * mq;
+            }
+            __syncthreads();
+        }
+}
+
 __device__ __forceinline__ double dot3(double a0, double a1, double a2, double b0, double b1, double b2) { return (a0 * b0 + a1 * b1) + a2 * b2; }
 
 // Horn's closed form with the scale left out: M[r][c] = sum over the centred pairs of b[r] * a[c]; R (row-major) is the rotation with
@@ -192,7 +236,7 @@ __device__ __forceinline__ void horn_rotation(const double (&M)[3][3], double (&
     R[8] = 1.0 - 2.0 * (x * x + y * y);
 }
 
-// ---- the host side: one handle and one batch call under ovs_sim3_*, ovs_pnp_*, ovs_sim3opt_* and ovs_twoview_*
+// ---- the host side: one handle and one batch call under ovs_sim3_*, ovs_pnp_*, ovs_sim3opt_*, ovs_twoview_* and ovs_essential_*
 struct ransac_handle {
     int device = 0;
     int max_problems = 0, max_total_matches = 0;
@@ -218,7 +262,7 @@ struct ransac_handle {
     }
 };
 
-// H: ovs_sim3, ovs_pnp, ovs_sim3opt or ovs_twoview. block_bytes: the solver's Layout at full capacity; initial_records: the models that fit without
+// H: ovs_sim3, ovs_pnp, ovs_sim3opt, ovs_twoview or ovs_essential. block_bytes: the solver's Layout at full capacity; initial_records: the models that fit without
 // growing; result_bytes: the solver's record per problem in the mapped result block where it is not ResultRec
 template <class H>
 ovs_status ransac_create(int32_t device, int32_t max_problems, int32_t max_total_matches, size_t block_bytes, size_t initial_records,

@@ -25,7 +25,11 @@ the rules; bit-exact in the same sense.
 
 initialize::perspective's reconstruct_with_H / reconstruct_with_F (expected: src/openvslam/initialize/{base,perspective}.{h,cc}): the pose
 hypotheses of the chosen model, check_pose over every inlier match and find_most_plausible_pose. All problems go to the device in ONE call
-(ovs_reconstruct_batch, csrc/two_view_reconstruct.hip): two launches. DESIGN.md 3.15 has the rules; bit-exact in the same sense."""
+(ovs_reconstruct_batch, csrc/two_view_reconstruct.hip): two launches. DESIGN.md 3.15 has the rules; bit-exact in the same sense.
+
+solve::essential_solver (expected: src/openvslam/solve/essential_solver.{h,cc}): the bearing-vector eight-point RANSAC
+robust::match_frame_and_keyframe runs after its brute-force match. All problems go to the device in ONE call (ovs_essential_solve_batch,
+csrc/essential_solve.hip): two launches. DESIGN.md 3.16 has the rules; bit-exact in the same sense."""
 import ctypes as C
 import math
 
@@ -525,6 +529,73 @@ class fundamental_solver(_two_view_solver):
 
     def get_best_F_21(self):
         return self._get("F_21")
+
+
+# ---- solve::essential_solver
+ESSENTIAL_DEFAULT_SEED = 0x45737365   # upstream draws from random_device; here a run is reproducible
+# upstream's residual_cos_thr as recalled: the float 0.01745240643f (one degree), widened to double
+ESSENTIAL_RESIDUAL_COS_THR = float(np.float32(0.01745240643))
+
+
+def essential_problem_seed(seed, p):
+    """The seed under which problem p of a batch, solved ALONE (as problem 0), draws the samples it draws in the batch (3.16 rule E1)."""
+    return (seed + _G * (p << 24)) & _MASK
+
+
+def essential_problem(bearings_1, bearings_2, matches_12):
+    """What the solver's constructor is given: the bearings of the matched pairs (idx_1, idx_2). bearings: (n, 3); matches_12: (m, 2)."""
+    m = np.asarray(matches_12, np.int64).reshape(-1, 2)
+    return dict(b1=np.asarray(bearings_1, np.float64).reshape(-1, 3)[m[:, 0]], b2=np.asarray(bearings_2, np.float64).reshape(-1, 3)[m[:, 1]])
+
+
+class _essential_handle(_ransac_handle):
+    """ovs_essential with its capacity."""
+    _abi = "ovs_essential"
+
+
+def solve_essential_batch(problems, residual_cos_thr=ESSENTIAL_RESIDUAL_COS_THR, max_num_iter=50, recompute=False, seed=ESSENTIAL_DEFAULT_SEED,
+                          handle=None, device=0):
+    """find_via_ransac of solve::essential_solver for every problem (dicts with b1, b2: (n, 3)) in one call: a list of dicts valid,
+    best_iter, num_inliers, score, E_21 (3 x 3) and inlier_flags (n, bool). The defaults are robust::match_frame_and_keyframe's: 50
+    iterations, no recompute. `handle`: an _essential_handle to reuse."""
+    P = len(problems)
+    if P == 0:
+        return []
+    offsets = np.zeros(P + 1, np.int32)
+    offsets[1:] = np.cumsum([len(np.asarray(q["b1"]).reshape(-1, 3)) for q in problems])
+    T = int(offsets[-1])
+    cat = lambda key: np.ascontiguousarray(np.concatenate([np.asarray(q[key], np.float64).reshape(-1, 3) for q in problems]) if T else np.zeros((0, 3)))
+    b1, b2 = cat("b1"), cat("b2")
+    if len(b1) != T or len(b2) != T:
+        raise ValueError("b1 and b2 of a problem must have one entry per match")
+    if handle is None:
+        handle = _essential_handle(P, max(T, 1), device)
+    E, scores = np.zeros((P, 3, 3)), np.zeros(P)
+    valid, best_iter, num, flags = np.zeros(P, np.int32), np.zeros(P, np.int32), np.zeros(P, np.int32), np.zeros(max(T, 1), np.uint8)
+    _lib.check(handle._L.ovs_essential_solve_batch(handle._h, P, _p(offsets), _p(b1), _p(b2), float(residual_cos_thr), int(max_num_iter),
+                                                   1 if recompute else 0, int(seed) & _MASK, _p(E), _p(scores), _p(valid), _p(best_iter), _p(num),
+                                                   _p(flags)), "ovs_essential_solve_batch")
+    return [{"valid": bool(valid[i]), "best_iter": int(best_iter[i]), "num_inliers": int(num[i]), "score": float(scores[i]), "E_21": E[i].copy(),
+             "inlier_flags": flags[offsets[i]:offsets[i + 1]].astype(bool)} for i in range(P)]
+
+
+class essential_solver(_ransac_solver):
+    """solve::essential_solver over one problem: upstream's constructor (bearings_1, bearings_2, matches_12), find_via_ransac and getters."""
+
+    def __init__(self, bearings_1, bearings_2, matches_12, device=0):
+        self._problem, self._device = essential_problem(bearings_1, bearings_2, matches_12), device
+
+    def find_via_ransac(self, max_num_iter, recompute=True, seed=ESSENTIAL_DEFAULT_SEED, residual_cos_thr=ESSENTIAL_RESIDUAL_COS_THR):
+        self._result = solve_essential_batch([self._problem], residual_cos_thr, max_num_iter, recompute, seed, device=self._device)[0]
+
+    def get_best_score(self):
+        return self._get("score")
+
+    def get_best_E_21(self):
+        return self._get("E_21")
+
+    def get_inlier_matches(self):
+        return self._get("inlier_flags")
 
 
 # ---- initialize::perspective's reconstruct_with_H / reconstruct_with_F, check_pose and find_most_plausible_pose
