@@ -6,11 +6,11 @@
 // compiler builds too (tests/essential_host.cc).
 //
 // One wavefront fits one model (fit_accumulate, the sweeps, fit_finish), the eight-match hypothesis and the refit over the winner's
-// inliers alike, in the form of two_view_solve.hip: the sums over the matches (rule 6 of 3.10) give lane j the matches j, j + 64, ... in
-// rank order and end in a butterfly of x + shfl_xor(x, d), d = 32 .. 1. The 9 x 9 eigenproblem lives in LDS (162 doubles) and is swept in
-// the parallel ordering of rule E3 (jacobi_lds_rounds of solve_internal.inc): 9 rounds of four disjoint pairs per sweep, sixteen lanes per
-// pair. The rank-two step every lane computes for itself in registers on compile-time indices: nothing is indexed dynamically, nothing
-// goes to scratch.
+// inliers alike, on the scaffold two_view_solve.hip shares (eight_point_internal.inc: the sums in rank order, the 9 x 9 eigenproblem in
+// LDS, the null vector, the score walk, the score slots and their winner, the invalid form, the handle and the batch call). This unit's
+// own: the row and the score term (essential_math.inc), the sweeps in the parallel ordering of rule E3 (jacobi_lds_rounds of
+// solve_internal.inc): 9 rounds of four disjoint pairs per sweep, sixteen lanes per pair; and the rank-two step, which every lane computes
+// for itself in registers on compile-time indices: nothing is indexed dynamically, nothing goes to scratch.
 //
 // k_essential_hypotheses: grid (hypotheses, problems), one wavefront per workgroup. After the fit the lanes walk the matches for the score;
 // lane 0 saves E_21 and the score into the slot of (problem, h). No atomics at all, no waiting between workgroups.
@@ -19,13 +19,12 @@
 #include <cmath>
 #include <cstring>
 
+#include "eight_point_internal.inc"
 #include "essential_math.inc"
 #include "ovs_common.h"
-#include "solve_internal.inc"
 
 namespace {
 
-constexpr int kSlotDoubles = 10;   // per (problem, h): E_21 (9, row-major) and the score
 constexpr int kSampleShare = 16;   // the counter share of a hypothesis (solve.essential_problem_seed: p << 24)
 
 // The staged block of one call, sections in this order: b1 f64 [3 T], b2 f64 [3 T], offsets i32 [P + 1].
@@ -48,17 +47,6 @@ struct EssentialRec {
 };
 static_assert(sizeof(EssentialRec) == 96, "EssentialRec is read by the host");
 
-// the 9 x 9 eigenproblem in LDS: the matrix and its vectors, row-major
-struct Eig {
-    double A[81], V[81];
-};
-
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int d = 32; d; d >>= 1) x = x + __shfl_xor(x, d);
-    return x;
-}
-
 // rule E2: A^T A over the m matches idx[0 .. m) of a problem, in that order, into e.A, and the identity into e.V. idx may point into LDS
 // or memory.
 __device__ __forceinline__ void fit_accumulate(const double* __restrict__ b1, const double* __restrict__ b2, const int32_t* idx, int m, Eig& e, int lane) {
@@ -75,61 +63,26 @@ __device__ __forceinline__ void fit_accumulate(const double* __restrict__ b1, co
 #pragma unroll
             for (int c = r; c < 9; ++c, ++k) acc[k] = acc[k] + a[r] * a[c];
     }
-    __syncthreads();   // whoever read e before has left it
-    int k = 0;
-#pragma unroll
-    for (int r = 0; r < 9; ++r)
-#pragma unroll
-        for (int c = r; c < 9; ++c, ++k) {
-            const double s = wave_sum(acc[k]);
-            if (lane == 0) e.A[r * 9 + c] = e.A[c * 9 + r] = s;
-        }
-    for (int i = lane; i < 81; i += 64) e.V[i] = (i / 9 == i % 9) ? 1.0 : 0.0;
-    __syncthreads();
+    store_sums(e, lane, acc);
 }
 
 // rules E3 (the choice of the vector) and E4 on the swept e: every lane returns the same E_21
 __device__ __forceinline__ void fit_finish(const Eig& e, double (&E)[9]) {
     double Gm[9];
-    int best = 0;   // the smallest diagonal entry, the lowest index on a tie
-    double smallest = e.A[0];
-#pragma unroll
-    for (int i = 1; i < 9; ++i) {
-        const double d = e.A[i * 10];
-        const bool take = d < smallest;
-        smallest = take ? d : smallest;
-        best = take ? i : best;
-    }
+    const int best = null_column(e);
 #pragma unroll
     for (int j = 0; j < 9; ++j) Gm[j] = e.V[j * 9 + best];
     ess::rank_two(Gm, E);
 }
 
-// rule E5 over the n matches of a problem by one wavefront: count and score in every lane; flags (one byte per match) and list (the
-// inliers by rank, in match order) are written where they are not null.
+// rule E5 over the n matches of a problem by one wavefront, in the form of score_matches
 __device__ __forceinline__ void score_wave(const double (&E)[9], const double* __restrict__ b1, const double* __restrict__ b2, int n, double thr, int lane,
                                            uint8_t* __restrict__ flags, int32_t* __restrict__ list, int& count, double& score) {
-    double part = 0.0;
-    count = 0;
-    for (int base = 0; base < n; base += 64) {
-        const int i = base + lane;
-        const bool in = i < n;
-        const size_t j = in ? (size_t)i : 0;
-        bool inl;
+    score_matches(n, lane, flags, list, count, score, [&](size_t j, bool& inl) __attribute__((always_inline)) {
         double r2, r1;
-        const double term = ess::match_term(E, b1 + 3 * j, b2 + 3 * j, thr, inl, r2, r1);
-        if (in) part = part + term;
-        inl = in && inl;
-        const unsigned long long mask = __ballot(inl);
-        if (flags && in) flags[i] = inl ? 1 : 0;
-        if (list && inl) list[count + __popcll(mask & ((1ull << lane) - 1ull))] = i;
-        count += __popcll(mask);
-    }
-    score = wave_sum(part);
+        return ess::match_term(E, b1 + 3 * j, b2 + 3 * j, thr, inl, r2, r1);
+    });
 }
-
-// where the slot of (problem, h) starts in the models' buffer
-__device__ __forceinline__ size_t slot_at(int p, int max_iter, int h) { return ((size_t)p * max_iter + h) * kSlotDoubles; }
 
 __global__ __launch_bounds__(64) void k_essential_hypotheses(const uint8_t* __restrict__ block, int P, int T, int max_iter, uint64_t seed, double thr,
                                                              double* __restrict__ wave_models) {
@@ -176,23 +129,7 @@ __global__ __launch_bounds__(64) void k_essential_finish(const uint8_t* __restri
     bool valid = false;
     double E[9], score = 0.0;
     int count = 0, best_iter = -1;
-    if (n >= 8) {
-        // rule E6: the greatest score above 0.0, the lowest h on a tie; a NaN never wins
-        const double* slots = wave_models + slot_at(p, max_iter, 0);
-        double best = 0.0;
-        for (int h = lane; h < max_iter; h += 64) {
-            const double s = slots[(size_t)h * kSlotDoubles + 9];
-            if (best < s) best = s, best_iter = h;
-        }
-#pragma unroll
-        for (int d = 32; d; d >>= 1) {
-            const double ob = __shfl_xor(best, d);
-            const int oh = __shfl_xor(best_iter, d);
-            const bool take = best < ob || (ob == best && oh >= 0 && oh < best_iter);
-            best = take ? ob : best;
-            best_iter = take ? oh : best_iter;
-        }
-    }
+    if (n >= 8) best_slot(wave_models + slot_at(p, max_iter, 0), max_iter, lane, best_iter);   // rule E6
     if (best_iter >= 0) {
         const double* md = wave_models + slot_at(p, max_iter, best_iter);   // the doubles the hypothesis kernel scored with
 #pragma unroll
@@ -206,22 +143,15 @@ __global__ __launch_bounds__(64) void k_essential_finish(const uint8_t* __restri
         jacobi_lds_rounds<9, ess::kSweeps>(e.A, e.V, lane);
         double E2[9];
         fit_finish(e, E2);
-        bool finite = true;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) finite = finite && __builtin_isfinite(E2[k]);
-        if (finite) {
+        if (all_finite(E2)) {
 #pragma unroll
             for (int k = 0; k < 9; ++k) E[k] = E2[k];
             score_wave(E, b1, b2, n, thr, lane, flags, nullptr, count, score);
             valid = score > 0.0 && count >= 8;
         }
     }
-    if (!valid) {   // rule E6's invalid form
-        for (int i = lane; i < n; i += 64) flags[i] = 0;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) E[k] = (k % 4 == 0) ? 1.0 : 0.0;
-        score = 0.0;
-        count = 0;
+    if (!valid) {   // rule E6
+        invalid_form(flags, n, lane, E, score, count);
         best_iter = -1;
     }
     if (lane == 0) {
@@ -238,8 +168,7 @@ __global__ __launch_bounds__(64) void k_essential_finish(const uint8_t* __restri
 
 }   // namespace
 
-struct ovs_essential : ransac_handle {
-    int32_t* d_inlier_idx = nullptr;   // [matches of the call] a winner's inliers by rank, per problem at its offset
+struct ovs_essential : eight_point_handle {
     EssentialRec* h_rec() { return reinterpret_cast<EssentialRec*>(h_result); }
     EssentialRec* m_rec() { return reinterpret_cast<EssentialRec*>(m_result); }
 };
@@ -247,15 +176,8 @@ struct ovs_essential : ransac_handle {
 extern "C" {
 
 ovs_status ovs_essential_create(int32_t device, int32_t max_problems, int32_t max_total_matches, ovs_essential** out) {
-    const ovs_status st = ransac_create(device, max_problems, max_total_matches, layout_of(max_problems, max_total_matches).bytes,
-                                        (size_t)max_problems * 32,   // 32 iterations per problem without growing
-                                        kSlotDoubles, out, sizeof(EssentialRec));
-    if (st != OVS_OK) return st;
-    std::unique_ptr<ovs_essential> owner(*out);
-    *out = nullptr;
-    OVS_HIP_TRY(owner->res.dev(&owner->d_inlier_idx, sizeof(int32_t) * (size_t)max_total_matches));
-    *out = owner.release();
-    return OVS_OK;
+    return eight_point_create(device, max_problems, max_total_matches, layout_of(max_problems, max_total_matches).bytes, 1, sizeof(EssentialRec), out,
+                              [](ovs_essential*) { return OVS_OK; });
 }
 
 ovs_status ovs_essential_destroy(ovs_essential* s) { return ransac_destroy(s); }
@@ -272,15 +194,13 @@ ovs_status ovs_essential_solve_batch(ovs_essential* s, int32_t n_problems, const
         }
         return OVS_OK;
     };
-    const auto reserve = [&] { return s->reserve_models((size_t)n_problems * (size_t)max_num_iter) != OVS_OK ? OVS_ERR_HIP : OVS_OK; };
-    const auto launch = [&](hipStream_t st, int32_t T) {
+    const auto hypotheses = [&](hipStream_t st, int32_t T) {
         hipLaunchKernelGGL(k_essential_hypotheses, dim3(max_num_iter, n_problems), dim3(64), 0, st, s->d_block, n_problems, T, max_num_iter, seed,
                            residual_cos_thr, s->d_wave_models);
-        OVS_HIP_TRY(hipGetLastError());
+    };
+    const auto finish = [&](hipStream_t st, int32_t T) {
         hipLaunchKernelGGL(k_essential_finish, dim3(n_problems), dim3(64), 0, st, s->d_block, n_problems, T, max_num_iter, recompute ? 1 : 0,
                            residual_cos_thr, s->d_wave_models, s->d_inlier_idx, s->m_rec(), s->m_flags);
-        OVS_HIP_TRY(hipGetLastError());
-        return OVS_OK;
     };
     const auto collect = [&](int32_t T) {
         for (int32_t p = 0; p < n_problems; ++p) {
@@ -293,8 +213,8 @@ ovs_status ovs_essential_solve_batch(ovs_essential* s, int32_t n_problems, const
         }
         if (T > 0) std::memcpy(out_inlier_flags, s->h_flags, (size_t)T);
     };
-    return run_staged(s, n_problems, offsets, {out_E_21, out_scores, out_valid, out_best_iter, out_num_inliers}, {bearings_1, bearings_2}, out_inlier_flags,
-                      layout_of, stage, reserve, launch, collect);
+    return run_slots(s, n_problems, offsets, {out_E_21, out_scores, out_valid, out_best_iter, out_num_inliers}, {bearings_1, bearings_2}, out_inlier_flags,
+                     layout_of, 1, max_num_iter, stage, hypotheses, finish, collect);
 }
 
 }   // extern "C"

@@ -8,7 +8,7 @@
 // One wavefront solves one EPnP (epnp_wave), the four-point hypothesis and the n-point refit alike. What does not depend on the match
 // (3 x 3 eigenproblem, control points, L, rho, the betas, Gauss-Newton, Horn's form) every lane computes for itself in registers, on
 // compile-time indices: the values are wave-uniform and nothing is indexed dynamically, so nothing goes to scratch. The sums over the
-// matches (rule 6) give lane j the matches j, j + 64, ... in rank order and end in a butterfly of x + shfl_xor(x, d), d = 32 .. 1: lane 0
+// matches (rule 6) give lane j the matches j, j + 64, ... in rank order and end in a butterfly of x + shfl_xor(x, d), d = 32 .. 1 (wave_sum of solve_internal.inc): lane 0
 // holds the rule's pairwise tree, and as IEEE addition commutes every lane holds the same bits. The 12 x 12 eigenproblem lives in LDS:
 // the rotation's angle in every lane, its 12 column pairs, 12 row pairs and 12 vector pairs one per lane.
 //
@@ -48,13 +48,6 @@ struct Lds {
     double A[144], V[144], vec[48];
     int32_t idx[4];
 };
-
-// rule 6's tree: lane 0's value is ((p0 + p32) + (p16 + p48)) + ... ; every lane ends with the same bits
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int d = 32; d; d >>= 1) x = x + __shfl_xor(x, d);
-    return x;
-}
 
 // min |rows x - b| over 6 rows of K columns: the normal equations, every entry a left-to-right sum of its six products, Gaussian
 // elimination without pivoting, back substitution. A zero pivot gives Inf / NaN, which flow on.

@@ -1,12 +1,13 @@
-// solve_internal.inc -- what the RANSAC solvers of solve/ share (sim3_solve.hip, pnp_solve.hip, two_view_solve.hip, essential_solve.hip). On the device: the
-// counter-based sampler, the hypothesis key, the result record and its invalid form, the cyclic Jacobi rotation (jacobi_math.inc), its
-// sweeps over a matrix in LDS and Horn's quaternion form of the absolute
-// orientation. DESIGN.md 3.9 rule 2 fixes every operation; the units are built with -ffp-contract=off. On the host: ransac_handle, the
-// batch scaffold under both C ABIs (create, reserve_models, run_batch). A solver supplies its model, its two kernels, the Layout of its
-// staged block, and to run_batch what stages its arrays and what launches its kernels. run_batch is run_staged with the RANSAC's two
-// launches; the Sim3 transform optimiser (sim3_opt.hip), a one-launch solver over the same handle, calls run_staged itself. (An .inc, not
-// an .h: bench.py fingerprints every .h of this directory into the committed counters of the extractor and matcher stages, which include
-// none of this.)
+// solve_internal.inc -- what the RANSAC solvers of solve/ share (sim3_solve.hip, pnp_solve.hip, and through eight_point_internal.inc
+// two_view_solve.hip and essential_solve.hip). On the device: the counter-based sampler, the hypothesis key, the result record and its
+// invalid form, the cyclic Jacobi rotation (jacobi_math.inc), its sweeps over a matrix in LDS, the wavefront's sum (wave_sum) and Horn's
+// quaternion form of the absolute orientation. DESIGN.md 3.9 rule 2 fixes every operation; the units are built with -ffp-contract=off. On
+// the host: ransac_handle, the batch scaffold under the C ABIs (create, reserve_models, run_staged, run_batch). A solver supplies its
+// model, its two kernels, the Layout of its staged block, and to run_batch what stages its arrays and what launches its kernels. run_batch
+// is run_staged with the two launches, the keys and the result record of Sim3 and EPnP; the eight-point solvers' score-slot form of it is
+// run_slots of eight_point_internal.inc; the Sim3 transform optimiser (sim3_opt.hip), a one-launch solver over the same handle, calls
+// run_staged itself. (An .inc, not an .h: bench.py fingerprints every .h of this directory into the committed counters of the extractor and
+// matcher stages, which include none of this.)
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -181,6 +182,14 @@ __device__ __forceinline__ void jacobi_lds_rounds(double* A, double* V, int lane
 }
 
 __device__ __forceinline__ double dot3(double a0, double a1, double a2, double b0, double b1, double b2) { return (a0 * b0 + a1 * b1) + a2 * b2; }
+
+// the tree of 3.10 rule 6 over a wavefront: lane 0's value is ((p0 + p32) + (p16 + p48)) + ... ; as IEEE addition commutes every lane
+// ends with the same bits
+__device__ __forceinline__ double wave_sum(double x) {
+#pragma unroll
+    for (int d = 32; d; d >>= 1) x = x + __shfl_xor(x, d);
+    return x;
+}
 
 // Horn's closed form with the scale left out: M[r][c] = sum over the centred pairs of b[r] * a[c]; R (row-major) is the rotation with
 // a = R b in the least-squares sense. Eight cyclic sweeps over the 4 x 4 matrix, the eigenvector of the largest diagonal entry (lowest

@@ -6,12 +6,13 @@
 // every operation rounded on its own (the unit is built with -ffp-contract=off).
 //
 // One wavefront fits one model (fit_accumulate, the sweeps, fit_finish), the eight-match hypothesis and the refit over the winner's
-// inliers alike. The sums over the matches (rule 6 of 3.10) give lane j the matches j, j + 64, ... in rank order and end in a butterfly
-// of x + shfl_xor(x, d), d = 32 .. 1: lane 0 holds the rule's pairwise tree, and as IEEE addition commutes every lane holds the same
-// bits. The 9 x 9 eigenproblem lives in LDS (162 doubles): the rotation's angle in every lane, its 9 column pairs, 9 row pairs and 9
-// vector pairs one per lane (jacobi_lds of solve_internal.inc, which pnp_solve.hip's 12 x 12 problem shares). What does not depend on
-// the match (the 3 x 3 products, the rank-two step, the inverse) every lane computes for itself in registers on compile-time indices:
-// nothing is indexed dynamically, nothing goes to scratch.
+// inliers alike, on the scaffold essential_solve.hip shares (eight_point_internal.inc: store_sums, null_column, score_matches, the
+// score slots and best_slot, the invalid form, the handle and run_slots). The sums over the matches (rule 6 of 3.10) give lane j the
+// matches j, j + 64, ... in rank order and end in wave_sum's butterfly of x + shfl_xor(x, d), d = 32 .. 1: lane 0 holds the rule's
+// pairwise tree, and as IEEE addition commutes every lane holds the same bits. The 9 x 9 eigenproblem lives in LDS (162 doubles): the
+// rotation's angle in every lane, its 9 column pairs, 9 row pairs and 9 vector pairs one per lane (jacobi_lds of solve_internal.inc,
+// which pnp_solve.hip's 12 x 12 problem shares). What does not depend on the match (the 3 x 3 products, the rank-two step, the inverse)
+// every lane computes for itself in registers on compile-time indices: nothing is indexed dynamically, nothing goes to scratch.
 //
 // k_twoview_hypotheses: grid (hypotheses, 2 models, problems), one wavefront per workgroup. Hypothesis h of a problem draws ONE sample for
 // both models. After the fit the lanes walk the matches for the score; lane 0 saves the matrix and the score into the slot of
@@ -23,13 +24,12 @@
 #include <cmath>
 #include <cstring>
 
+#include "eight_point_internal.inc"
 #include "ovs_common.h"
-#include "solve_internal.inc"
 
 namespace {
 
 constexpr int kSweeps = 8;
-constexpr int kSlotDoubles = 10;   // per (problem, model, h): the matrix (9, row-major) and the score
 constexpr int kSampleShare = 16;   // the counter share of a hypothesis (solve.two_view_problem_seed: p << 24)
 constexpr double kChiH = 5.991, kChiF = 3.841, kScore = 5.991;
 
@@ -52,17 +52,6 @@ struct TwoViewRec {
     int32_t valid[2], best_iter[2], num_inliers[2], selected, pad;
 };
 static_assert(sizeof(TwoViewRec) == 192, "TwoViewRec is read by the host");
-
-// a 9 x 9 eigenproblem in LDS: the matrix and its vectors, row-major
-struct Eig {
-    double A[81], V[81];
-};
-
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int d = 32; d; d >>= 1) x = x + __shfl_xor(x, d);
-    return x;
-}
 
 // a 3 x 3 product, rows times columns by dot3, zeros multiplied like any value
 __device__ __forceinline__ void mul3(const double (&A)[9], const double (&B)[9], double (&C)[9]) {
@@ -109,43 +98,31 @@ __device__ __forceinline__ Norm normalise(const double* __restrict__ x, int n, i
 template <int MODEL>
 __device__ __forceinline__ void fit_accumulate(const double* __restrict__ x1, const double* __restrict__ x2, const int32_t* idx, int m, const Norm& N1,
                                                const Norm& N2, Eig& e, int lane) {
-    {
-        double acc[45];
+    double acc[45];
 #pragma unroll
-        for (int k = 0; k < 45; ++k) acc[k] = 0.0;
-        for (int i = lane; i < m; i += 64) {
-            const size_t j = (size_t)idx[i];
-            const double ax = (x1[2 * j] - N1.mean[0]) * N1.s[0], ay = (x1[2 * j + 1] - N1.mean[1]) * N1.s[1];
-            const double bx = (x2[2 * j] - N2.mean[0]) * N2.s[0], by = (x2[2 * j + 1] - N2.mean[1]) * N2.s[1];
-            if (MODEL == 0) {
-                const double r1[9] = {0.0, 0.0, 0.0, -ax, -ay, -1.0, by * ax, by * ay, by};
-                const double r2[9] = {ax, ay, 1.0, 0.0, 0.0, 0.0, -(bx * ax), -(bx * ay), -bx};
-                int k = 0;
+    for (int k = 0; k < 45; ++k) acc[k] = 0.0;
+    for (int i = lane; i < m; i += 64) {
+        const size_t j = (size_t)idx[i];
+        const double ax = (x1[2 * j] - N1.mean[0]) * N1.s[0], ay = (x1[2 * j + 1] - N1.mean[1]) * N1.s[1];
+        const double bx = (x2[2 * j] - N2.mean[0]) * N2.s[0], by = (x2[2 * j + 1] - N2.mean[1]) * N2.s[1];
+        if (MODEL == 0) {
+            const double r1[9] = {0.0, 0.0, 0.0, -ax, -ay, -1.0, by * ax, by * ay, by};
+            const double r2[9] = {ax, ay, 1.0, 0.0, 0.0, 0.0, -(bx * ax), -(bx * ay), -bx};
+            int k = 0;
 #pragma unroll
-                for (int r = 0; r < 9; ++r)
+            for (int r = 0; r < 9; ++r)
 #pragma unroll
-                    for (int c = r; c < 9; ++c, ++k) acc[k] = acc[k] + (r1[r] * r1[c] + r2[r] * r2[c]);
-            } else {
-                const double r1[9] = {bx * ax, bx * ay, bx, by * ax, by * ay, by, ax, ay, 1.0};
-                int k = 0;
+                for (int c = r; c < 9; ++c, ++k) acc[k] = acc[k] + (r1[r] * r1[c] + r2[r] * r2[c]);
+        } else {
+            const double r1[9] = {bx * ax, bx * ay, bx, by * ax, by * ay, by, ax, ay, 1.0};
+            int k = 0;
 #pragma unroll
-                for (int r = 0; r < 9; ++r)
+            for (int r = 0; r < 9; ++r)
 #pragma unroll
-                    for (int c = r; c < 9; ++c, ++k) acc[k] = acc[k] + r1[r] * r1[c];
-            }
+                for (int c = r; c < 9; ++c, ++k) acc[k] = acc[k] + r1[r] * r1[c];
         }
-        __syncthreads();   // whoever read e before has left it
-        int k = 0;
-#pragma unroll
-        for (int r = 0; r < 9; ++r)
-#pragma unroll
-            for (int c = r; c < 9; ++c, ++k) {
-                const double s = wave_sum(acc[k]);
-                if (lane == 0) e.A[r * 9 + c] = e.A[c * 9 + r] = s;
-            }
-        for (int i = lane; i < 81; i += 64) e.V[i] = (i / 9 == i % 9) ? 1.0 : 0.0;
-        __syncthreads();
     }
+    store_sums(e, lane, acc);
 }
 
 // rules 3 (second half) to 5 on the swept e: the vector of the smallest diagonal entry as G, rank two for F, the denormalised model. Every
@@ -153,19 +130,9 @@ __device__ __forceinline__ void fit_accumulate(const double* __restrict__ x1, co
 template <int MODEL>
 __device__ __forceinline__ void fit_finish(const Eig& e, const Norm& N1, const Norm& N2, double (&M)[9]) {
     double Gm[9];
-    {
-        int best = 0;   // the smallest diagonal entry, the lowest index on a tie
-        double smallest = e.A[0];
+    const int best = null_column(e);
 #pragma unroll
-        for (int i = 1; i < 9; ++i) {
-            const double d = e.A[i * 10];
-            const bool take = d < smallest;
-            smallest = take ? d : smallest;
-            best = take ? i : best;
-        }
-#pragma unroll
-        for (int j = 0; j < 9; ++j) Gm[j] = e.V[j * 9 + best];
-    }
+    for (int j = 0; j < 9; ++j) Gm[j] = e.V[j * 9 + best];
     const double T1[9] = {N1.s[0], 0.0, -(N1.mean[0] * N1.s[0]), 0.0, N1.s[1], -(N1.mean[1] * N1.s[1]), 0.0, 0.0, 1.0};
     double GT[9];
     if (MODEL == 0) {
@@ -251,12 +218,7 @@ __device__ __forceinline__ void score_wave(const double (&M)[9], const double* _
     } else {
         transpose3(M, D1);
     }
-    double part = 0.0;
-    count = 0;
-    for (int base = 0; base < n; base += 64) {
-        const int i = base + lane;
-        const bool in = i < n;
-        const size_t j = in ? (size_t)i : 0;
+    score_matches(n, lane, flags, list, count, score, [&](size_t j, bool& inl) __attribute__((always_inline)) {
         const double ax = x1[2 * j], ay = x1[2 * j + 1], bx = x2[2 * j], by = x2[2 * j + 1];
         double chi1, chi2;
         if (MODEL == 0) {
@@ -267,22 +229,14 @@ __device__ __forceinline__ void score_wave(const double (&M)[9], const double* _
             chi2 = epipolar_chi(D1, bx, by, ax, ay, inv_sigma_sq);
         }
         const double thr = MODEL == 0 ? kChiH : kChiF;
-        const bool pass1 = chi1 <= thr, pass2 = pass1 && chi2 <= thr;
+        const bool pass1 = chi1 <= thr;
+        inl = pass1 && chi2 <= thr;
         double term = 0.0;
         term = pass1 ? term + (kScore - chi1) : term;
-        term = pass2 ? term + (kScore - chi2) : term;
-        if (in) part = part + term;
-        const bool inl = in && pass2;
-        const unsigned long long mask = __ballot(inl);
-        if (flags && in) flags[i] = inl ? 1 : 0;
-        if (list && inl) list[count + __popcll(mask & ((1ull << lane) - 1ull))] = i;
-        count += __popcll(mask);
-    }
-    score = wave_sum(part);
+        term = inl ? term + (kScore - chi2) : term;
+        return term;
+    });
 }
-
-// where the slot of (problem, model, h) starts in the models' buffer
-__device__ __forceinline__ size_t slot_at(int p, int model, int max_iter, int h) { return (((size_t)p * 2 + model) * max_iter + h) * kSlotDoubles; }
 
 template <int MODEL>
 __device__ __forceinline__ void hypothesis(const double* __restrict__ x1, const double* __restrict__ x2, int n, double inv_sigma_sq, const int32_t* idx,
@@ -319,7 +273,7 @@ __global__ __launch_bounds__(64) void k_twoview_hypotheses(const uint8_t* __rest
         for (int k = 0; k < 8; ++k) idx[k] = (int32_t)i[k];
     }
     __syncthreads();
-    double* slot = wave_models + slot_at(p, model, max_iter, h);
+    double* slot = wave_models + slot_at((size_t)p * 2 + model, max_iter, h);
     if (model == 0)
         hypothesis<0>(x1, x2, n, inv_sigma_sq, idx, e, lane, slot);
     else
@@ -343,21 +297,8 @@ __device__ __forceinline__ void winner_of(const double* __restrict__ x1, const d
     w.count = 0;
     w.best_iter = -1;
     if (!(requested && n >= 8)) return;
-    // the greatest score above 0.0, the lowest h on a tie; a NaN never wins
-    const double* slots = wave_models + slot_at(p, MODEL, max_iter, 0);
-    double best = 0.0;
-    for (int h = lane; h < max_iter; h += 64) {
-        const double s = slots[(size_t)h * kSlotDoubles + 9];
-        if (best < s) best = s, w.best_iter = h;
-    }
-#pragma unroll
-    for (int d = 32; d; d >>= 1) {
-        const double ob = __shfl_xor(best, d);
-        const int oh = __shfl_xor(w.best_iter, d);
-        const bool take = best < ob || (ob == best && oh >= 0 && oh < w.best_iter);
-        best = take ? ob : best;
-        w.best_iter = take ? oh : w.best_iter;
-    }
+    const double* slots = wave_models + slot_at((size_t)p * 2 + MODEL, max_iter, 0);
+    best_slot(slots, max_iter, lane, w.best_iter);
     if (w.best_iter < 0) return;
     const double* md = slots + (size_t)w.best_iter * kSlotDoubles;   // the doubles the hypothesis kernel scored with
 #pragma unroll
@@ -372,10 +313,7 @@ __device__ __forceinline__ void refit_of(const Eig& e, const Norm& N1, const Nor
                                          double inv_sigma_sq, uint8_t* __restrict__ flags, int lane, Model& w) {
     double M2[9];
     fit_finish<MODEL>(e, N1, N2, M2);
-    bool finite = true;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) finite = finite && __builtin_isfinite(M2[k]);
-    if (!finite) return;
+    if (!all_finite(M2)) return;
 #pragma unroll
     for (int k = 0; k < 9; ++k) w.M[k] = M2[k];
     score_wave<MODEL>(w.M, x1, x2, n, inv_sigma_sq, lane, flags, nullptr, w.count, w.score);
@@ -386,11 +324,7 @@ __device__ __forceinline__ void refit_of(const Eig& e, const Norm& N1, const Nor
 template <int MODEL>
 __device__ __forceinline__ void write_model(Model& w, int n, uint8_t* __restrict__ flags, int lane, TwoViewRec* __restrict__ rec) {
     if (!w.valid) {
-        for (int i = lane; i < n; i += 64) flags[i] = 0;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) w.M[k] = (k % 4 == 0) ? 1.0 : 0.0;
-        w.score = 0.0;
-        w.count = 0;
+        invalid_form(flags, n, lane, w.M, w.score, w.count);
         w.best_iter = -1;
     }
     if (lane == 0) {
@@ -449,8 +383,7 @@ __global__ __launch_bounds__(64) void k_twoview_finish(const uint8_t* __restrict
 
 }   // namespace
 
-struct ovs_twoview : ransac_handle {
-    int32_t* d_inlier_idx = nullptr;                      // [2][matches of the call] a winner's inliers by rank, per model and problem at its offset
+struct ovs_twoview : eight_point_handle {                 // its d_inlier_idx: [2][matches of the call], H's half and F's
     uint8_t *h_flags_f = nullptr, *m_flags_f = nullptr;   // F's flags; the scaffold's h_flags / m_flags hold H's
     TwoViewRec* h_rec() { return reinterpret_cast<TwoViewRec*>(h_result); }
     TwoViewRec* m_rec() { return reinterpret_cast<TwoViewRec*>(m_result); }
@@ -459,17 +392,12 @@ struct ovs_twoview : ransac_handle {
 extern "C" {
 
 ovs_status ovs_twoview_create(int32_t device, int32_t max_problems, int32_t max_total_matches, ovs_twoview** out) {
-    const ovs_status st = ransac_create(device, max_problems, max_total_matches, layout_of(max_problems, max_total_matches).bytes,
-                                        (size_t)max_problems * 2 * 32,   // 32 iterations of both models per problem without growing
-                                        kSlotDoubles, out, sizeof(TwoViewRec));
-    if (st != OVS_OK) return st;
-    std::unique_ptr<ovs_twoview> owner(*out);
-    *out = nullptr;
-    OVS_HIP_TRY(owner->res.dev(&owner->d_inlier_idx, sizeof(int32_t) * 2 * (size_t)max_total_matches));
-    OVS_HIP_TRY(owner->res.pinned(&owner->h_flags_f, (size_t)max_total_matches, hipHostMallocMapped));
-    OVS_HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&owner->m_flags_f), owner->h_flags_f, 0));
-    *out = owner.release();
-    return OVS_OK;
+    const auto flags_f = [&](ovs_twoview* s) {
+        OVS_HIP_TRY(s->res.pinned(&s->h_flags_f, (size_t)max_total_matches, hipHostMallocMapped));
+        OVS_HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->m_flags_f), s->h_flags_f, 0));
+        return OVS_OK;
+    };
+    return eight_point_create(device, max_problems, max_total_matches, layout_of(max_problems, max_total_matches).bytes, 2, sizeof(TwoViewRec), out, flags_f);
 }
 
 ovs_status ovs_twoview_destroy(ovs_twoview* s) { return ransac_destroy(s); }
@@ -487,15 +415,13 @@ ovs_status ovs_twoview_solve_batch(ovs_twoview* s, int32_t n_problems, const int
         }
         return OVS_OK;
     };
-    const auto reserve = [&] { return s->reserve_models((size_t)n_problems * 2 * (size_t)max_num_iter) != OVS_OK ? OVS_ERR_HIP : OVS_OK; };
-    const auto launch = [&](hipStream_t st, int32_t T) {
+    const auto hypotheses = [&](hipStream_t st, int32_t T) {
         hipLaunchKernelGGL(k_twoview_hypotheses, dim3(max_num_iter, 2, n_problems), dim3(64), 0, st, s->d_block, n_problems, T, max_num_iter, models, seed,
                            inv_sigma_sq, s->d_wave_models);
-        OVS_HIP_TRY(hipGetLastError());
+    };
+    const auto finish = [&](hipStream_t st, int32_t T) {
         hipLaunchKernelGGL(k_twoview_finish, dim3(n_problems), dim3(64), 0, st, s->d_block, n_problems, T, max_num_iter, models, recompute ? 1 : 0,
                            inv_sigma_sq, s->d_wave_models, s->d_inlier_idx, s->m_rec(), s->m_flags, s->m_flags_f);
-        OVS_HIP_TRY(hipGetLastError());
-        return OVS_OK;
     };
     const auto collect = [&](int32_t T) {
         for (int32_t p = 0; p < n_problems; ++p) {
@@ -515,8 +441,8 @@ ovs_status ovs_twoview_solve_batch(ovs_twoview* s, int32_t n_problems, const int
             std::memcpy(out_inlier_flags_F, s->h_flags_f, (size_t)T);
         }
     };
-    return run_staged(s, n_problems, offsets, {out_H_21, out_F_21, out_scores, out_valid, out_best_iter, out_num_inliers, out_selected},
-                      {x1, x2, out_inlier_flags_F}, out_inlier_flags_H, layout_of, stage, reserve, launch, collect);
+    return run_slots(s, n_problems, offsets, {out_H_21, out_F_21, out_scores, out_valid, out_best_iter, out_num_inliers, out_selected},
+                     {x1, x2, out_inlier_flags_F}, out_inlier_flags_H, layout_of, 2, max_num_iter, stage, hypotheses, finish, collect);
 }
 
 }   // extern "C"

@@ -1,4 +1,5 @@
-"""solve/ on the MI355X: the two RANSAC solvers whose candidates come in batches, and the Sim3 optimiser that follows the first.
+"""solve/ and its neighbours on the MI355X, every one a batch call over packed problems (_pack): the Sim3, EPnP, homography / fundamental and
+essential RANSACs, the Sim3 transform optimiser, the two-view triangulator and the monocular initialiser's pose recovery.
 
 solve::sim3_solver (expected: src/openvslam/solve/sim3_solver.{h,cc}) on the MI355X: the RANSAC the loop detector runs on every loop
 candidate between bow_tree::match_keyframes and projection::match_by_Sim3_transform. All candidates of a keyframe go to the device in ONE
@@ -104,20 +105,28 @@ class _pnp_handle(_ransac_handle):
     _abi = "ovs_pnp"
 
 
-def _solve_batch(handle_type, problems, arrays, count_key, error, middle, suffix, with_scale, handle, device):
-    """One solve_batch call of handle_type's ABI over `problems`. arrays: (key, dtype, width) of the per-match arrays in the ABI's order,
-    count_key the one whose length is a problem's number of matches, error the ValueError's text when another disagrees; middle: the ABI's
-    arguments between the arrays and the outputs; the returned dicts name the pose rot_<suffix>, trans_<suffix> (and scale_<suffix>)."""
+def _pack(problems, arrays, count_key, error):
+    """What every batch call stages: (P, offsets, T, packed). arrays: (key, dtype, width) of the per-match arrays in the ABI's order;
+    count_key names the one whose rows are a problem's matches: offsets (int32, P + 1) are their running sum and T the total. packed: every
+    array of all problems in one contiguous (T, width) array of its dtype; error is the ValueError's text when one has another length."""
     P = len(problems)
-    if P == 0:
-        return []
+    width = {key: w for key, _, w in arrays}[count_key]
     offsets = np.zeros(P + 1, np.int32)
-    offsets[1:] = np.cumsum([len(np.asarray(q[count_key])) for q in problems])
+    offsets[1:] = np.cumsum([len(np.asarray(q[count_key]).reshape(-1, width)) for q in problems])
     T = int(offsets[-1])
     cat = lambda key, dt, w: np.ascontiguousarray(np.concatenate([np.asarray(q[key], dt).reshape(-1, w) for q in problems]) if T else np.zeros((0, w), dt))
     packed = [cat(*a) for a in arrays]
     if any(len(a) != T for a in packed):
         raise ValueError(error)
+    return P, offsets, T, packed
+
+
+def _solve_batch(handle_type, problems, arrays, count_key, error, middle, suffix, with_scale, handle, device):
+    """One solve_batch call of handle_type's ABI over `problems`. arrays, count_key, error: as _pack takes them; middle: the ABI's
+    arguments between the arrays and the outputs; the returned dicts name the pose rot_<suffix>, trans_<suffix> (and scale_<suffix>)."""
+    P, offsets, T, packed = _pack(problems, arrays, count_key, error)
+    if P == 0:
+        return []
     if handle is None:
         handle = handle_type(P, max(T, 1), device)
     valid, best_iter, num = np.zeros(P, np.int32), np.zeros(P, np.int32), np.zeros(P, np.int32)
@@ -137,13 +146,16 @@ def _solve_batch(handle_type, problems, arrays, count_key, error, middle, suffix
     return out
 
 
+_SIM3_ARRAYS = (("p1", np.float64, 3), ("p2", np.float64, 3), ("thr1", np.float32, 1), ("thr2", np.float32, 1))
+_PNP_ARRAYS = (("bearings", np.float64, 3), ("pos_w", np.float64, 3), ("max_cos_error", np.float64, 1))
+
+
 def solve_sim3_batch(problems, fix_scale, min_num_inliers=20, max_num_iter=200, seed=DEFAULT_SEED, handle=None, device=0):
     """find_via_ransac for every problem (dicts as problem_from_keyframes returns them) in one call: a list of dicts valid, best_iter,
     num_inliers, rot_12 (3 x 3), trans_12 (3), scale_12, inlier_flags (n, bool). `handle`: a _handle to reuse (the loop detector keeps one)."""
     cams_1 = (_lib.Camera * len(problems))(*[q["cam_1"] for q in problems])
     cams_2 = (_lib.Camera * len(problems))(*[q["cam_2"] for q in problems])
-    return _solve_batch(_handle, problems, [("p1", np.float64, 3), ("p2", np.float64, 3), ("thr1", np.float32, 1), ("thr2", np.float32, 1)], "thr1",
-                        "p1, p2, thr1 and thr2 of a problem must have one entry per match",
+    return _solve_batch(_handle, problems, _SIM3_ARRAYS, "thr1", "p1, p2, thr1 and thr2 of a problem must have one entry per match",
                         [cams_1, cams_2, 1 if fix_scale else 0, int(min_num_inliers), int(max_num_iter), int(seed) & _MASK], "12", True, handle, device)
 
 
@@ -212,8 +224,7 @@ def pnp_problem(bearings, octaves, pos_w, scale_factors):
 def solve_pnp_batch(problems, min_num_inliers=10, max_num_iter=30, recompute=True, seed=PNP_DEFAULT_SEED, handle=None, device=0):
     """find_via_ransac for every problem (dicts as pnp_problem returns them) in one call: a list of dicts valid, best_iter, num_inliers,
     rot_cw (3 x 3), trans_cw (3), inlier_flags (n, bool). `handle`: a _pnp_handle to reuse (the relocaliser keeps one)."""
-    return _solve_batch(_pnp_handle, problems, [("bearings", np.float64, 3), ("pos_w", np.float64, 3), ("max_cos_error", np.float64, 1)], "max_cos_error",
-                        "bearings, pos_w and max_cos_error of a problem must have one entry per match",
+    return _solve_batch(_pnp_handle, problems, _PNP_ARRAYS, "max_cos_error", "bearings, pos_w and max_cos_error of a problem must have one entry per match",
                         [int(min_num_inliers), int(max_num_iter), 1 if recompute else 0, int(seed) & _MASK], "cw", False, handle, device)
 
 
@@ -258,21 +269,16 @@ class _transform_handle(_ransac_handle):
     _abi = "ovs_sim3opt"
 
 
+_OPT_ARRAYS = (("p1", np.float64, 3), ("p2", np.float64, 3), ("obs1", np.float64, 2), ("obs2", np.float64, 2), ("w1", np.float32, 1), ("w2", np.float32, 1))
+
+
 def optimize_transform_batch(problems, fix_scale, chi_sq=10.0, num_iter=10, handle=None, device=0, with_info=True):
     """transform_optimizer::optimize for every problem (dicts as transform_problem_from_keyframes returns them) in one call: a list of dicts
     num_inliers, rot_12 (3 x 3), trans_12 (3), scale_12, outlier_flags (n, bool) and info (8 doubles: iterations and trials of round 1, its
     robust chi-square, its outliers, the same three of round 2, the last lambda). `handle`: a _transform_handle to reuse."""
-    P = len(problems)
+    P, offsets, T, packed = _pack(problems, _OPT_ARRAYS, "w1", "p1, p2, obs1, obs2, w1 and w2 of a problem must have one entry per match")
     if P == 0:
         return []
-    offsets = np.zeros(P + 1, np.int32)
-    offsets[1:] = np.cumsum([len(np.asarray(q["w1"])) for q in problems])
-    T = int(offsets[-1])
-    cat = lambda key, dt, w: np.ascontiguousarray(np.concatenate([np.asarray(q[key], dt).reshape(-1, w) for q in problems]) if T else np.zeros((0, w), dt))
-    packed = [cat(*a) for a in (("p1", np.float64, 3), ("p2", np.float64, 3), ("obs1", np.float64, 2), ("obs2", np.float64, 2), ("w1", np.float32, 1),
-                                ("w2", np.float32, 1))]
-    if any(len(a) != T for a in packed):
-        raise ValueError("p1, p2, obs1, obs2, w1 and w2 of a problem must have one entry per match")
     cams_1 = (_lib.Camera * P)(*[q["cam_1"] for q in problems])
     cams_2 = (_lib.Camera * P)(*[q["cam_2"] for q in problems])
     rot_in = np.ascontiguousarray([np.asarray(q["R"], np.float64).reshape(3, 3) for q in problems])
@@ -389,16 +395,9 @@ def triangulate_batch(problems, ratio_factor, cos_rays_parallax_thr=cos_rays_par
     call: a list of dicts pos_w (n, 3), status (n, uint8: 0 accepted, else the gate that rejected, DESIGN.md 3.12 rule T9), method (n, uint8),
     accepted (n, bool) and num_accepted. ratio_factor: the caller's 1.5f * scale_factor. `handle`: a _triangulate_handle to reuse (the mapping
     thread keeps one)."""
-    P = len(problems)
+    P, offsets, T, packed = _pack(problems, _TRI_ARRAYS, "x_right_1", "every per-match array of a problem must have one entry per match")
     if P == 0:
         return []
-    offsets = np.zeros(P + 1, np.int32)
-    offsets[1:] = np.cumsum([len(np.asarray(q["x_right_1"]).ravel()) for q in problems])
-    T = int(offsets[-1])
-    cat = lambda key, dt, w: np.ascontiguousarray(np.concatenate([np.asarray(q[key], dt).reshape(-1, w) for q in problems]) if T else np.zeros((0, w), dt))
-    packed = [cat(*a) for a in _TRI_ARRAYS]
-    if any(len(a) != T for a in packed):
-        raise ValueError("every per-match array of a problem must have one entry per match")
     cams_1 = (_lib.Camera * P)(*[q["cam_1"] for q in problems])
     cams_2 = (_lib.Camera * P)(*[q["cam_2"] for q in problems])
     poses_1 = np.ascontiguousarray([_pose12(q["pose_cw_1"]) for q in problems])
@@ -464,20 +463,16 @@ class _two_view_handle(_ransac_handle):
     _abi = "ovs_twoview"
 
 
+_TWO_VIEW_ARRAYS = (("x1", np.float64, 2), ("x2", np.float64, 2))
+
+
 def solve_two_view_batch(problems, sigma=1.0, max_num_iter=100, recompute=True, seed=TWO_VIEW_DEFAULT_SEED, models=3, handle=None, device=0):
     """Both find_via_ransac of the monocular initialiser for every problem (dicts with x1, x2: (n, 2)) in one call: a list of dicts H and F
     (each valid, best_iter, num_inliers, score, the matrix H_21 / F_21 (3 x 3) and inlier_flags (n, bool); the invalid form for a model
     `models` leaves out) and selected (1: H, 2: F, 0: neither). `handle`: a _two_view_handle to reuse (the initialiser keeps one)."""
-    P = len(problems)
+    P, offsets, T, (x1, x2) = _pack(problems, _TWO_VIEW_ARRAYS, "x1", "x1 and x2 of a problem must have one entry per match")
     if P == 0:
         return []
-    offsets = np.zeros(P + 1, np.int32)
-    offsets[1:] = np.cumsum([len(np.asarray(q["x1"]).reshape(-1, 2)) for q in problems])
-    T = int(offsets[-1])
-    cat = lambda key: np.ascontiguousarray(np.concatenate([np.asarray(q[key], np.float64).reshape(-1, 2) for q in problems]) if T else np.zeros((0, 2)))
-    x1, x2 = cat("x1"), cat("x2")
-    if len(x1) != T or len(x2) != T:
-        raise ValueError("x1 and x2 of a problem must have one entry per match")
     if handle is None:
         handle = _two_view_handle(P, max(T, 1), device)
     mats = [np.zeros((P, 3, 3)), np.zeros((P, 3, 3))]
@@ -553,21 +548,17 @@ class _essential_handle(_ransac_handle):
     _abi = "ovs_essential"
 
 
+_ESSENTIAL_ARRAYS = (("b1", np.float64, 3), ("b2", np.float64, 3))
+
+
 def solve_essential_batch(problems, residual_cos_thr=ESSENTIAL_RESIDUAL_COS_THR, max_num_iter=50, recompute=False, seed=ESSENTIAL_DEFAULT_SEED,
                           handle=None, device=0):
     """find_via_ransac of solve::essential_solver for every problem (dicts with b1, b2: (n, 3)) in one call: a list of dicts valid,
     best_iter, num_inliers, score, E_21 (3 x 3) and inlier_flags (n, bool). The defaults are robust::match_frame_and_keyframe's: 50
     iterations, no recompute. `handle`: an _essential_handle to reuse."""
-    P = len(problems)
+    P, offsets, T, (b1, b2) = _pack(problems, _ESSENTIAL_ARRAYS, "b1", "b1 and b2 of a problem must have one entry per match")
     if P == 0:
         return []
-    offsets = np.zeros(P + 1, np.int32)
-    offsets[1:] = np.cumsum([len(np.asarray(q["b1"]).reshape(-1, 3)) for q in problems])
-    T = int(offsets[-1])
-    cat = lambda key: np.ascontiguousarray(np.concatenate([np.asarray(q[key], np.float64).reshape(-1, 3) for q in problems]) if T else np.zeros((0, 3)))
-    b1, b2 = cat("b1"), cat("b2")
-    if len(b1) != T or len(b2) != T:
-        raise ValueError("b1 and b2 of a problem must have one entry per match")
     if handle is None:
         handle = _essential_handle(P, max(T, 1), device)
     E, scores = np.zeros((P, 3, 3)), np.zeros(P)
@@ -639,16 +630,9 @@ def reconstruct_two_view_batch(problems, reproj_err_thr=4.0, parallax_deg_thr=1.
     """reconstruct_with_H / reconstruct_with_F for every problem (dicts as reconstruct_problem returns them) in one call: a list of dicts
     success, best (the winning hypothesis, -1), rot_ref_to_cur (3 x 3), trans_ref_to_cur (3), triangulated_pts (n, 3), is_triangulated
     (n, bool), counts (8) and parallax_deg (8, float32) per hypothesis. `handle`: a _reconstruct_handle to reuse (the initialiser keeps one)."""
-    P = len(problems)
+    P, offsets, T, packed = _pack(problems, _REC_ARRAYS, "inlier", "every per-match array of a problem must have one entry per match")
     if P == 0:
         return []
-    offsets = np.zeros(P + 1, np.int32)
-    offsets[1:] = np.cumsum([len(q["inlier"]) for q in problems])
-    T = int(offsets[-1])
-    cat = lambda key, dt, w: np.ascontiguousarray(np.concatenate([np.asarray(q[key], dt).reshape(-1, w) for q in problems]) if T else np.zeros((0, w), dt))
-    packed = [cat(*a) for a in _REC_ARRAYS]
-    if any(len(a) != T for a in packed):
-        raise ValueError("every per-match array of a problem must have one entry per match")
     models = np.ascontiguousarray([q["model"] for q in problems], np.int32)
     mats = np.ascontiguousarray([np.asarray(q["mat"], np.float64).reshape(3, 3) for q in problems])
     cams = (_lib.Camera * P)(*[q["cam"] for q in problems])

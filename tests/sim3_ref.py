@@ -67,7 +67,7 @@ def horn_N(a, b):
 
 
 def jacobi(N, sweeps=SWEEPS):
-    """Cyclic Jacobi, the rotation of essential_solver.h::compute_E_21, a fixed number of sweeps: (A, V), A nearly diagonal, V's columns the vectors."""
+    """Cyclic Jacobi, the rotation of csrc/jacobi_math.inc (jacobi_angle), a fixed number of sweeps: (A, V), A nearly diagonal, V's columns the vectors."""
     A = [row[:] for row in N]
     V = [[1.0 if r == c else 0.0 for c in range(4)] for r in range(4)]
     for _ in range(sweeps):
