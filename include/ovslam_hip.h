@@ -381,6 +381,42 @@ ovs_status ovs_projection_match_frame_and_keyframe(ovs_wmatcher* w, const ovs_ca
                                                    float log_scale_factor, float margin, uint32_t hamm_dist_thr, int32_t check_orientation,
                                                    int32_t* assigned, int32_t* num_matches);
 
+/* replaces: the body of  void tracking_module::search_local_landmarks()  (src/openvslam/tracking_module.cc) behind its first loop:
+ * frame::can_observe(lm, 0.5, reproj, x_right, pred_scale_level) of every local landmark AND projection::match_frame_and_landmarks on the
+ * survivors, in one call (rules V1 - V7). Frame side as for ovs_projection_match_frame_and_landmarks; pose_cw =
+ * curr_frm.cam_pose_cw_ as 12 doubles. Per local landmark (in the order of local_landmarks): lm_pos_w = get_pos_in_world(), lm_dist_min_max =
+ * the RAW (min_valid_dist_, max_valid_dist_) members (see ovs_fuse_replace_duplication), lm_normal = get_obs_mean_normal(), lm_desc =
+ * get_descriptor(), lm_search[l] != 0 iff lm && !will_be_erased() && lm->identifier_in_local_lm_search_ != curr_frm.id_ (NULL = all; rows of
+ * entries that are not searched are ignored). scale_factors / log_scale_factor = the frame's tables.
+ * Outputs per landmark: observable = is_observable_in_tracking_; reproj = reproj_in_tracking_, x_right = x_right_in_tracking_, level =
+ * scale_level_in_tracking_ (each may be NULL: then it is not copied down); a landmark that is not observable has reproj (0, 0), x_right -1,
+ * level 0 and assigned -1. assigned[l] = the frame keypoint landmark l is written to, or -1; *num_observable = the landmarks that passed
+ * can_observe, *num_matches = what match_frame_and_landmarks returns. m == 0: OK with both counts 0; n == 0: the visibility alone, every
+ * assigned -1. One staging copy up, one result block (counts, assigned, observable) down. */
+ovs_status ovs_tracking_search_local_landmarks(ovs_wmatcher* w, const ovs_camera* cam, const ovs_grid_params* gp, const ovs_keypoint* kps,
+                                               const uint8_t* desc, const float* stereo_x_right, const uint8_t* occupied, int32_t n,
+                                               const double* pose_cw, const double* lm_pos_w, const float* lm_dist_min_max, const double* lm_normal,
+                                               const uint8_t* lm_desc, const uint8_t* lm_search, int32_t m, const float* scale_factors,
+                                               int32_t num_levels, float log_scale_factor, float margin, float lowe_ratio, uint8_t* observable,
+                                               double* reproj, float* x_right, int32_t* level, int32_t* assigned, int32_t* num_observable,
+                                               int32_t* num_matches);
+/* The same with the frame resident (ovs_frame_dev; its grid parameters are the handle's). */
+ovs_status ovs_tracking_search_local_landmarks_f(ovs_wmatcher* w, const ovs_camera* cam, const ovs_frame_dev* frm, const uint8_t* occupied,
+                                                 const double* pose_cw, const double* lm_pos_w, const float* lm_dist_min_max, const double* lm_normal,
+                                                 const uint8_t* lm_desc, const uint8_t* lm_search, int32_t m, const float* scale_factors,
+                                                 int32_t num_levels, float log_scale_factor, float margin, float lowe_ratio, uint8_t* observable,
+                                                 double* reproj, float* x_right, int32_t* level, int32_t* assigned, int32_t* num_observable,
+                                                 int32_t* num_matches);
+/* Device-pointer form: every array in HBM (scale_factors and pose_cw stay host pointers), asynchronous on `stream`; stages nothing and
+ * synchronises nothing. d_reproj, d_x_right and d_level may be NULL. The hook for a landmark table that a front end keeps resident. */
+ovs_status ovs_tracking_search_local_landmarks_dev(ovs_wmatcher* w, const ovs_camera* cam, const ovs_grid_params* gp, const ovs_keypoint* d_kps,
+                                                   const uint8_t* d_desc, const float* d_stereo_x_right, const uint8_t* d_occupied, int32_t n,
+                                                   const double* pose_cw, const double* d_lm_pos_w, const float* d_lm_dist_min_max,
+                                                   const double* d_lm_normal, const uint8_t* d_lm_desc, const uint8_t* d_lm_search, int32_t m,
+                                                   const float* scale_factors, int32_t num_levels, float log_scale_factor, float margin,
+                                                   float lowe_ratio, uint8_t* d_observable, double* d_reproj, float* d_x_right, int32_t* d_level,
+                                                   int32_t* d_assigned, int32_t* d_num_observable, int32_t* d_num_matches, void* stream);
+
 /* replaces: the candidate search of  template<typename T> unsigned int fuse::replace_duplication(data::keyframe* keyfrm,
  *               const T& landmarks_to_check, const float margin)  (src/openvslam/match/fuse.{h,cc}); landmarks are independent there.
  * kps / desc / stereo_x_right = keyfrm->undist_keypts_ / descriptors_ / stereo_x_right_ (NULL = monocular); pose_cw = keyfrm pose.

@@ -168,6 +168,10 @@ SYMBOLS = {
                                                         _vp, C.POINTER(_i32)]),
     "ovs_projection_match_frame_and_landmarks_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _f,
                                                             _f, _vp, _vp, _vp]),
+    "ovs_tracking_search_local_landmarks": (_i32, [_vp] * 7 + [_i32] + [_vp] * 6 + [_i32, _vp, _i32, _f, _f, _f] + [_vp] * 5 +
+                                            [C.POINTER(_i32), C.POINTER(_i32)]),
+    "ovs_tracking_search_local_landmarks_f": (_i32, [_vp] * 10 + [_i32, _vp, _i32, _f, _f, _f] + [_vp] * 5 + [C.POINTER(_i32), C.POINTER(_i32)]),
+    "ovs_tracking_search_local_landmarks_dev": (_i32, [_vp] * 7 + [_i32] + [_vp] * 6 + [_i32, _vp, _i32, _f, _f, _f] + [_vp] * 8),
     "ovs_area_match_in_consistent_area": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _f, _i32, C.POINTER(_i32)]),
     "ovs_area_match_in_consistent_area_dev": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _f, _i32, _vp, _vp]),
     "ovs_bow_match_frame_and_keyframe": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _f, _i32,

@@ -106,6 +106,9 @@ public:
     float x_right_in_tracking_ = -1.0f;
     bool is_observable_in_tracking_ = false;
     int scale_level_in_tracking_ = 0;
+    unsigned int identifier_in_local_lm_search_ = 0;   // the frame whose search_local_landmarks already holds this landmark
+    unsigned int num_observable_ = 1;
+    void increase_num_observable(unsigned int num_observable = 1) { num_observable_ += num_observable; }
 };
 
 // The matcher-side data of a frame -- and of the keyframe made from it -- resident in HBM (ovs_frame_dev, include/ovslam_hip.h): created by

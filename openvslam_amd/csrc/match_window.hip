@@ -306,6 +306,55 @@ __global__ __launch_bounds__(256) void k_reproject_queries(CamP cam, const ovs_k
     q_valid[i] = valid ? 1 : 0;
 }
 
+// tracking_module::search_local_landmarks, the visibility pass: frame::can_observe(lm, 0.5, ...) of every local landmark, one lane per landmark
+// (ObserveArgs: match_window_plan.inc; rules V1 - V6 of DESIGN.md 3.17). The kModeProjection lists and the ratio resolver follow on the same stream
+// and read what this writes: q_xy / q_x_right / q_level, and observable as their q_valid.
+__global__ __launch_bounds__(256) void k_observe_landmarks(ObserveArgs a) {
+    const int l = blockIdx.x * 256 + threadIdx.x;
+    bool obs = false;
+    double u = 0.0, v = 0.0;
+    float xr = -1.0f;
+    int lvl = 0;
+    if (l < a.m && (!a.lm_search || a.lm_search[l])) {   // V1
+        const double* X = a.lm_pos_w + 3 * (size_t)l;
+        obs = reproject_to_image(a.cam, X, u, v, xr);   // V2
+        if (obs) {
+            const double dx = X[0] - a.cc[0], dy = X[1] - a.cc[1], dz = X[2] - a.cc[2];
+            const double dist = sqrt((dx * dx + dy * dy) + dz * dz);
+            // V3: landmark::is_inside_in_orb_scale through the getters (0.7 / 1.3 of the raw members, double product returned as float)
+            const float dmin = a.lm_dist[2 * l], dmax = a.lm_dist[2 * l + 1];
+            if (dist < (double)(float)(0.7 * (double)dmin) || (double)(float)(1.3 * (double)dmax) < dist) obs = false;
+            // V4: upstream's dot / dist < 0.5 in the product form (0.5 * dist is exact, and a quotient below one half cannot round up to it)
+            const double* nrm = a.lm_normal + 3 * (size_t)l;
+            if ((dx * nrm[0] + dy * nrm[1]) + dz * nrm[2] < 0.5 * dist) obs = false;
+            if (obs) {   // V5: landmark::predict_scale_level on the raw max_valid_dist_
+                lvl = (int)ceilf(__fdiv_rn(ovs_det_logf(__fdiv_rn(dmax, (float)dist)), a.log_scale_factor));
+                if (lvl < 0) lvl = 0;
+                else if (a.num_levels <= lvl) lvl = a.num_levels - 1;
+            }
+        }
+    }
+    if (!obs) {   // V6 (a landmark the image bounds rejected has been projected)
+        u = v = 0.0;
+        xr = -1.0f;
+        lvl = 0;
+    }
+    if (l < a.m) {
+        a.q_xy[2 * l] = (float)u;
+        a.q_xy[2 * l + 1] = (float)v;
+        a.q_x_right[l] = xr;
+        a.q_level[l] = lvl;
+        a.observable[l] = obs ? 1 : 0;
+        if (a.reproj) {
+            a.reproj[2 * l] = u;
+            a.reproj[2 * l + 1] = v;
+        }
+        if (a.assigned) a.assigned[l] = -1;
+    }
+    const unsigned long long any = __ballot(obs);
+    if ((threadIdx.x & 63) == 0 && any) atomicAdd(a.num_observable, (int32_t)__popcll(any));
+}
+
 // fuse::replace_duplication, candidate search (FuseArgs: match_window_plan.inc).
 // kFuseReplace: fuse::replace_duplication (chi-square gate); kFuseDetect: fuse::detect_duplication (no chi-square gate);
 // kFuseMutual: one direction of projection::match_keyframes_mutually (no viewing-angle gate, distance = |pos in the other keyframe|)
@@ -1162,6 +1211,92 @@ ovs_status projection_match_frame_and_landmarks_impl(ovs_wmatcher* w, const ovs_
     return fetch_results(w, m, assigned, num_matches, s);
 }
 
+// tracking_module::search_local_landmarks on device arrays: k_observe_landmarks, then (with keypoints to match against) the lists and the resolver
+// of projection::match_frame_and_landmarks on what it wrote -- one stream, no host step in between. d_num_observable and d_num_matches are written
+// on every path; without keypoints the kernel also sets every assigned to -1.
+ovs_status search_local_on_device(ovs_wmatcher* w, const CamP& cp, const double* cc, const TargetRef& t, const uint8_t* d_occupied, int n, const double* d_lm_pos_w,
+                                  const float* d_lm_dist, const double* d_lm_normal, const uint8_t* d_lm_desc, const uint8_t* d_lm_search, int m,
+                                  const float* scale_factors, int num_levels, float log_scale_factor, float margin, float lowe_ratio, float* d_xy,
+                                  float* d_x_right, int32_t* d_level, uint8_t* d_observable, double* d_reproj, int32_t* d_assigned, int32_t* d_num_observable,
+                                  int32_t* d_num_matches, hipStream_t s) {
+    ObserveArgs a{};
+    a.cam = cp;
+    std::memcpy(a.cc, cc, sizeof(a.cc));
+    a.lm_pos_w = d_lm_pos_w;
+    a.lm_dist = d_lm_dist;
+    a.lm_normal = d_lm_normal;
+    a.lm_search = d_lm_search;
+    a.m = m;
+    a.num_levels = num_levels;
+    a.log_scale_factor = log_scale_factor;
+    a.q_xy = d_xy;
+    a.q_x_right = d_x_right;
+    a.q_level = d_level;
+    a.observable = d_observable;
+    a.reproj = d_reproj;
+    a.assigned = n == 0 ? d_assigned : nullptr;
+    a.num_observable = d_num_observable;
+    OVS_HIP_TRY(hipMemsetAsync(d_num_observable, 0, sizeof(int32_t), s));
+    if (n == 0) OVS_HIP_TRY(hipMemsetAsync(d_num_matches, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(k_observe_landmarks, dim3((m + 255) / 256), dim3(256), 0, s, a);
+    OVS_HIP_TRY(hipGetLastError());
+    if (n == 0) return OVS_OK;   // upstream: `if (!found_proj_candidate) return;` -- and no keypoint can take a landmark
+    return frame_and_landmarks_on_device(w, t, d_occupied, n, d_xy, d_x_right, d_level, d_lm_desc, d_observable, m, scale_factors, num_levels, margin, lowe_ratio,
+                                         d_assigned, d_num_matches, s);
+}
+
+ovs_status tracking_search_local_landmarks_impl(ovs_wmatcher* w, const ovs_frame_dev* res, const ovs_camera* cam, const ovs_grid_params* gp,
+                                                const ovs_keypoint* kps, const uint8_t* desc, const float* stereo_x_right, const uint8_t* occupied, int32_t n,
+                                                const double* pose_cw, const double* lm_pos_w, const float* lm_dist_min_max, const double* lm_normal,
+                                                const uint8_t* lm_desc, const uint8_t* lm_search, int32_t m, const float* scale_factors, int32_t num_levels,
+                                                float log_scale_factor, float margin, float lowe_ratio, uint8_t* observable, double* reproj, float* x_right,
+                                                int32_t* level, int32_t* assigned, int32_t* num_observable, int32_t* num_matches) {
+    if (!w || !cam || !gp || !num_observable || !num_matches || n < 0 || m < 0 || !pose_cw || !scale_factors || num_levels < 1 ||
+        num_levels > OVS_MAX_LEVELS || (cam->model != 0 && cam->model != 1))
+        return OVS_ERR_INVALID;
+    *num_observable = *num_matches = 0;
+    if (m == 0) return OVS_OK;
+    if (!observable || !assigned || !lm_pos_w || !lm_dist_min_max || !lm_normal || !lm_desc || (n > 0 && !res && (!kps || !desc))) return OVS_ERR_INVALID;
+    if (n > w->max_t || m > w->max_q) return OVS_ERR_CAPACITY;
+    OVS_HIP_TRY(hipSetDevice(w->device));
+    hipStream_t s = w->stream;
+    CamP cp{};
+    fill_cam(cp, cam, gp, pose_cw);
+    double cc[3];
+    camera_centre(pose_cw, cc);
+    Stager stg(w);
+    TargetRef r;
+    ovs_status st = resident_side(w, res, n, &r);
+    if (st != OVS_OK) return st;
+    TargetRef tg = stage_target(stg, res ? &r : nullptr, kps, desc, stereo_x_right, nullptr, n);
+    const LocalLandmarks q = stage_local_landmarks(stg, occupied, n, lm_pos_w, lm_dist_min_max, lm_normal, lm_desc, lm_search, m, reproj != nullptr);
+    if ((st = stg.flush(s)) != OVS_OK) return st;
+    if (n > 0 && (st = index_target(w, gp, n, &tg, s)) != OVS_OK) return st;
+    uint8_t* const d_observable = reinterpret_cast<uint8_t*>(w->d_assigned + m);   // behind assigned[m]: the result block comes down with one copy
+    st = search_local_on_device(w, cp, cc, tg, q.occupied, n, q.pos, q.dist, q.normal, q.desc, q.search, m, scale_factors, num_levels, log_scale_factor, margin,
+                                lowe_ratio, q.xy, q.x_right, q.level, d_observable, q.reproj, w->d_assigned, w->d_num + 1, w->d_num, s);
+    if (st != OVS_OK) return st;
+    // the optional outputs come down only when asked for, through the pinned buffer at their arena offsets (the copy up is behind us on this stream)
+    auto mirror = [&](const void* d_ptr) { return w->h_stage + (reinterpret_cast<const unsigned char*>(d_ptr) - w->d_stage); };
+    if (reproj) OVS_HIP_TRY(hipMemcpyAsync(mirror(q.reproj), q.reproj, sizeof(double) * 2 * (size_t)m, hipMemcpyDeviceToHost, s));
+    if (x_right) OVS_HIP_TRY(hipMemcpyAsync(mirror(q.x_right), q.x_right, sizeof(float) * (size_t)m, hipMemcpyDeviceToHost, s));
+    if (level) OVS_HIP_TRY(hipMemcpyAsync(mirror(q.level), q.level, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, s));
+    OVS_HIP_TRY(hipMemcpyAsync(w->h_res, w->d_res_block, search_result_bytes(m), hipMemcpyDeviceToHost, s));
+    OVS_HIP_TRY(hipStreamSynchronize(s));
+    if (n > 0) {   // (without keypoints no list was built: the overflow word is whatever the last call left)
+        if (w->h_res[0]) return OVS_ERR_CAPACITY;
+        w->overflow_dirty = false;
+    }
+    std::memcpy(assigned, w->h_res + 8, sizeof(int32_t) * (size_t)m);
+    std::memcpy(observable, w->h_res + 8 + m, (size_t)m);
+    *num_matches = w->h_res[1];
+    *num_observable = w->h_res[2];
+    if (reproj) std::memcpy(reproj, mirror(q.reproj), sizeof(double) * 2 * (size_t)m);
+    if (x_right) std::memcpy(x_right, mirror(q.x_right), sizeof(float) * (size_t)m);
+    if (level) std::memcpy(level, mirror(q.level), sizeof(int32_t) * (size_t)m);
+    return OVS_OK;
+}
+
 ovs_status area_match_in_consistent_area_impl(ovs_wmatcher* w, const ovs_frame_dev* res_1, const ovs_frame_dev* res_2, const ovs_grid_params* gp,
                                               const ovs_keypoint* kps_1, const uint8_t* desc_1, int32_t n1, const ovs_keypoint* kps_2, const uint8_t* desc_2,
                                               int32_t n2, float* prev_matched_xy, int32_t* matched_2_in_1, int32_t margin, float lowe_ratio,
@@ -1543,12 +1678,14 @@ ovs_status ovs_wmatcher_create(int32_t max_targets, int32_t max_queries, int32_t
     OVS_HIP_TRY_RAW(w->res.dev(&w->d_offsets, sizeof(uint32_t) * (Q + 1)));
     OVS_HIP_TRY_RAW(w->res.dev(&w->d_keys, sizeof(uint32_t) * (size_t)max_entries));
     // result block: [0] overflow flag, [1..4] counts ([1] result count, [2] per-direction scratch count), [8..] assigned
-    OVS_HIP_TRY_RAW(w->res.dev(&w->d_res_block, sizeof(int32_t) * (8 + M)));
+    // (ovs_tracking_search_local_landmarks puts observable[m] behind assigned[m]: Q more bytes)
+    const size_t res_bytes = std::max(sizeof(int32_t) * (8 + M), search_result_bytes((int)Q));
+    OVS_HIP_TRY_RAW(w->res.dev(&w->d_res_block, res_bytes));
     w->d_overflow = w->d_res_block;
     w->d_num = reinterpret_cast<int32_t*>(w->d_res_block) + 1;
     w->d_assigned = reinterpret_cast<int32_t*>(w->d_res_block) + 8;
     OVS_HIP_TRY_RAW(hipMemset(w->d_res_block, 0, sizeof(int32_t) * 8));
-    OVS_HIP_TRY_RAW(w->res.pinned(&w->h_res, sizeof(int32_t) * (8 + M)));
+    OVS_HIP_TRY_RAW(w->res.pinned(&w->h_res, res_bytes));
     w->stage_cap = stage_capacity(T, Q);   // room for every array of the call that stages the most at n == max_targets, m == max_queries
     OVS_HIP_TRY_RAW(w->res.pinned(&w->h_stage, w->stage_cap));
     OVS_HIP_TRY_RAW(w->res.dev(&w->d_stage, w->stage_cap));
@@ -1612,6 +1749,45 @@ ovs_status ovs_area_match_in_consistent_area_dev(ovs_wmatcher* w, const ovs_grid
     return area_on_device(w, d_kps_1, d_desc_1, n1, t2, n2, d_prev_matched_xy, d_matched_2_in_1, margin, lowe_ratio, check_orientation, d_num_matches, s);
 }
 
+ovs_status ovs_tracking_search_local_landmarks_dev(ovs_wmatcher* w, const ovs_camera* cam, const ovs_grid_params* gp, const ovs_keypoint* d_kps,
+                                                   const uint8_t* d_desc, const float* d_stereo_x_right, const uint8_t* d_occupied, int32_t n,
+                                                   const double* pose_cw, const double* d_lm_pos_w, const float* d_lm_dist_min_max,
+                                                   const double* d_lm_normal, const uint8_t* d_lm_desc, const uint8_t* d_lm_search, int32_t m,
+                                                   const float* scale_factors, int32_t num_levels, float log_scale_factor, float margin,
+                                                   float lowe_ratio, uint8_t* d_observable, double* d_reproj, float* d_x_right, int32_t* d_level,
+                                                   int32_t* d_assigned, int32_t* d_num_observable, int32_t* d_num_matches, void* stream) {
+    if (!w || !cam || !gp || !d_num_observable || !d_num_matches || n < 0 || m < 0 || !pose_cw || !scale_factors || num_levels < 1 ||
+        num_levels > OVS_MAX_LEVELS || (cam->model != 0 && cam->model != 1) ||
+        (m > 0 && (!d_observable || !d_assigned || !d_lm_pos_w || !d_lm_dist_min_max || !d_lm_normal || !d_lm_desc || (n > 0 && (!d_kps || !d_desc)))))
+        return OVS_ERR_INVALID;
+    if (n > w->max_t || m > w->max_q) return OVS_ERR_CAPACITY;
+    OVS_HIP_TRY(hipSetDevice(w->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (m == 0) {
+        OVS_HIP_TRY(hipMemsetAsync(d_num_observable, 0, sizeof(int32_t), s));
+        OVS_HIP_TRY(hipMemsetAsync(d_num_matches, 0, sizeof(int32_t), s));
+        return OVS_OK;
+    }
+    CamP cp{};
+    fill_cam(cp, cam, gp, pose_cw);
+    double cc[3];
+    camera_centre(pose_cw, cc);
+    // nothing is staged: the context's arena only lends the queries' scratch (the float reprojection; x_right and level where the caller takes none)
+    StageWriter scratch(nullptr, w->d_stage, w->stage_cap);
+    float* const d_xy = scratch.reserve<float>((size_t)2 * m);
+    if (!d_x_right) d_x_right = scratch.reserve<float>((size_t)m);
+    if (!d_level) d_level = scratch.reserve<int32_t>((size_t)m);
+    if (scratch.overflow) return OVS_ERR_CAPACITY;
+    TargetRef tg{d_kps, d_desc, d_stereo_x_right, nullptr, nullptr, nullptr, GridP{}};
+    if (n > 0) {
+        const ovs_status st = index_target(w, gp, n, &tg, s);
+        if (st != OVS_OK) return st;
+    }
+    return search_local_on_device(w, cp, cc, tg, d_occupied, n, d_lm_pos_w, d_lm_dist_min_max, d_lm_normal, d_lm_desc, d_lm_search, m, scale_factors, num_levels,
+                                  log_scale_factor, margin, lowe_ratio, d_xy, d_x_right, d_level, d_observable, d_reproj, d_assigned, d_num_observable,
+                                  d_num_matches, s);
+}
+
 // ---- data::assign_keypoints_to_grid on its own (the matchers below build or bring their grids themselves) ----
 
 ovs_status ovs_assign_keypoints_to_grid(ovs_wmatcher* w, const ovs_grid_params* gp, const ovs_keypoint* kps, int32_t n,
@@ -1658,6 +1834,29 @@ ovs_status ovs_projection_match_frame_and_landmarks_f(ovs_wmatcher* w, const ovs
     if (!frm) return OVS_ERR_INVALID;
     return projection_match_frame_and_landmarks_impl(w, frm, &frm->gpp, nullptr, nullptr, nullptr, occupied, frm->n, lm_xy, lm_x_right, lm_level, lm_desc, lm_valid,
                                                      m, scale_factors, num_levels, margin, lowe_ratio, assigned, num_matches);
+}
+
+ovs_status ovs_tracking_search_local_landmarks(ovs_wmatcher* w, const ovs_camera* cam, const ovs_grid_params* gp, const ovs_keypoint* kps,
+                                               const uint8_t* desc, const float* stereo_x_right, const uint8_t* occupied, int32_t n,
+                                               const double* pose_cw, const double* lm_pos_w, const float* lm_dist_min_max, const double* lm_normal,
+                                               const uint8_t* lm_desc, const uint8_t* lm_search, int32_t m, const float* scale_factors,
+                                               int32_t num_levels, float log_scale_factor, float margin, float lowe_ratio, uint8_t* observable,
+                                               double* reproj, float* x_right, int32_t* level, int32_t* assigned, int32_t* num_observable,
+                                               int32_t* num_matches) {
+    return tracking_search_local_landmarks_impl(w, nullptr, cam, gp, kps, desc, stereo_x_right, occupied, n, pose_cw, lm_pos_w, lm_dist_min_max, lm_normal, lm_desc,
+                                                lm_search, m, scale_factors, num_levels, log_scale_factor, margin, lowe_ratio, observable, reproj, x_right, level,
+                                                assigned, num_observable, num_matches);
+}
+ovs_status ovs_tracking_search_local_landmarks_f(ovs_wmatcher* w, const ovs_camera* cam, const ovs_frame_dev* frm, const uint8_t* occupied,
+                                                 const double* pose_cw, const double* lm_pos_w, const float* lm_dist_min_max, const double* lm_normal,
+                                                 const uint8_t* lm_desc, const uint8_t* lm_search, int32_t m, const float* scale_factors,
+                                                 int32_t num_levels, float log_scale_factor, float margin, float lowe_ratio, uint8_t* observable,
+                                                 double* reproj, float* x_right, int32_t* level, int32_t* assigned, int32_t* num_observable,
+                                                 int32_t* num_matches) {
+    if (!frm) return OVS_ERR_INVALID;
+    return tracking_search_local_landmarks_impl(w, frm, cam, &frm->gpp, nullptr, nullptr, nullptr, occupied, frm->n, pose_cw, lm_pos_w, lm_dist_min_max, lm_normal,
+                                                lm_desc, lm_search, m, scale_factors, num_levels, log_scale_factor, margin, lowe_ratio, observable, reproj, x_right,
+                                                level, assigned, num_observable, num_matches);
 }
 
 ovs_status ovs_area_match_in_consistent_area(ovs_wmatcher* w, const ovs_grid_params* gp, const ovs_keypoint* kps_1, const uint8_t* desc_1,

@@ -232,6 +232,27 @@ struct FuseArgs {
     double P1[12];                // kFuseMutual: pose of the landmark's own keyframe (pos_1 = R_1w X + t_1w, then cam.P = [s R_21 | t_21])
 };
 
+// tracking_module::search_local_landmarks, the visibility pass (k_observe_landmarks, DESIGN.md 3.17 rules V1 - V6): frame::can_observe for every
+// local landmark. It writes the queries the kModeProjection lists read (q_xy, q_x_right, q_level; observable doubles as their q_valid) and the
+// caller's per-landmark outputs.
+struct ObserveArgs {
+    CamP cam;
+    double cc[3];                 // camera centre
+    const double* lm_pos_w;
+    const float* lm_dist;         // RAW (min_valid_dist_, max_valid_dist_)
+    const double* lm_normal;
+    const uint8_t* lm_search;     // V1: tested iff != 0 (nullptr: every landmark)
+    int m, num_levels;
+    float log_scale_factor;
+    float* q_xy;                  // [2 m] (float)reproj
+    float* q_x_right;             // [m]
+    int32_t* q_level;             // [m]
+    uint8_t* observable;          // [m]
+    double* reproj;               // [2 m] or nullptr
+    int32_t* assigned;            // nullptr, or [m] set to -1 (a call without keypoints runs no resolver that would write them)
+    int32_t* num_observable;      // zero on entry
+};
+
 // bow_tree: queries = the keyframe's feature-vector entries in walk order; the list of a query is its node's frame bucket
 struct BowArgs {
     const uint8_t* kf_desc;
@@ -368,6 +389,35 @@ inline LandmarkQueries stage_landmark_queries(StageWriter& stg, const uint8_t* o
     return q;
 }
 
+// tracking_module::search_local_landmarks: the frame's occupied flags, the local landmarks as the map holds them, and the queries
+// k_observe_landmarks makes of them (reproj only when the caller asks for it; observable and assigned live in the context's result block)
+struct LocalLandmarks {
+    const uint8_t* occupied;
+    const double *pos, *normal;
+    const float* dist;
+    const uint8_t *desc, *search;
+    float *xy, *x_right;
+    int32_t* level;
+    double* reproj;
+};
+inline LocalLandmarks stage_local_landmarks(StageWriter& stg, const uint8_t* occupied, int n, const double* lm_pos_w, const float* lm_dist_min_max,
+                                            const double* lm_normal, const uint8_t* lm_desc, const uint8_t* lm_search, int m, bool want_reproj) {
+    LocalLandmarks q{};
+    q.occupied = stg.put(occupied, (size_t)n);
+    q.pos = stg.put(lm_pos_w, (size_t)3 * m);
+    q.dist = stg.put(lm_dist_min_max, (size_t)2 * m);
+    q.normal = stg.put(lm_normal, (size_t)3 * m);
+    q.desc = stg.put(lm_desc, (size_t)32 * m);
+    q.search = stg.put(lm_search, (size_t)m);
+    q.xy = stg.reserve<float>((size_t)2 * m);
+    q.x_right = stg.reserve<float>((size_t)m);
+    q.level = stg.reserve<int32_t>((size_t)m);
+    q.reproj = want_reproj ? stg.reserve<double>((size_t)2 * m) : nullptr;
+    return q;
+}
+// the result block of a search_local_landmarks call: 8 words of flags and counts, assigned[m], then observable[m] -- one copy down
+inline size_t search_result_bytes(int m) { return sizeof(int32_t) * (8 + (size_t)m) + (size_t)m; }
+
 // what k_reproject_queries writes per query, in the staging arena
 struct QueryScratch {
     const uint8_t* valid_in;   // the caller's flags (nullptr: every query), read ...
@@ -443,6 +493,8 @@ inline BowSide stage_bow_side(StageWriter& stg, const uint8_t* valid, int n, con
 // n == max_targets (T) and m == max_queries (Q). Which one that is depends on T : Q, hence three sums (every other entry point stages a subset of
 // the first): the host form of projection::match_frame_and_keyframe (with the stereo_x_right that match_current_and_last_frames adds),
 // the host form of robust::match_for_triangulation, and the host form of projection::match_keyframes_mutually (n1, n2 <= min(T, Q)).
+// (tracking_module::search_local_landmarks stages no query keypoints, radius or level window but the search flags and the double reprojection:
+// 121 bytes per query against the first sum's 141, in 13 placements against its 15.)
 // tests/test_match_window_plan.py proves stage_need_* <= stage_capacity.
 inline size_t stage_capacity(size_t T, size_t Q) {
     const size_t N = std::min(T, Q);
@@ -558,6 +610,12 @@ inline size_t stage_need_frame_and_landmarks(StageWriter& stg, const StageSource
     TargetRef r;
     (void)stage_target(stg, stage_need_handle(s, resident, false, &r), s.kps, s.u8, s.f32, nullptr, n);
     (void)stage_landmark_queries(stg, s.u8, n, s.f32, s.f32, s.i32, s.u8, s.u8, m);
+    return stg.used;
+}
+inline size_t stage_need_search_local(StageWriter& stg, const StageSources& s, int n, int m, bool resident) {
+    TargetRef r;
+    (void)stage_target(stg, stage_need_handle(s, resident, false, &r), s.kps, s.u8, s.f32, nullptr, n);
+    (void)stage_local_landmarks(stg, s.u8, n, s.f64, s.f32, s.f64, s.u8, s.u8, m, true);
     return stg.used;
 }
 inline size_t stage_need_area(StageWriter& stg, const StageSources& s, int n, int m, bool resident) {   // n2 = n targets, n1 = m queries

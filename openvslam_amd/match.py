@@ -217,6 +217,42 @@ class projection(_window_ctx):
             float(margin), self.lowe_ratio_, _p(assigned), C.byref(n)), "ovs_projection_match_frame_and_landmarks")
         return assigned[:len(xy)].copy(), n.value
 
+    def search_local_landmarks(self, cam, gp, frm_keypts, frm_desc, pose_cw, lm_pos_w, lm_dist_min_max, lm_normal, lm_desc, scale_factors,
+                               log_scale_factor, margin=5.0, frm_stereo_x_right=None, frm_occupied=None, lm_search=None, fields=True):
+        """tracking_module::search_local_landmarks behind its first loop: frame::can_observe of every local landmark and
+        projection::match_frame_and_landmarks on the survivors in one device call. frm_keypts may be a frame_dev (gp, frm_desc and
+        frm_stereo_x_right are then the handle's). Returns (assigned, num_matches, observable, fields) with fields = None, or with
+        fields=True the dict {"reproj", "x_right", "level", "num_observable"} (reproj_in_tracking_ as doubles, x_right_in_tracking_,
+        scale_level_in_tracking_)."""
+        pw = np.ascontiguousarray(lm_pos_w, np.float64).reshape(-1, 3)
+        dm = np.ascontiguousarray(lm_dist_min_max, np.float32).reshape(-1, 2)
+        nr = np.ascontiguousarray(lm_normal, np.float64).reshape(-1, 3)
+        ld = np.ascontiguousarray(lm_desc, np.uint8).reshape(-1, 32)
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        occ = None if frm_occupied is None else np.ascontiguousarray(frm_occupied, np.uint8)
+        srch = None if lm_search is None else np.ascontiguousarray(lm_search, np.uint8)
+        m = len(pw)
+        observable = np.zeros(max(m, 1), np.uint8)
+        assigned = np.full(max(m, 1), -1, np.int32)
+        reproj = np.zeros((max(m, 1), 2), np.float64) if fields else None
+        x_right = np.full(max(m, 1), -1.0, np.float32) if fields else None
+        level = np.zeros(max(m, 1), np.int32) if fields else None
+        n_obs, n = C.c_int32(), C.c_int32()
+        tail = (_p(pw), _p(dm), _p(nr), _p(ld), _p(srch), m, _p(sf), len(sf), float(log_scale_factor), float(margin), self.lowe_ratio_,
+                _p(observable), _p(reproj), _p(x_right), _p(level), _p(assigned), C.byref(n_obs), C.byref(n))
+        if isinstance(frm_keypts, frame_dev):
+            _lib.check(self._L.ovs_tracking_search_local_landmarks_f(self._h, C.byref(cam), frm_keypts._h, _p(occ), _p(_pose12(pose_cw)), *tail),
+                       "ovs_tracking_search_local_landmarks_f")
+        else:
+            k = np.ascontiguousarray(frm_keypts, KP_DTYPE)
+            d = np.ascontiguousarray(frm_desc, np.uint8).reshape(-1, 32)
+            xr = None if frm_stereo_x_right is None else np.ascontiguousarray(frm_stereo_x_right, np.float32)
+            _lib.check(self._L.ovs_tracking_search_local_landmarks(self._h, C.byref(cam), C.byref(gp), _p(k), _p(d), _p(xr), _p(occ), len(k),
+                                                                   _p(_pose12(pose_cw)), *tail), "ovs_tracking_search_local_landmarks")
+        out = None
+        if fields:
+            out = {"reproj": reproj[:m].copy(), "x_right": x_right[:m].copy(), "level": level[:m].copy(), "num_observable": n_obs.value}
+        return assigned[:m].copy(), n.value, observable[:m].copy(), out
 
     def match_current_and_last_frames(self, cam, gp, curr_keypts, curr_desc, pose_cw_curr, last_keypts, last_pos_w, last_lm_desc,
                                       pose_cw_last, scale_factors, margin, curr_stereo_x_right=None, curr_occupied=None, last_valid=None):
