@@ -1,36 +1,39 @@
-// ba_graph.hip -- B1-B4 without atomics: a local-BA graph resident in HBM (edges indexed by landmark and by keyframe once per edge set),
-// deterministic linearisation, landmark elimination (Schur complement) and back-substitution on the device
-// (expected: src/openvslam/optimize/local_bundle_adjuster.cc; g2o BlockSolver_6_3::buildSystem / ::solve, OptimizationAlgorithmLevenberg).
-//
-// Why: k_ba_linearize issued 1.2 M scattered fp64 atomics per linearisation (0.022 of HBM, sums that change from
-// run to run), and ovs_local_ba_optimize downloaded 16 MB of blocks per Levenberg-Marquardt trial to eliminate the landmarks on the host.
-// Here every sum has a fixed order:
-//   k_linearize      (round 5: ONE launch for the two independent halves below, which ran one after the other until then)
-//     lin_landmark   one lane per landmark walks ITS edges in ascending index (mono first, then stereo -- the oracle's association):
-//                    Hll | bl exactly as a sequential loop would add them, Hpl per edge, per-landmark chi2 partials;
-//     lin_pose       one workgroup per keyframe over ITS edges: 21 + 6 pose-block terms per lane, fixed-shape tree reduction;
-//   k_reduce_scalars chi2 (and the Levenberg-Marquardt start damping: max |H_jj|) by one workgroup, fixed tree; at the end of an LM trial
-//                    also the sum of the landmarks' gain-ratio terms (the former k_sum_1024);
-//   k_lm_prepare     (Hll + lambda I)^-1 per landmark and Y_e = W_e Hll^-1 per edge;
-//   k_schur          (round 5: one launch)
-//     schur_pair     one workgroup per pair of free keyframes (a, b >= a): S_ab = [a == b](Hpp_a + lambda I) - sum over the landmarks both
-//                    observe of Y_ea W_eb^T; the common landmarks are found on the device (k_edge_table: keyframe x landmark -> edge);
-//     schur_rhs      g_a = bp_a - sum over a's edges of Y_e bl_j, one workgroup per free keyframe;
-//   ba_solve.hip     Cholesky of the reduced camera system (round 4; ovs_local_ba_set_solver(1): on the host as in rounds 1-3 and in
-//                    BASELINE's north star -- then 0.7 MB come down and 5 KB go up per trial);
-//   k_trial_update   (round 5: one launch)
-//     pose_update    T <- exp(dx) T per free keyframe (g2o SE3Quat::exp as in ba_host_math.h se3_oplus), the 7-double records the
-//                    linearisation reads, the keyframes' part of the gain ratio's denominator -- one workgroup;
-//     backsub_landmark  dxl_j = Hll^-1 (bl_j - sum W_e^T dxp), the trial points X + dxl and the landmark's term of g2o's gain-ratio scale
-//                    (k_backsub: the same on increments uploaded by the host solver).
-// Round 6 (DESIGN.md section 3.6 has the measurements): one lane per EDGE on both sides of the linearisation and in the back-substitution; both
-// halves of a linearisation in ONE launch again (k_linearize2: the keyframe side fell from 218 to 78 VGPRs with one entry per thread), the
-// keyframes' blocks finished by extra workgroups of k_reduce_scalars; every 144-byte record (Hpl, Y) leaves through LDS as whole lines -- a lane
-// storing its own record issued nine partial-line requests, and those, not bytes, were what the kernels queued behind; the pairs' common
-// landmarks listed once per graph (k_pair_lists) and k_schur_l gathering its records cooperatively, whole rows of the pair table per XCD; the
-// chi-square gates (k_edge_gate) and the graph build's landmark-order pass (k_edges_by_slot, k_dup_check) on the device.
-// Round 5's three mergers are side-by-side only (a workgroup runs one of the two bodies, chosen by its index): the arithmetic of every block,
-// landmark and keyframe is what it was, the results are the same bits, and a trial is 332 instead of 386 us of kernels (profiles/r05ai_*).
+// ba_graph.hip -- a local-BA graph resident in HBM: the edge set indexed by landmark and by keyframe once per graph, then linearisation,
+// landmark elimination (Schur complement), the trial state and the chi-square gates on the device, without floating-point atomics: every sum
+// has a fixed order (expected: src/openvslam/optimize/local_bundle_adjuster.cc; g2o BlockSolver_6_3::buildSystem / ::solve,
+// OptimizationAlgorithmLevenberg). What the host side decides with integers -- arena layouts, the index build, the work partitions -- is
+// ba_graph_plan.inc; DESIGN.md section 3.6 has the measurements, docs/HISTORY.md how the kernels came to this shape.
+//   graph build (graph_create)
+//     k_edges_by_slot  the edge records in lm_edges' order and the landmark of every slot;
+//     k_dup_check      refuses a keyframe with two edges to one landmark (the smallest {landmark, keyframe} report wins);
+//   linearisation (ba_graph_linearize)
+//     k_linearize2     one lane per EDGE on both sides, one launch. Landmark workgroups (runs of whole landmarks, at most kLmSlots edges) add a
+//                      landmark's Hll | bl | chi2 terms in ascending edge index, mono before stereo -- the oracle's association; keyframe
+//                      workgroups (half a chunk of kPoseChunk entries of a keyframe's edge list each) write Hpl per edge, through LDS as whole
+//                      lines, and a fixed-shape tree sum of the 21 + 6 pose-block terms;
+//     k_reduce_scalars chi2 and the Levenberg-Marquardt start damping (max |H_jj|) by one workgroup, fixed tree; further workgroups add the
+//                      keyframes' half-chunk sums in ascending order into Hpp | bp; at the end of an LM trial also the sum of the landmarks'
+//                      gain-ratio terms;
+//   solver work space, once per graph (solver_workspace_create)
+//     k_edge_table     (free keyframe, landmark) -> edge or -1;
+//     k_pair_lists     the landmarks every pair of free keyframes shares, as (edge of a, edge of b) entries per (pair, wave): counted, then
+//     k_scan_i32       (behind an exclusive scan of the counts) written in the order k_schur's queue would meet them;
+//   landmark elimination (ba_graph_schur)
+//     k_lm_prepare     (Hll + lambda I)^-1 per landmark and Y_e = W_e Hll^-1 per edge;
+//     k_schur_l        S_ab = [a == b](Hpp_a + lambda I) - sum over the landmarks both observe of Y_ea W_eb^T, one workgroup per pair (a, b >= a)
+//                      of free keyframes reading its lists, whole rows of the pair table per XCD; g_a = bp_a - sum over a's edges of Y_e bl_j,
+//                      one workgroup per free keyframe, in the same launch;
+//     k_schur          the same with every pair's common landmarks found by a scan per trial (no lists: OVS_BA_SCHUR_LISTS=0, or a bound of
+//                      the lists beyond kPairListCap); the same bits;
+//   ba_solve.hip       Cholesky of the reduced camera system (ovs_local_ba_set_solver(1): on the host);
+//   trial state
+//     k_trial_update   workgroup 0: T <- exp(dx) T per free keyframe (g2o SE3Quat::exp as in ba_host_math.h se3_oplus), the 7-double records
+//                      the linearisation reads, the keyframes' part of the gain ratio's denominator; the others, one lane per edge over the
+//                      landmark partition: dxl_j = Hll^-1 (bl_j - sum W_e^T dxp), the trial points X + dxl and the landmarks' gain-ratio terms;
+//     k_backsub        the landmarks' half of it on increments uploaded by the host solver;
+//   chi-square gates
+//     k_edge_chi2      per-edge chi2 and the sign of the depth;
+//     k_edge_gate      local_bundle_adjuster's outlier verdicts and the graph's active mask (an inactive edge contributes exact zeros).
 // Per-edge arithmetic is ba_edge.h's, shared with k_ba_linearize: the oracle's expression sequence (every product individually rounded), so
 // Hpl, Hll and bl are bit-identical to the CPU oracle; Hpp, bp and chi2 are tree sums (1e-15 relative), identical from run to run.
 #include <algorithm>
@@ -44,10 +47,17 @@
 #include <vector>
 
 #include "ba_edge.h"
+#include "ba_graph_plan.inc"
 #include "ba_internal.h"
 #include "owned_internal.inc"
 
 namespace ovs {
+
+// the host fills EdgeRec (ba_graph_plan.inc), the kernels read GEdge: one record
+static_assert(sizeof(EdgeRec) == sizeof(GEdge) && offsetof(EdgeRec, pose) == offsetof(GEdge, pose) && offsetof(EdgeRec, pt) == offsetof(GEdge, pt) &&
+                  offsetof(EdgeRec, ox) == offsetof(GEdge, ox) && offsetof(EdgeRec, oy) == offsetof(GEdge, oy) &&
+                  offsetof(EdgeRec, oxr) == offsetof(GEdge, oxr) && offsetof(EdgeRec, w) == offsetof(GEdge, w),
+              "EdgeRec and GEdge differ");
 
 struct GraphDev {   // device views shared by the kernels
     const GEdge* edges;
@@ -81,8 +91,7 @@ struct GraphDev {   // device views shared by the kernels
 // order: a landmark's contributions are added in ascending edge index, mono before stereo, exactly as the sequential loop did (Hll, bl, chi2
 // partials: the same bits as rounds 2-5 and as the oracle); a keyframe's 27 terms are a fixed-shape tree per chunk of 512 edges, the chunks
 // added in ascending order by k_reduce_scalars (deterministic; not the tree of rounds 2-5: last-bit differences in Hpp / bp).
-constexpr int kPoseChunk = 512;     // entries of pose_edges per chunk (k_linearize2: two keyframe workgroups, one entry per thread)
-constexpr int kLmSlots = 256;       // edges per landmark workgroup
+// (kPoseChunk, entries of pose_edges per chunk, and kLmSlots, edges per landmark workgroup: ba_graph_plan.inc)
 
 // sum of x over the wave in lane 63: row_shr 1 / 2 / 4 / 8 inside the 16-lane rows, then row_bcast 15 / 31 -- data-parallel moves in the
 // vector ALU (two per double and step) instead of ds_bpermute round trips through the LDS crossbar (round 2-5's xor-shuffle tree: 324 of
@@ -1184,61 +1193,34 @@ using namespace ovs;
 struct ovs_ba_graph {
     int device = 0;
     int n_pose = 0, n_pt = 0, n_mono = 0, n_stereo = 0, n_free = 0;
-    std::vector<uint8_t> fixed;
-    std::vector<int32_t> slot, slot_pose;   // pose -> reduced-system block (-1 fixed); block -> pose
+    std::vector<int32_t> slot;   // pose -> reduced-system block (-1 fixed)
     // device: ONE allocation + ONE upload per graph (a dozen hipMalloc / hipMemcpy pairs cost more than the kernels of a whole LM trial)
     unsigned char* d_arena = nullptr;
     unsigned char* d_solver_arena = nullptr;
     size_t arena_cap = 0, solver_cap = 0;   // allocation sizes (the arenas come from / go back to g_ba_pool)
+    // ba_graph_plan.inc: where the arrays of the two arenas lie, and the work counts of the partitions
+    GraphArena lay{};
+    GraphPartition part{};
+    SolverArena sol{};
     GraphDev dev{};   // what the kernels see (arrays of d_arena, the partition's counts, the camera): filled once by graph_create
     // arrays of d_arena the solver path's launches name besides `dev`
-    uint8_t* d_active = nullptr;   // dev.active, writable (k_edge_gate)
     int32_t *d_pair_ab = nullptr, *d_slot_pose = nullptr, *d_slot_of_pose = nullptr;
-    int32_t* d_wg_pair = nullptr;   // [n_pair_wg] k_schur_l's work order: whole rows of the pair table per XCD, -1 = no pair
-    int n_pairs = 0, n_pair_wg = 0;
-    double* d_lm_tmp = nullptr;   // [4 n_pt] per-landmark partials: chi2 pair, max |diagonal|, the gain ratio's scale term
-    // the pairs' common landmarks (k_pair_lists): [4 n_pairs + 1] offsets, one (edge of a, edge of b) per entry; pl_bound = sum over the landmarks of
-    // n (n + 1) / 2, n = the landmark's edges (graph_create): no list can be longer
-    size_t pl_bound = 0;
-    bool pl_ready = false;   // the lists exist (solver work space created, bound within the cap)
+    int32_t* d_wg_pair = nullptr;   // [part.n_pair_wg] k_schur_l's work order: whole rows of the pair table per XCD, -1 = no pair
+    double* d_lm_tmp = nullptr;     // [4 n_pt] per-landmark partials: chi2 pair, max |diagonal|, the gain ratio's scale term
+    bool pl_ready = false;   // the pairs' common landmarks are listed (solver work space created, sol.pl_ok)
     // solver work space (d_solver_arena, allocated on first use: ovs_ba_graph_linearize_dev alone does not need it)
     double *d_Hinv = nullptr, *d_Y = nullptr, *d_S = nullptr, *d_rhs = nullptr, *d_dxp = nullptr, *d_scal = nullptr;
     int32_t* d_fail = nullptr;      // two failure words, 256 bytes behind d_scal
     int32_t* d_edge_of = nullptr;   // [n_free x n_pt]
-    int32_t *d_pl_cnt = nullptr, *d_pl_off = nullptr;
-    int2* d_pl_ent = nullptr;
-    int s_pitch = 0;   // doubles per row of d_S
+    int32_t *d_pl_cnt = nullptr, *d_pl_off = nullptr;   // [4 n_pairs + 1] the lists' lengths and offsets
+    int2* d_pl_ent = nullptr;                           // one (edge of a, edge of b) per entry
 
     const GraphDev& view() const { return dev; }
     int n_edge() const { return n_mono + n_stereo; }
+    uint8_t* d_active() const { return d_arena + lay.o_active; }   // dev.active, writable (k_edge_gate)
+    int n_unknowns() const { return 6 * std::max(n_free, 1); }
+    int s_pitch() const { return dense_solve_pad(n_unknowns()); }   // doubles per row of d_S
 };
-
-namespace {
-
-// `trial_scale`: the linearisation closes a Levenberg-Marquardt trial -- the landmarks' gain-ratio terms the back-substitution left in
-// d_lm_tmp[3 n_pt ..) are summed into d_scal[0] by the same launch that sums chi2
-ovs_status graph_linearize(ovs_ba_graph* g, const double* d_poses, const double* d_points, double huber_mono, double huber_stereo, double* d_Hpp,
-                           double* d_bp, double* d_Hll, double* d_bl, double* d_Hpl, double* d_chi3, hipStream_t s, double* d_chi_mirror = nullptr,
-                           bool trial_scale = false, unsigned long long* host_ll = nullptr, unsigned int seq = 0) {
-    const GraphDev& v = g->view();
-    // One launch for both halves (k_linearize2): config 5 0.0325 -> 0.0249 ms, a million edges 0.124 -> 0.1005 ms per linearisation against the
-    // two launches of rounds 5-6 (a launch and its gap less; the Hpl records leave through LDS as whole lines; the keyframe side's stores and the
-    // landmark side's LDS reductions overlap). Before the stores were coalesced the merged launch LOST at a million edges (0.131 against
-    // 0.125 ms): the partial-line write requests of the keyframe side were what both halves queued behind.
-    const unsigned n_wg = (unsigned)(2 * v.n_chunks + v.n_lm_wg);
-    if (v.model == 1)
-        hipLaunchKernelGGL(k_linearize2<1>, dim3(n_wg), dim3(256), 0, s, v, d_poses, d_points, huber_mono, huber_stereo, d_Hpl, d_Hll, d_bl, g->d_lm_tmp, d_chi3);
-    else
-        hipLaunchKernelGGL(k_linearize2<0>, dim3(n_wg), dim3(256), 0, s, v, d_poses, d_points, huber_mono, huber_stereo, d_Hpl, d_Hll, d_bl, g->d_lm_tmp, d_chi3);
-    OVS_LAUNCH_TRY("k_linearize2");
-    hipLaunchKernelGGL(k_reduce_scalars, dim3(1 + (27 * g->n_pose + 1023) / 1024), dim3(1024), 0, s, v, g->d_lm_tmp, d_chi3, d_chi_mirror,
-                       trial_scale ? g->d_lm_tmp + 3 * (size_t)g->n_pt : (const double*)nullptr, trial_scale ? g->d_scal : (double*)nullptr,
-                       trial_scale ? host_ll : (unsigned long long*)nullptr, seq, (const int32_t*)g->d_fail, d_Hpp, d_bp);
-    OVS_LAUNCH_TRY("k_reduce_scalars");
-    return OVS_OK;
-}
-
-}   // namespace
 
 // The two device arenas of a graph (5.8 MB + 18 MB at config 5) are recycled: mapping_module builds one graph per new keyframe, and a hipMalloc /
 // hipFree pair per arena cost ~0.3 ms of a 7.7 ms ovs_local_ba_optimize (hipFree synchronises the device). Per device, first fit among the few
@@ -1328,6 +1310,7 @@ ovs_status ovs_ba_graph_destroy(ovs_ba_graph* g) {
 static ovs_status graph_create(int model, int32_t device, int32_t n_pose, const uint8_t* pose_fixed, int32_t n_pt, const ovs_ba_edge* mono,
                                int32_t n_mono, const ovs_ba_edge_stereo* stereo, int32_t n_stereo, const ovs_ba_cam* cam, double focal_x_baseline,
                                ovs_ba_graph** out) {
+    // 1. the arguments
     if (!out || !cam || n_pose < 1 || n_pt < 1 || n_mono < 0 || n_stereo < 0 || (n_mono > 0 && !mono) || (n_stereo > 0 && !stereo))
         return OVS_ERR_INVALID;
     *out = nullptr;
@@ -1339,231 +1322,130 @@ static ovs_status graph_create(int model, int32_t device, int32_t n_pose, const 
     std::unique_ptr<ovs_ba_graph, decltype(&ovs_ba_graph_destroy)> owner(new (std::nothrow) ovs_ba_graph(), &ovs_ba_graph_destroy);
     ovs_ba_graph* const g = owner.get();
     if (!g) return OVS_ERR_INVALID;
+    const int ne = n_mono + n_stereo;
     g->device = device;
     g->n_pose = n_pose;
     g->n_pt = n_pt;
     g->n_mono = n_mono;
     g->n_stereo = n_stereo;
-    g->fixed.assign((size_t)n_pose, 0);
-    if (pose_fixed) g->fixed.assign(pose_fixed, pose_fixed + n_pose);
-    g->slot.assign((size_t)n_pose, -1);
-    for (int k = 0; k < n_pose; ++k)
-        if (!g->fixed[k]) {
-            g->slot[k] = g->n_free++;
-            g->slot_pose.push_back(k);
-        }
-    const int ne = n_mono + n_stereo;
-    // The build's temporaries and the host image of the arena belong to the calling thread and keep their pages between calls (mapping_module
-    // builds a graph per keyframe: 13 MB of fresh vectors per call were ~3000 page faults, most of the build's 0.6 ms on the host -- round 5).
-    // The image is laid out first and filled in place: no per-array vector, no second copy.
-    // Round 6: the image is page-locked, so the edge records (4.8 of the 6.0 MB at config 5) go up while the host is still sorting.
+
+    // 2. the plan (ba_graph_plan.inc). The build's temporaries and the host image of the arena belong to the calling thread and keep their
+    // pages between calls: mapping_module builds a graph per keyframe, and 13 MB of fresh vectors per call were ~3000 page faults, most of
+    // the build's host time. The image is page-locked, so the edge records (4.0 of the 5.6 MB at config 5) go up while the host is still
+    // sorting; it is laid out like the arena and filled in place: no per-array vector, no second copy.
     struct Scratch {
-        std::vector<int32_t> edge_pose, edge_pt, fl, fp;
+        std::vector<int32_t> slot_pose, edge_pose, edge_pt, lm_cursor, pose_cursor;
         ovs::PinnedBuffer image;
     };
     static thread_local Scratch sc;
-    // One layout for the host image and the device arena: the arrays the host fills (uploaded as they are), then, on the device, scratch the
-    // kernels write; in the image, only the word the duplicate check's verdict comes down to.
-    ovs::ArenaLayout lay;
-    const int nf = g->n_free, n_pairs = nf * (nf + 1) / 2;
-    const size_t max_chunks = (size_t)ne / kPoseChunk + (size_t)n_pose;   // (an upper bound: the partition is built below, from the counting sorts)
-    const size_t o_edges = lay.place<GEdge>((size_t)ne), o_lm_start = lay.place<int32_t>((size_t)n_pt + 1), o_lm_edges = lay.place<int32_t>((size_t)ne),
-                 o_lm_nmono = lay.place<int32_t>((size_t)n_pt), o_pose_start = lay.place<int32_t>((size_t)n_pose + 1),
-                 o_pose_edges = lay.place<int32_t>((size_t)ne), o_fixed = lay.place<uint8_t>((size_t)n_pose), o_active = lay.place<uint8_t>((size_t)ne),
-                 o_slot_of_pose = lay.place<int32_t>((size_t)n_pose), o_pose_pt = lay.place<int32_t>((size_t)ne),
-                 o_pair_ab = lay.place<int32_t>(2 * (size_t)n_pairs), o_slot_pose = lay.place<int32_t>((size_t)nf),
-                 o_wg_pair = lay.place<int32_t>(8 * ((size_t)n_pairs / 8 + (size_t)nf + 1)), o_lm_wg_first = lay.place<int32_t>((size_t)n_pt + 1),
-                 o_chunk_kf = lay.place<int32_t>(max_chunks), o_chunk_start = lay.place<int32_t>((size_t)n_pose + 1);
-    const size_t upload_bytes = lay.bytes();   // what the device reads before writing it ends here
-    ovs::ArenaLayout host = lay;
-    const size_t o_dup_host = host.place<unsigned long long>(1), image_bytes = host.bytes();
-    const size_t o_lm_of_slot = lay.place<int32_t>((size_t)ne), o_dup = lay.place<unsigned long long>(1), o_lm_tmp = lay.place<double>(4 * (size_t)n_pt),
-                 o_pose_part = lay.place<double>(27 * 2 * max_chunks),   // (k_linearize2: one sum per HALF chunk)
-                 o_ledges = lay.place<GEdge>((size_t)ne);
-    const size_t arena_bytes = lay.bytes();
-    OVS_HIP_TRY_RAW(sc.image.ensure(image_bytes, image_bytes + image_bytes / 4));   // (head room: the next local map is a little larger more often than not)
+    auto at_least = [](std::vector<int32_t>& v, int n) {
+        if (v.size() < (size_t)n) v.resize((size_t)n);
+        return v.data();
+    };
+    g->slot.resize((size_t)n_pose);
+    const int nf = g->n_free = assign_slots(pose_fixed, n_pose, g->slot.data(), at_least(sc.slot_pose, n_pose));
+    g->lay = graph_arena_of(n_pose, n_pt, ne, nf);
+    const GraphArena& L = g->lay;
+    GraphPartition& part = g->part;
+
+    // 3. the arena
+    OVS_HIP_TRY_RAW(sc.image.ensure(L.image_bytes, L.image_bytes + L.image_bytes / 4));   // (head room: the next local map is a little larger more often than not)
     unsigned char* const img = sc.image.p;
-    g->d_arena = g_ba_pool.take(device, arena_bytes, &g->arena_cap);
+    g->d_arena = g_ba_pool.take(device, L.arena_bytes, &g->arena_cap);
     OVS_HIP_TRY_RAW(g->d_arena ? hipSuccess : hipErrorOutOfMemory);
+
+    // 4. the kernels' view and the handle's own pointers, once
     using AL = ovs::ArenaLayout;
     unsigned char* const A = g->d_arena;
-    {   // the kernels' view and the handle's own pointers, once
-        GraphDev& v = g->dev;
-        v.edges = AL::at<GEdge>(A, o_edges);
-        v.n_mono = n_mono;
-        v.n_edge = ne;
-        v.n_pose = n_pose;
-        v.n_pt = n_pt;
-        v.lm_start = AL::at<int32_t>(A, o_lm_start);
-        v.lm_edges = AL::at<int32_t>(A, o_lm_edges);
-        v.lm_nmono = AL::at<int32_t>(A, o_lm_nmono);
-        v.pose_start = AL::at<int32_t>(A, o_pose_start);
-        v.pose_edges = AL::at<int32_t>(A, o_pose_edges);
-        v.pose_pt = AL::at<int32_t>(A, o_pose_pt);
-        v.fixed = AL::at<uint8_t>(A, o_fixed);
-        v.active = g->d_active = AL::at<uint8_t>(A, o_active);
-        v.ledges = AL::at<GEdge>(A, o_ledges);
-        v.lm_of_slot = AL::at<int32_t>(A, o_lm_of_slot);
-        v.lm_wg_first = AL::at<int32_t>(A, o_lm_wg_first);
-        v.chunk_kf = AL::at<int32_t>(A, o_chunk_kf);
-        v.chunk_start = AL::at<int32_t>(A, o_chunk_start);
-        v.pose_part = AL::at<double>(A, o_pose_part);
-        v.cam = *cam;
-        v.bf = focal_x_baseline;
-        v.model = model;
-        g->d_lm_tmp = AL::at<double>(A, o_lm_tmp);
-        g->d_slot_of_pose = AL::at<int32_t>(A, o_slot_of_pose);
-        if (nf > 0) {
-            g->d_pair_ab = AL::at<int32_t>(A, o_pair_ab);
-            g->d_wg_pair = AL::at<int32_t>(A, o_wg_pair);
-            g->d_slot_pose = AL::at<int32_t>(A, o_slot_pose);
-        }
+    GraphDev& v = g->dev;
+    v.edges = AL::at<GEdge>(A, L.o_edges);
+    v.n_mono = n_mono;
+    v.n_edge = ne;
+    v.n_pose = n_pose;
+    v.n_pt = n_pt;
+    v.lm_start = AL::at<int32_t>(A, L.o_lm_start);
+    v.lm_edges = AL::at<int32_t>(A, L.o_lm_edges);
+    v.lm_nmono = AL::at<int32_t>(A, L.o_lm_nmono);
+    v.pose_start = AL::at<int32_t>(A, L.o_pose_start);
+    v.pose_edges = AL::at<int32_t>(A, L.o_pose_edges);
+    v.pose_pt = AL::at<int32_t>(A, L.o_pose_pt);
+    v.fixed = AL::at<uint8_t>(A, L.o_fixed);
+    v.active = g->d_active();
+    v.ledges = AL::at<GEdge>(A, L.o_ledges);
+    v.lm_of_slot = AL::at<int32_t>(A, L.o_lm_of_slot);
+    v.lm_wg_first = AL::at<int32_t>(A, L.o_lm_wg_first);
+    v.chunk_kf = AL::at<int32_t>(A, L.o_chunk_kf);
+    v.chunk_start = AL::at<int32_t>(A, L.o_chunk_start);
+    v.pose_part = AL::at<double>(A, L.o_pose_part);
+    v.cam = *cam;
+    v.bf = focal_x_baseline;
+    v.model = model;
+    g->d_lm_tmp = AL::at<double>(A, L.o_lm_tmp);
+    g->d_slot_of_pose = AL::at<int32_t>(A, L.o_slot_of_pose);
+    if (nf > 0) {
+        g->d_pair_ab = AL::at<int32_t>(A, L.o_pair_ab);
+        g->d_wg_pair = AL::at<int32_t>(A, L.o_wg_pair);
+        g->d_slot_pose = AL::at<int32_t>(A, L.o_slot_pose);
     }
-    GEdge* const edges = AL::at<GEdge>(img, o_edges);
-    int32_t *const lm_start = AL::at<int32_t>(img, o_lm_start), *const lm_edges = AL::at<int32_t>(img, o_lm_edges),
-                   *const lm_nmono = AL::at<int32_t>(img, o_lm_nmono), *const pose_start = AL::at<int32_t>(img, o_pose_start),
-                   *const pose_edges = AL::at<int32_t>(img, o_pose_edges), *const pose_pt = AL::at<int32_t>(img, o_pose_pt);
-    if (sc.edge_pose.size() < (size_t)ne) {
-        sc.edge_pose.resize((size_t)ne);
-        sc.edge_pt.resize((size_t)ne);
-    }
-    int32_t* const edge_pose = sc.edge_pose.data();
-    int32_t* const edge_pt = sc.edge_pt.data();
-    // counting sorts: ascending edge index inside every landmark / keyframe (mono edges have the lower indices, so "mono first" is free).
-    // Four passes over the edges in all (round 6: the histograms ride on the record fill, pose_pt on the scatter, the landmark of a slot on the
-    // duplicate check -- eight passes were 0.69 ms of a 6 ms ovs_local_ba_optimize at config 5).
-    std::memset(lm_start, 0, sizeof(int32_t) * ((size_t)n_pt + 1));
-    std::memset(lm_nmono, 0, sizeof(int32_t) * (size_t)n_pt);
-    std::memset(pose_start, 0, sizeof(int32_t) * ((size_t)n_pose + 1));
-    bool bad_index = false;   // (round 6: the range check rides on the first pass instead of being a pass of its own)
-    for (int i = 0; i < n_mono; ++i) {
-        const int32_t kp = mono[i].pose_idx, pt = mono[i].point_idx;
-        if ((uint32_t)kp >= (uint32_t)n_pose || (uint32_t)pt >= (uint32_t)n_pt) {
-            bad_index = true;
-            break;
-        }
-        edges[i] = GEdge{kp, pt, mono[i].obs_x, mono[i].obs_y, 0.0, mono[i].inv_sigma_sq};
-        edge_pose[i] = kp;
-        edge_pt[i] = pt;
-        ++lm_start[(size_t)pt + 1];
-        ++lm_nmono[pt];
-        ++pose_start[(size_t)kp + 1];
-    }
-    for (int i = 0; i < n_stereo && !bad_index; ++i) {
-        const int32_t kp = stereo[i].pose_idx, pt = stereo[i].point_idx;
-        if ((uint32_t)kp >= (uint32_t)n_pose || (uint32_t)pt >= (uint32_t)n_pt) {
-            bad_index = true;
-            break;
-        }
-        edges[(size_t)n_mono + i] = GEdge{kp, pt, stereo[i].obs_x, stereo[i].obs_y, stereo[i].obs_x_right, stereo[i].inv_sigma_sq};
-        edge_pose[(size_t)n_mono + i] = kp;
-        edge_pt[(size_t)n_mono + i] = pt;
-        ++lm_start[(size_t)pt + 1];
-        ++pose_start[(size_t)kp + 1];
-    }
-    if (bad_index) {
+
+    // 5. pass 1: the records, the histograms, the range check
+    int32_t *const lm_start = AL::at<int32_t>(img, L.o_lm_start), *const pose_start = AL::at<int32_t>(img, L.o_pose_start);
+    int32_t *const edge_pose = at_least(sc.edge_pose, ne), *const edge_pt = at_least(sc.edge_pt, ne);
+    if (index_pass1(mono, n_mono, stereo, n_stereo, n_pose, n_pt, AL::at<EdgeRec>(img, L.o_edges), edge_pose, edge_pt, lm_start,
+                    AL::at<int32_t>(img, L.o_lm_nmono), pose_start) >= 0) {
         ovs::set_last_error_text("ovs_ba_graph_create: an edge's keyframe or landmark index is out of range");
         return OVS_ERR_INVALID;
     }
     const double t_p1 = now();
-    // the records are final: they travel (null stream, page-locked source: the call returns at once) under the remaining passes
-    const size_t early_bytes = o_lm_start;   // (the records are the image's first array: they end where the next one starts)
-    if (ne > 0) OVS_HIP_TRY_RAW(hipMemcpyAsync(g->d_arena, img, early_bytes, hipMemcpyHostToDevice, nullptr));
-    for (int j = 0; j < n_pt; ++j) lm_start[(size_t)j + 1] += lm_start[j];
-    for (int k = 0; k < n_pose; ++k) pose_start[(size_t)k + 1] += pose_start[k];
-    sc.fl.assign(lm_start, lm_start + n_pt);
-    sc.fp.assign(pose_start, pose_start + n_pose);
-    for (int e = 0; e < ne; ++e) {
-        const int32_t pt = edge_pt[e];
-        lm_edges[(size_t)sc.fl[pt]++] = e;
-        const int32_t at = sc.fp[edge_pose[e]]++;
-        pose_edges[(size_t)at] = e;
-        pose_pt[(size_t)at] = pt;   // the landmark of every entry of pose_edges: k_schur's pair blocks and k_linearize2 walk a keyframe's observations without the 48-byte records
-    }
+
+    // 6. the records are final: they travel (null stream, page-locked source: the call returns at once) under the remaining passes
+    if (ne > 0) OVS_HIP_TRY_RAW(hipMemcpyAsync(A, img, L.early_bytes, hipMemcpyHostToDevice, nullptr));
+
+    // 7. pass 2, the partitions, the other arrays
+    index_pass2(edge_pose, edge_pt, ne, n_pose, n_pt, lm_start, pose_start, at_least(sc.lm_cursor, n_pt), at_least(sc.pose_cursor, n_pose),
+                AL::at<int32_t>(img, L.o_lm_edges), AL::at<int32_t>(img, L.o_pose_edges), AL::at<int32_t>(img, L.o_pose_pt));
     const double t_p2 = now();
-    // k_linearize2's landmark partition: runs of whole landmarks with at most kLmSlots edges (and 256 landmarks). (The landmark of every slot and
-    // the check that a keyframe observes a landmark at most once -- upstream: landmark::add_observation ignores a second observation by the same
-    // keyframe; the reduced system relies on it: k_edge_table keeps ONE edge per (keyframe, landmark), two edges of one free keyframe to one
-    // landmark would need cross terms while Hpp / Hll / rhs would still count both, so such an edge list is refused -- moved to the device in
-    // round 6: k_edges_by_slot, k_dup_check below.)
-    {
-        int32_t* const wg_first = AL::at<int32_t>(img, o_lm_wg_first);
-        int n_wg = 0, first = 0;
-        size_t pl_bound = 0;
-        for (int j = 0; j < n_pt; ++j) {
-            const size_t nj = (size_t)(lm_start[(size_t)j + 1] - lm_start[j]);
-            pl_bound += nj * (nj + 1) / 2;
-            if (j > first && (lm_start[(size_t)j + 1] - lm_start[first] > kLmSlots || j - first >= 256)) {   // j does not fit: it opens the next run
-                wg_first[n_wg++] = first;
-                first = j;
-            }
-        }
-        wg_first[n_wg++] = first;
-        wg_first[n_wg] = n_pt;
-        g->dev.n_lm_wg = n_wg;
-        g->pl_bound = pl_bound;
-        // k_linearize2's keyframe side: chunks of kPoseChunk entries of a keyframe's edge list (two workgroups each)
-        int32_t *const chunk_kf = AL::at<int32_t>(img, o_chunk_kf), *const chunk_start = AL::at<int32_t>(img, o_chunk_start);
-        int n_ch = 0;
-        for (int k = 0; k < n_pose; ++k) {
-            chunk_start[k] = n_ch;
-            for (int i = pose_start[k]; i < pose_start[(size_t)k + 1]; i += kPoseChunk) chunk_kf[n_ch++] = k;
-        }
-        chunk_start[n_pose] = n_ch;
-        g->dev.n_chunks = n_ch;
-    }
+    partition_landmarks(lm_start, n_pt, AL::at<int32_t>(img, L.o_lm_wg_first), part);
+    partition_chunks(pose_start, n_pose, AL::at<int32_t>(img, L.o_chunk_kf), AL::at<int32_t>(img, L.o_chunk_start), part);
+    v.n_lm_wg = part.n_lm_wg;
+    v.n_chunks = part.n_chunks;
     const double t1 = now();
-    std::memcpy(img + o_fixed, g->fixed.data(), (size_t)n_pose);
-    std::memset(img + o_active, 1, (size_t)std::max(ne, 1));
-    std::memcpy(img + o_slot_of_pose, g->slot.data(), sizeof(int32_t) * (size_t)n_pose);   // keyframe -> block of the reduced system or -1
-    // reduced system: the blocks (a, b), a <= b in slot order, one workgroup each (which landmarks two keyframes share is found on the device)
-    if (nf > 0) {
-        int32_t* const pab = AL::at<int32_t>(img, o_pair_ab);
-        // a-major: a row (a, a .. nf - 1) stays together (k_schur_l hands contiguous runs of pairs to one XCD) and starts with its longest list,
-        // the diagonal pair's (all of a's landmarks). "All diagonal pairs first" was measured: no change.
-        int p = 0;
-        for (int a = 0; a < nf; ++a)
-            for (int b = a; b < nf; ++b) {
-                pab[(size_t)2 * p] = a;
-                pab[(size_t)2 * p + 1] = b;
-                ++p;
-            }
-        g->n_pairs = n_pairs;
-        // k_schur_l's work order. Rows are dealt to the eight XCDs in serpentine order (rows 0 .. 7 to XCDs 0 .. 7, rows 8 .. 15 to XCDs 7 .. 0,
-        // ...: row a has nf - a pairs, so the eight sums come out within a row's length of each other); XCD x's i-th pair is workgroup 8 i + x.
-        {
-            int32_t* const wp = AL::at<int32_t>(img, o_wg_pair);
-            int fill[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            const int cap = n_pairs / 8 + nf + 1;
-            for (int i = 0; i < 8 * cap; ++i) wp[i] = -1;
-            int first = 0;   // index of pair (a, a)
-            for (int a = 0; a < nf; ++a) {
-                const int x = ((a >> 3) & 1) ? 7 - (a & 7) : (a & 7);
-                for (int b = a; b < nf; ++b) wp[(size_t)8 * fill[x]++ + x] = first + (b - a);
-                first += nf - a;
-            }
-            g->n_pair_wg = 8 * *std::max_element(fill, fill + 8);
-        }
-        std::memcpy(img + o_slot_pose, g->slot_pose.data(), sizeof(int32_t) * (size_t)nf);
+    if (pose_fixed) std::memcpy(img + L.o_fixed, pose_fixed, (size_t)n_pose);
+    else std::memset(img + L.o_fixed, 0, (size_t)n_pose);
+    std::memset(img + L.o_active, 1, (size_t)std::max(ne, 1));
+    std::memcpy(img + L.o_slot_of_pose, g->slot.data(), sizeof(int32_t) * (size_t)n_pose);
+    if (nf > 0) {   // the reduced system's blocks, one workgroup each (which landmarks two keyframes share is found on the device)
+        pair_table(nf, AL::at<int32_t>(img, L.o_pair_ab));
+        pair_work_order(nf, AL::at<int32_t>(img, L.o_wg_pair), part);
+        std::memcpy(img + L.o_slot_pose, sc.slot_pose.data(), sizeof(int32_t) * (size_t)nf);
     }
     const double t2 = now();
+
+    // 8. the rest of the upload
     {
-        const size_t from = ne > 0 ? early_bytes : 0;
-        if (upload_bytes > from) OVS_HIP_TRY_RAW(hipMemcpyAsync(g->d_arena + from, img + from, upload_bytes - from, hipMemcpyHostToDevice, nullptr));
+        const size_t from = ne > 0 ? L.early_bytes : 0;
+        if (L.upload_bytes > from) OVS_HIP_TRY_RAW(hipMemcpyAsync(A + from, img + from, L.upload_bytes - from, hipMemcpyHostToDevice, nullptr));
     }
+
+    // 9. the landmark-order pass on the device: the records and the landmark of every slot in lm_edges' order, and the check that a keyframe
+    // observes a landmark at most once. Upstream's landmark::add_observation ignores a second observation by the same keyframe, and the reduced
+    // system relies on it: k_edge_table keeps ONE edge per (keyframe, landmark); two edges of one free keyframe to one landmark would need
+    // cross terms while Hpp / Hll / rhs would still count both, so such an edge list is refused.
     if (ne > 0) {   // null stream: ordered behind the upload above and before whatever stream the caller linearises on (the wait costs ~10 us)
-        unsigned long long* const d_dup = AL::at<unsigned long long>(A, o_dup);
-        hipLaunchKernelGGL(k_edges_by_slot, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, nullptr, g->dev.edges, g->dev.lm_edges, ne,
-                           AL::at<GEdge>(A, o_ledges), AL::at<int32_t>(A, o_lm_of_slot), d_dup);
+        unsigned long long* const d_dup = AL::at<unsigned long long>(A, L.o_dup);
+        hipLaunchKernelGGL(k_edges_by_slot, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, nullptr, v.edges, v.lm_edges, ne, AL::at<GEdge>(A, L.o_ledges),
+                           AL::at<int32_t>(A, L.o_lm_of_slot), d_dup);
         OVS_HIP_TRY_RAW(hipGetLastError());
-        hipLaunchKernelGGL(k_dup_check, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, nullptr, g->dev.ledges, g->dev.lm_start, ne, d_dup);
+        hipLaunchKernelGGL(k_dup_check, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, nullptr, v.ledges, v.lm_start, ne, d_dup);
         OVS_HIP_TRY_RAW(hipGetLastError());
-        OVS_HIP_TRY_RAW(hipMemcpyAsync(img + o_dup_host, d_dup, sizeof(unsigned long long), hipMemcpyDeviceToHost, nullptr));
+        OVS_HIP_TRY_RAW(hipMemcpyAsync(img + L.o_dup_host, d_dup, sizeof(unsigned long long), hipMemcpyDeviceToHost, nullptr));
     }
     OVS_HIP_TRY_RAW(hipStreamSynchronize(nullptr));   // the image is this thread's next graph's as well: nothing of it may still be on its way
+
+    // 10. the verdict
     if (ne > 0) {
         unsigned long long dup;
-        std::memcpy(&dup, img + o_dup_host, sizeof(dup));
+        std::memcpy(&dup, img + L.o_dup_host, sizeof(dup));
         if (dup != ~0ull) {
             ovs::set_last_error_text("ovs_ba_graph_create: keyframe " + std::to_string((uint32_t)dup) + " has two edges to landmark " +
                                      std::to_string((uint32_t)(dup >> 32)));
@@ -1573,7 +1455,7 @@ static ovs_status graph_create(int model, int32_t device, int32_t n_pose, const 
     if (trace)
         std::fprintf(stderr, "[ovs_ba_graph_create] %.2f ms: edge records + histograms %.2f, scatter %.2f, landmark-order pass %.2f, other arrays %.2f, rest of "
                              "the %.1f MB upload + k_edges_by_slot %.2f\n",
-                     now() - t0, t_p1 - t0, t_p2 - t_p1, t1 - t_p2, t2 - t1, upload_bytes / 1e6, now() - t2);
+                     now() - t0, t_p1 - t0, t_p2 - t_p1, t1 - t_p2, t2 - t1, L.upload_bytes / 1e6, now() - t2);
     *out = owner.release();
     return OVS_OK;
 }
@@ -1595,7 +1477,7 @@ ovs_status ovs_ba_graph_linearize_dev(ovs_ba_graph* g, const double* d_poses, co
                                       double* d_Hpp, double* d_bp, double* d_Hll, double* d_bl, double* d_Hpl, double* d_chi2, void* stream) {
     if (!g || !d_poses || !d_points || !d_Hpp || !d_bp || !d_Hll || !d_bl || !d_Hpl || !d_chi2) return OVS_ERR_INVALID;
     OVS_HIP_TRY(hipSetDevice(g->device));
-    return graph_linearize(g, d_poses, d_points, huber_mono, huber_stereo, d_Hpp, d_bp, d_Hll, d_bl, d_Hpl, d_chi2, (hipStream_t)stream);
+    return ba_graph_linearize(g, d_poses, d_points, huber_mono, huber_stereo, d_Hpp, d_bp, d_Hll, d_bl, d_Hpl, d_chi2, (hipStream_t)stream);
 }
 
 }   // extern "C"
@@ -1604,6 +1486,27 @@ ovs_status ovs_ba_graph_linearize_dev(ovs_ba_graph* g, const double* d_poses, co
 // Levenberg-Marquardt on top of the graph (used by ovs_local_ba_optimize in ba_optimize.hip)
 // ---------------------------------------------------------------------------------------------------------------------------
 namespace ovs {
+
+// `trial_scale`: the linearisation closes a Levenberg-Marquardt trial -- the landmarks' gain-ratio terms the back-substitution left in
+// d_lm_tmp[3 n_pt ..) are summed into d_scal[0] by the same launch that sums chi2
+ovs_status ba_graph_linearize(ovs_ba_graph* g, const double* d_poses, const double* d_points, double huber_mono, double huber_stereo, double* d_Hpp,
+                              double* d_bp, double* d_Hll, double* d_bl, double* d_Hpl, double* d_chi3, hipStream_t s, double* d_chi_mirror,
+                              bool trial_scale, unsigned long long* host_ll, unsigned int seq) {
+    const GraphDev& v = g->view();
+    // One launch for both halves (k_linearize2): a launch and its gap less than two, the Hpl records leave through LDS as whole lines, and the
+    // keyframe side's stores overlap the landmark side's LDS reductions (config 5: 0.0249 against 0.0325 ms per linearisation).
+    const unsigned n_wg = (unsigned)(2 * v.n_chunks + v.n_lm_wg);
+    if (v.model == 1)
+        hipLaunchKernelGGL(k_linearize2<1>, dim3(n_wg), dim3(256), 0, s, v, d_poses, d_points, huber_mono, huber_stereo, d_Hpl, d_Hll, d_bl, g->d_lm_tmp, d_chi3);
+    else
+        hipLaunchKernelGGL(k_linearize2<0>, dim3(n_wg), dim3(256), 0, s, v, d_poses, d_points, huber_mono, huber_stereo, d_Hpl, d_Hll, d_bl, g->d_lm_tmp, d_chi3);
+    OVS_LAUNCH_TRY("k_linearize2");
+    hipLaunchKernelGGL(k_reduce_scalars, dim3(1 + (27 * g->n_pose + 1023) / 1024), dim3(1024), 0, s, v, g->d_lm_tmp, d_chi3, d_chi_mirror,
+                       trial_scale ? g->d_lm_tmp + 3 * (size_t)g->n_pt : (const double*)nullptr, trial_scale ? g->d_scal : (double*)nullptr,
+                       trial_scale ? host_ll : (unsigned long long*)nullptr, seq, (const int32_t*)g->d_fail, d_Hpp, d_bp);
+    OVS_LAUNCH_TRY("k_reduce_scalars");
+    return OVS_OK;
+}
 
 // The reduced camera system is stored the way the device solver wants it (ba_solve.hip): pitch n_pad = 6 n_free rounded up to 16, an identity
 // block on the padding, the right-hand side as row n_pad, zero rows behind it. The padding survives a solve, so it is written once here.
@@ -1622,62 +1525,50 @@ ovs_status ba_graph_ensure_solver(ovs_ba_graph* g, hipStream_t s) {
 }
 
 static ovs_status solver_workspace_create(ovs_ba_graph* g, hipStream_t s) {
-    const size_t ne = std::max<size_t>((size_t)g->n_edge(), 1);
-    const int n = 6 * std::max(g->n_free, 1), n_pad = dense_solve_pad(n);
-    const size_t n_lists = (size_t)4 * (size_t)std::max(g->n_pairs, 0);
-    // the lists' offsets are 32-bit and their storage is sized by the bound: a map whose bound is beyond 2^28 entries (2 GB; e.g. hundreds of
-    // keyframes that all observe the same landmarks) keeps the per-trial scan (k_schur) instead
-    const bool pl_ok = g->pl_bound <= ((size_t)1 << 28);
-    ArenaLayout lay;
-    const size_t o_hinv = lay.place<double>(9 * (size_t)g->n_pt), o_y = lay.place<double>(18 * ne),
-                 o_s = lay.place<double>(dense_solve_doubles(n) + 6 * (size_t)g->n_pose),   // padded system
-                 o_dxp = lay.place<double>(6 * (size_t)g->n_pose),
-                 o_scal = lay.place<double>(32), o_fail = lay.place<int32_t>(64),   // (256 bytes each: one 264-byte download takes d_scal and both failure words)
-                 o_tab = lay.place<int32_t>((size_t)std::max(g->n_free, 1) * (size_t)g->n_pt), o_pl_cnt = lay.place<int32_t>(n_lists + 1),
-                 o_pl_off = lay.place<int32_t>(n_lists + 1), o_pl_ent = lay.place<int2>(pl_ok ? std::max<size_t>(g->pl_bound, 1) : 1);
-    g->d_solver_arena = g_ba_pool.take(g->device, lay.bytes(), &g->solver_cap);
+    g->sol = solver_arena_of(g->n_pose, g->n_pt, g->n_edge(), g->n_free, g->lay.n_pairs, g->part.pl_bound, dense_solve_doubles(g->n_unknowns()));
+    const SolverArena& L = g->sol;
+    g->d_solver_arena = g_ba_pool.take(g->device, L.arena_bytes, &g->solver_cap);
     OVS_HIP_TRY(g->d_solver_arena ? hipSuccess : hipErrorOutOfMemory);
     unsigned char* const A = g->d_solver_arena;
-    g->d_Hinv = ArenaLayout::at<double>(A, o_hinv);
-    g->d_Y = ArenaLayout::at<double>(A, o_y);
-    g->d_S = ArenaLayout::at<double>(A, o_s);
-    g->d_dxp = ArenaLayout::at<double>(A, o_dxp);
-    g->d_scal = ArenaLayout::at<double>(A, o_scal);
-    g->d_fail = ArenaLayout::at<int32_t>(A, o_fail);
-    g->d_edge_of = ArenaLayout::at<int32_t>(A, o_tab);
-    g->d_pl_cnt = ArenaLayout::at<int32_t>(A, o_pl_cnt);
-    g->d_pl_off = ArenaLayout::at<int32_t>(A, o_pl_off);
-    g->d_pl_ent = ArenaLayout::at<int2>(A, o_pl_ent);
+    g->d_Hinv = ArenaLayout::at<double>(A, L.o_hinv);
+    g->d_Y = ArenaLayout::at<double>(A, L.o_y);
+    g->d_S = ArenaLayout::at<double>(A, L.o_s);
+    g->d_rhs = g->d_S + (size_t)g->s_pitch() * g->s_pitch();
+    g->d_dxp = ArenaLayout::at<double>(A, L.o_dxp);
+    g->d_scal = ArenaLayout::at<double>(A, L.o_scal);
+    g->d_fail = ArenaLayout::at<int32_t>(A, L.o_fail);
+    g->d_edge_of = ArenaLayout::at<int32_t>(A, L.o_edge_of);
+    g->d_pl_cnt = ArenaLayout::at<int32_t>(A, L.o_pl_cnt);
+    g->d_pl_off = ArenaLayout::at<int32_t>(A, L.o_pl_off);
+    g->d_pl_ent = ArenaLayout::at<int2>(A, L.o_pl_ent);
     OVS_HIP_TRY(hipMemsetAsync(g->d_fail, 0, 2 * sizeof(int32_t), s));   // both failure words (ba_graph_schur)
-    OVS_HIP_TRY(hipMemsetAsync(g->d_edge_of, 0xff, o_pl_cnt - o_tab, s));   // -1 (the table and its alignment padding)
+    OVS_HIP_TRY(hipMemsetAsync(g->d_edge_of, 0xff, L.ff_bytes, s));   // -1 (the table and its alignment padding)
     if (g->n_edge() > 0 && g->n_free > 0) {
         hipLaunchKernelGGL(k_edge_table, dim3((g->n_edge() + 255) / 256), dim3(256), 0, s, g->dev.edges, g->n_edge(), g->d_slot_of_pose, g->n_pt, g->d_edge_of);
         OVS_LAUNCH_TRY("k_edge_table");
     }
     g->pl_ready = false;
-    if (pl_ok && g->n_edge() > 0 && g->n_free > 0 && g->n_pairs > 0) {   // behind k_edge_table on the same stream
+    if (L.pl_ok && g->n_edge() > 0 && g->n_free > 0 && g->lay.n_pairs > 0) {   // behind k_edge_table on the same stream
         g->pl_ready = true;
-        hipLaunchKernelGGL(k_pair_lists<false>, dim3(g->n_pairs), dim3(256), 0, s, g->dev.pose_start, g->dev.pose_edges, g->dev.pose_pt, g->d_pair_ab, g->d_slot_pose,
+        hipLaunchKernelGGL(k_pair_lists<false>, dim3(g->lay.n_pairs), dim3(256), 0, s, g->dev.pose_start, g->dev.pose_edges, g->dev.pose_pt, g->d_pair_ab, g->d_slot_pose,
                            g->d_edge_of, g->n_pt, g->d_pl_cnt, (const int32_t*)nullptr, (int2*)nullptr);
         OVS_LAUNCH_TRY("k_pair_lists<count>");
-        hipLaunchKernelGGL(k_scan_i32, dim3(1), dim3(1024), 0, s, g->d_pl_cnt, (int)n_lists, g->d_pl_off);
+        hipLaunchKernelGGL(k_scan_i32, dim3(1), dim3(1024), 0, s, g->d_pl_cnt, (int)L.n_lists, g->d_pl_off);
         OVS_LAUNCH_TRY("k_scan_i32");
-        hipLaunchKernelGGL(k_pair_lists<true>, dim3(g->n_pairs), dim3(256), 0, s, g->dev.pose_start, g->dev.pose_edges, g->dev.pose_pt, g->d_pair_ab, g->d_slot_pose,
+        hipLaunchKernelGGL(k_pair_lists<true>, dim3(g->lay.n_pairs), dim3(256), 0, s, g->dev.pose_start, g->dev.pose_edges, g->dev.pose_pt, g->d_pair_ab, g->d_slot_pose,
                            g->d_edge_of, g->n_pt, (int32_t*)nullptr, g->d_pl_off, g->d_pl_ent);
         OVS_LAUNCH_TRY("k_pair_lists<fill>");
     }
-    g->s_pitch = n_pad;
-    g->d_rhs = g->d_S + (size_t)n_pad * n_pad;
     return ba_graph_reset_system(g, s);
 }
 
 // The padded system's constant part: everything zero, an identity block on rows / columns n .. n_pad - 1 (ba_solve.hip: "the padding reproduces
 // itself"). Written when the workspace is created -- and again after a FAILED solve: a non-finite entry of S reaches the padding through the
 // trailing update (0 * NaN) before any pivot is tested, and the schur kernels rewrite the n x n part and the right-hand side only, so without the
-// repair every later trial on this graph would fail as well, whatever lambda grows to (ADVICE round 4).
+// repair every later trial on this graph would fail as well, whatever lambda grows to.
 ovs_status ba_graph_reset_system(ovs_ba_graph* g, hipStream_t s) {
     if (!g->d_S) return OVS_OK;
-    const int n = 6 * std::max(g->n_free, 1), n_pad = g->s_pitch;
+    const int n = g->n_unknowns(), n_pad = g->s_pitch();
     OVS_HIP_TRY(hipMemsetAsync(g->d_S, 0, sizeof(double) * dense_solve_doubles(n), s));
     static const double ones[16] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};   // (n_pad - n < 16; static: the copy needs no wait here)
     if (n_pad > n)
@@ -1686,7 +1577,7 @@ ovs_status ba_graph_reset_system(ovs_ba_graph* g, hipStream_t s) {
     return OVS_OK;
 }
 
-// (H + lambda I) dx = b, landmarks eliminated on the device: S (pitch g->s_pitch) and rhs at g->d_S.
+// (H + lambda I) dx = b, landmarks eliminated on the device: S (pitch g->s_pitch()) and rhs at g->d_S.
 // `fail_word`: 0 / 1 -- which of the two failure words (d_fail[0..1]) this trial reports in; `clear_first`: zero it by a memset here (the host-solver
 // path; the device-solver path has k_trial_update clear the other word for the next trial, and both words at the start of a round)
 ovs_status ba_graph_schur(ovs_ba_graph* g, const double* d_Hpp, const double* d_bp, const double* d_Hll, const double* d_bl, const double* d_Hpl,
@@ -1698,11 +1589,11 @@ ovs_status ba_graph_schur(ovs_ba_graph* g, const double* d_Hpp, const double* d_
     OVS_LAUNCH_TRY("k_lm_prepare");
     if (g->n_free > 0) {
         if (!tuning().ba_schur_lists || !g->pl_ready)
-            hipLaunchKernelGGL(k_schur, dim3(g->n_free + g->n_pairs), dim3(256), 0, s, v, g->n_free, g->dev.pose_pt, g->d_pair_ab, g->d_slot_pose,
-                               g->d_edge_of, d_Hpp, d_bp, d_bl, d_Hpl, g->d_Y, lambda, g->s_pitch, g->d_S, g->d_rhs);
+            hipLaunchKernelGGL(k_schur, dim3(g->n_free + g->lay.n_pairs), dim3(256), 0, s, v, g->n_free, g->dev.pose_pt, g->d_pair_ab, g->d_slot_pose,
+                               g->d_edge_of, d_Hpp, d_bp, d_bl, d_Hpl, g->d_Y, lambda, g->s_pitch(), g->d_S, g->d_rhs);
         else
-            hipLaunchKernelGGL(k_schur_l, dim3(g->n_free + g->n_pair_wg), dim3(256), 0, s, v, g->n_free, g->d_pair_ab, g->d_slot_pose, g->d_pl_off,
-                               g->d_pl_ent, d_Hpp, d_bp, d_bl, d_Hpl, g->d_Y, lambda, g->s_pitch, g->d_S, g->d_rhs, g->d_wg_pair, g->n_pair_wg);
+            hipLaunchKernelGGL(k_schur_l, dim3(g->n_free + g->part.n_pair_wg), dim3(256), 0, s, v, g->n_free, g->d_pair_ab, g->d_slot_pose, g->d_pl_off,
+                               g->d_pl_ent, d_Hpp, d_bp, d_bl, d_Hpl, g->d_Y, lambda, g->s_pitch(), g->d_S, g->d_rhs, g->d_wg_pair, g->part.n_pair_wg);
         OVS_LAUNCH_TRY("k_schur");
     }
     return OVS_OK;
@@ -1742,22 +1633,13 @@ ovs_status ba_graph_edge_gate(ovs_ba_graph* g, double thr_mono, double thr_stere
                               const uint8_t* d_out1, bool use_final, uint8_t* d_out, bool write_active, int32_t* d_n_active, hipStream_t s) {
     if (g->n_edge() == 0) return OVS_OK;
     hipLaunchKernelGGL(k_edge_gate, dim3((g->n_edge() + 255) / 256), dim3(256), 0, s, g->n_edge(), g->n_mono, thr_mono, thr_stereo, d_chi, d_depth, d_chi_r1,
-                       d_out1, use_final ? 1 : 0, d_out, write_active ? g->d_active : nullptr, d_n_active);
+                       d_out1, use_final ? 1 : 0, d_out, write_active ? g->d_active() : nullptr, d_n_active);
     OVS_LAUNCH_TRY("k_edge_gate");
     return OVS_OK;
 }
 
-ovs_status ba_graph_linearize(ovs_ba_graph* g, const double* d_poses, const double* d_points, double huber_mono, double huber_stereo, double* d_Hpp,
-                              double* d_bp, double* d_Hll, double* d_bl, double* d_Hpl, double* d_chi3, hipStream_t s, double* d_chi_mirror,
-                              bool trial_scale, unsigned long long* host_ll, unsigned int seq) {
-    return graph_linearize(g, d_poses, d_points, huber_mono, huber_stereo, d_Hpp, d_bp, d_Hll, d_bl, d_Hpl, d_chi3, s, d_chi_mirror, trial_scale, host_ll,
-                           seq);
-}
-
-}   // namespace ovs
-
-namespace ovs {
 BaGraphInfo ba_graph_info(ovs_ba_graph* g) {
-    return BaGraphInfo{g->n_free, g->slot.data(), g->d_S, g->d_dxp, g->d_scal, g->d_fail, g->d_slot_of_pose, g->s_pitch, g->d_rhs};
+    return BaGraphInfo{g->n_free, g->slot.data(), g->d_S, g->d_dxp, g->d_scal, g->d_fail, g->d_slot_of_pose, g->s_pitch(), g->d_rhs};
 }
+
 }   // namespace ovs
