@@ -1101,6 +1101,82 @@ ovs_status ovs_projection_match_keyframes_mutually_f(ovs_wmatcher* w, const ovs_
 #define OVS_DETMATH_EXP 8
 ovs_status ovs_detmath_eval(int32_t device, int32_t fn, const double* a, const double* b, double* out, int32_t n);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Image front end (rules I1 to I8).  replaces: util::stereo_rectifier (src/openvslam/util/stereo_rectifier.{h,cc}: the
+ * cv::initUndistortRectifyMap calls of its constructor and the two cv::remap calls of rectify()) and util::image_converter
+ * (src/openvslam/util/image_converter.{h,cc}: convert_to_grayscale's cv::cvtColor, run by every frame constructor).
+ *   stereo_rectifier ctor  -> ovs_imgprep_create + ovs_imgprep_set_rectifier (or ovs_imgprep_set_maps with the caller's own float maps)
+ *   rectify(l, r, l', r') and convert_to_grayscale(img, order) -> ovs_imgprep_run (host) / ovs_imgprep_run_dev (device, asynchronous)
+ *   rectify + convert_to_grayscale + extract of the frame constructors -> ovs_orb_extract_pair_prepared / ovs_orb_extract_prepared
+ * One launch of one kernel prepares both sides: every channel is remapped bilinearly in 5-bit fixed point and rounded to a byte, gray is
+ * taken from the rounded bytes (upstream's order). Sources are 8-bit with 1, 3 or 4 channels; source and result have one size.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct ovs_imgprep ovs_imgprep;
+/* upstream's color_order_t. A 1-channel source passes through under any of them; 3 and 4 channels need RGB or BGR (alpha is ignored) */
+#define OVS_COLOR_GRAY 0
+#define OVS_COLOR_RGB 1
+#define OVS_COLOR_BGR 2
+#define OVS_RECTIFY_PERSPECTIVE 0   /* D = k1 k2 p1 p2 [k3 [k4 k5 k6]]: n_dist 0, 4, 5 or 8 */
+#define OVS_RECTIFY_FISHEYE 1       /* D = k1 k2 k3 k4: n_dist 4 */
+/* one camera of a rig: K (3x3, row-major), D (the first n_dist used, the rest taken as 0), R (3x3, row-major: the rectifying rotation) */
+typedef struct ovs_rectify_side {
+    int32_t model;
+    int32_t n_dist;
+    double K[9];
+    double D[8];
+    double R[9];
+} ovs_rectify_side;
+
+/* A preparer for images of up to max_rows x max_cols (each 1 .. 16384) on HIP device `device`. All device memory (raw and prepared staging
+ * planes of both sides, both resident maps at 6 bytes per pixel) is allocated here; the library holds no page-locked memory for it. One
+ * mutex per handle: calls on one handle serialise, two handles run concurrently. */
+ovs_status ovs_imgprep_create(int32_t device, int32_t max_rows, int32_t max_cols, ovs_imgprep** out);
+ovs_status ovs_imgprep_destroy(ovs_imgprep* p);
+/* Builds the fixed-point maps of a rig on the host (rules I3 to I5, f64) and uploads them. rect_fx_fy_cx_cy: the rectified camera (upstream:
+ * the rectified projection matrix's fx, fy, cx, cy). right may be NULL (a single camera: side 0 only). OVS_ERR_INVALID: a NULL left or
+ * rectified camera, an unknown model, n_dist outside {0, 4, 5, 8} (perspective) / other than 4 (fisheye), a non-finite K, D, R or rectified
+ * parameter, a singular P R; OVS_ERR_CAPACITY: rows x cols beyond the handle's. A refused call leaves the handle's map as it was. */
+ovs_status ovs_imgprep_set_rectifier(ovs_imgprep* p, int32_t rows, int32_t cols, const ovs_rectify_side* left, const ovs_rectify_side* right,
+                                     const double* rect_fx_fy_cx_cy);
+/* The caller's own float maps (rows x cols, dense; e.g. cv::initUndistortRectifyMap's CV_32FC1 pair), converted by rule I5: NaN and values
+ * whose 32-fold lies beyond +-2^30 read as far outside. The right pair may be NULL (both). */
+ovs_status ovs_imgprep_set_maps(ovs_imgprep* p, int32_t rows, int32_t cols, const float* map_x_left, const float* map_y_left,
+                                const float* map_x_right, const float* map_y_right);
+/* Reads the resident map of `side` (0 left, 1 right) back from the device: ixy = rows x cols x (ix, iy) int16, fxy = rows x cols x (fx, fy)
+ * bytes of 0 .. 31. Either may be NULL. OVS_ERR_INVALID without a map of that side. */
+ovs_status ovs_imgprep_get_maps(ovs_imgprep* p, int32_t side, int16_t* ixy, uint8_t* fxy);
+/* Host form: one upload of the raw image(s), one launch, one download. src: rows x cols x channels bytes with src_stride bytes per row;
+ * out: rows x cols bytes with out_stride per row. src_right and out_right are NULL (both) for one image. rectify != 0 applies the
+ * handle's map (OVS_ERR_INVALID if none is set, it has another size, or a right image comes with a map of the left side only); rectify == 0
+ * is rule I1 alone. OVS_ERR_INVALID: a NULL required pointer, channels outside {1, 3, 4}, an unknown colour order, a stride below
+ * cols x channels (out: cols); OVS_ERR_CAPACITY: an image larger than the handle's. Both are decided before any launch and before any output
+ * is written. rows or cols of 0: OK, nothing is written. */
+ovs_status ovs_imgprep_run(ovs_imgprep* p, const uint8_t* src_left, const uint8_t* src_right, int32_t rows, int32_t cols, size_t src_stride,
+                           int32_t channels, int32_t color_order, int32_t rectify, uint8_t* out_left, uint8_t* out_right, size_t out_stride);
+/* Device form: every image pointer is in HBM; asynchronous on `stream`, stages nothing, synchronises nothing. Any base and stride work; a
+ * 4-byte aligned d_out_left / d_out_right / out_stride (ovs_orb_extract_batch_dev's rule) is stored one dword per lane, and the pair is then
+ * that call's d_images with frame_stride = d_out_right - d_out_left. */
+ovs_status ovs_imgprep_run_dev(ovs_imgprep* p, const uint8_t* d_src_left, const uint8_t* d_src_right, int32_t rows, int32_t cols, size_t src_stride,
+                               int32_t channels, int32_t color_order, int32_t rectify, uint8_t* d_out_left, uint8_t* d_out_right, size_t out_stride,
+                               void* stream);
+/* replaces: the stereo frame constructor's  rectifier->rectify(...), util::convert_to_grayscale(left / right), extract x 2  (src/openvslam/
+ * data/frame.cc and the example runners): uploads the RAW pair, prepares it straight into the planes ovs_orb_extract_pair uploads into and
+ * continues exactly as that call does. Masks refer to the rectified image. Keypoints, descriptors and counts are byte-equal to ovs_imgprep_run
+ * followed by ovs_orb_extract_pair, and match::stereo (ovs_stereo_compute) reads the same device pyramid afterwards. out_gray_left /
+ * out_gray_right (both or neither; rows x cols with out_gray_stride): the prepared images, for a caller that wants them on the host; NULL:
+ * nothing comes down but the keypoints. Errors: ovs_orb_extract_pair's and ovs_imgprep_run's, and OVS_ERR_INVALID for handles on different
+ * devices. */
+ovs_status ovs_orb_extract_pair_prepared(ovs_orb* h, ovs_imgprep* p, const uint8_t* raw_left, const uint8_t* raw_right, int32_t rows, int32_t cols,
+                                         size_t stride, int32_t channels, int32_t color_order, int32_t rectify, const uint8_t* mask_left,
+                                         const uint8_t* mask_right, size_t mask_stride, ovs_keypoint* kps_left, uint8_t* desc_left, int32_t* n_left,
+                                         ovs_keypoint* kps_right, uint8_t* desc_right, int32_t* n_right, int32_t cap, uint8_t* out_gray_left,
+                                         uint8_t* out_gray_right, size_t out_gray_stride);
+/* The same for one image (the monocular colour camera; rectify = 0, or a single camera's undistortion map): byte-equal to ovs_imgprep_run
+ * followed by ovs_orb_extract. */
+ovs_status ovs_orb_extract_prepared(ovs_orb* h, ovs_imgprep* p, const uint8_t* raw, int32_t rows, int32_t cols, size_t stride, int32_t channels,
+                                    int32_t color_order, int32_t rectify, const uint8_t* mask, size_t mask_stride, ovs_keypoint* kps, uint8_t* desc,
+                                    int32_t cap, int32_t* n_out, uint8_t* out_gray, size_t out_gray_stride);
+
 #ifdef __cplusplus
 }
 #endif

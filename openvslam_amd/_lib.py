@@ -198,7 +198,22 @@ SYMBOLS = {
     "ovs_stereo_compute": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _f, _f, _vp, _vp, C.POINTER(_i32)]),
     "ovs_detmath_eval": (_i32, [_i32, _i32, _vp, _vp, _vp, _i32]),
     "ovs_stereo_compute_dev": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _f, _f, _vp, _vp, _vp, _vp]),
+    "ovs_imgprep_create": (_i32, [_i32, _i32, _i32, C.POINTER(_vp)]),
+    "ovs_imgprep_destroy": (_i32, [_vp]),
+    "ovs_imgprep_set_rectifier": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp]),
+    "ovs_imgprep_set_maps": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "ovs_imgprep_get_maps": (_i32, [_vp, _i32, _vp, _vp]),
+    "ovs_imgprep_run": (_i32, [_vp, _vp, _vp, _i32, _i32, _sz, _i32, _i32, _i32, _vp, _vp, _sz]),
+    "ovs_imgprep_run_dev": (_i32, [_vp, _vp, _vp, _i32, _i32, _sz, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "ovs_orb_extract_pair_prepared": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _sz, _i32, _i32, _i32, _vp, _vp, _sz, _vp, _vp, C.POINTER(_i32), _vp, _vp,
+                                             C.POINTER(_i32), _i32, _vp, _vp, _sz]),
+    "ovs_orb_extract_prepared": (_i32, [_vp, _vp, _vp, _i32, _i32, _sz, _i32, _i32, _i32, _vp, _sz, _vp, _vp, _i32, C.POINTER(_i32), _vp, _sz]),
 }
+
+
+class RectifySide(C.Structure):
+    """One camera of a rig (ovs_rectify_side). model: 0 perspective, 1 fisheye; D: the first n_dist coefficients are used."""
+    _fields_ = [("model", C.c_int32), ("n_dist", C.c_int32), ("K", C.c_double * 9), ("D", C.c_double * 8), ("R", C.c_double * 9)]
 
 
 class Camera(C.Structure):

@@ -24,8 +24,10 @@ static_assert(sizeof(KeyPoint) == 28, "cv::KeyPoint layout");
 
 constexpr int CV_8U = 0;
 constexpr int CV_8UC1 = 0;
+constexpr int CV_8UC3 = 16;   // OpenCV's encoding: depth | (channels - 1) << 3
+constexpr int CV_8UC4 = 24;
 
-// single-channel 8-bit matrix header; owning (shared, reference counted) or aliasing external memory
+// 8-bit matrix header of 1, 3 or 4 interleaved channels (the hot path past the image front end only ever sees one); owning (shared, reference counted) or aliasing external memory
 struct Mat {
     int rows = 0, cols = 0;
     size_t step = 0;
@@ -33,28 +35,33 @@ struct Mat {
     std::shared_ptr<std::vector<uint8_t>> storage;   // null for headers over external memory
 
     Mat() = default;
-    Mat(int r, int c, int /*type*/) { create(r, c, CV_8U); }
-    Mat(int r, int c, int /*type*/, void* ext, size_t ext_step) : rows(r), cols(c), step(ext_step), data(static_cast<uint8_t*>(ext)) {}
-    void create(int r, int c, int /*type*/) {
-        if (r == rows && c == cols && data) return;   // OpenCV: no reallocation when the size already fits
-        storage = std::make_shared<std::vector<uint8_t>>((size_t)r * c, (uint8_t)0);
+    Mat(int r, int c, int type) { create(r, c, type); }
+    Mat(int r, int c, int type, void* ext, size_t ext_step) : rows(r), cols(c), step(ext_step), data(static_cast<uint8_t*>(ext)), type_(type) {}
+    void create(int r, int c, int type) {
+        if (r == rows && c == cols && type == type_ && data) return;   // OpenCV: no reallocation when the size already fits
+        type_ = type;
+        storage = std::make_shared<std::vector<uint8_t>>((size_t)r * c * channels(), (uint8_t)0);
         rows = r;
         cols = c;
-        step = (size_t)c;
+        step = (size_t)c * channels();
         data = storage->data();
     }
     bool empty() const { return rows == 0 || cols == 0 || data == nullptr; }
-    int type() const { return CV_8UC1; }
-    bool isContinuous() const { return step == (size_t)cols; }
+    int type() const { return type_; }
+    int channels() const { return (type_ >> 3) + 1; }
+    bool isContinuous() const { return step == (size_t)cols * channels(); }
     uint8_t* ptr(int r) { return data + (size_t)r * step; }
     const uint8_t* ptr(int r) const { return data + (size_t)r * step; }
-    Mat row(int r) const { return Mat(1, cols, CV_8U, data + (size_t)r * step, step); }
+    Mat row(int r) const { return Mat(1, cols, type_, data + (size_t)r * step, step); }
     Mat clone() const {
-        Mat m(rows, cols, CV_8U);
+        Mat m(rows, cols, type_);
         for (int r = 0; r < rows; ++r)
-            for (int c = 0; c < cols; ++c) m.ptr(r)[c] = ptr(r)[c];
+            for (int c = 0; c < cols * channels(); ++c) m.ptr(r)[c] = ptr(r)[c];
         return m;
     }
+
+private:
+    int type_ = CV_8UC1;
 };
 
 // read-only proxy: upstream's `const cv::_InputArray&` parameters accept a cv::Mat through this implicit conversion

@@ -34,7 +34,7 @@ orb_extractor::~orb_extractor() {
 void orb_extractor::release() {
     if (h_) ovs_orb_destroy(h_);
     h_ = nullptr;
-    h_rows_ = h_cols_ = 0;
+    h_rows_ = h_cols_ = h_batch_ = 0;
 }
 
 void orb_extractor::initialize() {
@@ -60,8 +60,9 @@ void orb_extractor::set_num_scale_levels(const unsigned int v) { orb_params_.num
 void orb_extractor::set_initial_fast_threshold(const unsigned int v) { orb_params_.ini_fast_thr_ = v; initialize(); }
 void orb_extractor::set_minimum_fast_threshold(const unsigned int v) { orb_params_.min_fast_thr = v; initialize(); }
 
-void orb_extractor::ensure_handle(int rows, int cols) {
-    if (h_ && rows <= h_rows_ && cols <= h_cols_) return;
+void orb_extractor::ensure_handle(int rows, int cols, int batch) {
+    if (h_ && rows <= h_rows_ && cols <= h_cols_ && batch <= h_batch_) return;
+    rows = std::max(rows, h_rows_), cols = std::max(cols, h_cols_), batch = std::max(batch, h_batch_);   // a handle only ever grows
     release();
     ovs_orb_params p;
     p.max_num_keypts = (int32_t)orb_params_.max_num_keypts_;
@@ -69,7 +70,7 @@ void orb_extractor::ensure_handle(int rows, int cols) {
     p.num_levels = (int32_t)orb_params_.num_levels_;
     p.ini_fast_thr = (int32_t)orb_params_.ini_fast_thr_;
     p.min_fast_thr = (int32_t)orb_params_.min_fast_thr;
-    const int st = ovs_orb_create(&p, rows, cols, 1, device_, &h_);
+    const int st = ovs_orb_create(&p, rows, cols, batch, device_, &h_);
     if (st != OVS_OK) {
         h_ = nullptr;
         throw util::device_error(st, std::string("ovs_orb_create: ") + ovs_last_error());   // caught by run_guarded in extract()
@@ -77,6 +78,7 @@ void orb_extractor::ensure_handle(int rows, int cols) {
     ovs_orb_set_host_pyramid(h_, download_pyramid_ ? 1 : 0);
     h_rows_ = rows;
     h_cols_ = cols;
+    h_batch_ = batch;
 }
 
 void orb_extractor::create_rectangle_mask(const unsigned int cols, const unsigned int rows) {
@@ -152,6 +154,70 @@ void orb_extractor::extract(const cv::_InputArray& in_image, const cv::_InputArr
         }
         image_pyramid_[l] = cv::Mat(pyr_rows[l], pyr_cols[l], cv::CV_8U, const_cast<uint8_t*>(pyr_base[l].first), (size_t)pyr_base[l].second);
     }
+}
+
+void orb_extractor::extract_pair_prepared(const util::stereo_rectifier* rectifier, const cv::Mat& raw_left, const cv::Mat& raw_right,
+                                          const camera::color_order_t color_order, const cv::_InputArray& mask_left, const cv::_InputArray& mask_right,
+                                          std::vector<cv::KeyPoint>& keypts_left, const cv::_OutputArray& descriptors_left, std::vector<cv::KeyPoint>& keypts_right,
+                                          const cv::_OutputArray& descriptors_right, cv::Mat* out_gray_left, cv::Mat* out_gray_right) {
+    keypts_left.clear();
+    keypts_right.clear();
+    if (raw_left.empty() || raw_right.empty()) return;   // upstream: early return
+    const int rows = raw_left.rows, cols = raw_left.cols, ch = raw_left.channels();
+    if (raw_right.rows != rows || raw_right.cols != cols || raw_right.channels() != ch || raw_right.step != raw_left.step || (out_gray_left == nullptr) != (out_gray_right == nullptr))
+        throw std::invalid_argument("orb_extractor::extract_pair_prepared: the two images must have one size, channel count and step; gray outputs both or neither");
+    cv::Mat masks[2];
+    if (!mask_left.empty() && !mask_right.empty()) {
+        masks[0] = mask_left.getMat();
+        masks[1] = mask_right.getMat();
+    } else if (!orb_params_.mask_rects_.empty()) {
+        create_rectangle_mask(cols, rows);
+        masks[0] = masks[1] = rect_mask_;
+    }
+    cv::Mat gray[2];
+    if (out_gray_left) gray[0] = cv::Mat(rows, cols, cv::CV_8UC1), gray[1] = cv::Mat(rows, cols, cv::CV_8UC1);
+    util::detail::thread_preparer& tp = util::detail::thread_preparer::of_this_thread();
+    int n[2] = {0, 0};
+    const bool ok = util::run_guarded(
+        "orb_extractor::extract_pair_prepared",
+        [&] {
+            ensure_handle(rows, cols, 2);
+            ovs_imgprep* prep = rectifier ? rectifier->preparer() : tp.get(device_, rows, cols);
+            const int cap = ovs_orb_max_keypoints(h_);
+            keypts_left.resize(cap);
+            keypts_right.resize(cap);
+            desc_buf_.resize((size_t)cap * 32);
+            desc_buf_right_.resize((size_t)cap * 32);
+            // (the two masks share one stride: both are the caller's of one size, or both the rectangle mask)
+            return (int)ovs_orb_extract_pair_prepared(h_, prep, raw_left.data, raw_right.data, rows, cols, raw_left.step, ch, (int)color_order, rectifier ? 1 : 0,
+                                                      masks[0].empty() ? nullptr : masks[0].data, masks[1].empty() ? nullptr : masks[1].data,
+                                                      masks[0].empty() ? 0 : masks[0].step, reinterpret_cast<ovs_keypoint*>(keypts_left.data()), desc_buf_.data(), &n[0],
+                                                      reinterpret_cast<ovs_keypoint*>(keypts_right.data()), desc_buf_right_.data(), &n[1], cap, gray[0].data, gray[1].data,
+                                                      out_gray_left ? gray[0].step : 0);
+        },
+        [&] {
+            release();
+            if (rectifier) rectifier->reset();
+            else tp.drop();
+        });
+    if (!ok) {
+        release();
+        n[0] = n[1] = 0;
+        gray[0] = gray[1] = cv::Mat();
+    }
+    keypts_left.resize(n[0]);
+    keypts_right.resize(n[1]);
+    const cv::_OutputArray* dout[2] = {&descriptors_left, &descriptors_right};
+    const std::vector<uint8_t>* dbuf[2] = {&desc_buf_, &desc_buf_right_};
+    for (int s = 0; s < 2; ++s) {
+        dout[s]->create(n[s], 32, cv::CV_8U);
+        if (!n[s]) continue;
+        cv::Mat descriptors = dout[s]->getMat();
+        for (int i = 0; i < n[s]; ++i) std::copy(dbuf[s]->begin() + (size_t)i * 32, dbuf[s]->begin() + (size_t)(i + 1) * 32, descriptors.ptr(i));
+    }
+    if (out_gray_left) *out_gray_left = gray[0], *out_gray_right = gray[1];
+    image_pyramid_[0] = gray[0];
+    for (unsigned int l = 1; l < orb_params_.num_levels_; ++l) image_pyramid_[l] = cv::Mat();
 }
 
 void orb_extractor::set_image_pyramid_download(const bool enable) {

@@ -4,6 +4,8 @@
 #include <vector>
 
 #include "../../cv_stub.h"
+#include "../util/image_converter.h"
+#include "../util/stereo_rectifier.h"
 #include "orb_params.h"
 
 struct ovs_orb;
@@ -55,6 +57,15 @@ public:
     //! HIP device this extractor runs on (before the first extract). Stereo rigs may put left / right on two GPUs.
     //! the device the frame's matcher-side cache belongs on: data::frame's constructor sets device_cache_->device = extractor_->get_device()
     int get_device() const { return device_; }
+    //! The stereo frame constructor's  rectifier->rectify(l, r, ...); convert_to_grayscale(l); convert_to_grayscale(r); extract x 2  in one call
+    //! (ovs_orb_extract_pair_prepared): the RAW pair (8-bit, 1, 3 or 4 channels) is uploaded and prepared on the device straight into the
+    //! extractor's planes. rectifier: nullptr = gray conversion alone. Masks (both or neither, or the extractor's rectangles) refer to the
+    //! rectified image. out_gray_*: nullptr, or the prepared images. image_pyramid_ is left empty above what out_gray_left gives level 0
+    //! (match::stereo reads the device copy). Failure policy as extract(): one retry, then no keypoints and empty gray images.
+    void extract_pair_prepared(const util::stereo_rectifier* rectifier, const cv::Mat& raw_left, const cv::Mat& raw_right, const camera::color_order_t color_order,
+                               const cv::_InputArray& mask_left, const cv::_InputArray& mask_right, std::vector<cv::KeyPoint>& keypts_left,
+                               const cv::_OutputArray& descriptors_left, std::vector<cv::KeyPoint>& keypts_right, const cv::_OutputArray& descriptors_right,
+                               cv::Mat* out_gray_left = nullptr, cv::Mat* out_gray_right = nullptr);
     void set_device(const int device) {
         if (device != device_) release();
         device_ = device;
@@ -63,7 +74,7 @@ public:
 private:
     void initialize();
     void release();
-    void ensure_handle(int rows, int cols);
+    void ensure_handle(int rows, int cols, int batch = 1);
     void create_rectangle_mask(const unsigned int cols, const unsigned int rows);
     void register_self();
     void unregister_self();
@@ -72,10 +83,10 @@ private:
     std::vector<float> scale_factors_, inv_scale_factors_, level_sigma_sq_, inv_level_sigma_sq_;
     cv::Mat rect_mask_;
     ovs_orb* h_ = nullptr;
-    int h_rows_ = 0, h_cols_ = 0;
+    int h_rows_ = 0, h_cols_ = 0, h_batch_ = 0;
     int device_ = 0;
     bool download_pyramid_ = true;
-    std::vector<uint8_t> desc_buf_;
+    std::vector<uint8_t> desc_buf_, desc_buf_right_;
 };
 
 }   // namespace feature

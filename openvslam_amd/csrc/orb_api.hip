@@ -14,6 +14,7 @@
 #include "ovs_common.h"
 #include "orb_plan.inc"
 #include "owned_internal.inc"
+#include "image_prep_internal.inc"
 
 namespace ovs {
 
@@ -637,11 +638,18 @@ ovs_status upload_plane(ovs_orb* h, const uint8_t* src, size_t stride, int rows,
     return OVS_OK;
 }
 
-}   // namespace
+// The fused entries (ovs_orb_extract_prepared / _pair_prepared): the image argument is the RAW source, staged in the preparer's planes and
+// prepared into the plane the gray image is otherwise uploaded into. The arguments have passed imgprep_check; the caller holds p->mu.
+struct RawInput {
+    ovs_imgprep* p;
+    int channels, color_order, rectify;
+    uint8_t* gray[2];   // or null: the prepared images on the host
+    size_t gray_stride;
+};
 
-ovs_status ovs_orb_extract_submit(ovs_orb* h, const uint8_t* image, int32_t rows, int32_t cols, size_t stride, const uint8_t* mask,
-                                  size_t mask_stride) {
-    if (!h || !image || rows <= 0 || cols <= 0 || stride < (size_t)cols || (mask && mask_stride < (size_t)cols)) return OVS_ERR_INVALID;
+ovs_status submit_frame(ovs_orb* h, const uint8_t* image, int32_t rows, int32_t cols, size_t stride, const uint8_t* mask, size_t mask_stride,
+                        const RawInput* raw) {
+    if (!h || !image || rows <= 0 || cols <= 0 || (!raw && stride < (size_t)cols) || (mask && mask_stride < (size_t)cols)) return OVS_ERR_INVALID;
     if (rows > h->max_rows || cols > h->max_cols) return OVS_ERR_CAPACITY;
     if (h->n_submitted - h->n_collected >= 2) return OVS_ERR_CAPACITY;   // both slots in flight: collect first
     OVS_HIP_TRY(hipSetDevice(h->device));
@@ -657,7 +665,8 @@ ovs_status ovs_orb_extract_submit(ovs_orb* h, const uint8_t* image, int32_t rows
     // the candidate counters are cleared while the image is still on its way (a 4 us fill kernel that used to run between the upload and the pyramid)
     OVS_HIP_TRY(hipMemsetAsync(h->d.cand_count, 0, sizeof(uint32_t) * (size_t)h->plan.geo.num_levels, s));
     if (timed) OVS_HIP_TRY(hipEventRecord(sl.t[0], cs));
-    st = upload_plane(h, image, stride, rows, cols, sl.h_in, sl.d_img);
+    if (raw) OVS_HIP_TRY(hipMemcpy2DAsync(raw->p->d_src[0], raw->p->src_pitch, image, stride, (size_t)cols * raw->channels, (size_t)rows, hipMemcpyHostToDevice, cs));
+    else st = upload_plane(h, image, stride, rows, cols, sl.h_in, sl.d_img);
     if (st != OVS_OK) return st;
     if (mask) {
         if (!sl.d_mask) OVS_HIP_TRY(h->res.dev(&sl.d_mask, h->img_pitch * h->max_rows));
@@ -668,11 +677,16 @@ ovs_status ovs_orb_extract_submit(ovs_orb* h, const uint8_t* image, int32_t rows
     if (timed) OVS_HIP_TRY(hipEventRecord(sl.t[1], cs));
     OVS_HIP_TRY(hipEventRecord(sl.ev_h2d, cs));
     OVS_HIP_TRY(hipStreamWaitEvent(s, sl.ev_h2d, 0));
+    if (raw)
+        OVS_HIP_TRY(imgprep_enqueue(raw->p, raw->p->d_src[0], nullptr, rows, cols, raw->p->src_pitch, raw->channels, raw->color_order, raw->rectify, sl.d_img, nullptr,
+                                    h->img_pitch, s));
     // the kernels write counts + keypoints + descriptors straight into the slot's pinned block (no D2H copy); the counters are cleared above
     st = run_extract(h, ExtractJob{sl.d_img, h->img_pitch, h->img_pitch * (size_t)rows, mask ? sl.d_mask : nullptr, rows, cols, 1, h->d_out_kps,
                                    h->d_out_desc, h->d_out_counts, h->out_cap, sl.h_out, true}, s);
     if (st != OVS_OK) return st;
     if (timed) OVS_HIP_TRY(hipEventRecord(sl.t[2], s));
+    if (raw && raw->gray[0])
+        OVS_HIP_TRY(hipMemcpy2DAsync(raw->gray[0], raw->gray_stride, sl.d_img, h->img_pitch, (size_t)cols, (size_t)rows, hipMemcpyDeviceToHost, s));
     sl.has_pyr = false;
     if (h->host_pyr && h->p.num_levels > 1) {
         if (!sl.h_pyr) OVS_HIP_TRY(h->res.pinned(&sl.h_pyr, h->d.pyr_frame_bytes));
@@ -689,6 +703,13 @@ ovs_status ovs_orb_extract_submit(ovs_orb* h, const uint8_t* image, int32_t rows
     sl.cols = cols;
     ++h->n_submitted;
     return OVS_OK;
+}
+
+}   // namespace
+
+ovs_status ovs_orb_extract_submit(ovs_orb* h, const uint8_t* image, int32_t rows, int32_t cols, size_t stride, const uint8_t* mask,
+                                  size_t mask_stride) {
+    return submit_frame(h, image, rows, cols, stride, mask, mask_stride, nullptr);
 }
 
 ovs_status ovs_orb_extract_collect(ovs_orb* h, ovs_keypoint* kps, uint8_t* desc, int32_t cap, int32_t* n_out) {
@@ -730,13 +751,15 @@ ovs_status ovs_orb_extract(ovs_orb* h, const uint8_t* image, int32_t rows, int32
     return ovs_orb_extract_collect(h, kps, desc, cap, n_out);
 }
 
-ovs_status ovs_orb_extract_pair(ovs_orb* h, const uint8_t* left, const uint8_t* right, int32_t rows, int32_t cols, size_t stride,
-                                const uint8_t* mask_left, const uint8_t* mask_right, size_t mask_stride, ovs_keypoint* kps_left,
-                                uint8_t* desc_left, int32_t* n_left, ovs_keypoint* kps_right, uint8_t* desc_right, int32_t* n_right, int32_t cap) {
+namespace {
+// ovs_orb_extract_pair; with `raw`, left / right are the raw sources (ovs_orb_extract_pair_prepared)
+ovs_status extract_pair(ovs_orb* h, const uint8_t* left, const uint8_t* right, int32_t rows, int32_t cols, size_t stride, const uint8_t* mask_left,
+                        const uint8_t* mask_right, size_t mask_stride, ovs_keypoint* kps_left, uint8_t* desc_left, int32_t* n_left, ovs_keypoint* kps_right,
+                        uint8_t* desc_right, int32_t* n_right, int32_t cap, const RawInput* raw) {
     if (!h || !n_left || !n_right) return OVS_ERR_INVALID;
     *n_left = *n_right = 0;
     if (!left || !right || rows <= 0 || cols <= 0) return OVS_OK;   // upstream: empty image -> early return
-    if (cap < 0 || (cap > 0 && (!kps_left || !desc_left || !kps_right || !desc_right)) || stride < (size_t)cols) return OVS_ERR_INVALID;
+    if (cap < 0 || (cap > 0 && (!kps_left || !desc_left || !kps_right || !desc_right)) || (!raw && stride < (size_t)cols)) return OVS_ERR_INVALID;
     if ((mask_left == nullptr) != (mask_right == nullptr) || (mask_left && mask_stride < (size_t)cols)) return OVS_ERR_INVALID;
     if (h->max_batch < 2 || rows > h->max_rows || cols > h->max_cols) return OVS_ERR_CAPACITY;
     if (h->n_submitted != h->n_collected) return OVS_ERR_INVALID;   // frames submitted asynchronously must be collected first
@@ -762,8 +785,14 @@ ovs_status ovs_orb_extract_pair(ovs_orb* h, const uint8_t* left, const uint8_t* 
     pb.off_desc = 32 + ((2 * sizeof(ovs_keypoint) * (size_t)fcap + 31) & ~(size_t)31);
     pb.out_bytes = pb.off_desc + (size_t)64 * fcap;
     hipStream_t s = h->stream, cs = h->copy_stream;
-    st = upload_plane(h, left, stride, rows, cols, nullptr, pb.d_img);
-    if (st == OVS_OK) st = upload_plane(h, right, stride, rows, cols, nullptr, pb.d_img + pb.frame_bytes);
+    if (raw) {
+        const uint8_t* const src[2] = {left, right};
+        for (int f = 0; f < 2; ++f)
+            OVS_HIP_TRY(hipMemcpy2DAsync(raw->p->d_src[f], raw->p->src_pitch, src[f], stride, (size_t)cols * raw->channels, (size_t)rows, hipMemcpyHostToDevice, cs));
+    } else {
+        st = upload_plane(h, left, stride, rows, cols, nullptr, pb.d_img);
+        if (st == OVS_OK) st = upload_plane(h, right, stride, rows, cols, nullptr, pb.d_img + pb.frame_bytes);
+    }
     if (st != OVS_OK) return st;
     if (mask_left) {
         if (!pb.d_mask) OVS_HIP_TRY(h->res.dev(&pb.d_mask, 2 * pb.frame_bytes));
@@ -773,10 +802,15 @@ ovs_status ovs_orb_extract_pair(ovs_orb* h, const uint8_t* left, const uint8_t* 
     }
     OVS_HIP_TRY(hipEventRecord(pb.ev_h2d, cs));
     OVS_HIP_TRY(hipStreamWaitEvent(s, pb.ev_h2d, 0));
+    if (raw)
+        OVS_HIP_TRY(imgprep_enqueue(raw->p, raw->p->d_src[0], raw->p->d_src[1], rows, cols, raw->p->src_pitch, raw->channels, raw->color_order, raw->rectify, pb.d_img,
+                                    pb.d_img + pb.frame_bytes, h->img_pitch, s));
     st = run_extract(h, ExtractJob{pb.d_img, h->img_pitch, pb.frame_bytes, mask_left ? pb.d_mask : nullptr, rows, cols, 2,
                                    reinterpret_cast<ovs_keypoint*>(pb.d_out + pb.off_kps), pb.d_out + pb.off_desc, reinterpret_cast<int32_t*>(pb.d_out), fcap}, s);
     if (st != OVS_OK) return st;
     OVS_HIP_TRY(hipMemcpyAsync(pb.h_out, pb.d_out, pb.out_bytes, hipMemcpyDeviceToHost, s));
+    for (int f = 0; raw && raw->gray[0] && f < 2; ++f)
+        OVS_HIP_TRY(hipMemcpy2DAsync(raw->gray[f], raw->gray_stride, pb.d_img + pb.frame_bytes * f, h->img_pitch, (size_t)cols, (size_t)rows, hipMemcpyDeviceToHost, s));
     OVS_HIP_TRY(hipStreamSynchronize(s));
     const int32_t* cnt = reinterpret_cast<const int32_t*>(pb.h_out);
     ovs_keypoint* const kout[2] = {kps_left, kps_right};
@@ -794,6 +828,50 @@ ovs_status ovs_orb_extract_pair(ovs_orb* h, const uint8_t* left, const uint8_t* 
     }
     h->last_host_count = *n_left;
     return over ? OVS_ERR_CAPACITY : OVS_OK;
+}
+}   // namespace
+
+ovs_status ovs_orb_extract_pair(ovs_orb* h, const uint8_t* left, const uint8_t* right, int32_t rows, int32_t cols, size_t stride,
+                                const uint8_t* mask_left, const uint8_t* mask_right, size_t mask_stride, ovs_keypoint* kps_left,
+                                uint8_t* desc_left, int32_t* n_left, ovs_keypoint* kps_right, uint8_t* desc_right, int32_t* n_right, int32_t cap) {
+    return extract_pair(h, left, right, rows, cols, stride, mask_left, mask_right, mask_stride, kps_left, desc_left, n_left, kps_right, desc_right, n_right, cap,
+                        nullptr);
+}
+
+ovs_status ovs_orb_extract_pair_prepared(ovs_orb* h, ovs_imgprep* p, const uint8_t* raw_left, const uint8_t* raw_right, int32_t rows, int32_t cols,
+                                         size_t stride, int32_t channels, int32_t color_order, int32_t rectify, const uint8_t* mask_left,
+                                         const uint8_t* mask_right, size_t mask_stride, ovs_keypoint* kps_left, uint8_t* desc_left, int32_t* n_left,
+                                         ovs_keypoint* kps_right, uint8_t* desc_right, int32_t* n_right, int32_t cap, uint8_t* out_gray_left,
+                                         uint8_t* out_gray_right, size_t out_gray_stride) {
+    if (!h || !p || !n_left || !n_right || !raw_left || !raw_right || (out_gray_left == nullptr) != (out_gray_right == nullptr)) return OVS_ERR_INVALID;
+    *n_left = *n_right = 0;
+    if (h->device != p->device) return OVS_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(p->mu);
+    const ovs_status st = imgprep_check(p, rows, cols, stride, channels, color_order, rectify, 2);
+    if (st != OVS_OK) return st;
+    if (out_gray_left && out_gray_stride < (size_t)cols) return OVS_ERR_INVALID;
+    const RawInput raw{p, channels, color_order, rectify, {out_gray_left, out_gray_right}, out_gray_stride};
+    return extract_pair(h, raw_left, raw_right, rows, cols, stride, mask_left, mask_right, mask_stride, kps_left, desc_left, n_left, kps_right, desc_right, n_right,
+                        cap, &raw);
+}
+
+ovs_status ovs_orb_extract_prepared(ovs_orb* h, ovs_imgprep* p, const uint8_t* raw, int32_t rows, int32_t cols, size_t stride, int32_t channels,
+                                    int32_t color_order, int32_t rectify, const uint8_t* mask, size_t mask_stride, ovs_keypoint* kps, uint8_t* desc,
+                                    int32_t cap, int32_t* n_out, uint8_t* out_gray, size_t out_gray_stride) {
+    if (!h || !p || !n_out || !raw) return OVS_ERR_INVALID;
+    *n_out = 0;
+    if (h->device != p->device) return OVS_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(p->mu);
+    ovs_status st = imgprep_check(p, rows, cols, stride, channels, color_order, rectify, 1);
+    if (st != OVS_OK) return st;
+    if (out_gray && out_gray_stride < (size_t)cols) return OVS_ERR_INVALID;
+    if (rows == 0 || cols == 0) return OVS_OK;   // upstream: empty image -> early return
+    if (cap < 0 || (cap > 0 && (!kps || !desc))) return OVS_ERR_INVALID;
+    if (h->n_submitted != h->n_collected) return OVS_ERR_INVALID;   // frames submitted asynchronously must be collected first
+    const RawInput in{p, channels, color_order, rectify, {out_gray, nullptr}, out_gray_stride};
+    st = submit_frame(h, raw, rows, cols, stride, mask, mask_stride, &in);
+    if (st != OVS_OK) return st;
+    return ovs_orb_extract_collect(h, kps, desc, cap, n_out);   // waits for the frame's last event: the gray download has ended too
 }
 
 ovs_status ovs_orb_set_host_pyramid(ovs_orb* h, int32_t enable) {

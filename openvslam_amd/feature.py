@@ -182,6 +182,50 @@ class orb_extractor:
                    "ovs_orb_extract_pair")
         return tuple((k[:n.value].copy(), d[:n.value].copy()) for k, d, n in out)
 
+    def extract_pair_prepared(self, preparer, raw_left, raw_right, color_order=0, rectify=False, mask_left=None, mask_right=None, return_gray=False):
+        """The stereo frame constructor's rectify + convert_to_grayscale + two extracts in one call (ovs_orb_extract_pair_prepared): the RAW pair
+        (8-bit, 1, 3 or 4 channels) is uploaded, prepared on the device by `preparer` (image.image_preparer) and extracted. Masks refer to the
+        rectified image. Returns ((kps, desc) left, (kps, desc) right), and with return_gray also the two prepared images."""
+        from . import image as _image
+        left, rows, cols, ch, stride = _image._image(raw_left)
+        right, rows_r, cols_r, ch_r, stride_r = _image._image(raw_right)
+        if (rows_r, cols_r, ch_r) != (rows, cols, ch):
+            raise TypeError("both images must have one size and channel count")
+        if stride_r != stride:
+            left, right, stride = np.ascontiguousarray(left), np.ascontiguousarray(right), cols * ch
+        if (mask_left is None) != (mask_right is None):
+            raise ValueError("masks: both or neither")
+        if mask_left is not None:
+            mask_left, mask_right = np.ascontiguousarray(mask_left, np.uint8), np.ascontiguousarray(mask_right, np.uint8)
+            if mask_left.shape != (rows, cols) or mask_right.shape != (rows, cols):
+                raise ValueError("masks must have the images' size")
+        cap = self.max_keypoints
+        out = [(np.zeros(cap, KP_DTYPE), np.zeros((cap, 32), np.uint8), C.c_int32(0)) for _ in range(2)]
+        gray = [np.zeros((rows, cols), np.uint8) for _ in range(2)] if return_gray else [None, None]
+        _lib.check(self._L.ovs_orb_extract_pair_prepared(self._h, preparer._h, _p(left), _p(right), rows, cols, stride, ch, _image.COLOR_ORDERS[color_order],
+                                                         1 if rectify else 0, _p(mask_left), _p(mask_right), cols if mask_left is not None else 0,
+                                                         _p(out[0][0]), _p(out[0][1]), C.byref(out[0][2]), _p(out[1][0]), _p(out[1][1]), C.byref(out[1][2]), cap,
+                                                         _p(gray[0]), _p(gray[1]), cols), "ovs_orb_extract_pair_prepared")
+        res = tuple((k[:n.value].copy(), d[:n.value].copy()) for k, d, n in out)
+        return res + (gray[0], gray[1]) if return_gray else res
+
+    def extract_prepared(self, preparer, raw, color_order=0, rectify=False, mask=None, return_gray=False):
+        """The same for one image (ovs_orb_extract_prepared): the monocular colour camera. Returns (kps, desc) and, with return_gray, the prepared image."""
+        from . import image as _image
+        raw, rows, cols, ch, stride = _image._image(raw)
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, np.uint8)
+            if mask.shape != (rows, cols):
+                raise ValueError("mask must have the image's size")
+        cap = self.max_keypoints
+        kps, desc, n = np.zeros(cap, KP_DTYPE), np.zeros((cap, 32), np.uint8), C.c_int32(0)
+        gray = np.zeros((rows, cols), np.uint8) if return_gray else None
+        _lib.check(self._L.ovs_orb_extract_prepared(self._h, preparer._h, _p(raw), rows, cols, stride, ch, _image.COLOR_ORDERS[color_order], 1 if rectify else 0,
+                                                    _p(mask), cols if mask is not None else 0, _p(kps), _p(desc), cap, C.byref(n), _p(gray), cols),
+                   "ovs_orb_extract_prepared")
+        res = (kps[:n.value].copy(), desc[:n.value].copy())
+        return res + (gray,) if return_gray else res
+
     def set_fast_split(self, enable):
         """Level-0 FAST beside the pyramid on an internal stream (default on); off = one FAST launch after the pyramid."""
         _lib.check(self._L.ovs_orb_set_fast_split(self._h, 1 if enable else 0), "ovs_orb_set_fast_split")
