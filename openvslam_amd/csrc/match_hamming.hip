@@ -18,16 +18,15 @@
 // Pairs are emitted in upstream's order (ascending idx_2).
 #include <algorithm>
 #include <cmath>
+#include <memory>
 #include <new>
 #include <vector>
 
 #include "ovs_common.h"
+#include "match_bf_plan.inc"   // kNearSplit, kNearSeg, kTopK, kNearQueries, kNearPopcQueries; the resolver's LDS layout; the host side's plan
+#include "owned_internal.inc"
 
 namespace ovs {
-
-constexpr int kNearSplit = 4;         // waves per workgroup; each scans a quarter of the frame descriptors for the same 64 queries
-constexpr int kNearSeg = 64;          // near-list capacity per (query, wave); beyond it: cooperative full scan, still exact
-constexpr int kTopK = 8;              // sorted smallest keys kept per query for the resolver's fast path
 
 __device__ __forceinline__ uint32_t hamming256(const uint32_t (&a)[8], const uint32_t* __restrict__ b) {
     uint32_t d = 0;
@@ -82,7 +81,7 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v8i __attribute__((ext_vector_type(8)));
 typedef float v16f __attribute__((ext_vector_type(16)));
 
-constexpr int kNearQueries = 256;   // queries per workgroup (4 waves x 2 tiles of 32)
+static_assert(kNearQueries == 256, "a workgroup is 4 waves x 2 tiles of 32 queries");
 constexpr int kQueueSlots = 128;    // per-wave ring of queued C-tile columns (drained 64 at a time)
 static_assert(kNearSplit == 4, "segment counts are stored as one uint4 per query");
 
@@ -420,17 +419,18 @@ __global__ __launch_bounds__(256) void k_hamming_near_popc(const uint8_t* __rest
                                                      const uint8_t* __restrict__ valid_2, int max_n2, uint32_t near_thr,
                                                      uint32_t* __restrict__ near_cnt, uint32_t* __restrict__ near_list,
                                                      uint32_t* __restrict__ near_top, int chunks, int total_wg) {
-    __shared__ uint32_t s_top[kNearSplit][kTopK][64];
+    static_assert(kNearPopcQueries == 64, "one query per lane, the same 64 in all four waves");
+    __shared__ uint32_t s_top[kNearSplit][kTopK][kNearPopcQueries];
     // XCD-major work order (workgroup b runs on XCD b % 8): XCD k takes the k-th contiguous eighth of the (problem, chunk) sequence
     const int per_xcd = gridDim.x >> 3;
     const int wg = ((int)blockIdx.x & 7) * per_xcd + ((int)blockIdx.x >> 3);
     if (wg >= total_wg) return;
     const int p = wg / chunks, chunk_id = wg - p * chunks;
     const int n1 = n1_arr[p], n2 = n2_arr[p];
-    if (chunk_id * 64 >= n2) return;
+    if (chunk_id * kNearPopcQueries >= n2) return;
     // wave index made provably uniform so the descriptor addresses below stay scalar (s_load_dwordx8)
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int q = chunk_id * 64 + lane;
+    const int q = chunk_id * kNearPopcQueries + lane;
     const bool active = q < n2 && (!valid_2 || valid_2[(size_t)p * (stride_2 / 32) + q]);
     uint32_t a[8];
     {
@@ -551,8 +551,9 @@ __global__ __launch_bounds__(64 * NW) void k_bf_resolve(const uint8_t* __restric
     typedef __attribute__((address_space(3))) volatile uint8_t lds_u8;
     __shared__ uint32_t s_wave[NW];   // per-wave first affected thread / per-wave match count
     constexpr int T = 64 * NW;
-    lds_u32* mark = (lds_u32*)(smem);                                  // [max_n1]
-    lds_u8* claimed = (lds_u8*)(smem + (size_t)max_n1 * 4);            // [max_n1]
+    const BfResolveLds lay = bf_resolve_lds(max_n1, max_n2);
+    lds_u32* mark = (lds_u32*)(smem + lay.mark);                       // [max_n1]
+    lds_u8* claimed = (lds_u8*)(smem + lay.claimed);                   // [max_n1]
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int p = blockIdx.x;
     const int n1 = n1_arr[p], n2 = n2_arr[p];
@@ -581,8 +582,8 @@ __global__ __launch_bounds__(64 * NW) void k_bf_resolve(const uint8_t* __restric
     // STAGED: every query's segment counts and sorted top-8 are copied into LDS up front (independent 16-byte loads in flight), so
     // the replay loop below never waits on HBM: nothing else hides that latency, and hipcc cannot keep a software prefetch in flight
     // across the loop's back edge (it drains vmcnt to 0 at the first use).
-    lds_u32* s_tops = (lds_u32*)(smem + (((size_t)max_n1 * 5 + 15) & ~(size_t)15));   // [n2][8]
-    lds_u32* s_cnts = s_tops + (size_t)max_n2 * kTopK;                                // [n2] four saturated u8 counts
+    lds_u32* s_tops = (lds_u32*)(smem + lay.tops);   // [n2][8]
+    lds_u32* s_cnts = s_tops + (lay.cnts - lay.tops) / sizeof(uint32_t);   // [n2] four saturated u8 counts
     if (STAGED) {
         for (int q = tid; q < n2; q += 4 * T) {
             uint4 cc[4], lo[4], hi[4];
@@ -851,10 +852,13 @@ __global__ __launch_bounds__(256) void k_hamming_best2(const uint8_t* __restrict
 
 using namespace ovs;
 
+
 struct ovs_matcher {
     int device = 0;
-    int max_n1 = 0, max_n2 = 0, max_batch = 0;
+    BfCaps caps{};
     int near_path = OVS_NEAR_PATH_MATRIX;
+    BfResolvePlan resolve{};
+    Owned res;
     hipStream_t stream = nullptr;
     uint32_t* d_near_cnt = nullptr;
     uint32_t* d_near_list = nullptr;
@@ -870,47 +874,44 @@ struct ovs_matcher {
     int32_t* d_best_idx = nullptr;
     uint16_t* d_best = nullptr;
     uint16_t* d_second = nullptr;
-    size_t resolve_lds = 0;        // mark + claimed
-    size_t resolve_lds_staged = 0; // + per-query top-8 and counts (0 = does not fit: the resolver reads them from HBM)
     StageProfiler<2> prof;
+    ~ovs_matcher() {
+        res.clear();      // drains the stream first: no stage event is still pending when the profiler lets go of them
+        prof.destroy();
+    }
 };
 
 namespace {
 
-// Largest distance that can still influence brute_force_match's accept/reject decision (see file header).
-uint32_t near_threshold(float lowe_ratio) {
-    uint32_t tau = 257;
-    for (uint32_t s = 0; s <= 256; ++s) {
-        const volatile float lhs = lowe_ratio * (float)s;   // one float multiply, as the device does (__fmul_rn)
-        if (!(lhs < (float)OVS_HAMMING_DIST_THR_LOW)) { tau = s; break; }
-    }
-    uint32_t thr = std::max<uint32_t>(OVS_HAMMING_DIST_THR_LOW, tau - 1);
-    // a distance of 256 can never become best (strict '<' against the initial MAX_HAMMING_DIST) and as `second` equals "none"
-    return std::min<uint32_t>(thr, OVS_MAX_HAMMING_DIST - 1);
+// hipFuncAttributeMaxDynamicSharedMemorySize of the resolver form a handle runs, raised to its size on the current device (never lowered: a
+// smaller handle created later leaves a larger one's launches valid)
+hipError_t raise_resolve_lds(const BfResolvePlan& rp) {
+    static LdsAttrCache staged, one_wave;   // one per instantiation (each per device)
+    if (rp.staged) return ensure_dynamic_lds(reinterpret_cast<const void*>(k_bf_resolve<true, 4>), rp.lds_bytes, staged);
+    return ensure_dynamic_lds(reinterpret_cast<const void*>(k_bf_resolve<false, 1>), rp.lds_bytes, one_wave);
 }
 
 ovs_status run_bf(ovs_matcher* m, const uint8_t* d1, size_t stride_1, const int32_t* d_n1, const uint8_t* d_valid_1, const uint8_t* d2,
                   size_t stride_2, const int32_t* d_n2, const uint8_t* d_valid, int batch, float lowe_ratio, int32_t* d_pairs, int32_t* d_counts, int cap,
                   hipStream_t s) {
     const uint32_t thr = near_threshold(lowe_ratio);
+    const BfNearLaunch near = bf_near_launch(m->caps.max_n2, batch, m->near_path);
+    const BfResolvePlan& rp = m->resolve;
     OVS_HIP_TRY(m->prof.begin(s));
-    if (m->near_path == OVS_NEAR_PATH_POPCOUNT) {
-        const int chunks = (m->max_n2 + 63) / 64, total_wg = chunks * batch;
-        hipLaunchKernelGGL(k_hamming_near_popc, dim3(((total_wg + 7) / 8) * 8), dim3(256), 0, s, d1, stride_1, d_n1, d2, stride_2, d_n2, d_valid,
-                           m->max_n2, thr, m->d_near_cnt, m->d_near_list, m->d_near_top, chunks, total_wg);
-    } else {
-        const int chunks = (m->max_n2 + kNearQueries - 1) / kNearQueries, total_wg = chunks * batch;
-        hipLaunchKernelGGL(k_hamming_near, dim3(((total_wg + 7) / 8) * 8), dim3(256), 0, s, d1, stride_1, d_n1, d2, stride_2, d_n2, d_valid,
-                           m->max_n2, thr, m->d_near_cnt, m->d_near_list, m->d_near_top, chunks, total_wg);
-    }
+    if (m->near_path == OVS_NEAR_PATH_POPCOUNT)
+        hipLaunchKernelGGL(k_hamming_near_popc, dim3(near.grid), dim3(256), 0, s, d1, stride_1, d_n1, d2, stride_2, d_n2, d_valid, m->caps.max_n2, thr,
+                           m->d_near_cnt, m->d_near_list, m->d_near_top, near.chunks, near.total_wg);
+    else
+        hipLaunchKernelGGL(k_hamming_near, dim3(near.grid), dim3(256), 0, s, d1, stride_1, d_n1, d2, stride_2, d_n2, d_valid, m->caps.max_n2, thr,
+                           m->d_near_cnt, m->d_near_list, m->d_near_top, near.chunks, near.total_wg);
     OVS_HIP_TRY(hipGetLastError());
     OVS_HIP_TRY(m->prof.mark(1, s));
-    if (m->resolve_lds_staged)
-        hipLaunchKernelGGL((k_bf_resolve<true, 4>), dim3(batch), dim3(256), m->resolve_lds_staged, s, d1, stride_1, d_n1, d_valid_1, d2, stride_2,
-                           d_n2, m->max_n1, m->max_n2, lowe_ratio, m->d_near_cnt, m->d_near_list, m->d_near_top, d_pairs, d_counts, cap);
+    if (rp.staged)
+        hipLaunchKernelGGL((k_bf_resolve<true, 4>), dim3(batch), dim3(rp.block), rp.lds_bytes, s, d1, stride_1, d_n1, d_valid_1, d2, stride_2, d_n2,
+                           m->caps.max_n1, m->caps.max_n2, lowe_ratio, m->d_near_cnt, m->d_near_list, m->d_near_top, d_pairs, d_counts, cap);
     else
-        hipLaunchKernelGGL((k_bf_resolve<false, 1>), dim3(batch), dim3(64), m->resolve_lds, s, d1, stride_1, d_n1, d_valid_1, d2, stride_2, d_n2,
-                           m->max_n1, m->max_n2, lowe_ratio, m->d_near_cnt, m->d_near_list, m->d_near_top, d_pairs, d_counts, cap);
+        hipLaunchKernelGGL((k_bf_resolve<false, 1>), dim3(batch), dim3(rp.block), rp.lds_bytes, s, d1, stride_1, d_n1, d_valid_1, d2, stride_2, d_n2,
+                           m->caps.max_n1, m->caps.max_n2, lowe_ratio, m->d_near_cnt, m->d_near_list, m->d_near_top, d_pairs, d_counts, cap);
     OVS_HIP_TRY(hipGetLastError());
     OVS_HIP_TRY(m->prof.mark(2, s));
     return OVS_OK;
@@ -921,78 +922,40 @@ ovs_status run_bf(ovs_matcher* m, const uint8_t* d1, size_t stride_1, const int3
 extern "C" {
 
 ovs_status ovs_matcher_create(int32_t max_n1, int32_t max_n2, int32_t max_batch, int32_t device, ovs_matcher** out) {
-    if (!out || max_n1 < 1 || max_n2 < 1 || max_batch < 1 || max_n1 > 65535 || max_n2 > 65535) return OVS_ERR_INVALID;
+    const ovs_status args = bf_check_create(out != nullptr, max_n1, max_n2, max_batch);
+    if (args == OVS_ERR_INVALID) return args;
     *out = nullptr;
     if (ovs_device_count() <= device || device < 0) return OVS_ERR_NO_DEVICE;
-    ovs_matcher* m = new (std::nothrow) ovs_matcher();
+    if (args != OVS_OK) return args;   // OVS_ERR_CAPACITY
+    std::unique_ptr<ovs_matcher> owner(new (std::nothrow) ovs_matcher());
+    ovs_matcher* const m = owner.get();
     if (!m) return OVS_ERR_INVALID;
     m->device = device;
-    m->max_n1 = max_n1;
-    m->max_n2 = max_n2;
-    m->max_batch = max_batch;
-    m->resolve_lds = (size_t)max_n1 * 4 + (((size_t)max_n1 + 15) & ~(size_t)15);
-    if (m->resolve_lds > 150 * 1024) {
-        delete m;
-        return OVS_ERR_CAPACITY;
-    }
-    {
-        const size_t staged = (((size_t)max_n1 * 5 + 15) & ~(size_t)15) + (size_t)max_n2 * (kTopK + 1) * 4;
-        m->resolve_lds_staged = staged <= 150 * 1024 ? staged : 0;
-    }
-#define CREATE_TRY(expr)                       \
-    do {                                       \
-        hipError_t _e = (expr);                \
-        if (_e != hipSuccess) {                \
-            ovs::set_last_error(#expr, _e);    \
-            ovs_matcher_destroy(m);            \
-            return OVS_ERR_HIP;                \
-        }                                      \
-    } while (0)
-    CREATE_TRY(hipSetDevice(device));
-    CREATE_TRY(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
-    const size_t B = (size_t)max_batch;
-    CREATE_TRY(hipMalloc(&m->d_near_cnt, sizeof(uint32_t) * B * max_n2 * kNearSplit));
-    CREATE_TRY(hipMalloc(&m->d_near_list, sizeof(uint32_t) * B * max_n2 * kNearSplit * kNearSeg));
-    CREATE_TRY(hipMalloc(&m->d_near_top, sizeof(uint32_t) * B * max_n2 * kTopK));
-    CREATE_TRY(hipMalloc(&m->d_desc_1, (size_t)max_n1 * 32));
-    CREATE_TRY(hipMalloc(&m->d_desc_2, (size_t)max_n2 * 32));
-    CREATE_TRY(hipMalloc(&m->d_valid, (size_t)std::max(max_n1, max_n2)));
-    CREATE_TRY(hipMalloc(&m->d_valid_1, (size_t)max_n1));
-    CREATE_TRY(hipMalloc(&m->d_n, sizeof(int32_t) * 2));
-    CREATE_TRY(hipMalloc(&m->d_pairs, sizeof(int32_t) * 2 * max_n2));
-    CREATE_TRY(hipMalloc(&m->d_count, sizeof(int32_t)));
-    CREATE_TRY(hipMalloc(&m->d_best_idx, sizeof(int32_t) * max_n2));
-    CREATE_TRY(hipMalloc(&m->d_best, sizeof(uint16_t) * max_n2));
-    CREATE_TRY(hipMalloc(&m->d_second, sizeof(uint16_t) * max_n2));
-    if (m->resolve_lds > 64 * 1024)
-        CREATE_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bf_resolve<false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)m->resolve_lds));
-    if (m->resolve_lds_staged > 64 * 1024)
-        CREATE_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bf_resolve<true, 4>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)m->resolve_lds_staged));
-#undef CREATE_TRY
-    *out = m;
+    m->caps = BfCaps{max_n1, max_n2, max_batch};
+    m->resolve = bf_resolve_plan(max_n1, max_n2);
+    const BfBuffers b = bf_buffer_bytes(m->caps);
+    OVS_HIP_TRY_RAW(hipSetDevice(device));
+    OVS_HIP_TRY_RAW(m->res.stream(&m->stream));
+    OVS_HIP_TRY_RAW(m->res.dev(&m->d_near_cnt, b.near_cnt));
+    OVS_HIP_TRY_RAW(m->res.dev(&m->d_near_list, b.near_list));
+    OVS_HIP_TRY_RAW(m->res.dev(&m->d_near_top, b.near_top));
+    OVS_HIP_TRY_RAW(m->res.dev(&m->d_desc_1, b.desc_1));
+    OVS_HIP_TRY_RAW(m->res.dev(&m->d_desc_2, b.desc_2));
+    OVS_HIP_TRY_RAW(m->res.dev(&m->d_valid, b.valid));
+    OVS_HIP_TRY_RAW(m->res.dev(&m->d_valid_1, b.valid_1));
+    OVS_HIP_TRY_RAW(m->res.dev(&m->d_n, b.n));
+    OVS_HIP_TRY_RAW(m->res.dev(&m->d_pairs, b.pairs));
+    OVS_HIP_TRY_RAW(m->res.dev(&m->d_count, b.count));
+    OVS_HIP_TRY_RAW(m->res.dev(&m->d_best_idx, b.best_idx));
+    OVS_HIP_TRY_RAW(m->res.dev(&m->d_best, b.best));
+    OVS_HIP_TRY_RAW(m->res.dev(&m->d_second, b.second));
+    if (m->resolve.raise_attr) OVS_HIP_TRY_RAW(raise_resolve_lds(m->resolve));
+    *out = owner.release();
     return OVS_OK;
 }
 
 ovs_status ovs_matcher_destroy(ovs_matcher* m) {
     if (!m) return OVS_OK;
-    if (m->stream) hipStreamSynchronize(m->stream);
-    hipFree(m->d_near_cnt);
-    hipFree(m->d_near_list);
-    hipFree(m->d_near_top);
-    hipFree(m->d_desc_1);
-    hipFree(m->d_desc_2);
-    hipFree(m->d_valid);
-    hipFree(m->d_valid_1);
-    hipFree(m->d_n);
-    hipFree(m->d_pairs);
-    hipFree(m->d_count);
-    hipFree(m->d_best_idx);
-    hipFree(m->d_best);
-    hipFree(m->d_second);
-    m->prof.destroy();
-    if (m->stream) hipStreamDestroy(m->stream);
     delete m;
     return OVS_OK;
 }
@@ -1022,9 +985,9 @@ ovs_status ovs_robust_brute_force_match_batch_dev(ovs_matcher* m, const uint8_t*
                                                   const uint8_t* d_valid_1, const uint8_t* d_desc_2, size_t stride_2, const int32_t* d_n2,
                                                   const uint8_t* d_valid_2, int32_t batch, float lowe_ratio, int32_t* d_pairs,
                                                   int32_t* d_counts, int32_t cap, void* stream) {
-    if (!m || !d_desc_1 || !d_desc_2 || !d_n1 || !d_n2 || !d_pairs || !d_counts || batch < 1 || cap < 1) return OVS_ERR_INVALID;
-    if (batch > m->max_batch || stride_1 > (size_t)m->max_n1 * 32 || stride_2 > (size_t)m->max_n2 * 32) return OVS_ERR_CAPACITY;
-    if (((uintptr_t)d_desc_1 & 3) || ((uintptr_t)d_desc_2 & 3) || (stride_1 & 31) || (stride_2 & 31)) return OVS_ERR_ALIGN;
+    const ovs_status args = bf_check_batch_dev(m ? &m->caps : nullptr, d_desc_1 && d_desc_2 && d_n1 && d_n2 && d_pairs && d_counts, (uintptr_t)d_desc_1,
+                                               stride_1, (uintptr_t)d_desc_2, stride_2, batch, cap);
+    if (args != OVS_OK) return args;
     OVS_HIP_TRY(hipSetDevice(m->device));
     hipStream_t s = (hipStream_t)stream;   // verbatim: NULL is HIP's default stream (torch's default stream handle is 0)
     return run_bf(m, d_desc_1, stride_1, d_n1, d_valid_1, d_desc_2, stride_2, d_n2, d_valid_2, batch, lowe_ratio, d_pairs, d_counts, cap, s);
@@ -1032,13 +995,12 @@ ovs_status ovs_robust_brute_force_match_batch_dev(ovs_matcher* m, const uint8_t*
 
 ovs_status ovs_robust_brute_force_match(ovs_matcher* m, const uint8_t* desc_1, int32_t n1, const uint8_t* valid_1, const uint8_t* desc_2,
                                         int32_t n2, const uint8_t* valid_2, float lowe_ratio, int32_t* pairs, int32_t cap, int32_t* n_out) {
-    if (!m || !n_out || n1 < 0 || n2 < 0 || cap < 0) return OVS_ERR_INVALID;
-    *n_out = 0;
-    if (n1 == 0 || n2 == 0) return OVS_OK;
-    if (!desc_1 || !desc_2 || (cap > 0 && !pairs)) return OVS_ERR_INVALID;
-    if (n1 > m->max_n1 || n2 > m->max_n2) return OVS_ERR_CAPACITY;
+    bool run = false;
+    const ovs_status args = bf_check_match(m ? &m->caps : nullptr, desc_1 != nullptr, n1, desc_2 != nullptr, n2, pairs != nullptr, cap, n_out, &run);
+    if (!run) return args;
     OVS_HIP_TRY(hipSetDevice(m->device));
     hipStream_t s = m->stream;
+    const BfBuffers b = bf_buffer_bytes(m->caps);   // (the staged descriptors' strides: the whole buffers)
     const int32_t nn[2] = {n1, n2};
     OVS_HIP_TRY(hipMemcpyAsync(m->d_desc_1, desc_1, (size_t)n1 * 32, hipMemcpyHostToDevice, s));
     OVS_HIP_TRY(hipMemcpyAsync(m->d_desc_2, desc_2, (size_t)n2 * 32, hipMemcpyHostToDevice, s));
@@ -1046,8 +1008,8 @@ ovs_status ovs_robust_brute_force_match(ovs_matcher* m, const uint8_t* desc_1, i
     if (valid_1) OVS_HIP_TRY(hipMemcpyAsync(m->d_valid_1, valid_1, (size_t)n1, hipMemcpyHostToDevice, s));
     OVS_HIP_TRY(hipMemcpyAsync(m->d_n, nn, sizeof(nn), hipMemcpyHostToDevice, s));
     OVS_HIP_TRY(hipStreamSynchronize(s));   // nn is a stack array
-    ovs_status st = run_bf(m, m->d_desc_1, (size_t)m->max_n1 * 32, m->d_n, valid_1 ? m->d_valid_1 : nullptr, m->d_desc_2, (size_t)m->max_n2 * 32, m->d_n + 1,
-                           valid_2 ? m->d_valid : nullptr, 1, lowe_ratio, m->d_pairs, m->d_count, m->max_n2, s);
+    ovs_status st = run_bf(m, m->d_desc_1, b.desc_1, m->d_n, valid_1 ? m->d_valid_1 : nullptr, m->d_desc_2, b.desc_2, m->d_n + 1,
+                           valid_2 ? m->d_valid : nullptr, 1, lowe_ratio, m->d_pairs, m->d_count, m->caps.max_n2, s);
     if (st != OVS_OK) return st;
     int32_t n = 0;
     OVS_HIP_TRY(hipMemcpyAsync(&n, m->d_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -1063,11 +1025,9 @@ ovs_status ovs_robust_brute_force_match(ovs_matcher* m, const uint8_t* desc_1, i
 
 ovs_status ovs_hamming_best2(ovs_matcher* m, const uint8_t* q, int32_t nq, const uint8_t* t, int32_t nt, const uint8_t* t_valid,
                              int32_t* best_idx, uint16_t* best, uint16_t* second) {
-    if (!m || nq < 0 || nt < 0) return OVS_ERR_INVALID;
-    if (nq == 0) return OVS_OK;
-    if (!q || (nt > 0 && !t) || !best_idx || !best || !second) return OVS_ERR_INVALID;
-    // queries ride in the idx_2 buffers, targets in the idx_1 buffers
-    if (nq > m->max_n2 || nt > m->max_n1) return OVS_ERR_CAPACITY;
+    bool run = false;
+    const ovs_status args = bf_check_best2(m ? &m->caps : nullptr, q != nullptr, nq, t != nullptr, nt, best_idx && best && second, &run);
+    if (!run) return args;
     OVS_HIP_TRY(hipSetDevice(m->device));
     hipStream_t s = m->stream;
     OVS_HIP_TRY(hipMemcpyAsync(m->d_desc_2, q, (size_t)nq * 32, hipMemcpyHostToDevice, s));

@@ -1,7 +1,7 @@
 // owned_internal.inc -- the one owner of HIP resources on the host side of the C ABI. A handle (or a per-thread work space) acquires its
 // device memory, page-locked memory, streams and events through its Owned member; ~Owned gives back exactly those, on every exit path, so a
 // create needs no clean-up branch and a destroy no list. (An .inc, not an .h: bench.py fingerprints every .h of this directory into the
-// committed counters of the extractor and matcher stages, which include none of this.)
+// committed counters of the extractor and matcher stages, which host-only code should not age.)
 #pragma once
 #include <atomic>
 #include <cstdint>

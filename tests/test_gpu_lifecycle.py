@@ -63,6 +63,10 @@ def cycle(m, kind):
         ex = new_extractor(m)
         ex.extract(m.left)
         ex.__del__()
+    elif kind == "matcher":
+        mt = m.match.robust(0.9, False, max_n1=128, max_n2=128)
+        mt.brute_force_match(m.desc[:1], m.desc[:1])
+        mt.__del__()
     elif kind == "wmatcher":
         w = m.match.projection(0.8, False, max_targets=4096, max_queries=16)
         w.assign_keypoints_to_grid(m.grid, m.kps[:1])
@@ -106,7 +110,7 @@ def cycle(m, kind):
         multi_cycle(m, 2)
 
 
-@pytest.mark.parametrize("kind", ["orb", "wmatcher", "frame_dev", "stereo", "vocab", "bowdb", "sim3", "pnp", "ba_graph", "ba_multi_1", "ba_multi_2"])
+@pytest.mark.parametrize("kind", ["orb", "matcher", "wmatcher", "frame_dev", "stereo", "vocab", "bowdb", "sim3", "pnp", "ba_graph", "ba_multi_1", "ba_multi_2"])
 def test_balanced(m, kind):
     """Four create / call / destroy cycles after a warm one leave the count exactly where it was."""
     if kind == "ba_multi_2" and m.L.ovs_device_count() < 2:
@@ -143,6 +147,23 @@ def test_lazy_members_of_an_extractor(m):
     assert m.live() > created   # the late allocations are counted ...
     ex.__del__()
     assert m.live() == before   # ... and given back
+
+
+def test_matcher_with_its_profiler_and_a_refused_create(m):
+    """A brute-force matcher whose stage profiler created its events (outside the count) gives back what the create took; a create the plan refuses
+    (the one-wave resolver's LDS beyond 150 KiB) takes nothing and hands back no handle."""
+    ERR_CAPACITY = -4
+    before = m.live()
+    mt = m.match.robust(0.9, False, max_n1=128, max_n2=128)
+    assert m.live() > before
+    assert m.L.ovs_matcher_profile_enable(mt._h, 1) == OK
+    mt.brute_force_match(m.desc[:8], m.desc[:8])
+    stage_ms, ncalls = (C.c_float * 2)(), C.c_int32()
+    assert m.L.ovs_matcher_profile_read(mt._h, stage_ms, C.byref(ncalls)) == OK and ncalls.value == 1
+    mt.__del__()
+    assert m.live() == before
+    h = C.c_void_p(1)
+    assert m.L.ovs_matcher_create(30721, 1, 1, 0, C.byref(h)) == ERR_CAPACITY and not h.value and m.live() == before
 
 
 def test_lazy_members_of_frame_and_solver_handles(m):

@@ -53,7 +53,13 @@ def test_brute_force_match(match, oracle, n1, n2, n_true, ratio, near_path):
         assert len(want) > n_true // 3 and 0 < len(want1) < len(want)
 
 
-def test_claim_conflicts(match, oracle, near_path):
+# Handle capacities of the resolver's two forms (tests/test_match_bf_plan.py holds the table): the four-wave form with every query's counts and top-8
+# staged in LDS, and the one-wave form that reads them from memory -- the one the C++ class layer's 4096 x 4096 handles run
+ONE_WAVE = dict(max_n1=2048, max_n2=4096)
+
+
+@pytest.mark.parametrize("caps", [dict(max_n1=256, max_n2=256), ONE_WAVE], ids=["staged", "one_wave"])
+def test_claim_conflicts(match, oracle, near_path, caps):
     """Several keyframe descriptors compete for the same frame descriptor: exercises the already-matched rule."""
     rng = np.random.default_rng(3)
     base = rng.integers(0, 256, size=(40, 32), dtype=np.uint8)
@@ -65,28 +71,68 @@ def test_claim_conflicts(match, oracle, near_path):
             bits[rng.permutation(256)[:int(rng.integers(0, 12))]] ^= 1
             d[i] = np.packbits(bits)
     for ratio in (0.6, 0.9, 1.0):
-        m = match.robust(ratio, False, max_n1=256, max_n2=256, near_path=near_path)
+        m = match.robust(ratio, False, near_path=near_path, **caps)
         assert np.array_equal(m.brute_force_match(d1, d2), oracle.robust_brute_force_match(d1, d2, None, ratio))
         v1 = (np.arange(len(d1)) % 3 != 0).astype(np.uint8)   # the first of every triplet is masked: claimants fall through to the next
         assert np.array_equal(m.brute_force_match(d1, d2, frm_valid=v1), oracle.robust_brute_force_match(d1, d2, None, ratio, frm_valid=v1))
 
 
-def test_overflowing_near_lists_fall_back_exactly(match, oracle, near_path):
+@pytest.mark.parametrize("caps", [dict(max_n1=128, max_n2=128), ONE_WAVE], ids=["staged", "one_wave"])
+def test_overflowing_near_lists_fall_back_exactly(match, oracle, near_path, caps):
     """Many identical descriptors overflow the near lists -> literal serial replay path."""
     d1 = np.zeros((100, 32), np.uint8)
     d2 = np.zeros((60, 32), np.uint8)
     d1[::7, 0] = 1
     d2[::5, 3] = 0x80
     for ratio in (0.6, 0.9):
-        m = match.robust(ratio, False, max_n1=128, max_n2=128, near_path=near_path)
+        m = match.robust(ratio, False, near_path=near_path, **caps)
         assert np.array_equal(m.brute_force_match(d1, d2), oracle.robust_brute_force_match(d1, d2, None, ratio))
         v1 = (np.arange(len(d1)) % 3 != 0).astype(np.uint8)   # the first of every triplet is masked: claimants fall through to the next
         assert np.array_equal(m.brute_force_match(d1, d2, frm_valid=v1), oracle.robust_brute_force_match(d1, d2, None, ratio, frm_valid=v1))
     # ratio 1.01: duplicates are accepted one by one until the frame side runs out
-    m = match.robust(1.01, False, max_n1=128, max_n2=128, near_path=near_path)
+    m = match.robust(1.01, False, near_path=near_path, **caps)
     got = m.brute_force_match(d1, d2)
     want = oracle.robust_brute_force_match(d1, d2, None, 1.01)
     assert np.array_equal(got, want) and len(want) > 10
+
+
+@pytest.mark.parametrize("caps", [dict(max_n1=128, max_n2=128), ONE_WAVE], ids=["staged", "one_wave"])
+def test_dry_top8_rescans_the_near_list(match, oracle, near_path, caps):
+    """24 frame and 24 keyframe descriptors, all within 4 bits of one base descriptor: every query's near list names all 24 frame descriptors, none
+    overflows. From the ninth query on the eight keys held in registers are all claimed while the list is longer, so the resolver rescans the whole
+    list (and refills the registers). At ratio 1.01 every query accepts as long as an unclaimed frame descriptor is left (best <= 50, second >= best):
+    24 pairs by the oracle alone."""
+    rng = np.random.default_rng(24)
+    base = np.unpackbits(rng.integers(0, 256, size=32, dtype=np.uint8))
+
+    def near_copies(n):
+        out = np.empty((n, 32), np.uint8)
+        for i in range(n):
+            bits = base.copy()
+            bits[rng.permutation(256)[:int(rng.integers(0, 5))]] ^= 1
+            out[i] = np.packbits(bits)
+        return out
+
+    d1, d2 = near_copies(24), near_copies(24)
+    for ratio in (1.01, 0.9):
+        want = oracle.robust_brute_force_match(d1, d2, None, ratio)
+        if ratio == 1.01:
+            assert len(want) == 24
+        m = match.robust(ratio, False, near_path=near_path, **caps)
+        assert np.array_equal(m.brute_force_match(d1, d2), want), ratio
+
+
+def test_a_smaller_handle_leaves_a_larger_ones_launches_valid(match, oracle):
+    """Both handles need more dynamic LDS than a kernel gets by default (123008 and 83968 bytes of the same resolver form); the limit is a property of
+    the kernel, not of the handle, and the second create must not lower what the first one raised."""
+    rng = np.random.default_rng(70)
+    d1, d2 = _descs(rng, 70, 70, 50)
+    want = oracle.robust_brute_force_match(d1, d2, None, 0.9)
+    large = match.robust(0.9, False, max_n1=3000, max_n2=3000)
+    small = match.robust(0.9, False, max_n1=2048, max_n2=2048)
+    assert len(want) > 10
+    assert np.array_equal(small.brute_force_match(d1, d2), want)
+    assert np.array_equal(large.brute_force_match(d1, d2), want)
 
 
 def test_best2_and_distance_identities(match, oracle):
