@@ -668,7 +668,11 @@ ovs_status ovs_ba_multi_linearize(ovs_ba_multi* m, const double* poses, const do
  * node_desc n_nodes x 32 bytes, node_weight (word weights; inner nodes ignored), node_word_id (-1 for inner nodes), depth = L.
  * Per feature: word_id, weight (the leaf's) and node_id (the ancestor at level L - levelsup, 0 if levelsup >= L). The BowVector
  * (v[word] += weight in feature order, then L1-normalised) and the FeatureVector (fv[node].push_back(i)) are std::maps the shim fills
- * from these arrays exactly as DBoW2 does. The _dev form takes the extractor's device outputs (descriptors B x cap x 32, counts B). */
+ * from these arrays exactly as DBoW2 does. The _dev form takes the extractor's device outputs (descriptors B x cap x 32, counts B).
+ * ovs_vocab_create checks on the host, before the device is touched, that the child list is a tree: child_start starts at 0 and does not
+ * decrease, a node has at most 65535 children, every entry of children is in [1, n_nodes) (the root is nobody's child) and no node is
+ * listed as a child more than once. Anything else is OVS_ERR_INVALID: the descent follows children until a node has none, so a list with a
+ * cycle would never end. A feature whose leaf lies above level L - levelsup gets node_id 0 (the root). */
 typedef struct ovs_vocab ovs_vocab;
 ovs_status ovs_vocab_create(int32_t device, int32_t n_nodes, const int32_t* child_start, const int32_t* children, const uint8_t* node_desc,
                             const double* node_weight, const int32_t* node_word_id, int32_t depth, int32_t max_features, ovs_vocab** out);

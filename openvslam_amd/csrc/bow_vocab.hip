@@ -10,7 +10,8 @@
 //
 // Layout: the vocabulary lives in HBM as a CSR of children with the child descriptors stored in CSR order, so the k children of a node
 // are k consecutive 32-byte rows (k = 10 in ORBvoc: 320 B, one or two 256-byte requests). One 16-lane row of a wave per descriptor, one
-// lane per child; the minimum over the row is a key reduction on (distance << 8 | child) with row-local shuffles. A frame's 2000
+// lane per child, 16 children per pass; the minimum over the row is a key reduction on (distance << 16 | child position in the node: a node
+// has at most 65535 children, ovs_vocab_create refuses more) with row-local shuffles, the smaller key kept across passes. A frame's 2000
 // descriptors make 500 waves; the top levels of the tree (1 + 10 + 100 + 1000 nodes = 36 KB) stay in L2, the two bottom levels are
 // random 320-byte reads (1.3 MB per frame) -- the kernel is latency-bound and tiny next to the extraction.
 #include <algorithm>
@@ -105,8 +106,13 @@ ovs_status ovs_vocab_create(int32_t device, int32_t n_nodes, const int32_t* chil
         if (c < 0 || c > 65535) return OVS_ERR_INVALID;
         max_children = std::max(max_children, c);
     }
-    for (int i = 0; i < n_edges; ++i)
-        if (children[i] <= 0 || children[i] >= n_nodes) return OVS_ERR_INVALID;   // node 0 is the root and nobody's child
+    // node 0 is the root and nobody's child, every other node is a child at most once: what the root reaches is then a tree, and the
+    // kernel's descent (which follows `children` until a node has none) ends. A list with a cycle would keep it walking for ever.
+    std::vector<uint8_t> is_child((size_t)n_nodes, 0);
+    for (int i = 0; i < n_edges; ++i) {
+        if (children[i] <= 0 || children[i] >= n_nodes || is_child[children[i]]) return OVS_ERR_INVALID;
+        is_child[children[i]] = 1;
+    }
     if (ovs_device_count() <= device || device < 0) return OVS_ERR_NO_DEVICE;
     OVS_HIP_TRY(hipSetDevice(device));
     std::unique_ptr<ovs_vocab> owner(new ovs_vocab());

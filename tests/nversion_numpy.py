@@ -873,11 +873,9 @@ def bow_transform(vocab, desc, levelsup=4):
     bits = np.unpackbits(np.asarray(desc, np.uint8).reshape(-1, 32), axis=1).astype(np.int32)
     n, depth = len(bits), int(vocab["depth"])
     cur = np.zeros(n, np.int64)
-    node_at = np.zeros(n, np.int64)                     # the root, unless the descent passes level depth - levelsup
+    node_at = np.zeros(n, np.int64)                     # the root, unless the feature itself moves into level depth - levelsup (> 0)
     level = 0
     while True:
-        if level == depth - levelsup:
-            node_at = cur.copy()
         n_kids = cs[cur + 1] - cs[cur]
         moving = np.nonzero(n_kids > 0)[0]
         if len(moving) == 0:
@@ -889,6 +887,6 @@ def bow_transform(vocab, desc, levelsup=4):
         dist = np.where(slot < n_kids[moving][:, None], dist, 1 << 20)
         cur[moving] = kid[np.arange(len(moving)), np.argmin(dist, axis=1)]
         level += 1
-    if levelsup <= 0:
-        node_at = cur.copy()
+        if level == depth - levelsup:                   # a feature whose leaf is shallower never gets here and keeps the root
+            node_at[moving] = cur[moving]
     return np.asarray(vocab["word_id"])[cur].astype(np.int32), np.asarray(vocab["weight"], np.float64)[cur], node_at.astype(np.int32)

@@ -706,11 +706,17 @@ def test_whole_extractor_in_numpy_equals_the_oracle(oracle, rows, cols, nfeat, s
         assert len(k) == len(wk) and k.tobytes() == np.ascontiguousarray(wk).tobytes() and np.array_equal(d, wd), (len(k), len(wk))
 
 
-@pytest.mark.parametrize("k,depth", [(10, 4), (6, 3), (3, 6)])
+@pytest.mark.parametrize("k,depth", [(10, 4), (6, 3), (3, 6), ("ragged", 4)])
 def test_bow_transform_second_restatement(oracle, k, depth):
     """Rule 29 (DBoW2 transform): the level-synchronous numpy descent (bit-vector distances, first minimum in child order, ragged last level,
-    zero-weight words) equals the oracle's per-feature loop for every levelsup, on descriptors near the words and on random ones."""
-    vocab = synth.synth_vocabulary(k, depth, seed=k + depth)
+    zero-weight words) equals the oracle's per-feature loop for every levelsup, on descriptors near the words and on random ones. `ragged`
+    (tests/bow_trees.py) adds leaves above the last level: a feature that stops there keeps the root as its node."""
+    if k == "ragged":
+        import bow_trees
+        vocab = bow_trees.ragged()[0]
+        assert vocab["depth"] == depth
+    else:
+        vocab = synth.synth_vocabulary(k, depth, seed=k + depth)
     rng = np.random.default_rng(9)
     leaves = np.nonzero(vocab["word_id"] >= 0)[0]
     near = np.stack([synth.flip_bits(rng, vocab["desc"][i], 30) for i in rng.choice(leaves, 600)])

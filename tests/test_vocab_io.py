@@ -16,15 +16,24 @@ def _vocab(k=7, depth=4, seed=5):
     return synth_vocabulary(k=k, depth=depth, seed=seed)
 
 
-@pytest.mark.parametrize("fmt,code", [("text", 1), ("dbow2", 2), ("fbow", 3)])
+def _bow_trees():
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import bow_trees
+    return bow_trees
+
+
+@pytest.mark.parametrize("fmt,code", [("text", 1), ("dbow2", 2), ("fbow", 3), ("text-ragged", 1), ("dbow2-ragged", 2), ("fbow-ragged", 3)])
 def test_formats_round_trip_on_the_host(tmp_path, fmt, code):
+    """`-ragged`: tests/bow_trees.py's tree (leaves at levels 1, 2 and 3, nodes of 1 to 33 children, declared depth 4) instead of synth's"""
     import vocab_io
     from openvslam_amd import bow
-    v = _vocab()
+    fmt, _, tree = fmt.partition("-")
+    v = _bow_trees().ragged()[0] if tree else _vocab()
     path = tmp_path / ("orb_vocab." + fmt)
     vocab_io.WRITERS[fmt](str(path), v)
     got, fcode = bow.load_vocabulary_tree(path)
-    assert fcode == code and got["depth"] == v["depth"]
+    # FBoW has no depth field: the reader reports the deepest node's level (ragged: 3 under a declared 4; synth: the declared depth)
+    assert fcode == code and got["depth"] == (_bow_trees().depth_on_disk(v, fmt) if tree else v["depth"])
     n = len(v["word_id"])
     if fmt == "fbow":   # FBoW numbers inner nodes in block order: compare through that permutation
         order = vocab_io.fbow_node_order(v)
