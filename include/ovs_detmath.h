@@ -414,4 +414,47 @@ OVS_DM_FN double ovs_det_exp(double x) {
     return e;
 }
 
+// log (double) for the pose-graph optimiser's Sim3 logarithm (DESIGN.md 3.19 rule G4), in the manner of the three above. Range reduction:
+// x = 2^k m with m in [1, 2) read from the bits (a subnormal is scaled by 2^54 first); m > RN(sqrt 2) is halved and k raised, so that
+// f = m - 1 (exact) lies in [-0.2929, 0.4143). With s = f / (2 + f) and z = s s, log(1 + f) = 2 s + s R(z), where R(z) = z (2/3 + z (2/5 +
+// ... + z 2/21)) is the Horner form of the atanh series whose coefficients are the exact rationals 2 / (2 j + 1), j = 1 .. 10, rounded ONCE
+// to double (the hex literals below; tests/posegraph_ref.py recomputes them from fractions). It is summed in fdlibm's order
+// k ln2_hi - ((h - (s (h + R) + k ln2_lo)) - f) with h = 0.5 (f f), ln2_hi = ln 2 cut to 32 significant bits (k ln2_hi is exact), ln2_lo the rest.
+// The result is NaN for x <= 0, a NaN and an infinity: a Sim3 scale that is none of a positive finite number costs the trial.
+// Measured against glibc 2.35 on 400 000 random points of [0.25, 4] (tests/test_posegraph_ref.py): at most 1 ulp.
+OVS_DM_FN double ovs_det_log(double x) {
+    using namespace ovs_dm;
+    const double ln2_hi = 0x1.62e42fee00000p-1, ln2_lo = 0x1.a39ef35793c76p-33, sqrt2 = 0x1.6a09e667f3bcdp+0;
+    if (!(x > 0.0) || !(x < from_bits(0x7ff0000000000000ull))) return nan_d();
+    int k = 0;
+    if (x < 0x1p-1022) {   // a subnormal
+        x = x * 0x1p54;
+        k = -54;
+    }
+    const uint64_t u = bits_of(x);
+    k += (int)(u >> 52) - 1023;
+    double m = from_bits((u & 0x000fffffffffffffull) | 0x3ff0000000000000ull);
+    if (m > sqrt2) {
+        m = m * 0.5;
+        k += 1;
+    }
+    const double f = m - 1.0;
+    const double s = f / (2.0 + f);
+    const double z = s * s;
+    double p = 0x1.8618618618618p-4;
+    p = 0x1.af286bca1af28p-4 + z * p;
+    p = 0x1.e1e1e1e1e1e1ep-4 + z * p;
+    p = 0x1.1111111111111p-3 + z * p;
+    p = 0x1.3b13b13b13b14p-3 + z * p;
+    p = 0x1.745d1745d1746p-3 + z * p;
+    p = 0x1.c71c71c71c71cp-3 + z * p;
+    p = 0x1.2492492492492p-2 + z * p;
+    p = 0x1.999999999999ap-2 + z * p;
+    p = 0x1.5555555555555p-1 + z * p;
+    const double R = z * p;
+    const double h = 0.5 * (f * f);
+    const double dk = (double)k;
+    return dk * ln2_hi - ((h - (s * (h + R) + dk * ln2_lo)) - f);
+}
+
 #endif   // OVS_DETMATH_H_

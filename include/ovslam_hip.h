@@ -1089,6 +1089,38 @@ ovs_status ovs_projection_match_keyframes_mutually_f(ovs_wmatcher* w, const ovs_
                                                      int32_t* num_matches);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Pose-graph optimiser for loop correction.  replaces: optimize::graph_optimizer::optimize(loop_keyfrm, curr_keyfrm, non_corrected_Sim3s,
+ *   pre_corrected_Sim3s, loop_connections) (src/openvslam/optimize/graph_optimizer.{h,cc}): the g2o graph of one Sim3 vertex per keyframe
+ *   and one Sim3 edge per essential-graph connection, Levenberg-Marquardt over it, and the write-back that moves every landmark with its
+ *   reference keyframe, in ONE call of two launches (rules G1 to G11).
+ * ovs_posegraph_create: a handle for up to max_vertices keyframes, max_edges edges and max_landmarks landmarks; one internal mutex
+ *   serialises the calls on a handle.
+ * ovs_posegraph_optimize: vertex v starts at S_vw = (rot_in (9, row-major), trans_in (3), scale_in); fixed[v] = 1 keeps it outside the
+ *   system (upstream fixes the loop keyframe). nc_rot / nc_trans / nc_scale: the caller's non-corrected S_vw per vertex, read by the
+ *   landmark write-back only. Edge e joins vertices i = edge_ij[2 e] and j = edge_ij[2 e + 1] with the measurement M_ji = (edge_rot,
+ *   edge_trans, edge_scale): its error is log(M_ji S_i S_j^-1), its information the identity. fix_scale: non-zero freezes every scale.
+ *   num_iter: upstream runs 50. pcg_max_iter: the cap of the linear solver's iterations per trial, 0 = 7 x (free vertices). Landmark m
+ *   with lm_ref_vertex[m] = r moves to S_r^-1 (nc_r p) with the optimised S_r; r = -1 copies it. Outputs: the optimised (R, t, s) per
+ *   vertex (a pose is rot_cw = R, trans_cw = t / s) and the landmarks. out_info: NULL, or 8 doubles: the Levenberg-Marquardt iterations,
+ *   the trials, the initial and the final chi-square, the last lambda, the PCG iterations in total and of the last solve, and a status
+ *   word: 0 = ran, 1 = nothing to do (no free vertex or no edge: the vertices come back as they came), 2 = non-finite sums. A NaN or Inf in
+ *   a vertex or a measurement is not an error and the call returns: no trial is accepted and the vertices come back as they came, status 2.
+ *   Results are bit-exact functions of the inputs, whatever the handle's capacity or history.
+ * OVS_ERR_INVALID: a NULL required pointer (out_info may be NULL; an array of a count that is 0 may be NULL), a negative count,
+ *   num_iter < 1, pcg_max_iter < 0, an edge index outside [0, n_vertices), an edge with i == j, a landmark reference outside
+ *   [-1, n_vertices), a fixed byte other than 0 or 1. OVS_ERR_CAPACITY: more than the handle was created for (no output is written).
+ *   Both are decided before any launch. */
+typedef struct ovs_posegraph ovs_posegraph;
+ovs_status ovs_posegraph_create(int32_t device, int32_t max_vertices, int32_t max_edges, int32_t max_landmarks, ovs_posegraph** out);
+ovs_status ovs_posegraph_destroy(ovs_posegraph* s);
+ovs_status ovs_posegraph_optimize(ovs_posegraph* s, int32_t n_vertices, const double* rot_in, const double* trans_in, const double* scale_in,
+                                  const uint8_t* fixed, const double* nc_rot, const double* nc_trans, const double* nc_scale, int32_t n_edges,
+                                  const int32_t* edge_ij, const double* edge_rot, const double* edge_trans, const double* edge_scale,
+                                  int32_t fix_scale, int32_t num_iter, int32_t pcg_max_iter, int32_t n_landmarks, const int32_t* lm_ref_vertex,
+                                  const double* lm_pos_in, double* out_rot, double* out_trans, double* out_scale, double* out_lm_pos,
+                                  double* out_info);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Self-test of include/ovs_detmath.h on the device: out[i] = fn(a[i] (, b[i])) evaluated by a gfx950 kernel. The four functions
  * replace libm calls upstream makes where a float decides a match pair (landmark::predict_scale_level's std::log(float),
  * camera::equirectangular::reproject_to_image's asin / atan2, match::robust::check_epipolar_constraint's acos); the same header is
@@ -1103,6 +1135,7 @@ ovs_status ovs_projection_match_keyframes_mutually_f(ovs_wmatcher* w, const ovs_
 #define OVS_DETMATH_SIN 6     /* double: the transform optimiser's exponential map (DESIGN.md 3.11 rule 3) */
 #define OVS_DETMATH_COS 7
 #define OVS_DETMATH_EXP 8
+#define OVS_DETMATH_LOG 9     /* double: the pose-graph optimiser's Sim3 logarithm (DESIGN.md 3.19 rule G4) */
 ovs_status ovs_detmath_eval(int32_t device, int32_t fn, const double* a, const double* b, double* out, int32_t n);
 
 /* ------------------------------------------------------------------------------------------------------------------

@@ -128,6 +128,9 @@ SYMBOLS = {
     "ovs_sim3opt_destroy": (_i32, [_vp]),
     "ovs_sim3opt_optimize_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _f, _i32, _vp, _vp, _vp, _vp, _vp,
                                           _vp]),
+    "ovs_posegraph_create": (_i32, [_i32, _i32, _i32, _i32, C.POINTER(_vp)]),
+    "ovs_posegraph_destroy": (_i32, [_vp]),
+    "ovs_posegraph_optimize": (_i32, [_vp, _i32] + [_vp] * 7 + [_i32] + [_vp] * 4 + [_i32, _i32, _i32, _i32] + [_vp] * 7),
     "ovs_twoview_create": (_i32, [_i32, _i32, _i32, C.POINTER(_vp)]),
     "ovs_twoview_destroy": (_i32, [_vp]),
     "ovs_twoview_solve_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, C.c_double, _i32, _i32, C.c_uint64, _i32] + [_vp] * 9),

@@ -57,9 +57,15 @@ namespace data {
 class keyframe;
 
 // data::map_database: only the lock local_bundle_adjuster takes around its write-back
+class landmark;
 class map_database {
 public:
     static inline std::mutex mtx_database_;
+    // what optimize::graph_optimizer walks (upstream: the values of keyframes_ / landmarks_)
+    std::vector<keyframe*> get_all_keyframes() const { return keyframes_; }
+    std::vector<landmark*> get_all_landmarks() const { return landmarks_; }
+    std::vector<keyframe*> keyframes_;
+    std::vector<landmark*> landmarks_;
 };
 
 using bow_feature_vector = std::map<unsigned int, std::vector<unsigned int>>;   // DBoW2::FeatureVector
@@ -185,6 +191,20 @@ public:
     std::set<keyframe*> get_connected_keyframes() const { return connected_keyfrms_; }
     std::vector<keyframe*> covisibilities_;
     std::set<keyframe*> connected_keyfrms_;   // every keyframe sharing a landmark (upstream: the keys of connected_keyfrms_and_weights_)
+    // the essential graph optimize::graph_optimizer reads: weights, the spanning tree, the loop edges
+    unsigned int get_weight(keyframe* keyfrm) const {
+        const auto it = connected_keyfrms_and_weights_.find(keyfrm);
+        return it == connected_keyfrms_and_weights_.end() ? 0u : it->second;
+    }
+    inline std::vector<keyframe*> get_covisibilities_over_weight(const unsigned int weight) const;   // defined after keyframe
+    keyframe* get_spanning_parent() const { return spanning_parent_; }
+    std::set<keyframe*> get_spanning_children() const { return spanning_children_; }
+    bool has_spanning_child(keyframe* keyfrm) const { return spanning_children_.count(keyfrm) != 0; }
+    std::set<keyframe*> get_loop_edges() const { return loop_edges_; }
+    std::map<keyframe*, unsigned int> connected_keyfrms_and_weights_;
+    keyframe* spanning_parent_ = nullptr;
+    std::set<keyframe*> spanning_children_;
+    std::set<keyframe*> loop_edges_;
 };
 
 class keyframe {
@@ -247,6 +267,18 @@ public:
         return c;
     }
 };
+
+// graph_node::get_covisibilities_over_weight: the connected keyframes of at least `weight`, strongest first, ties by ascending id
+inline std::vector<keyframe*> graph_node::get_covisibilities_over_weight(const unsigned int weight) const {
+    std::vector<keyframe*> out;
+    for (const auto& kw : connected_keyfrms_and_weights_)
+        if (kw.second >= weight) out.push_back(kw.first);
+    std::sort(out.begin(), out.end(), [this](keyframe* a, keyframe* b) {
+        const unsigned int wa = get_weight(a), wb = get_weight(b);
+        return wa != wb ? wa > wb : a->id_ < b->id_;
+    });
+    return out;
+}
 
 // landmark::replace(lm): this landmark's observations move to lm (keyframes that already see lm just drop this one), then it is erased
 inline void landmark::replace(landmark* lm) {

@@ -23,6 +23,7 @@ __global__ __launch_bounds__(256) void k_detmath_eval(int fn, const double* __re
         case OVS_DETMATH_SIN: r = ovs_det_sin(a[i]); break;
         case OVS_DETMATH_COS: r = ovs_det_cos(a[i]); break;
         case OVS_DETMATH_EXP: r = ovs_det_exp(a[i]); break;
+        case OVS_DETMATH_LOG: r = ovs_det_log(a[i]); break;
         default: r = 0.0; break;
     }
     out[i] = r;
@@ -31,7 +32,7 @@ __global__ __launch_bounds__(256) void k_detmath_eval(int fn, const double* __re
 }   // namespace ovs
 
 extern "C" ovs_status ovs_detmath_eval(int32_t device, int32_t fn, const double* a, const double* b, double* out, int32_t n) {
-    if (n < 0 || !a || !out || fn < OVS_DETMATH_LOGF || fn > OVS_DETMATH_EXP || (fn == OVS_DETMATH_ATAN2 && !b)) return OVS_ERR_INVALID;
+    if (n < 0 || !a || !out || fn < OVS_DETMATH_LOGF || fn > OVS_DETMATH_LOG || (fn == OVS_DETMATH_ATAN2 && !b)) return OVS_ERR_INVALID;
     if (ovs_device_count() < 1) return OVS_ERR_NO_DEVICE;
     if (n == 0) return OVS_OK;
     if (hipSetDevice(device) != hipSuccess) return OVS_ERR_HIP;

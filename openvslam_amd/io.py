@@ -23,7 +23,7 @@ from dataclasses import dataclass, field
 import msgpack
 import numpy as np
 
-from .ba import EDGE_DTYPE, EDGE_STEREO_DTYPE
+from .ba import EDGE_DTYPE, EDGE_STEREO_DTYPE, quat_to_rot
 from .match import KP_DTYPE
 
 
@@ -84,9 +84,8 @@ class map_database:
                     obs[lid].append((kid, int(idx)))
         return obs
 
-    def covisibilities(self, keyfrm_id, weight_thr=15):
-        """graph_node::update_connections: keyframes sharing >= weight_thr landmarks with keyfrm_id (the best one if none reaches it),
-        strongest first; ties by ascending id."""
+    def covisibility_weights(self, keyfrm_id):
+        """keyframe id -> the number of landmarks it shares with keyfrm_id (graph_node's connected_keyfrms_and_weights_), zeros left out."""
         mine = self.keyframes[keyfrm_id].lm_ids
         mine = set(int(v) for v in mine[mine >= 0])
         w = {}
@@ -97,6 +96,12 @@ class map_database:
             n = sum(1 for v in ids if int(v) in mine)
             if n:
                 w[kid] = n
+        return w
+
+    def covisibilities(self, keyfrm_id, weight_thr=15):
+        """graph_node::update_connections: keyframes sharing >= weight_thr landmarks with keyfrm_id (the best one if none reaches it),
+        strongest first; ties by ascending id."""
+        w = self.covisibility_weights(keyfrm_id)
         keep = [k for k, n in w.items() if n >= weight_thr]
         if not keep and w:
             keep = [max(sorted(w), key=lambda k: w[k])]
@@ -236,6 +241,89 @@ def local_ba_problem(db, curr_keyfrm_id):
             "cam": np.array([cam["fx"], cam["fy"], cam["cx"], cam["cy"]], np.float64), "focal_x_baseline": float(cam.get("focal_x_baseline", 0.0)),
             "setup_type": {"Monocular": 0, "Stereo": 1, "RGBD": 2}.get(cam.get("setup_type", "Monocular"), 0),
             "keyfrm_ids": keyfrm_ids, "lm_ids": lm_ids, "n_local": len(local)}
+
+
+def _sim3(R, t, s):
+    return [float(v) for v in np.asarray(R, np.float64).ravel()], [float(v) for v in np.asarray(t, np.float64).ravel()], float(s)
+
+
+def _sim3_inverse(S):
+    """DESIGN.md 3.19 rule G1 in Python floats: R' = R^T, s' = 1 / s, t' = (-s') (R^T t)."""
+    R, t, s = S
+    si = 1.0 / s
+    return ([R[0], R[3], R[6], R[1], R[4], R[7], R[2], R[5], R[8]],
+            [(-si) * ((R[r] * t[0] + R[3 + r] * t[1]) + R[6 + r] * t[2]) for r in range(3)], si)
+
+
+def _sim3_product(A, B):
+    """Rule G1's A B = (R_A R_B, s_A (R_A t_B) + t_A, s_A s_B), every sum left to right."""
+    Ra, ta, sa = A
+    Rb, tb, sb = B
+    return ([(Ra[3 * i] * Rb[j] + Ra[3 * i + 1] * Rb[3 + j]) + Ra[3 * i + 2] * Rb[6 + j] for i in range(3) for j in range(3)],
+            [sa * ((Ra[3 * i] * tb[0] + Ra[3 * i + 1] * tb[1]) + Ra[3 * i + 2] * tb[2]) + ta[i] for i in range(3)], sa * sb)
+
+
+def pose_graph_problem(db, loop_keyfrm_id, curr_keyfrm_id, non_corrected, pre_corrected, loop_connections, min_weight=100):
+    """The graph optimize::graph_optimizer::optimize(loop_keyfrm, curr_keyfrm, non_corrected_Sim3s, pre_corrected_Sim3s, loop_connections)
+    builds (expected: src/openvslam/optimize/graph_optimizer.cc, as recalled), as the flat arrays of ovs_posegraph_optimize.
+    non_corrected / pre_corrected: keyframe id -> (R (3, 3), t (3), s), the Sim3_cw before / after the loop's correction of the current
+    keyframe's neighbourhood; loop_connections: keyframe id -> the ids it newly connects to. Vertices in ascending keyframe id: a vertex
+    starts from pre_corrected if present, otherwise from (rot_cw, trans_cw, 1.0); the loop keyframe is fixed. Edges, measurement Sim3_21 =
+    Sim3_2w Sim3_1w^-1 with vertex 0 = keyframe 1, in upstream's order: (a) the loop connections from the vertices' start states, kept at
+    weight >= min_weight or when the pair is (current, loop); then per keyframe in ascending id, with the non-corrected Sim3 of either end
+    where there is one: (b) its spanning-tree parent, (c) its earlier loop edges (id2 < id1), (d) its covisibilities of weight >= min_weight
+    that are neither its parent nor its child nor a loop edge, id2 < id1, and whose pair has not been inserted by (a). The landmark
+    write-back reads the start state of the landmark's reference keyframe (upstream's Sim3s_cw), so nc_* are the start states. Returns the
+    arrays plus keyfrm_ids, lm_ids and edge_class (one of "loop", "parent", "loop_edge", "covis" per edge)."""
+    keyfrm_ids = sorted(db.keyframes)
+    index = {k: i for i, k in enumerate(keyfrm_ids)}
+    start = {}
+    for k in keyfrm_ids:
+        kf = db.keyframes[k]
+        start[k] = _sim3(*pre_corrected[k]) if k in pre_corrected else _sim3(quat_to_rot(kf.rot_cw), kf.trans_cw, 1.0)
+    nc = {k: _sim3(*v) for k, v in non_corrected.items()}
+    edges, meas, classes, inserted = [], [], [], set()
+
+    def insert(id1, id2, S_1w, S_2w, cls):
+        edges.append((index[id1], index[id2]))
+        meas.append(_sim3_product(S_2w, _sim3_inverse(S_1w)))
+        classes.append(cls)
+
+    for id1 in sorted(loop_connections):   # (upstream walks a map and sets keyed by pointer, which is no order: ascending ids here)
+        w = db.covisibility_weights(id1)
+        for id2 in sorted(loop_connections[id1]):
+            if (id1 != curr_keyfrm_id or id2 != loop_keyfrm_id) and w.get(id2, 0) < min_weight:
+                continue
+            insert(id1, id2, start[id1], start[id2], "loop")
+            inserted.add((min(id1, id2), max(id1, id2)))
+    of = lambda k: nc[k] if k in nc else start[k]
+    for id1 in keyfrm_ids:
+        kf = db.keyframes[id1]
+        parent = kf.span_parent if kf.span_parent in index else -1
+        if parent >= 0:
+            insert(id1, parent, of(id1), of(parent), "parent")
+        for id2 in kf.loop_edges:
+            if id2 in index and id2 < id1:
+                insert(id1, id2, of(id1), of(id2), "loop_edge")
+        w = db.covisibility_weights(id1)
+        for id2 in sorted((k for k, n in w.items() if n >= min_weight), key=lambda k: (-w[k], k)):
+            if id2 == parent or id2 in kf.span_children or id2 in kf.loop_edges or not id2 < id1:
+                continue
+            if (id2, id1) in inserted:
+                continue
+            insert(id1, id2, of(id1), of(id2), "covis")
+    lm_ids = sorted(db.landmarks)
+    n_v, n_e = len(keyfrm_ids), len(edges)
+    S = [start[k] for k in keyfrm_ids]
+    arr = lambda rows, w: np.array(rows, np.float64).reshape(len(rows), w)
+    return {"rot": arr([s[0] for s in S], 9), "trans": arr([s[1] for s in S], 3), "scale": np.array([s[2] for s in S], np.float64),
+            "fixed": np.array([1 if k == loop_keyfrm_id else 0 for k in keyfrm_ids], np.uint8),
+            "nc_rot": arr([s[0] for s in S], 9), "nc_trans": arr([s[1] for s in S], 3), "nc_scale": np.array([s[2] for s in S], np.float64),
+            "edge_ij": np.array(edges, np.int32).reshape(n_e, 2), "edge_rot": arr([m[0] for m in meas], 9),
+            "edge_trans": arr([m[1] for m in meas], 3), "edge_scale": np.array([m[2] for m in meas], np.float64),
+            "lm_ref": np.array([index.get(db.landmarks[l].ref_keyfrm, -1) for l in lm_ids], np.int32),
+            "lm_pos": arr([[float(v) for v in db.landmarks[l].pos_w] for l in lm_ids], 3), "keyfrm_ids": keyfrm_ids, "lm_ids": lm_ids,
+            "edge_class": classes, "n_vertices": n_v}
 
 
 def top_covisibilities_of(map_db, n=10):
