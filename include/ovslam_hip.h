@@ -989,6 +989,32 @@ int32_t ovs_local_ba_get_solver(void);
  * rhs (n) -> x (n); n <= 1024. OVS_ERR_INVALID when a pivot is not positive. */
 ovs_status ovs_ba_dense_solve(int32_t device, const double* S, const double* rhs, int32_t n, double* x);
 
+/* Global bundle adjustment.  replaces: the optimisation inside optimize::global_bundle_adjuster::optimize
+ * (src/openvslam/optimize/global_bundle_adjuster.{h,cc}): every keyframe and landmark the caller flattened, ONE optimizer.optimize(num_iter)
+ * round (upstream's default: 10), no outlier gates, no second round. poses, pose_fixed, points, mono, stereo, cam, focal_x_baseline as for
+ * ovs_local_ba_optimize. huber_mono / huber_stereo: the Huber deltas of the two edge kinds, 0.0 = no kernel.
+ * solver: 0 = by size (the one-workgroup Cholesky up to 1024 unknowns = 170 free keyframes, the conjugate gradient beyond), 1 = Cholesky
+ * (OVS_ERR_CAPACITY beyond its size), 2 = conjugate gradient (block-Jacobi preconditioned, tol 1e-10, at most 12 iterations
+ * per free keyframe). OVS_ERR_CAPACITY beyond ovs_ba_pcg_max_free() free keyframes, decided before anything is allocated.
+ * info (8 doubles or NULL): robust chi2 before, after, LM iterations, LM trials, solver used (1 / 2), conjugate-gradient iterations in total,
+ * solves stopped at the cap, failed solves. When no trial was accepted (num_iter 0, force_stop_flag set, no edges, nothing free) poses and
+ * points keep their bits. Fixed keyframes always keep theirs. */
+ovs_status ovs_global_ba_optimize(int32_t device, double* poses, const uint8_t* pose_fixed, int32_t n_pose, double* points, int32_t n_pt,
+                                  const ovs_ba_edge* mono, int32_t n_mono, const ovs_ba_edge_stereo* stereo, int32_t n_stereo, const ovs_ba_cam* cam,
+                                  double focal_x_baseline, double huber_mono, double huber_stereo, int32_t num_iter, int32_t solver,
+                                  const volatile uint8_t* force_stop_flag, double* info);
+ovs_status ovs_global_ba_optimize_equirect(int32_t device, double* poses, const uint8_t* pose_fixed, int32_t n_pose, double* points, int32_t n_pt,
+                                           const ovs_ba_edge* mono, int32_t n_mono, int32_t cols, int32_t rows, double huber_mono, int32_t num_iter,
+                                           int32_t solver, const volatile uint8_t* force_stop_flag, double* info);
+/* The conjugate-gradient solver alone on host arrays (test entry): S (n x n, row-major, symmetric, both triangles read), rhs (n) -> x (n);
+ * n a multiple of 6, at most 6 ovs_ba_pcg_max_free(). tol in (0, 1); max_iter 0 = 2 n; check_every 0 = the default: iterations queued
+ * between two looks at the done word (the result does not depend on it). info (3 doubles or NULL): iterations, 1.0 when stopped at the cap,
+ * the last dn / d0. OVS_ERR_INVALID on a bad argument and when the solve FAILED (a diagonal block that is not positive definite, p.q not
+ * positive and finite); OVS_ERR_CAPACITY beyond the size. */
+ovs_status ovs_ba_pcg_solve(int32_t device, const double* S, const double* rhs, int32_t n, double tol, int32_t max_iter, int32_t check_every, double* x,
+                            double* info);
+int32_t ovs_ba_pcg_max_free(void);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Pose-only optimisation of one frame.  replaces: unsigned int optimize::pose_optimizer::optimize(data::frame& frm) const
  * (src/openvslam/optimize/pose_optimizer.{h,cc}; perspective mono / stereo pose_opt edges): 4 rounds x 10 Levenberg-Marquardt

@@ -108,6 +108,113 @@ def dense_solve(S, rhs, device=0):
     return x
 
 
+def pcg_solve(S, rhs, tol=1e-10, max_iter=0, check_every=0, device=0):
+    """ovs_ba_pcg_solve: the reduced camera system's conjugate-gradient solver alone (S symmetric, both triangles, n a
+    multiple of 6). Returns (x, info) with info = (iterations, stopped at the cap, last dn / d0). Raises OvsError(OVS_ERR_INVALID) on FAILED."""
+    S = np.ascontiguousarray(S, np.float64)
+    rhs = np.ascontiguousarray(rhs, np.float64)
+    n = S.shape[0]
+    assert S.shape == (n, n) and rhs.shape == (n,)
+    x, info = np.empty(n, np.float64), np.zeros(3)
+    _lib.check(_lib.lib().ovs_ba_pcg_solve(device, S.ctypes.data, rhs.ctypes.data, n, float(tol), int(max_iter), int(check_every), x.ctypes.data,
+                                           info.ctypes.data), "ovs_ba_pcg_solve")
+    return x, (int(info[0]), bool(info[1]), float(info[2]))
+
+
+def pcg_max_free():
+    """Free keyframes the conjugate-gradient solver accepts (ovs_ba_pcg_max_free)."""
+    return int(_lib.lib().ovs_ba_pcg_max_free())
+
+
+SOLVER_BY_SIZE, SOLVER_CHOLESKY, SOLVER_PCG = 0, 1, 2
+# Lm::huber_mono / huber_stereo of the rig (ORACLE_SPEC rule 25): sqrtf(5.99146f) and sqrtf(7.81473f) widened to double
+HUBER_2D, HUBER_3D = float(np.sqrt(np.float32(5.99146))), float(np.sqrt(np.float32(7.81473)))
+
+
+def huber_deltas(setup_type, use_huber_kernel=True):
+    """The two deltas the class layers pass to global_ba_optimize: what local BA's first round uses for the rig (0 Monocular, 1 Stereo, 2 RGBD)."""
+    if not use_huber_kernel:
+        return 0.0, 0.0
+    return (HUBER_2D if setup_type == 0 else HUBER_3D), HUBER_3D
+
+
+def global_ba_optimize(poses, pose_fixed, points, edges, cam, stereo_edges=None, focal_x_baseline=0.0, huber_mono=HUBER_2D, huber_stereo=HUBER_3D,
+                       num_iter=10, solver=SOLVER_BY_SIZE, force_stop_flag=None, device=0):
+    """optimize::global_bundle_adjuster::optimize behind the flattening (ovs_global_ba_optimize): one round of num_iter iterations over
+    every keyframe and landmark, no outlier gates. Returns dict(poses, points, info) with info = (robust chi2 before, after, LM iterations,
+    LM trials, solver used, PCG iterations, PCG solves stopped at the cap, failed solves)."""
+    L = _lib.lib()
+    P = np.array(poses, np.float64).reshape(-1, 7).copy()
+    X = np.array(points, np.float64).reshape(-1, 3).copy()
+    em = np.ascontiguousarray(edges if edges is not None else np.zeros(0, EDGE_DTYPE), EDGE_DTYPE)
+    es = np.ascontiguousarray(stereo_edges if stereo_edges is not None else np.zeros(0, EDGE_STEREO_DTYPE), EDGE_STEREO_DTYPE)
+    fixed = None if pose_fixed is None else np.ascontiguousarray(pose_fixed, np.uint8)
+    info = np.zeros(8)
+    c = BaCam(*cam)
+    _lib.check(L.ovs_global_ba_optimize(device, _p(P), _p(fixed), len(P), _p(X), len(X), _p(em) if len(em) else None, len(em),
+                                        _p(es) if len(es) else None, len(es), C.byref(c), float(focal_x_baseline), float(huber_mono),
+                                        float(huber_stereo), int(num_iter), int(solver), _p(force_stop_flag), _p(info)), "ovs_global_ba_optimize")
+    return dict(poses=P, points=X, info=info)
+
+
+def global_ba_optimize_equirect(poses, pose_fixed, points, edges, cols, rows, huber_mono=HUBER_2D, num_iter=10, solver=SOLVER_BY_SIZE,
+                                force_stop_flag=None, device=0):
+    """global_bundle_adjuster::optimize for an equirectangular map (ovs_global_ba_optimize_equirect: every edge monocular)."""
+    L = _lib.lib()
+    P = np.array(poses, np.float64).reshape(-1, 7).copy()
+    X = np.array(points, np.float64).reshape(-1, 3).copy()
+    em = np.ascontiguousarray(edges if edges is not None else np.zeros(0, EDGE_DTYPE), EDGE_DTYPE)
+    fixed = None if pose_fixed is None else np.ascontiguousarray(pose_fixed, np.uint8)
+    info = np.zeros(8)
+    _lib.check(L.ovs_global_ba_optimize_equirect(device, _p(P), _p(fixed), len(P), _p(X), len(X), _p(em) if len(em) else None, len(em), int(cols),
+                                                 int(rows), float(huber_mono), int(num_iter), int(solver), _p(force_stop_flag), _p(info)),
+               "ovs_global_ba_optimize_equirect")
+    return dict(poses=P, points=X, info=info)
+
+
+class global_bundle_adjuster:
+    """optimize::global_bundle_adjuster (expected: src/openvslam/optimize/global_bundle_adjuster.{h,cc}) over an io.map_database: the
+    whole map in one ovs_global_ba_optimize call. The Huber deltas are those local BA's first round uses for the rig (huber_deltas)."""
+
+    def __init__(self, map_db, num_iter=10, use_huber_kernel=True, device=0, solver=SOLVER_BY_SIZE):
+        self.map_db, self.num_iter, self.use_huber_kernel, self.device, self.solver = map_db, int(num_iter), bool(use_huber_kernel), device, solver
+        self.info = None
+
+    def optimize(self, lead_keyfrm_id_in_global_BA=0, force_stop_flag=None):
+        """Lead id 0: poses and positions go straight into the map (set_cam_pose / set_pos_in_world). Any other lead id: they are stored
+        as the after-loop-BA pose / the after-global-BA position with the lead id as loop-BA identifier, for loop_bundle_adjuster to
+        propagate. A force_stop_flag that is set when the call returns leaves the map untouched, as upstream does."""
+        from . import io
+        prob = io.global_ba_problem(self.map_db)
+        if not len(prob["keyfrm_ids"]) or not len(prob["lm_ids"]):
+            return
+        hm, hs = huber_deltas(prob["setup_type"], self.use_huber_kernel)
+        if prob["model"] == 1:
+            res = global_ba_optimize_equirect(prob["poses"], prob["pose_fixed"], prob["points"], prob["mono"], prob["cols"], prob["rows"], hm,
+                                              self.num_iter, self.solver, force_stop_flag, self.device)
+        else:
+            res = global_ba_optimize(prob["poses"], prob["pose_fixed"], prob["points"], prob["mono"], prob["cam"], prob["stereo"],
+                                     prob["focal_x_baseline"], hm, hs, self.num_iter, self.solver, force_stop_flag, self.device)
+        self.info = res["info"]
+        if force_stop_flag is not None and force_stop_flag[0]:
+            return
+        lead = int(lead_keyfrm_id_in_global_BA)
+        for i, kid in enumerate(prob["keyfrm_ids"]):
+            kf = self.map_db.keyframes[kid]
+            if lead == 0:
+                kf.trans_cw, kf.rot_cw = res["poses"][i, :3].copy(), res["poses"][i, 3:].copy()
+            else:
+                kf.trans_cw_after_loop_BA, kf.rot_cw_after_loop_BA = res["poses"][i, :3].copy(), res["poses"][i, 3:].copy()
+                kf.loop_BA_identifier = lead
+        for i, lid in enumerate(prob["lm_ids"]):
+            lm = self.map_db.landmarks[lid]
+            if lead == 0:
+                lm.pos_w = res["points"][i].copy()
+            else:
+                lm.pos_w_after_global_BA = res["points"][i].copy()
+                lm.loop_BA_identifier = lead
+
+
 def pose_set_variant(which, value):
     """ovs_pose_set_variant: "reset_each_round" (0 | 1), process-wide (oracle/ORACLE_SPEC.md rule 25 (iv))."""
     _lib.check(_lib.lib().ovs_pose_set_variant({"reset_each_round": 0}[which], int(value)), "ovs_pose_set_variant")

@@ -56,7 +56,7 @@ namespace data {
 
 class keyframe;
 
-// data::map_database: only the lock local_bundle_adjuster takes around its write-back
+// data::map_database: the lock local_bundle_adjuster takes around its write-back, and the two lists the whole-map optimisers walk
 class landmark;
 class map_database {
 public:
@@ -115,6 +115,9 @@ public:
     unsigned int identifier_in_local_lm_search_ = 0;   // the frame whose search_local_landmarks already holds this landmark
     unsigned int num_observable_ = 1;
     void increase_num_observable(unsigned int num_observable = 1) { num_observable_ += num_observable; }
+    // what optimize::global_bundle_adjuster leaves for loop_bundle_adjuster when the lead keyframe is not 0
+    Vec3_t pos_w_after_global_BA_;
+    unsigned int loop_BA_identifier_ = 0;
 };
 
 // The matcher-side data of a frame -- and of the keyframe made from it -- resident in HBM (ovs_frame_dev, include/ovslam_hip.h): created by
@@ -246,6 +249,9 @@ public:
     std::vector<float> depths_;   // per keypoint, read only where stereo_x_right_ is not negative (module::two_view_triangulator)
     float scale_factor_ = 1.2f;
     Mat44_t get_cam_pose() const { return cam_pose_cw_; }
+    // what optimize::global_bundle_adjuster leaves for loop_bundle_adjuster when the lead keyframe is not 0
+    Mat44_t cam_pose_cw_after_loop_BA_;
+    unsigned int loop_BA_identifier_ = 0;
     std::vector<landmark*> get_landmarks() const { return landmarks_; }
     landmark* get_landmark(unsigned int idx) const { return landmarks_.at(idx); }
     void add_landmark(landmark* lm, unsigned int idx) { landmarks_.at(idx) = lm; }

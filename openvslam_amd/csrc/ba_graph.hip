@@ -49,6 +49,7 @@
 #include "ba_edge.h"
 #include "ba_graph_plan.inc"
 #include "ba_internal.h"
+#include "ba_pcg_internal.inc"
 #include "owned_internal.inc"
 
 namespace ovs {
@@ -1198,6 +1199,8 @@ struct ovs_ba_graph {
     unsigned char* d_arena = nullptr;
     unsigned char* d_solver_arena = nullptr;
     size_t arena_cap = 0, solver_cap = 0;   // allocation sizes (the arenas come from / go back to g_ba_pool)
+    unsigned char* d_pcg_arena = nullptr;   // ba_pcg.hip's vectors and scalars (global BA): taken on first use, goes back with the others
+    size_t pcg_cap = 0;
     // ba_graph_plan.inc: where the arrays of the two arenas lie, and the work counts of the partitions
     GraphArena lay{};
     GraphPartition part{};
@@ -1303,6 +1306,7 @@ ovs_status ovs_ba_graph_destroy(ovs_ba_graph* g) {
     (void)hipDeviceSynchronize();   // the arenas go back to the pool: nothing of this graph may still be running (hipFree synchronised implicitly)
     g_ba_pool.give(g->device, g->d_arena, g->arena_cap);          // every array of the graph lives in one of the two arenas
     g_ba_pool.give(g->device, g->d_solver_arena, g->solver_cap);
+    g_ba_pool.give(g->device, g->d_pcg_arena, g->pcg_cap);
     delete g;
     return OVS_OK;
 }
@@ -1635,6 +1639,15 @@ ovs_status ba_graph_edge_gate(ovs_ba_graph* g, double thr_mono, double thr_stere
     hipLaunchKernelGGL(k_edge_gate, dim3((g->n_edge() + 255) / 256), dim3(256), 0, s, g->n_edge(), g->n_mono, thr_mono, thr_stereo, d_chi, d_depth, d_chi_r1,
                        d_out1, use_final ? 1 : 0, d_out, write_active ? g->d_active() : nullptr, d_n_active);
     OVS_LAUNCH_TRY("k_edge_gate");
+    return OVS_OK;
+}
+
+ovs_status ba_graph_pcg_arena(ovs_ba_graph* g, unsigned char** d_arena) {
+    if (!g->d_pcg_arena) {
+        g->d_pcg_arena = g_ba_pool.take(g->device, pcg_arena_bytes(), &g->pcg_cap);
+        OVS_HIP_TRY(g->d_pcg_arena ? hipSuccess : hipErrorOutOfMemory);
+    }
+    *d_arena = g->d_pcg_arena;
     return OVS_OK;
 }
 

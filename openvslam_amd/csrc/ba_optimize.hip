@@ -21,6 +21,7 @@
 
 #include "ba_host_math.h"
 #include "ba_internal.h"
+#include "ba_pcg_internal.inc"
 #include "owned_internal.inc"
 
 namespace ovs {
@@ -61,15 +62,17 @@ struct Mailbox {
     double scale_lm, scale_kf;   // the gain ratio's denominator: the landmarks' and the keyframes' part
     int32_t fail;                // the trial's failure word
     TrialBlock blk;
+    ovs::PcgHostBlock pcg;       // what a conjugate-gradient solve brings down (global BA)
     volatile unsigned long long ll[16];   // k_reduce_scalars' flag-carrying words {seq : 32 | half a double : 32}, twelve in use
 };
 struct PinLayout {
     size_t stage, mailbox, bytes;   // (the padded system | bp come first, at offset 0)
 };
-static PinLayout pin_layout(int n_pose) {
+// `host_system`: room for the system as the host solver downloads it (global BA never takes that path: 300 MB at 1024 keyframes)
+static PinLayout pin_layout(int n_pose, bool host_system) {
     ArenaLayout lay;
     PinLayout p;
-    lay.place<double>(ovs::dense_solve_doubles(6 * n_pose) + 6 * (size_t)n_pose);
+    lay.place<double>(host_system ? ovs::dense_solve_doubles(6 * n_pose) + 6 * (size_t)n_pose : 0);
     p.stage = lay.place<double>(19 * (size_t)n_pose);   // the keyframes' records on their way up: 7 + 12 per keyframe
     p.mailbox = lay.place<Mailbox>(1);
     p.bytes = lay.bytes();
@@ -107,6 +110,11 @@ struct Lm {
     // OVS_BA_TRACE=1: wall-clock breakdown on stderr (where a call's milliseconds go; tools/time_lba.py)
     double t_schur = 0, t_chol = 0, t_trial = 0;
     int n_trials = 0;
+    // global BA: the deltas come from the caller (0.0 = no kernel) instead of the rig; what the conjugate-gradient solves and the trials did
+    bool huber_given = false;
+    double huber_mono_given = 0.0, huber_stereo_given = 0.0;
+    long long pcg_iterations = 0;
+    int pcg_capped = 0, failed_solves = 0, n_accepted = 0;
     bool err_at_trial = false;   // the active edges' errors were last computed at the trial state (d_poses_n, d_Xn), which was then rejected
     static double now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
     hipStream_t stream = nullptr;
@@ -126,7 +134,7 @@ struct Lm {
     unsigned char* h_edge = nullptr;   // LmScratch::edge
     bool ll_notify = true;
 
-    ovs_status init(int device, int np, int npt, size_t ne_max, const double* points) {
+    ovs_status init(int device, int np, int npt, size_t ne_max, const double* points, bool host_system = true) {
         static thread_local LmScratch sc;
         n_pose = np;
         n_pt = npt;
@@ -159,7 +167,7 @@ struct Lm {
         d_echi = ArenaLayout::at<double>(sc.d, o_echi), d_echi_r1 = ArenaLayout::at<double>(sc.d, o_echi_r1), d_echi_s = ArenaLayout::at<double>(sc.d, o_echi_s);
         d_edepth = sc.d + o_edepth, d_out1 = sc.d + o_out1, d_outf = sc.d + o_outf;
         d_nact = ArenaLayout::at<int32_t>(sc.d, o_nact);
-        const PinLayout pl = pin_layout(np);
+        const PinLayout pl = pin_layout(np, host_system);
         OVS_HIP_TRY(sc.pin.ensure(pl.bytes, pl.bytes));
         h_sys = ArenaLayout::at<double>(sc.pin.p, 0);
         h_stage = ArenaLayout::at<double>(sc.pin.p, pl.stage);
@@ -206,8 +214,8 @@ struct Lm {
         return OVS_OK;
     }
 
-    double huber_mono(bool robust) const { return robust ? (setup_type == 0 ? kSqrtChi2D : kSqrtChi3D) : 0.0; }
-    double huber_stereo(bool robust) const { return robust ? kSqrtChi3D : 0.0; }
+    double huber_mono(bool robust) const { return !robust ? 0.0 : huber_given ? huber_mono_given : setup_type == 0 ? kSqrtChi2D : kSqrtChi3D; }
+    double huber_stereo(bool robust) const { return !robust ? 0.0 : huber_given ? huber_stereo_given : kSqrtChi3D; }
 
     // Round 6: the trial's last kernel wrote the outcome into the mailbox as twelve words {seq | half a double}; poll them (no copy command, no
     // stream wait). Every 4096 polls the stream is asked whether it still runs: a launch that died would otherwise never write the words.
@@ -230,12 +238,22 @@ struct Lm {
 
     // ---- one trial, the whole of it on the device: Schur complement, solve, keyframe / landmark updates, linearisation at the trial state (into
     //      the `work` set: a failed solve must leave the last evaluated trial state, which edge_chi2 may still need, untouched)
-    ovs_status trial_on_device(ovs_ba_graph* g, const ovs::BaGraphInfo& gi, int n, double lambda, bool robust, Trial& r) {
+    //      `solver`: 1 = ba_solve.hip's Cholesky, 2 = ba_pcg.hip's conjugate gradient (global BA beyond the Cholesky's size), which reads S only
+    ovs_status trial_on_device(ovs_ba_graph* g, const ovs::BaGraphInfo& gi, int n, double lambda, bool robust, Trial& r, int solver = 1) {
         const double t0 = now();
         const int fw = n_trials & 1;   // the trials alternate between two failure words
         ovs_status st = ovs::ba_graph_schur(g, cur.Hpp, cur.bp, cur.Hll, cur.bl, cur.Hpl, lambda, stream, fw, false);
         if (st != OVS_OK) return st;
-        if (n > 0) {
+        if (n > 0 && solver == 2) {
+            unsigned char* d_pcg = nullptr;
+            st = ovs::ba_graph_pcg_arena(g, &d_pcg);
+            if (st != OVS_OK) return st;
+            ovs::PcgResult pr;
+            st = ovs::launch_pcg_solve(gi.d_S, gi.s_pitch, gi.d_rhs, n, gi.d_fail + fw, d_pcg, &mb->pcg, 1e-10, 0, 0, stream, &pr);
+            if (st != OVS_OK) return st;
+            pcg_iterations += pr.iterations;
+            pcg_capped += pr.capped ? 1 : 0;
+        } else if (n > 0) {
             st = ovs::launch_dense_solve(gi.d_S, n, gi.d_fail + fw, stream);
             if (st != OVS_OK) return st;
         }
@@ -275,6 +293,7 @@ struct Lm {
             mb->fail = mb->blk.fail[fw];
         }
         r.ok = mb->fail == 0;
+        failed_solves += r.ok ? 0 : 1;
         if (!r.ok) {   // a failed factorisation may have left non-finite values in the padding, which no later trial rewrites
             st = ovs::ba_graph_reset_system(g, stream);
             if (st != OVS_OK) return st;
@@ -291,6 +310,7 @@ struct Lm {
         return OVS_OK;
     }
     void accept_on_device() {
+        ++n_accepted;
         std::swap(d_X, d_Xn);
         std::swap(d_poses, d_poses_n);
         std::swap(d_T, d_Tn);
@@ -404,14 +424,15 @@ struct Lm {
     }
 
     // one optimizer.optimize(iters) call on graph g. Returns the number of iterations entered.
+    // `solver`: 0 = local BA's selection (below), 1 / 2 = trial_on_device's (global BA, which has chosen by size)
     ovs_status run_round(ovs_ba_graph* g, std::vector<Pose>& T, int iters, bool robust, const volatile uint8_t* stop, double* chi_start,
-                         double* chi_end, int* n_iter) {
+                         double* chi_end, int* n_iter, int solver = 0) {
         ovs_status st = ovs::ba_graph_ensure_solver(g, stream);   // (before ba_graph_info: the work space is allocated on first use)
         if (st != OVS_OK) return st;
         const ovs::BaGraphInfo gi = ovs::ba_graph_info(g);
         const int n = 6 * gi.n_free;
         // the reduced camera system is solved where ovs_local_ba_set_solver says; systems beyond the one-workgroup solver's LDS go to the host
-        const bool dev_solve = ovs::g_lba_solver.load(std::memory_order_relaxed) == 0 && n <= ovs::dense_solve_max_n();
+        const bool dev_solve = solver != 0 || (ovs::g_lba_solver.load(std::memory_order_relaxed) == 0 && n <= ovs::dense_solve_max_n());
         st = upload_poses(T, d_poses, dev_solve ? d_T : nullptr);
         if (st != OVS_OK) return st;
         // both failure words start a round clear: the device solver's trials rely on the PREVIOUS trial's k_trial_update to clear the word they
@@ -432,8 +453,8 @@ struct Lm {
         if (iters <= 0) return OVS_OK;
         const double lambda0 = 1e-5 * mb->chi[2];   // computeLambdaInit: tau * the largest diagonal entry of the active vertices' Hessian blocks
         if (dev_solve) {
-            st = lm_iterate([&](double lambda, Trial& r) { return trial_on_device(g, gi, n, lambda, robust, r); }, [&] { accept_on_device(); }, iters,
-                            stop, lambda0, &current_chi, n_iter);
+            st = lm_iterate([&](double lambda, Trial& r) { return trial_on_device(g, gi, n, lambda, robust, r, solver == 2 ? 2 : 1); },
+                            [&] { accept_on_device(); }, iters, stop, lambda0, &current_chi, n_iter);
         } else {
             HostState h{T, {}, {}, {}, {}};
             st = lm_iterate([&](double lambda, Trial& r) { return trial_on_host(g, gi, n, lambda, robust, h, r); }, [&] { accept_on_host(h); }, iters,
@@ -582,7 +603,81 @@ static ovs_status local_ba_optimize_impl(int model, int32_t device, double* pose
     return OVS_OK;
 }
 
+// optimize::global_bundle_adjuster::optimize behind the flattening: every keyframe and landmark, ONE optimizer.optimize(num_iter) round, Huber
+// kernels with the caller's deltas, no outlier gates. With solver 1 the launches are those of local BA's first round.
+static ovs_status global_ba_optimize_impl(int model, int32_t device, double* poses, const uint8_t* pose_fixed, int32_t n_pose, double* points, int32_t n_pt,
+                                          const ovs_ba_edge* mono, int32_t n_mono, const ovs_ba_edge_stereo* stereo, int32_t n_stereo, const ovs_ba_cam* cam,
+                                          double focal_x_baseline, double huber_mono, double huber_stereo, int32_t num_iter, int32_t solver,
+                                          const volatile uint8_t* force_stop_flag, double* info) {
+    if (!poses || !points || !cam || n_pose < 1 || n_pt < 1 || n_mono < 0 || n_stereo < 0 || (n_mono > 0 && !mono) || (n_stereo > 0 && !stereo) ||
+        num_iter < 0 || solver < 0 || solver > 2 || !(huber_mono >= 0.0 && huber_mono < __builtin_inf()) ||
+        !(huber_stereo >= 0.0 && huber_stereo < __builtin_inf()))
+        return OVS_ERR_INVALID;
+    // ---- the solver, by the number of free keyframes alone: before the device and any allocation
+    int n_free = 0;
+    for (int k = 0; k < n_pose; ++k) n_free += (pose_fixed && pose_fixed[k]) ? 0 : 1;
+    const int n = 6 * n_free;
+    const int used = solver != 0 ? solver : n <= ovs::dense_solve_max_n() ? 1 : 2;
+    if (used == 1 ? n > ovs::dense_solve_max_n() : n_free > ovs::pcg_max_free()) return OVS_ERR_CAPACITY;
+    if (ovs_device_count() <= device || device < 0) return OVS_ERR_NO_DEVICE;
+    OVS_HIP_TRY(hipSetDevice(device));
+    const size_t ne = (size_t)n_mono + n_stereo;
+    Lm L;
+    L.huber_given = true;
+    L.huber_mono_given = huber_mono;
+    L.huber_stereo_given = huber_stereo;
+    ovs_status st = L.init(device, n_pose, n_pt, ne, points, false);
+    if (st != OVS_OK) return st;
+    GraphGuard g1;
+    st = model == 1 ? ovs_ba_graph_create_equirect(device, n_pose, pose_fixed, n_pt, mono, n_mono, (int32_t)cam->fx, (int32_t)cam->fy, &g1.g)
+                    : ovs_ba_graph_create(device, n_pose, pose_fixed, n_pt, mono, n_mono, stereo, n_stereo, cam, focal_x_baseline, &g1.g);
+    if (st != OVS_OK) {
+        (void)hipStreamSynchronize(L.stream);   // (the landmarks' upload reads the thread's page-locked block)
+        return st;
+    }
+    std::vector<Pose> T((size_t)n_pose);
+    for (int k = 0; k < n_pose; ++k) {
+        quat_to_rot(poses + 7 * (size_t)k + 3, T[k].R);
+        for (int a = 0; a < 3; ++a) T[k].t[a] = poses[7 * (size_t)k + a];
+    }
+    double chi0 = 0, chi1 = 0;
+    int it = 0;
+    st = L.run_round(g1.g, T, ne == 0 ? 0 : num_iter, true, force_stop_flag, &chi0, &chi1, &it, used);
+    if (st != OVS_OK) return st;
+    if (L.n_accepted > 0) {   // (no accepted trial: the caller's arrays keep their bits, a quaternion is not taken through a matrix and back)
+        OVS_HIP_TRY(hipMemcpyAsync(L.h_pts, L.d_X, sizeof(double) * 3 * (size_t)n_pt, hipMemcpyDeviceToHost, L.stream));
+        OVS_HIP_TRY(hipStreamSynchronize(L.stream));
+        std::vector<double> p7;
+        Lm::pack_poses(T, p7);
+        for (int k = 0; k < n_pose; ++k)
+            if (!(pose_fixed && pose_fixed[k])) std::memcpy(poses + 7 * (size_t)k, &p7[(size_t)7 * k], sizeof(double) * 7);
+        std::memcpy(points, L.h_pts, sizeof(double) * 3 * (size_t)n_pt);
+    }
+    if (info) {
+        const double out[8] = {chi0, chi1, (double)it, (double)L.n_trials, (double)used, (double)L.pcg_iterations, (double)L.pcg_capped, (double)L.failed_solves};
+        std::memcpy(info, out, sizeof(out));
+    }
+    return OVS_OK;
+}
+
 extern "C" {
+
+ovs_status ovs_global_ba_optimize(int32_t device, double* poses, const uint8_t* pose_fixed, int32_t n_pose, double* points, int32_t n_pt,
+                                  const ovs_ba_edge* mono, int32_t n_mono, const ovs_ba_edge_stereo* stereo, int32_t n_stereo, const ovs_ba_cam* cam,
+                                  double focal_x_baseline, double huber_mono, double huber_stereo, int32_t num_iter, int32_t solver,
+                                  const volatile uint8_t* force_stop_flag, double* info) {
+    return global_ba_optimize_impl(0, device, poses, pose_fixed, n_pose, points, n_pt, mono, n_mono, stereo, n_stereo, cam, focal_x_baseline, huber_mono,
+                                   huber_stereo, num_iter, solver, force_stop_flag, info);
+}
+
+ovs_status ovs_global_ba_optimize_equirect(int32_t device, double* poses, const uint8_t* pose_fixed, int32_t n_pose, double* points, int32_t n_pt,
+                                           const ovs_ba_edge* mono, int32_t n_mono, int32_t cols, int32_t rows, double huber_mono, int32_t num_iter,
+                                           int32_t solver, const volatile uint8_t* force_stop_flag, double* info) {
+    if (cols < 1 || rows < 1) return OVS_ERR_INVALID;
+    const ovs_ba_cam cam = {(double)cols, (double)rows, 0.0, 0.0};
+    return global_ba_optimize_impl(1, device, poses, pose_fixed, n_pose, points, n_pt, mono, n_mono, nullptr, 0, &cam, 0.0, huber_mono, 0.0, num_iter, solver,
+                                   force_stop_flag, info);
+}
 
 ovs_status ovs_local_ba_optimize(int32_t device, double* poses, const uint8_t* pose_fixed, int32_t n_pose, double* points, int32_t n_pt,
                                  const ovs_ba_edge* mono, int32_t n_mono, const ovs_ba_edge_stereo* stereo, int32_t n_stereo,

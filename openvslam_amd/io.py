@@ -47,6 +47,11 @@ class keyframe:
     span_parent: int = -1
     span_children: list = field(default_factory=list)
     loop_edges: list = field(default_factory=list)
+    # not stored in the file: what optimize::global_bundle_adjuster reads and, for a lead keyframe other than 0, writes
+    will_be_erased: bool = False
+    loop_BA_identifier: int = 0
+    rot_cw_after_loop_BA: np.ndarray = None      # cam_pose_cw_after_loop_BA_: quaternion and translation
+    trans_cw_after_loop_BA: np.ndarray = None
 
 
 @dataclass
@@ -62,6 +67,9 @@ class landmark:
     mean_normal: np.ndarray = None     # (3,) float64
     min_valid_dist: float = None       # the raw members, before the getters' 0.7 / 1.3
     max_valid_dist: float = None
+    will_be_erased: bool = False
+    loop_BA_identifier: int = 0
+    pos_w_after_global_BA: np.ndarray = None
 
 
 class map_database:
@@ -241,6 +249,51 @@ def local_ba_problem(db, curr_keyfrm_id):
             "cam": np.array([cam["fx"], cam["fy"], cam["cx"], cam["cy"]], np.float64), "focal_x_baseline": float(cam.get("focal_x_baseline", 0.0)),
             "setup_type": {"Monocular": 0, "Stereo": 1, "RGBD": 2}.get(cam.get("setup_type", "Monocular"), 0),
             "keyfrm_ids": keyfrm_ids, "lm_ids": lm_ids, "n_local": len(local)}
+
+
+def global_ba_problem(db):
+    """The graph optimize::global_bundle_adjuster::optimize builds (expected: src/openvslam/optimize/global_bundle_adjuster.cc): every
+    keyframe that is not to be erased, in ascending id, keyframe 0 fixed; every landmark that is not to be erased and has at least one
+    observation in such a keyframe (upstream removes a landmark vertex without edges again and does not write it back), in ascending id;
+    the edges in upstream's insertion order: landmark by landmark, its observations in the order map_database.observations() gives.
+    Returns the arrays of ovs_global_ba_optimize plus `keyfrm_ids` and `lm_ids`, which map rows back to the map, `model` (0 perspective,
+    1 equirectangular) and `cols` / `rows`."""
+    keyfrm_ids = [k for k in sorted(db.keyframes) if not db.keyframes[k].will_be_erased]
+    pose_index = {k: i for i, k in enumerate(keyfrm_ids)}
+    cam = db.cameras[db.keyframes[keyfrm_ids[0]].cam] if keyfrm_ids else {}
+    equirect = cam.get("model_type") == "Equirectangular"
+    obs = db.observations()
+    inv_sig = {k: inv_level_sigma_sq(db.keyframes[k].scale_factor, db.keyframes[k].n_scale_levels) for k in keyfrm_ids}
+    lm_ids, mono, stereo = [], [], []
+    for lid in sorted(db.landmarks):
+        if db.landmarks[lid].will_be_erased:
+            continue
+        seen = [(kid, idx) for kid, idx in obs[lid] if kid in pose_index]
+        if not seen:
+            continue
+        pi = len(lm_ids)
+        lm_ids.append(lid)
+        for kid, idx in seen:
+            kf = db.keyframes[kid]
+            w = float(inv_sig[kid][int(kf.keypts["octave"][idx])])
+            ux, uy, xr = float(kf.undists[idx, 0]), float(kf.undists[idx, 1]), float(kf.x_rights[idx])
+            if xr < 0 or equirect:
+                mono.append((pose_index[kid], pi, ux, uy, w))
+            else:
+                stereo.append((pose_index[kid], pi, ux, uy, xr, w))
+    poses = np.zeros((len(keyfrm_ids), 7))
+    for i, k in enumerate(keyfrm_ids):
+        poses[i, :3] = db.keyframes[k].trans_cw
+        poses[i, 3:] = db.keyframes[k].rot_cw
+    e_mono = np.array(mono, EDGE_DTYPE) if mono else np.zeros(0, EDGE_DTYPE)
+    e_st = np.array(stereo, EDGE_STEREO_DTYPE) if stereo else np.zeros(0, EDGE_STEREO_DTYPE)
+    return {"poses": poses, "pose_fixed": np.array([1 if k == 0 else 0 for k in keyfrm_ids], np.uint8),
+            "points": np.array([db.landmarks[l].pos_w for l in lm_ids], np.float64).reshape(-1, 3), "mono": e_mono, "stereo": e_st,
+            "cam": np.array([cam.get("fx", 0.0), cam.get("fy", 0.0), cam.get("cx", 0.0), cam.get("cy", 0.0)], np.float64),
+            "focal_x_baseline": float(cam.get("focal_x_baseline", 0.0)),
+            "setup_type": {"Monocular": 0, "Stereo": 1, "RGBD": 2}.get(cam.get("setup_type", "Monocular"), 0),
+            "model": 1 if equirect else 0, "cols": int(cam.get("cols", 0)), "rows": int(cam.get("rows", 0)),
+            "keyfrm_ids": keyfrm_ids, "lm_ids": lm_ids}
 
 
 def _sim3(R, t, s):
