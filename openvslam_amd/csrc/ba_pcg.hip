@@ -14,6 +14,7 @@
 // cooperative launch, no graph capture; the host queues pcgplan::chunk_passes passes, reads the done word and queues the next chunk, up to
 // pass max_iter: the number of launches never depends on the data. S is only read.
 #include <cstring>
+#include <limits>
 #include <vector>
 
 #include "ba_internal.h"
@@ -216,7 +217,10 @@ ovs_status ovs_ba_pcg_solve(int32_t device, const double* S, const double* rhs, 
     if (ovs_device_count() <= device || device < 0) return OVS_ERR_NO_DEVICE;
     OVS_HIP_TRY(hipSetDevice(device));
     const int pitch = ovs::dense_solve_pad(n);
-    std::vector<double> h((size_t)(pitch + 1) * pitch, 0.0);   // the graph's layout: S with its row padding, then the right-hand side's row
+    // the graph's layout: S with its row padding, then the right-hand side's row. What the kernels must not read -- the padding columns of
+    // every row, the rows between n and pitch, the padding behind the right-hand side -- holds a quiet NaN, as it may in the real call (which
+    // is why ba_graph_reset_system exists): one such value in a sum and no test of the solver's bits passes.
+    std::vector<double> h((size_t)(pitch + 1) * pitch, std::numeric_limits<double>::quiet_NaN());
     for (int i = 0; i < n; ++i) std::memcpy(&h[(size_t)i * pitch], S + (size_t)i * n, sizeof(double) * n);
     std::memcpy(&h[(size_t)pitch * pitch], rhs, sizeof(double) * n);
     ovs::Owned tmp;

@@ -164,7 +164,10 @@ def spd(rng, n, cond):
     return 0.5 * (S + S.T)
 
 
-SIZES = (6, 12, 60, 66, 384, 390, 1020, 1026, 1032)   # below / above 64 entries per row, 64 / 65 blocks, both sides of the Cholesky's limit
+# below / above 64 entries per row, 64 / 65 blocks, both sides of the Cholesky's limit, 256 / 257 blocks: one full workgroup of the lane-per-block
+# kernels, and a second one holding one lane
+SIZES = (6, 12, 60, 66, 384, 390, 1020, 1026, 1032, 1536, 1542)
+BLOCK_SIZES = (3078, 6144)   # block_case: 513 blocks (three workgroups, the last with one lane) and the capacity (four full ones, pitch == n)
 _cache = {}
 
 
@@ -186,4 +189,63 @@ def solved(n, cond=1e3, max_iter=0):
     if key not in _cache:
         S, g = case(n, cond)
         _cache[key] = solve(S, g, TOL, max_iter)
+    return _cache[key]
+
+
+def failure_cases(n):
+    """Rule P5's failures placed in the LAST block of case(n) (at n = 1542 block 256: lane 0 of the second workgroup of the lane-per-block
+    kernels): name -> (S, g). Every one makes solve raise Failed."""
+    S0, g0 = case(n)
+    b = n // 6 - 1
+    assert b >= 1
+    out = {}
+    S = np.array(S0)
+    S[6 * b + 1, 6 * b + 1] = -1.0
+    out["bad pivot"] = (S, g0)
+    S = np.array(S0)
+    S[1, 6 * b + 2] = S[6 * b + 2, 1] = np.nan
+    out["nan off the diagonal blocks"] = (S, g0)
+    S = np.array(S0)
+    S[6 * b + 3, 6 * b + 3] = np.nan
+    out["nan on the diagonal"] = (S, g0)
+    # positive definite blocks, a coupling of -3 between the last two: p = g in the first pass, p.q = 12 - 36
+    S = np.eye(n)
+    i = np.arange(6 * (b - 1), 6 * b)
+    S[i, i + 6] = S[i + 6, i] = -3.0
+    g = np.zeros(n)
+    g[6 * (b - 1):] = 1.0
+    out["indefinite"] = (S, g)
+    return out
+
+
+def block_spd(rng, n):
+    """A block-dominant system, what block-Jacobi is made for (spd() needs a QR of the whole matrix and then some 300 iterations: too slow at
+    thousands of unknowns): a dense coupling of rank 8 and weight 0.5, and on every 6x6 diagonal block a random Gram matrix plus 6 .. 60 on the
+    diagonal, the blocks drawn in ascending order."""
+    W = rng.standard_normal((n, 8))
+    S = (0.5 / 8) * W @ W.T
+    for b in range(n // 6):
+        A = rng.standard_normal((6, 6))
+        S[6 * b:6 * b + 6, 6 * b:6 * b + 6] += A @ A.T + 6 * np.eye(6) * (1 + 9 * rng.random())
+    return 0.5 * (S + S.T)
+
+
+def block_case(n):
+    """(S, g) of the block-dominant family: computed once, shared, not to be written to."""
+    key = ("block", n)
+    if key not in _cache:
+        rng = np.random.default_rng(7000 + n)
+        S = block_spd(rng, n)
+        g = S @ rng.standard_normal(n)
+        S.setflags(write=False)
+        g.setflags(write=False)
+        _cache[key] = (S, g)
+    return _cache[key]
+
+
+def block_solved(n):
+    key = ("block x", n)
+    if key not in _cache:
+        S, g = block_case(n)
+        _cache[key] = solve(S, g, TOL, 0)
     return _cache[key]

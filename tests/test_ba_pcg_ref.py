@@ -50,6 +50,26 @@ def test_reference_against_a_dense_solve_on_random_spectra(n, cond, max_iter):
     assert np.abs(x - want).max() / np.abs(want).max() <= cond * res
 
 
+@pytest.mark.parametrize("n", ref.BLOCK_SIZES)
+def test_reference_on_block_dominant_systems(n):
+    """R1 at the sizes of more than two workgroups of the lane-per-block kernels (3078: 513 blocks; 6144: the capacity): not capped, at least
+    8 iterations (so that check_every = 7 spans two chunks), relative residual <= 100 tol. Found: 15 iterations at both sizes, residuals
+    2.4e-11 and 7.1e-11. At 3078 the solution also agrees with numpy.linalg.solve within cond x residual (found: cond 38.5, 3.8e-10
+    against 9.4e-10); no dense solve at 6144."""
+    S, g = ref.block_case(n)
+    x, (iters, capped, ratio) = ref.block_solved(n)
+    res = _residual(S, g, x)
+    print("block n %d: %d iterations, capped %s, residual %.3g, dn / d0 %.3g" % (n, iters, capped, res, ratio))
+    assert not capped and 8 <= iters < 12 * (n // 6)
+    assert res <= 100 * ref.TOL
+    if n == 3078:
+        want = np.linalg.solve(S, g)
+        cond = float(np.linalg.cond(S))
+        err = np.abs(x - want).max() / np.abs(want).max()
+        print("cond %.3g, against the dense solve %.3g, bound %.3g" % (cond, err, cond * res))
+        assert err <= cond * res
+
+
 def test_reference_reports_the_cap_on_a_system_it_is_too_small_for():
     x, (iters, capped, ratio) = ref.solved(66, 1e6)
     assert iters == 132 and capped and ratio > ref.TOL ** 2
@@ -87,13 +107,38 @@ def test_reference_edges():
     assert info[0] == 3 and info[1] is True
 
 
+def nonfinite_rhs(n):
+    """case(n)'s right-hand side with a NaN, and with an Inf, in the first entry of the last block (1542: entry 1536)."""
+    S, g = ref.case(n)
+    out = []
+    for v in (np.nan, np.inf):
+        h = np.array(g)
+        h[n - 6] = v
+        out.append((S, h))
+    return out
+
+
+@pytest.mark.parametrize("n", [12, 1542])
+def test_reference_edges_in_the_last_block(n):
+    """P5 with the offending entry in the last block: every failure case raises; a right-hand side that is not finite is no failure but the
+    outcome of g = 0 (P4's test is false at k = 0)."""
+    for name, (S, g) in ref.failure_cases(n).items():
+        with pytest.raises(ref.Failed):
+            ref.solve(S, g)
+    for S, g in nonfinite_rhs(n):
+        x, info = ref.solve(S, g)
+        assert info == (0, False, 0.0) and not x.any()
+
+
 def _run_host(exe, tmp_path, cases):
-    buf = [float(len(cases))]
-    for S, g, max_iter in cases:
-        buf += [float(len(g)), ref.TOL, float(max_iter)]
-        buf += np.asarray(S).ravel().tolist() + np.asarray(g).tolist()
     fin, fout = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
-    np.array(buf, np.float64).tofile(fin)
+    with open(fin, "wb") as f:   # the arrays go out as they are: a Python list of a 3078-square matrix's entries would take seconds to build
+        np.array([len(cases)], np.float64).tofile(f)
+        for S, g, max_iter in cases:
+            assert np.shape(S) == (len(g), len(g))
+            np.array([len(g), ref.TOL, max_iter], np.float64).tofile(f)
+            np.ascontiguousarray(S, np.float64).tofile(f)
+            np.ascontiguousarray(g, np.float64).tofile(f)
     subprocess.check_call([exe, "solve", fin, fout])
     out, at, res = np.fromfile(fout), 0, []
     for S, g, _ in cases:
@@ -112,6 +157,24 @@ def test_host_program_gives_the_references_bits(host, tmp_path):
         assert ok
         assert np.array_equal(ref.bits(x), ref.bits(wx))
         assert info[0] == iters and bool(info[1]) == capped and ref.bits(info[2]) == ref.bits(ratio)
+
+
+def test_host_program_gives_the_references_bits_at_513_blocks(host, tmp_path):
+    """R2 on the block-dominant system of 3078 unknowns (the capacity is left to the device test: the host program has no workgroups)."""
+    (ok, x, info), = _run_host(host, tmp_path, [ref.block_case(3078) + (0,)])
+    wx, (iters, capped, ratio) = ref.block_solved(3078)
+    assert ok
+    assert np.array_equal(ref.bits(x), ref.bits(wx))
+    assert info[0] == iters and bool(info[1]) == capped and ref.bits(info[2]) == ref.bits(ratio)
+
+
+def test_host_program_edges_in_the_last_block(host, tmp_path):
+    """The shared arithmetic decides the 1542-unknown failure cases and the right-hand sides that are not finite as the reference does."""
+    fails = list(ref.failure_cases(1542).values())
+    res = _run_host(host, tmp_path, [c + (0,) for c in fails + nonfinite_rhs(1542)])
+    assert [ok for ok, _, _ in res] == [False] * len(fails) + [True, True]
+    for ok, x, info in res[len(fails):]:
+        assert not x.any() and info.tolist() == [0.0, 0.0, 0.0]
 
 
 def test_host_plan_and_edges_under_the_sanitizers(host_san, tmp_path):

@@ -19,8 +19,10 @@ def _same_bits(a, b):
 # ---- A1: the solver, bit for bit --------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n", ref.SIZES)
 def test_pcg_solve_gives_the_references_bits(n):
-    """Below and above 64 entries per row (6 .. 66), 64 and 65 blocks (384, 390), both sides of the Cholesky's limit (1020 .. 1032); the
-    chunk the host queues between two looks at the done word changes nothing."""
+    """Below and above 64 entries per row (6 .. 66), 64 and 65 blocks (384, 390), both sides of the Cholesky's limit (1020 .. 1032), one full
+    workgroup of the lane-per-block kernels and a second one holding one lane (1536, 1542); the chunk the host queues between two looks at
+    the done word changes nothing. (The test entry stages NaN into everything the kernels must not read: the padding columns, the padding
+    rows, the padding behind the right-hand side.)"""
     from openvslam_amd import ba
     S, g = ref.case(n)
     want_x, want_info = ref.solved(n)
@@ -42,7 +44,83 @@ def test_pcg_solve_stops_at_the_cap_and_says_so():
         assert _same_bits(x, want_x)
 
 
+@pytest.mark.parametrize("n", ref.BLOCK_SIZES)
+def test_pcg_solve_gives_the_references_bits_on_block_dominant_systems(n):
+    """513 blocks (three workgroups of the lane-per-block kernels, the last with one lane) and the capacity (1024 blocks, four full
+    workgroups, pitch == n, a system of 302 MB: the default chunk and check_every = 7 only). 15 iterations at both sizes."""
+    from openvslam_amd import ba
+    assert n // 6 <= ba.pcg_max_free() and (n < 6144 or n // 6 == ba.pcg_max_free())
+    S, g = ref.block_case(n)
+    want_x, want_info = ref.block_solved(n)
+    x, info = ba.pcg_solve(S, g)
+    assert info[:2] == want_info[:2] and ref.bits(info[2]) == ref.bits(want_info[2]), (info, want_info)
+    assert _same_bits(x, want_x)
+    for check_every in (1, 7) if n < 6144 else (7,):
+        x2, info2 = ba.pcg_solve(S, g, check_every=check_every)
+        assert _same_bits(x2, want_x) and info2 == info
+
+
+@pytest.mark.parametrize("max_iter,iters,capped", [(125, 125, False), (124, 124, True), (126, 125, False)])
+def test_pcg_solve_where_convergence_and_the_cap_meet(max_iter, iters, capped):
+    """n = 66 converges in 125 iterations: a cap of 125 is not met, one of 124 is, one of 126 changes nothing. With check_every equal to the
+    iteration count the deciding pass is the first of a chunk, with one more the last."""
+    from openvslam_amd import ba
+    S, g = ref.case(66)
+    assert ref.solved(66)[1][:2] == (125, False)
+    want_x, want_info = ref.solved(66, max_iter=max_iter)
+    assert want_info[:2] == (iters, capped)
+    if not capped:
+        assert _same_bits(want_x, ref.solved(66)[0]) and want_info == ref.solved(66)[1]
+    for check_every in (iters, iters + 1):
+        x, info = ba.pcg_solve(S, g, max_iter=max_iter, check_every=check_every)
+        assert info[:2] == want_info[:2] and ref.bits(info[2]) == ref.bits(want_info[2]), (check_every, info, want_info)
+        assert _same_bits(x, want_x)
+
+
+def test_pcg_solve_stops_at_the_cap_with_a_second_workgroup():
+    from openvslam_amd import ba
+    S, g = ref.case(1542)
+    want_x, want_info = ref.solved(1542, max_iter=3)
+    assert want_info[:2] == (3, True) and 0.0165 < want_info[2] < 0.0166
+    for check_every in (0, 1, 2):
+        x, info = ba.pcg_solve(S, g, max_iter=3, check_every=check_every)
+        assert info == want_info
+        assert _same_bits(x, want_x)
+
+
 # ---- A2: the solver's error contract -----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["bad pivot", "nan off the diagonal blocks", "nan on the diagonal", "indefinite"])
+def test_pcg_solve_failures_found_by_a_later_workgroup(name):
+    """1542 unknowns, the offending entries in block 256: lane 0 of the second workgroup of k_pcg_init meets the pivot; the indefinite
+    system is one k_pcg_update detects, where workgroup 0 alone records it. Status -1, and a good solve on the same thread afterwards."""
+    from openvslam_amd import ba
+    from openvslam_amd._lib import OvsError
+    M, h = ref.failure_cases(1542)[name]
+    with pytest.raises(ref.Failed):
+        ref.solve(M, h)
+    with pytest.raises(OvsError) as e:
+        ba.pcg_solve(M, h)
+    assert e.value.status == -1
+    S, g = ref.case(1542)
+    x, info = ba.pcg_solve(S, g)
+    assert _same_bits(x, ref.solved(1542)[0]) and info == ref.solved(1542)[1]
+
+
+@pytest.mark.parametrize("n", [12, 1542])
+def test_pcg_solve_right_hand_side_that_is_not_finite(n):
+    """A NaN or an Inf in g (first entry of the last block; 1542: entry 1536, the second workgroup's lane): P4's test is false at k = 0, so it
+    is no failure but the outcome of g = 0, on the device as in the reference."""
+    from openvslam_amd import ba
+    S, g = ref.case(n)
+    for v in (np.nan, np.inf):
+        h = np.array(g)
+        h[n - 6] = v
+        want_x, want_info = ref.solve(S, h)
+        assert want_info == (0, False, 0.0) and not want_x.any()
+        x, info = ba.pcg_solve(S, h)
+        assert info == (0, False, 0.0) and _same_bits(x, np.zeros(n))
+
+
 def test_pcg_solve_error_contract():
     from openvslam_amd import ba
     from openvslam_amd._lib import OvsError
@@ -154,6 +232,35 @@ def test_by_size_takes_the_pcg_at_1026_unknowns(oracle):
     with pytest.raises(OvsError) as e:
         ba.global_ba_optimize(*args, hm, hs, N_SWITCH, ba.SOLVER_CHOLESKY)
     assert e.value.status == -4
+
+
+@pytest.mark.parametrize("also_fixed,n_free", [((), 258), ((130,), 257)])
+def test_whole_call_with_a_second_lane_per_block_workgroup(oracle, also_fixed, n_free):
+    """A ring of 259 keyframes, mono edges, three LM iterations: 258 free keyframes (keyframe 0 fixed), and 257 with keyframe 130 fixed as
+    well (the fixed mask is no prefix, and the last workgroup of the lane-per-block kernels holds one lane). The bounds are those of the
+    1026-unknown test between the same pairs. Beyond this size the suite compares the whole call with nothing."""
+    from oracle import lba
+    from openvslam_amd import ba
+    d = dict(global_ba_ref.ring(259, 6000, 100))
+    fixed = np.array(d["pose_fixed"], np.uint8)
+    fixed[list(also_fixed)] = 1
+    assert int((fixed == 0).sum()) == n_free and fixed[0] == 1
+    hm, hs = ba.huber_deltas(0)
+    args = (d["poses"], fixed, d["points"], d["edges"], d["cam"], None, 0.0)
+    got = ba.global_ba_optimize(*args, hm, hs, N_SWITCH, ba.SOLVER_BY_SIZE)
+    assert got["info"][4] == 2 and got["info"][5] > 16 * got["info"][3] and got["info"][6] == 0 and got["info"][7] == 0   # more than one chunk per solve
+    want = lba.local_ba_optimize(*args, N_SWITCH, 0)
+    print("info", got["info"], want["info"], "vs oracle: poses %.3g points %.3g" % (np.abs(got["poses"] - want["poses"]).max(),
+                                                                                     np.abs(got["points"] - want["points"]).max()))
+    assert got["info"][2] == want["info"][4]
+    assert np.allclose(got["info"][:2], want["info"][:2], rtol=1e-7)
+    assert np.allclose(got["poses"], want["poses"], rtol=1e-7, atol=1e-8) and np.allclose(got["points"], want["points"], rtol=1e-7, atol=1e-8)
+    host = ba.local_ba_optimize(*args, N_SWITCH, 0)   # local BA's host path
+    print("vs local BA's host path: poses %.3g points %.3g" % (np.abs(got["poses"] - host["poses"]).max(), np.abs(got["points"] - host["points"]).max()))
+    assert np.allclose(got["poses"], host["poses"], rtol=1e-9, atol=1e-10) and np.allclose(got["points"], host["points"], rtol=1e-9, atol=1e-10)
+    rows = np.flatnonzero(fixed)
+    assert _same_bits(got["poses"][rows], np.asarray(d["poses"], np.float64)[rows])
+    assert np.abs(got["poses"][fixed == 0] - np.asarray(d["poses"])[fixed == 0]).max() > 1e-3   # (the free ones move by far more than the bounds)
 
 
 # ---- A6: Huber and edge kinds -----------------------------------------------------------------------------------------------------------
