@@ -5,8 +5,8 @@
 // finish kernel scans a problem slot's slots for its winner (best_slot: the one statement of 3.13 rule 7 and 3.16 rule E6). A solver
 // supplies its rows, its score term, its sweeps and everything between the null vector and the model. The one callable (score_matches'
 // term) is a lambda on compile-time indices: nothing is indexed dynamically, nothing goes to scratch. The helpers' shapes are those that
-// leave the kernels' instruction streams what they were (DESIGN.md 3.16 has the comparison). On the host: eight_point_handle, its create,
-// and run_slots, the batch call of two launches. (An .inc, not an .h: see solve_internal.inc.)
+// leave the kernels' instruction streams what they were (DESIGN.md 3.16 has the comparison). On the host: eight_point_handle, its create
+// (batch_create with the inlier lists), and run_slots, the batch call of two launches. (An .inc, not an .h: see solve_internal.inc.)
 #pragma once
 #include "solve_internal.inc"
 
@@ -113,35 +113,29 @@ __device__ __forceinline__ void invalid_form(uint8_t* __restrict__ flags, int n,
 }
 
 // ---- the host side: the handle under ovs_twoview_* and ovs_essential_*
-struct eight_point_handle : ransac_handle {
+struct eight_point_handle : batch_handle {
     int32_t* d_inlier_idx = nullptr;   // [lists][matches of the call] a winner's inliers by rank, per problem slot at the problem's offset
 };
 
 // H: ovs_twoview (lists = 2: both models) or ovs_essential (1). `lists` x 32 iterations per problem fit without growing; extra(handle)
-// allocates what the solver's handle adds.
+// acquires what the solver's handle adds to the lists.
 template <class H, class Extra>
 ovs_status eight_point_create(int32_t device, int32_t max_problems, int32_t max_total_matches, size_t block_bytes, int lists, size_t result_bytes,
                               H** out, Extra extra) {
-    const ovs_status st = ransac_create(device, max_problems, max_total_matches, block_bytes, (size_t)max_problems * lists * 32, kSlotDoubles, out, result_bytes);
-    if (st != OVS_OK) return st;
-    std::unique_ptr<H> owner(*out);
-    *out = nullptr;
-    OVS_HIP_TRY(owner->res.dev(&owner->d_inlier_idx, sizeof(int32_t) * lists * (size_t)max_total_matches));
-    const ovs_status added = extra(owner.get());
-    if (added != OVS_OK) return added;
-    *out = owner.release();
-    return OVS_OK;
+    return batch_create(device, max_problems, max_total_matches, block_bytes, (size_t)max_problems * lists * 32, kSlotDoubles, result_bytes, out, [&](H* s) -> ovs_status {
+        OVS_HIP_TRY(s->res.dev(&s->d_inlier_idx, sizeof(int32_t) * lists * (size_t)max_total_matches));
+        return extra(s);
+    });
 }
 
 // One solve_batch call of a slot solver: run_staged with room for n_problems x lists x max_num_iter slots and the two launches,
 // hypotheses(stream, T) and finish(stream, T).
-template <class Layout, class Stage, class Hypotheses, class Finish, class Collect>
-ovs_status run_slots(eight_point_handle* s, int32_t n_problems, const int32_t* offsets, std::initializer_list<const void*> required,
-                     std::initializer_list<const void*> per_match, const void* per_match_out, Layout (*layout_of)(int, int), int lists,
-                     int32_t max_num_iter, Stage stage, Hypotheses hypotheses, Finish finish, Collect collect) {
+template <class Stage, class Hypotheses, class Finish, class Collect>
+ovs_status run_slots(eight_point_handle* s, const splan::Checked& checked, size_t upload_bytes, int32_t n_problems, int lists, int32_t max_num_iter,
+                     Stage stage, Hypotheses hypotheses, Finish finish, Collect collect) {
     return run_staged(
-        s, n_problems, offsets, required, per_match, per_match_out, layout_of, stage,
-        [&] { return s->reserve_models((size_t)n_problems * lists * (size_t)max_num_iter) != OVS_OK ? OVS_ERR_HIP : OVS_OK; },
+        s, checked, upload_bytes, stage,
+        [&] { return s->reserve((size_t)n_problems * lists * (size_t)max_num_iter) != OVS_OK ? OVS_ERR_HIP : OVS_OK; },
         [&](hipStream_t stream, int32_t T) {
             hypotheses(stream, T);
             OVS_HIP_TRY(hipGetLastError());

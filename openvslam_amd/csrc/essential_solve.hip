@@ -27,18 +27,9 @@ namespace {
 
 constexpr int kSampleShare = 16;   // the counter share of a hypothesis (solve.essential_problem_seed: p << 24)
 
-// The staged block of one call, sections in this order: b1 f64 [3 T], b2 f64 [3 T], offsets i32 [P + 1].
-struct Layout {
-    size_t b1, b2, offsets, bytes;
-};
-__host__ __device__ inline Layout layout_of(int P, int T) {
-    Layout l;
-    l.b1 = 0;
-    l.b2 = l.b1 + 24 * (size_t)T;
-    l.offsets = l.b2 + 24 * (size_t)T;
-    l.bytes = l.offsets + 4 * ((size_t)P + 1);
-    return l;
-}
+// the staged block of one call: solve_plan.inc
+using splan::essential::Layout;
+using splan::essential::layout_of;
 
 // per problem in the result block
 struct EssentialRec {
@@ -168,43 +159,35 @@ __global__ __launch_bounds__(64) void k_essential_finish(const uint8_t* __restri
 
 }   // namespace
 
-struct ovs_essential : eight_point_handle {
-    EssentialRec* h_rec() { return reinterpret_cast<EssentialRec*>(h_result); }
-    EssentialRec* m_rec() { return reinterpret_cast<EssentialRec*>(m_result); }
-};
+struct ovs_essential : eight_point_handle {};
 
 extern "C" {
 
 ovs_status ovs_essential_create(int32_t device, int32_t max_problems, int32_t max_total_matches, ovs_essential** out) {
     return eight_point_create(device, max_problems, max_total_matches, layout_of(max_problems, max_total_matches).bytes, 1, sizeof(EssentialRec), out,
-                              [](ovs_essential*) { return OVS_OK; });
+                              no_extra);
 }
 
-ovs_status ovs_essential_destroy(ovs_essential* s) { return ransac_destroy(s); }
+ovs_status ovs_essential_destroy(ovs_essential* s) { return batch_destroy(s); }
 
 ovs_status ovs_essential_solve_batch(ovs_essential* s, int32_t n_problems, const int32_t* offsets, const double* bearings_1, const double* bearings_2,
                                      double residual_cos_thr, int32_t max_num_iter, int32_t recompute, uint64_t seed, double* out_E_21, double* out_scores,
                                      int32_t* out_valid, int32_t* out_best_iter, int32_t* out_num_inliers, uint8_t* out_inlier_flags) {
-    if (max_num_iter < 1 || max_num_iter > kMaxIter || !std::isfinite(residual_cos_thr) || !(residual_cos_thr > 0.0) || !(residual_cos_thr <= 1.0))
-        return OVS_ERR_INVALID;
-    const auto stage = [&](uint8_t* h_block, const Layout& lay, int32_t T) {
-        if (T > 0) {
-            std::memcpy(h_block + lay.b1, bearings_1, 24 * (size_t)T);
-            std::memcpy(h_block + lay.b2, bearings_2, 24 * (size_t)T);
-        }
-        return OVS_OK;
-    };
+    const splan::essential::Call call{s != nullptr, n_problems, offsets, bearings_1, bearings_2, residual_cos_thr, max_num_iter, out_E_21,
+                                      out_scores, out_valid, out_best_iter, out_num_inliers, out_inlier_flags};
+    const splan::Checked checked = splan::essential::check(call, caps_of(s));
+    const Layout lay = layout_of(n_problems, checked.T);
     const auto hypotheses = [&](hipStream_t st, int32_t T) {
         hipLaunchKernelGGL(k_essential_hypotheses, dim3(max_num_iter, n_problems), dim3(64), 0, st, s->d_block, n_problems, T, max_num_iter, seed,
-                           residual_cos_thr, s->d_wave_models);
+                           residual_cos_thr, s->d_records);
     };
     const auto finish = [&](hipStream_t st, int32_t T) {
         hipLaunchKernelGGL(k_essential_finish, dim3(n_problems), dim3(64), 0, st, s->d_block, n_problems, T, max_num_iter, recompute ? 1 : 0,
-                           residual_cos_thr, s->d_wave_models, s->d_inlier_idx, s->m_rec(), s->m_flags);
+                           residual_cos_thr, s->d_records, s->d_inlier_idx, s->m_rec<EssentialRec>(), s->m_flags);
     };
     const auto collect = [&](int32_t T) {
         for (int32_t p = 0; p < n_problems; ++p) {
-            const EssentialRec& r = s->h_rec()[p];
+            const EssentialRec& r = s->h_rec<EssentialRec>()[p];
             std::memcpy(out_E_21 + 9 * (size_t)p, r.mat, sizeof(r.mat));
             out_scores[p] = r.score;
             out_valid[p] = r.valid;
@@ -213,8 +196,8 @@ ovs_status ovs_essential_solve_batch(ovs_essential* s, int32_t n_problems, const
         }
         if (T > 0) std::memcpy(out_inlier_flags, s->h_flags, (size_t)T);
     };
-    return run_slots(s, n_problems, offsets, {out_E_21, out_scores, out_valid, out_best_iter, out_num_inliers}, {bearings_1, bearings_2}, out_inlier_flags,
-                     layout_of, 1, max_num_iter, stage, hypotheses, finish, collect);
+    return run_slots(s, checked, lay.bytes, n_problems, 1, max_num_iter, [&] { splan::essential::stage(call, lay, s->h_block); }, hypotheses, finish,
+                     collect);
 }
 
 }   // extern "C"

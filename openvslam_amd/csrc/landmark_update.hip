@@ -3,9 +3,11 @@
 // after the fuse step, and the end of map_database::from_json. Rules: DESIGN.md 3.14 (L1 to L9); the algebra is landmark_math.inc, which a
 // plain host compiler builds too.
 //
-// On the batch scaffold of solve_internal.inc: a "problem" is a landmark, its "matches" are its observations. The staged block is
-// structure-of-arrays. Observations name their keyframe by slot into a per-call table (camera centres, and in the _f form the device pointers
-// of the resident keyframes' descriptors), staged once per call in a buffer of its own.
+// On the batch scaffold of solve_internal.inc: a "problem" is a landmark, its "matches" are its observations. What a call decides on the
+// host (argument errors, capacity, the block's layout, staging, the two size lists, the read-back) is splan::landmarks of solve_plan.inc;
+// this unit keeps the kernels and their launches. The staged block is structure-of-arrays. Observations name their keyframe by slot into a
+// per-call table (camera centres, and in the _f form the device pointers of the resident keyframes' descriptors), staged once per call in
+// a buffer of its own.
 //
 // k_landmark_geometry: a lane per landmark, 256 lanes per workgroup; the lane walks its observations in list order, which is what makes
 //   the sum's bits the sequential reference's. The first kLdsCentres camera centres are copied into LDS once per workgroup, the others are
@@ -31,41 +33,10 @@ namespace {
 constexpr int kGeoLanes = 256;
 constexpr int kLdsCentres = 256;    // camera centres held in LDS (6 KiB); slots from here on are read from memory
 constexpr int kLdsDescs64 = 128;    // descriptors of a G = 64 landmark held in LDS (4 KiB); the others are read from memory
-constexpr int kMaxObsPerLandmark = 1 << 22;   // the ordinal's share of the winner's key
 
-__host__ __device__ inline size_t al16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-// The staged block of one call, every section 16-byte aligned. Inputs: pos f64 [3][P] (planes), sf_ref f32 [P] (scale_factors[ref_level]),
-// ref_slot i32 [P], offsets i32 [P + 1], obs_slot i32 [T], used i32 [T] (per landmark, from its offset on: the observations that take part in
-// the descriptor, as indices into the call's observations), n_used i32 [P], list8 i32 [P], list64 i32 [P], obs_kp i32 [T] (_f form), desc
-// u8 [T][32]. Then what the kernels write and the host copies back: normal f64 [3][P], range f32 [2][P], best i32 [P], out_desc u8 [P][32].
-// `bytes` is what a call uploads: WITH_DESC = false ends it before the descriptors (a geometry-only call, or the _f form).
-struct Layout {
-    size_t pos, sf_ref, ref_slot, offsets, obs_slot, used, n_used, list8, list64, obs_kp, desc, normal, range, best, out_desc, total, bytes;
-};
-template <bool WITH_DESC>
-__host__ __device__ inline Layout layout_of(int P, int T) {
-    Layout l;
-    const size_t p4 = al16(4 * (size_t)P), t4 = al16(4 * (size_t)T);
-    l.pos = 0;
-    l.sf_ref = l.pos + al16(24 * (size_t)P);
-    l.ref_slot = l.sf_ref + p4;
-    l.offsets = l.ref_slot + p4;
-    l.obs_slot = l.offsets + al16(4 * ((size_t)P + 1));
-    l.used = l.obs_slot + t4;
-    l.n_used = l.used + t4;
-    l.list8 = l.n_used + p4;
-    l.list64 = l.list8 + p4;
-    l.obs_kp = l.list64 + p4;
-    l.desc = l.obs_kp + t4;
-    l.normal = l.desc + 32 * (size_t)T;
-    l.range = l.normal + al16(24 * (size_t)P);
-    l.best = l.range + al16(8 * (size_t)P);
-    l.out_desc = l.best + p4;
-    l.total = l.out_desc + 32 * (size_t)P;
-    l.bytes = WITH_DESC ? l.normal : l.desc;
-    return l;
-}
+// the staged block of one call (structure-of-arrays, every section 16-byte aligned; the kernels' outputs are its last sections): solve_plan.inc
+using splan::landmarks::Layout;
+using splan::landmarks::layout_of;
 
 __global__ __launch_bounds__(kGeoLanes) void k_landmark_geometry(uint8_t* __restrict__ block, const double* __restrict__ centres, int P, int T, int K,
                                                                  float sf_last_level) {
@@ -181,163 +152,56 @@ __global__ __launch_bounds__(64) void k_landmark_descriptor(uint8_t* __restrict_
 
 }   // namespace
 
-struct ovs_landmarks : ransac_handle {
+struct ovs_landmarks : batch_handle {   // the results come back through the staged block: no records, no result block, no flags
     int max_keyframes = 0;
     // the per-call keyframe table: camera centres f64 [K][3], then the descriptors' device pointers [K] (_f form), and its page-locked twin
     uint8_t *d_table = nullptr, *h_table = nullptr;
+    const double* d_centres() const { return reinterpret_cast<const double*>(d_table); }
+    const uint8_t* const* d_desc_of_slot(int32_t K) const { return reinterpret_cast<const uint8_t* const*>(d_table + splan::landmarks::table_ptrs_at(K)); }
 };
 
 namespace {
 
-struct Inputs {
-    int32_t what, n;
-    const int32_t* offsets;
-    const double* pos_w;
-    const int32_t *ref_keyfrm, *ref_level, *obs_keyfrm;
-    const uint8_t* obs_desc;
-    bool resident;
-    const ovs_frame_dev* const* keyfrms;
-    const int32_t* obs_keypoint;
-    const uint8_t* obs_use;
-    const double* cam_centers;
-    int32_t n_keyframes;
-    const float* scale_factors;
-    int32_t num_levels;
-    double* out_mean_normal;
-    float* out_min_max_dist;
-    int32_t* out_best_obs;
-    uint8_t *out_desc, *out_status;
-};
+using splan::landmarks::Call;
 
-ovs_status update_batch(ovs_landmarks* s, const Inputs& a) {
-    if (!s || a.n < 0 || a.what < 1 || a.what > 3) return OVS_ERR_INVALID;
-    if (a.n == 0) return OVS_OK;
-    const bool geo = (a.what & 1) != 0, dsc = (a.what & 2) != 0;
-    const int32_t P = a.n, K = a.n_keyframes;
-    const bool slots = geo || (dsc && a.resident);   // whether obs_keyfrm and the keyframe table are read
-    if (geo && (a.num_levels < 1 || a.num_levels > OVS_MAX_LEVELS)) return OVS_ERR_INVALID;
-    if (slots && K < 0) return OVS_ERR_INVALID;
-    const void* const unused = s;   // stands for an array this call does not read
-    const auto when = [&](bool on, const void* q) { return on ? q : unused; };
-    int32_t n8 = 0, n64 = 0;
-    Layout used{};
-    const size_t ptrs_at = 24 * (size_t)(K > 0 ? K : 0);
-    const auto stage = [&](uint8_t* h_block, const Layout& lay, int32_t T) {
-        used = lay;
-        if (slots && K > s->max_keyframes) return OVS_ERR_CAPACITY;
-        for (int32_t p = 0; p < P; ++p) {
-            const int32_t count = a.offsets[p + 1] - a.offsets[p];
-            if (count >= kMaxObsPerLandmark) return OVS_ERR_INVALID;
-            if (geo && count > 0 && (a.ref_keyfrm[p] < 0 || a.ref_keyfrm[p] >= K || a.ref_level[p] < 0 || a.ref_level[p] >= a.num_levels)) return OVS_ERR_INVALID;
-        }
-        if (slots)
-            for (int32_t t = 0; t < T; ++t)
-                if (a.obs_keyfrm[t] < 0 || a.obs_keyfrm[t] >= K) return OVS_ERR_INVALID;
-        if (dsc && a.resident) {
-            const uint8_t** ptrs = reinterpret_cast<const uint8_t**>(s->h_table + ptrs_at);
-            for (int32_t k = 0; k < K; ++k) {
-                if (!a.keyfrms[k]) return OVS_ERR_INVALID;
-                if (a.keyfrms[k]->device != s->device) return OVS_ERR_INVALID;
-                ptrs[k] = a.keyfrms[k]->d_desc;
-            }
-            for (int32_t t = 0; t < T; ++t)
-                if (a.obs_keypoint[t] < 0 || a.obs_keypoint[t] >= a.keyfrms[a.obs_keyfrm[t]]->n) return OVS_ERR_INVALID;
-            if (T > 0) std::memcpy(h_block + lay.obs_kp, a.obs_keypoint, 4 * (size_t)T);
-        }
-        if (slots && T > 0) std::memcpy(h_block + lay.obs_slot, a.obs_keyfrm, 4 * (size_t)T);
-        if (geo) {
-            double* pos = reinterpret_cast<double*>(h_block + lay.pos);
-            float* sf_ref = reinterpret_cast<float*>(h_block + lay.sf_ref);
-            int32_t* ref_slot = reinterpret_cast<int32_t*>(h_block + lay.ref_slot);
-            for (int32_t p = 0; p < P; ++p) {
-                for (int x = 0; x < 3; ++x) pos[(size_t)x * P + p] = a.pos_w[3 * (size_t)p + x];
-                const bool empty = a.offsets[p + 1] == a.offsets[p];
-                sf_ref[p] = empty ? 0.0f : a.scale_factors[a.ref_level[p]];
-                ref_slot[p] = empty ? 0 : a.ref_keyfrm[p];
-            }
-            if (K > 0) std::memcpy(s->h_table, a.cam_centers, 24 * (size_t)K);
-        }
-        if (dsc) {
-            // the host plan: which observations take part (rule L6), and each landmark into the list of the kernel that serves its size
-            int32_t* used_obs = reinterpret_cast<int32_t*>(h_block + lay.used);
-            int32_t* n_used = reinterpret_cast<int32_t*>(h_block + lay.n_used);
-            int32_t* list8 = reinterpret_cast<int32_t*>(h_block + lay.list8);
-            int32_t* list64 = reinterpret_cast<int32_t*>(h_block + lay.list64);
-            for (int32_t p = 0; p < P; ++p) {
-                int32_t M = 0;
-                for (int32_t t = a.offsets[p]; t < a.offsets[p + 1]; ++t)
-                    if (!a.obs_use || a.obs_use[t]) used_obs[a.offsets[p] + M++] = t;
-                n_used[p] = M;
-                if (M > 8) list64[n64++] = p;
-                else if (M > 0) list8[n8++] = p;
-            }
-            if (!a.resident && T > 0) std::memcpy(h_block + lay.desc, a.obs_desc, 32 * (size_t)T);
-        }
-        return OVS_OK;
-    };
+ovs_status update_batch(ovs_landmarks* s, const Call& call) {
+    const splan::Checked checked =
+        splan::landmarks::check(call, [s] { return splan::Caps{s->max_problems, s->max_total_matches, s->max_keyframes, s->device}; });
+    const int32_t P = call.n_landmarks, K = call.n_keyframes;
+    const Layout lay = splan::landmarks::layout_for(call, checked.T);
+    splan::landmarks::Lists lists{0, 0};
     const auto launch = [&](hipStream_t st, int32_t T) {
         if (T == 0) return OVS_OK;
-        if (slots && K > 0) OVS_HIP_TRY(hipMemcpyAsync(s->d_table, s->h_table, ptrs_at + 8 * (size_t)K, hipMemcpyHostToDevice, st));
-        if (geo) {
+        if (call.slots() && K > 0) OVS_HIP_TRY(hipMemcpyAsync(s->d_table, s->h_table, splan::landmarks::table_bytes(K), hipMemcpyHostToDevice, st));
+        if (call.geo()) {
             hipLaunchKernelGGL(k_landmark_geometry, dim3((P + kGeoLanes - 1) / kGeoLanes), dim3(kGeoLanes), 0, st, s->d_block,
-                               reinterpret_cast<const double*>(s->d_table), P, T, K, a.scale_factors[a.num_levels - 1]);
+                               s->d_centres(), P, T, K, call.scale_factors[call.num_levels - 1]);
             OVS_HIP_TRY(hipGetLastError());
         }
-        if (dsc && a.resident) {
-            hipLaunchKernelGGL(k_landmark_gather, dim3((unsigned)((8 * (size_t)T + 255) / 256)), dim3(256), 0, st, s->d_block,
-                               reinterpret_cast<const uint8_t* const*>(s->d_table + ptrs_at), P, T);
+        if (call.gathers()) {
+            hipLaunchKernelGGL(k_landmark_gather, dim3((unsigned)((8 * (size_t)T + 255) / 256)), dim3(256), 0, st, s->d_block, s->d_desc_of_slot(K), P, T);
             OVS_HIP_TRY(hipGetLastError());
         }
-        if (n8 > 0) {
-            hipLaunchKernelGGL(k_landmark_descriptor<8>, dim3((n8 + 7) / 8), dim3(64), 0, st, s->d_block, P, T, n8);
+        if (lists.n8 > 0) {
+            hipLaunchKernelGGL(k_landmark_descriptor<8>, dim3((lists.n8 + 7) / 8), dim3(64), 0, st, s->d_block, P, T, lists.n8);
             OVS_HIP_TRY(hipGetLastError());
         }
-        if (n64 > 0) {
-            hipLaunchKernelGGL(k_landmark_descriptor<64>, dim3(n64), dim3(64), 0, st, s->d_block, P, T, n64);
+        if (lists.n64 > 0) {
+            hipLaunchKernelGGL(k_landmark_descriptor<64>, dim3(lists.n64), dim3(64), 0, st, s->d_block, P, T, lists.n64);
             OVS_HIP_TRY(hipGetLastError());
         }
-        OVS_HIP_TRY(hipMemcpyAsync(s->h_block + used.normal, s->d_block + used.normal, used.total - used.normal, hipMemcpyDeviceToHost, st));
+        OVS_HIP_TRY(hipMemcpyAsync(s->h_block + lay.normal, s->d_block + lay.normal, lay.total - lay.normal, hipMemcpyDeviceToHost, st));
         return OVS_OK;
     };
-    const auto collect = [&](int32_t) {
-        const double* normal = reinterpret_cast<const double*>(s->h_block + used.normal);
-        const float* range = reinterpret_cast<const float*>(s->h_block + used.range);
-        const int32_t* best = reinterpret_cast<const int32_t*>(s->h_block + used.best);
-        const int32_t* n_used = reinterpret_cast<const int32_t*>(s->h_block + used.n_used);
-        for (int32_t p = 0; p < P; ++p) {
-            const bool empty = a.offsets[p + 1] == a.offsets[p];
-            a.out_status[p] = empty ? 1 : 0;
-            if (geo && !empty) {
-                for (int x = 0; x < 3; ++x) a.out_mean_normal[3 * (size_t)p + x] = normal[(size_t)x * P + p];
-                a.out_min_max_dist[2 * (size_t)p] = range[p];
-                a.out_min_max_dist[2 * (size_t)p + 1] = range[(size_t)P + p];
-            }
-            if (dsc && !empty) {
-                if (n_used[p] == 0) {
-                    a.out_best_obs[p] = -1;
-                } else {
-                    a.out_best_obs[p] = best[p] - a.offsets[p];
-                    std::memcpy(a.out_desc + 32 * (size_t)p, s->h_block + used.out_desc + 32 * (size_t)p, 32);
-                }
-            }
-        }
-    };
-    const std::initializer_list<const void*> required = {a.out_status,
-                                                         when(geo, a.pos_w),
-                                                         when(geo, a.ref_keyfrm),
-                                                         when(geo, a.ref_level),
-                                                         when(geo, a.cam_centers),
-                                                         when(geo, a.scale_factors),
-                                                         when(geo, a.out_mean_normal),
-                                                         when(geo, a.out_min_max_dist),
-                                                         when(dsc, a.out_best_obs),
-                                                         when(dsc, a.out_desc),
-                                                         when(dsc && a.resident, a.keyfrms)};
-    const std::initializer_list<const void*> per_observation = {when(slots, a.obs_keyfrm), when(dsc && !a.resident, a.obs_desc),
-                                                                when(dsc && a.resident, a.obs_keypoint)};
-    if (dsc && !a.resident)
-        return run_staged(s, P, a.offsets, required, per_observation, unused, layout_of<true>, stage, [] { return OVS_OK; }, launch, collect);
-    return run_staged(s, P, a.offsets, required, per_observation, unused, layout_of<false>, stage, [] { return OVS_OK; }, launch, collect);
+    return run_staged(
+        s, checked, lay.bytes, [&] { lists = splan::landmarks::stage(call, lay, s->h_block, s->h_table); }, nothing_to_reserve, launch,
+        [&](int32_t) { splan::landmarks::collect(call, lay, s->h_block); });
+}
+
+// entry k of the _f form's keyframes as the plan reads it
+splan::landmarks::KeyframeView keyframe_view(const void* keyfrms, int32_t k) {
+    const ovs_frame_dev* f = static_cast<const ovs_frame_dev* const*>(keyfrms)[k];
+    return f ? splan::landmarks::KeyframeView{f->device, f->n, f->d_desc} : splan::landmarks::KeyframeView{-1, 0, nullptr};
 }
 
 }   // namespace
@@ -348,29 +212,25 @@ ovs_status ovs_landmarks_create(int32_t device, int32_t max_landmarks, int32_t m
     if (!out) return OVS_ERR_INVALID;
     *out = nullptr;
     if (max_keyframes < 1) return OVS_ERR_INVALID;
-    ovs_landmarks* s = nullptr;
-    const ovs_status st = ransac_create(device, max_landmarks, max_total_observations, layout_of<true>(max_landmarks, max_total_observations).total, 0, 0, &s, 8);
-    if (st != OVS_OK) return st;
-    s->max_keyframes = max_keyframes;
-    const size_t table_bytes = 32 * (size_t)max_keyframes;
-    if (s->res.dev(&s->d_table, table_bytes) != hipSuccess || s->res.pinned(&s->h_table, table_bytes) != hipSuccess) {
-        ransac_destroy(s);
-        return OVS_ERR_HIP;
-    }
-    *out = s;
-    return OVS_OK;
+    return batch_create(device, max_landmarks, max_total_observations, layout_of<true>(max_landmarks, max_total_observations).total, 0, 0, 0, out,
+                        [&](ovs_landmarks* s) {
+                            s->max_keyframes = max_keyframes;
+                            const size_t table_bytes = splan::landmarks::table_bytes(max_keyframes);
+                            if (s->res.dev(&s->d_table, table_bytes) != hipSuccess || s->res.pinned(&s->h_table, table_bytes) != hipSuccess) return OVS_ERR_HIP;
+                            return OVS_OK;
+                        });
 }
 
-ovs_status ovs_landmarks_destroy(ovs_landmarks* s) { return ransac_destroy(s); }
+ovs_status ovs_landmarks_destroy(ovs_landmarks* s) { return batch_destroy(s); }
 
 ovs_status ovs_landmarks_update_batch(ovs_landmarks* s, int32_t what, int32_t n_landmarks, const int32_t* offsets, const double* pos_w,
                                       const int32_t* ref_keyfrm, const int32_t* ref_level, const int32_t* obs_keyfrm, const uint8_t* obs_desc,
                                       const uint8_t* obs_use, const double* cam_centers, int32_t n_keyframes, const float* scale_factors,
                                       int32_t num_levels, double* out_mean_normal, float* out_min_max_dist, int32_t* out_best_obs, uint8_t* out_desc,
                                       uint8_t* out_status) {
-    return update_batch(s, Inputs{what, n_landmarks, offsets, pos_w, ref_keyfrm, ref_level, obs_keyfrm, obs_desc, false, nullptr, nullptr, obs_use,
-                                  cam_centers, n_keyframes, scale_factors, num_levels, out_mean_normal, out_min_max_dist, out_best_obs, out_desc,
-                                  out_status});
+    return update_batch(s, Call{s != nullptr, what, n_landmarks, offsets, pos_w, ref_keyfrm, ref_level, obs_keyfrm, obs_desc, false, nullptr, nullptr, nullptr,
+                                obs_use, cam_centers, n_keyframes, scale_factors, num_levels, out_mean_normal, out_min_max_dist, out_best_obs, out_desc,
+                                out_status});
 }
 
 ovs_status ovs_landmarks_update_batch_f(ovs_landmarks* s, int32_t what, int32_t n_landmarks, const int32_t* offsets, const double* pos_w,
@@ -379,9 +239,9 @@ ovs_status ovs_landmarks_update_batch_f(ovs_landmarks* s, int32_t what, int32_t 
                                         const double* cam_centers, int32_t n_keyframes, const float* scale_factors, int32_t num_levels,
                                         double* out_mean_normal, float* out_min_max_dist, int32_t* out_best_obs, uint8_t* out_desc,
                                         uint8_t* out_status) {
-    return update_batch(s, Inputs{what, n_landmarks, offsets, pos_w, ref_keyfrm, ref_level, obs_keyfrm, nullptr, true, keyfrms, obs_keypoint, obs_use,
-                                  cam_centers, n_keyframes, scale_factors, num_levels, out_mean_normal, out_min_max_dist, out_best_obs, out_desc,
-                                  out_status});
+    return update_batch(s, Call{s != nullptr, what, n_landmarks, offsets, pos_w, ref_keyfrm, ref_level, obs_keyfrm, nullptr, true, keyfrms, keyframe_view,
+                                obs_keypoint, obs_use, cam_centers, n_keyframes, scale_factors, num_levels, out_mean_normal, out_min_max_dist, out_best_obs,
+                                out_desc, out_status});
 }
 
 }   // extern "C"

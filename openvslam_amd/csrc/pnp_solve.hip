@@ -27,21 +27,9 @@ namespace {
 
 constexpr int kSweeps = 8;          // every symmetric eigenproblem (DESIGN.md 3.10 rule 2)
 constexpr int kModelDoubles = 12;   // R 9, t 3
-// The staged block of one call, sections in this order: keys u64 [P] (zero), bearings f64 [3 T], pos_w f64 [3 T], max_cos_error f64 [T],
-// offsets i32 [P + 1].
-struct Layout {
-    size_t keys, bearings, pos_w, max_cos, offsets, bytes;
-};
-__host__ __device__ inline Layout layout_of(int P, int T) {
-    Layout l;
-    l.keys = 0;
-    l.bearings = l.keys + 8 * (size_t)P;
-    l.pos_w = l.bearings + 24 * (size_t)T;
-    l.max_cos = l.pos_w + 24 * (size_t)T;
-    l.offsets = l.max_cos + 8 * (size_t)T;
-    l.bytes = l.offsets + 4 * ((size_t)P + 1);
-    return l;
-}
+// the staged block of one call: solve_plan.inc
+using splan::pnp::Layout;
+using splan::pnp::layout_of;
 
 // one wavefront's LDS: the 12 x 12 matrix and its vectors (row-major), the four chosen eigenvectors, a hypothesis's four indices
 struct Lds {
@@ -532,48 +520,41 @@ __global__ __launch_bounds__(64) void k_pnp_finish(const uint8_t* __restrict__ b
 
 }   // namespace
 
-struct ovs_pnp : ransac_handle {
+struct ovs_pnp : batch_handle {
     int32_t* d_inlier_idx = nullptr;   // [max_total_matches] the winner's inliers by rank, per problem at its offset
 };
 
 extern "C" {
 
 ovs_status ovs_pnp_create(int32_t device, int32_t max_problems, int32_t max_total_matches, ovs_pnp** out) {
-    const ovs_status st = ransac_create(device, max_problems, max_total_matches, layout_of(max_problems, max_total_matches).bytes,
-                                        (size_t)max_problems * 64,   // 64 iterations per problem without growing
-                                        kModelDoubles, out);
-    if (st != OVS_OK) return st;
-    std::unique_ptr<ovs_pnp> owner(*out);
-    *out = nullptr;
-    OVS_HIP_TRY(owner->res.dev(&owner->d_inlier_idx, sizeof(int32_t) * (size_t)max_total_matches));
-    *out = owner.release();
-    return OVS_OK;
+    return batch_create(device, max_problems, max_total_matches, layout_of(max_problems, max_total_matches).bytes,
+                        (size_t)max_problems * 64,   // 64 iterations per problem without growing
+                        kModelDoubles, sizeof(ResultRec), out, [&](ovs_pnp* s) {
+                            OVS_HIP_TRY(s->res.dev(&s->d_inlier_idx, sizeof(int32_t) * (size_t)max_total_matches));
+                            return OVS_OK;
+                        });
 }
 
-ovs_status ovs_pnp_destroy(ovs_pnp* s) { return ransac_destroy(s); }
+ovs_status ovs_pnp_destroy(ovs_pnp* s) { return batch_destroy(s); }
 
 ovs_status ovs_pnp_solve_batch(ovs_pnp* s, int32_t n_problems, const int32_t* offsets, const double* bearings, const double* pos_w,
                                const double* max_cos_errors, int32_t min_num_inliers, int32_t max_num_iter, int32_t recompute, uint64_t seed,
                                int32_t* out_valid, int32_t* out_best_iter, int32_t* out_num_inliers, double* out_rot_cw, double* out_trans_cw,
                                uint8_t* out_inlier_flags) {
-    const auto stage = [&](uint8_t* h_block, const Layout& lay, int32_t T) {
-        if (T > 0) {
-            std::memcpy(h_block + lay.bearings, bearings, 24 * (size_t)T);
-            std::memcpy(h_block + lay.pos_w, pos_w, 24 * (size_t)T);
-            std::memcpy(h_block + lay.max_cos, max_cos_errors, 8 * (size_t)T);
-        }
-        return OVS_OK;
-    };
+    const splan::pnp::Call call{s != nullptr, n_problems, offsets, bearings, pos_w, max_cos_errors, min_num_inliers, max_num_iter, out_valid,
+                                out_best_iter, out_num_inliers, out_rot_cw, out_trans_cw, out_inlier_flags};
+    const splan::Checked checked = splan::pnp::check(call, caps_of(s));
+    const Layout lay = layout_of(n_problems, checked.T);
     const auto hypotheses = [&](hipStream_t st, int, int32_t T) {
-        hipLaunchKernelGGL(k_pnp_hypotheses, dim3(max_num_iter, n_problems), dim3(64), 0, st, s->d_block, n_problems, T, max_num_iter, seed,
-                           s->d_wave_models);
+        hipLaunchKernelGGL(k_pnp_hypotheses, dim3(max_num_iter, n_problems), dim3(64), 0, st, s->d_block, n_problems, T, max_num_iter, seed, s->d_records);
     };
     const auto finish = [&](hipStream_t st, int, int32_t T) {
         hipLaunchKernelGGL(k_pnp_finish, dim3(n_problems), dim3(64), 0, st, s->d_block, n_problems, T, min_num_inliers, max_num_iter, recompute ? 1 : 0,
-                           s->d_wave_models, s->d_inlier_idx, s->m_result, s->m_flags);
+                           s->d_records, s->d_inlier_idx, s->m_rec<ResultRec>(), s->m_flags);
     };
-    return run_batch(s, n_problems, offsets, {}, {bearings, pos_w, max_cos_errors}, min_num_inliers, max_num_iter, 1, layout_of,
-                     {out_valid, out_best_iter, out_num_inliers, out_rot_cw, out_trans_cw, nullptr, out_inlier_flags}, stage, hypotheses, finish);
+    return run_batch(s, checked, lay.bytes, n_problems, max_num_iter, 1,
+                     {out_valid, out_best_iter, out_num_inliers, out_rot_cw, out_trans_cw, nullptr, out_inlier_flags},
+                     [&] { splan::pnp::stage(call, lay, s->h_block); }, hypotheses, finish);
 }
 
 }   // extern "C"

@@ -23,30 +23,9 @@
 
 namespace {
 
-static_assert(sizeof(s3::Cam) == 40, "s3::Cam is laid out in the staged block by the host");
-
-// The staged block of one call, sections in this order (each a multiple of 8 bytes but the last two): cameras s3::Cam [2 P] (side 1 then
-// side 2 of a problem), init f64 [13 P] (R12, t12, s12), p1 f64 [3 T], p2 f64 [3 T], obs1 f64 [2 T], obs2 f64 [2 T], w1 f32 [T'], w2 f32 [T'],
-// offsets i32 [P + 1], work u8 [T] (the kernel's outlier flags; nothing is staged there); T' = T rounded up to even.
-struct Layout {
-    size_t cams, init, p1, p2, obs1, obs2, w1, w2, offsets, work, bytes;
-};
-__host__ __device__ inline Layout layout_of(int P, int T) {
-    const size_t Te = ((size_t)T + 1) & ~(size_t)1;
-    Layout l;
-    l.cams = 0;
-    l.init = l.cams + sizeof(s3::Cam) * 2 * (size_t)P;
-    l.p1 = l.init + 8 * 13 * (size_t)P;
-    l.p2 = l.p1 + 24 * (size_t)T;
-    l.obs1 = l.p2 + 24 * (size_t)T;
-    l.obs2 = l.obs1 + 16 * (size_t)T;
-    l.w1 = l.obs2 + 16 * (size_t)T;
-    l.w2 = l.w1 + 4 * Te;
-    l.offsets = l.w2 + 4 * Te;
-    l.work = l.offsets + 4 * ((size_t)P + 1);
-    l.bytes = l.work + (size_t)T;
-    return l;
-}
+// the staged block of one call: solve_plan.inc
+using splan::sim3opt::Layout;
+using splan::sim3opt::layout_of;
 
 // per problem in the result block
 struct OptRec {
@@ -144,59 +123,39 @@ __global__ __launch_bounds__(64) void k_sim3_optimize(uint8_t* __restrict__ bloc
 
 }   // namespace
 
-struct ovs_sim3opt : ransac_handle {
-    OptRec* h_rec() { return reinterpret_cast<OptRec*>(h_result); }
-    OptRec* m_rec() { return reinterpret_cast<OptRec*>(m_result); }
-};
+struct ovs_sim3opt : batch_handle {};
 
 extern "C" {
 
 ovs_status ovs_sim3opt_create(int32_t device, int32_t max_problems, int32_t max_total_matches, ovs_sim3opt** out) {
-    return ransac_create(device, max_problems, max_total_matches, layout_of(max_problems, max_total_matches).bytes, 0, 0, out, sizeof(OptRec));
+    return batch_create(device, max_problems, max_total_matches, layout_of(max_problems, max_total_matches).bytes, 0, 0, sizeof(OptRec), out, no_extra);
 }
 
-ovs_status ovs_sim3opt_destroy(ovs_sim3opt* s) { return ransac_destroy(s); }
+ovs_status ovs_sim3opt_destroy(ovs_sim3opt* s) { return batch_destroy(s); }
 
 ovs_status ovs_sim3opt_optimize_batch(ovs_sim3opt* s, int32_t n_problems, const int32_t* offsets, const double* p1, const double* p2, const double* obs1,
                                       const double* obs2, const float* inv_sigma_sq_1, const float* inv_sigma_sq_2, const ovs_camera* cams_1,
                                       const ovs_camera* cams_2, const double* rot_12_in, const double* trans_12_in, const double* scale_12_in,
                                       int32_t fix_scale, float chi_sq, int32_t num_iter, int32_t* out_num_inliers, double* out_rot_12, double* out_trans_12,
                                       double* out_scale_12, uint8_t* out_outlier_flags, double* out_info) {
-    if (!(chi_sq > 0.0f) || !std::isfinite(chi_sq) || num_iter < 1) return OVS_ERR_INVALID;
-    s3::Params prm;
+    const splan::sim3opt::Call call{s != nullptr, n_problems, offsets, p1, p2, obs1, obs2, inv_sigma_sq_1, inv_sigma_sq_2, cams_1, cams_2, rot_12_in,
+                                    trans_12_in, scale_12_in, chi_sq, num_iter, out_num_inliers, out_rot_12, out_trans_12, out_scale_12, out_outlier_flags};
+    const splan::Checked checked = splan::sim3opt::check(call, caps_of(s));
+    const Layout lay = layout_of(n_problems, checked.T);
+    s3::Params prm;   // (read only where the check accepted chi_sq)
     prm.fix_scale = fix_scale ? 1 : 0;
     prm.num_iter = num_iter;
     prm.chi_sq = (double)chi_sq;
     prm.delta = (double)std::sqrt(chi_sq);   // sqrtf: rule 4
     prm.delta_sq = prm.delta * prm.delta;
-    const auto stage = [&](uint8_t* h_block, const Layout& lay, int32_t T) {
-        s3::Cam* cams = reinterpret_cast<s3::Cam*>(h_block + lay.cams);
-        double* init = reinterpret_cast<double*>(h_block + lay.init);
-        for (int32_t p = 0; p < n_problems; ++p) {
-            if (!camera_ok(cams_1[p], &cams[2 * p]) || !camera_ok(cams_2[p], &cams[2 * p + 1])) return OVS_ERR_INVALID;
-            std::memcpy(init + 13 * (size_t)p, rot_12_in + 9 * (size_t)p, 72);
-            std::memcpy(init + 13 * (size_t)p + 9, trans_12_in + 3 * (size_t)p, 24);
-            init[13 * (size_t)p + 12] = scale_12_in[p];
-        }
-        if (T > 0) {
-            std::memcpy(h_block + lay.p1, p1, 24 * (size_t)T);
-            std::memcpy(h_block + lay.p2, p2, 24 * (size_t)T);
-            std::memcpy(h_block + lay.obs1, obs1, 16 * (size_t)T);
-            std::memcpy(h_block + lay.obs2, obs2, 16 * (size_t)T);
-            std::memcpy(h_block + lay.w1, inv_sigma_sq_1, 4 * (size_t)T);
-            std::memcpy(h_block + lay.w2, inv_sigma_sq_2, 4 * (size_t)T);
-            std::memset(h_block + lay.work, 0, (size_t)T);
-        }
-        return OVS_OK;
-    };
     const auto launch = [&](hipStream_t st, int32_t T) {
-        hipLaunchKernelGGL(k_sim3_optimize, dim3(n_problems), dim3(64), 0, st, s->d_block, n_problems, T, prm, s->m_rec(), s->m_flags);
+        hipLaunchKernelGGL(k_sim3_optimize, dim3(n_problems), dim3(64), 0, st, s->d_block, n_problems, T, prm, s->m_rec<OptRec>(), s->m_flags);
         OVS_HIP_TRY(hipGetLastError());
         return OVS_OK;
     };
     const auto collect = [&](int32_t T) {
         for (int32_t p = 0; p < n_problems; ++p) {
-            const OptRec& r = s->h_rec()[p];
+            const OptRec& r = s->h_rec<OptRec>()[p];
             out_num_inliers[p] = r.num_inliers;
             std::memcpy(out_rot_12 + 9 * (size_t)p, r.rot, sizeof(r.rot));
             std::memcpy(out_trans_12 + 3 * (size_t)p, r.trans, sizeof(r.trans));
@@ -205,8 +164,7 @@ ovs_status ovs_sim3opt_optimize_batch(ovs_sim3opt* s, int32_t n_problems, const 
         }
         if (T > 0) std::memcpy(out_outlier_flags, s->h_flags, (size_t)T);
     };
-    return run_staged(s, n_problems, offsets, {cams_1, cams_2, rot_12_in, trans_12_in, scale_12_in, out_num_inliers, out_rot_12, out_trans_12, out_scale_12},
-                      {p1, p2, obs1, obs2, inv_sigma_sq_1, inv_sigma_sq_2}, out_outlier_flags, layout_of, stage, [] { return OVS_OK; }, launch, collect);
+    return run_staged(s, checked, lay.bytes, [&] { splan::sim3opt::stage(call, lay, s->h_block); }, nothing_to_reserve, launch, collect);
 }
 
 }   // extern "C"

@@ -28,31 +28,10 @@ constexpr int kHypPerWave = 4;      // hypotheses per wavefront (DESIGN.md 3.9: 
 constexpr int kModelDoubles = 17;   // R12 9, t12 3, s12, s21, t21 3
 constexpr int kFinishThreads = 256;
 
-// one side's camera as the kernels read it: perspective (fx, fy, cx, cy) or equirectangular ((double)cols, (double)rows, -, -)
-struct CamRec {
-    double a, b, c, d;
-    int32_t model, pad;
-};
-static_assert(sizeof(CamRec) == 40, "CamRec is laid out in the staged block by the host");
-
-// The staged block of one call, sections in this order (each a multiple of 8 bytes but the last): keys u64 [P] (zero), cameras CamRec [2 P]
-// (side 1 then side 2 of a problem), p1 f64 [3 T], p2 f64 [3 T], thr1 f32 [T'], thr2 f32 [T'], offsets i32 [P + 1]; T' = T rounded up to even.
-struct Layout {
-    size_t keys, cams, p1, p2, thr1, thr2, offsets, bytes;
-};
-__host__ __device__ inline Layout layout_of(int P, int T) {
-    const size_t Te = ((size_t)T + 1) & ~(size_t)1;
-    Layout l;
-    l.keys = 0;
-    l.cams = l.keys + 8 * (size_t)P;
-    l.p1 = l.cams + sizeof(CamRec) * 2 * (size_t)P;
-    l.p2 = l.p1 + 24 * (size_t)T;
-    l.thr1 = l.p2 + 24 * (size_t)T;
-    l.thr2 = l.thr1 + 4 * Te;
-    l.offsets = l.thr2 + 4 * Te;
-    l.bytes = l.offsets + 4 * ((size_t)P + 1);
-    return l;
-}
+// the staged block of one call and one side's camera in it: solve_plan.inc
+using splan::sim3::CamRec;
+using splan::sim3::Layout;
+using splan::sim3::layout_of;
 
 struct Model {
     double R[9], t12[3], s12, s21, t21[3];
@@ -267,44 +246,37 @@ __global__ __launch_bounds__(kFinishThreads) void k_sim3_finish(const uint8_t* _
 
 }   // namespace
 
-struct ovs_sim3 : ransac_handle {};
+struct ovs_sim3 : batch_handle {};
 
 extern "C" {
 
 ovs_status ovs_sim3_create(int32_t device, int32_t max_problems, int32_t max_total_matches, ovs_sim3** out) {
-    return ransac_create(device, max_problems, max_total_matches, layout_of(max_problems, max_total_matches).bytes,
-                         (size_t)max_problems * (256 / kHypPerWave),   // 256 iterations per problem without growing
-                         kModelDoubles, out);
+    return batch_create(device, max_problems, max_total_matches, layout_of(max_problems, max_total_matches).bytes,
+                        (size_t)max_problems * (256 / kHypPerWave),   // 256 iterations per problem without growing
+                        kModelDoubles, sizeof(ResultRec), out, no_extra);
 }
 
-ovs_status ovs_sim3_destroy(ovs_sim3* s) { return ransac_destroy(s); }
+ovs_status ovs_sim3_destroy(ovs_sim3* s) { return batch_destroy(s); }
 
 ovs_status ovs_sim3_solve_batch(ovs_sim3* s, int32_t n_problems, const int32_t* offsets, const double* p1, const double* p2, const float* thr1,
                                 const float* thr2, const ovs_camera* cams_1, const ovs_camera* cams_2, int32_t fix_scale, int32_t min_num_inliers,
                                 int32_t max_num_iter, uint64_t seed, int32_t* out_valid, int32_t* out_best_iter, int32_t* out_num_inliers,
                                 double* out_rot_12, double* out_trans_12, double* out_scale_12, uint8_t* out_inlier_flags) {
-    const auto stage = [&](uint8_t* h_block, const Layout& lay, int32_t T) {
-        CamRec* cams = reinterpret_cast<CamRec*>(h_block + lay.cams);
-        for (int32_t p = 0; p < n_problems; ++p)
-            if (!camera_ok(cams_1[p], &cams[2 * p]) || !camera_ok(cams_2[p], &cams[2 * p + 1])) return OVS_ERR_INVALID;
-        if (T > 0) {
-            std::memcpy(h_block + lay.p1, p1, 24 * (size_t)T);
-            std::memcpy(h_block + lay.p2, p2, 24 * (size_t)T);
-            std::memcpy(h_block + lay.thr1, thr1, 4 * (size_t)T);
-            std::memcpy(h_block + lay.thr2, thr2, 4 * (size_t)T);
-        }
-        return OVS_OK;
-    };
+    const splan::sim3::Call call{s != nullptr, n_problems, offsets, p1, p2, thr1, thr2, cams_1, cams_2, min_num_inliers, max_num_iter, out_valid,
+                                 out_best_iter, out_num_inliers, out_rot_12, out_trans_12, out_scale_12, out_inlier_flags};
+    const splan::Checked checked = splan::sim3::check(call, caps_of(s));
+    const Layout lay = layout_of(n_problems, checked.T);
     const auto hypotheses = [&](hipStream_t st, int blocks, int32_t T) {
         hipLaunchKernelGGL(k_sim3_hypotheses, dim3(blocks, n_problems), dim3(64), 0, st, s->d_block, n_problems, T, fix_scale ? 1 : 0, max_num_iter, seed,
-                           s->d_wave_models);
+                           s->d_records);
     };
     const auto finish = [&](hipStream_t st, int blocks, int32_t T) {
-        hipLaunchKernelGGL(k_sim3_finish, dim3(n_problems), dim3(kFinishThreads), 0, st, s->d_block, n_problems, T, min_num_inliers, blocks,
-                           s->d_wave_models, s->m_result, s->m_flags);
+        hipLaunchKernelGGL(k_sim3_finish, dim3(n_problems), dim3(kFinishThreads), 0, st, s->d_block, n_problems, T, min_num_inliers, blocks, s->d_records,
+                           s->m_rec<ResultRec>(), s->m_flags);
     };
-    return run_batch(s, n_problems, offsets, {cams_1, cams_2, out_scale_12}, {p1, p2, thr1, thr2}, min_num_inliers, max_num_iter, kHypPerWave, layout_of,
-                     {out_valid, out_best_iter, out_num_inliers, out_rot_12, out_trans_12, out_scale_12, out_inlier_flags}, stage, hypotheses, finish);
+    return run_batch(s, checked, lay.bytes, n_problems, max_num_iter, kHypPerWave,
+                     {out_valid, out_best_iter, out_num_inliers, out_rot_12, out_trans_12, out_scale_12, out_inlier_flags},
+                     [&] { splan::sim3::stage(call, lay, s->h_block); }, hypotheses, finish);
 }
 
 }   // extern "C"

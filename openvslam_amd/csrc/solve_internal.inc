@@ -1,18 +1,19 @@
-// solve_internal.inc -- what the RANSAC solvers of solve/ share (sim3_solve.hip, pnp_solve.hip, and through eight_point_internal.inc
-// two_view_solve.hip and essential_solve.hip). On the device: the counter-based sampler, the hypothesis key, the result record and its
-// invalid form, the cyclic Jacobi rotation (jacobi_math.inc), its sweeps over a matrix in LDS, the wavefront's sum (wave_sum) and Horn's
-// quaternion form of the absolute orientation. DESIGN.md 3.9 rule 2 fixes every operation; the units are built with -ffp-contract=off. On
-// the host: ransac_handle, the batch scaffold under the C ABIs (create, reserve_models, run_staged, run_batch). A solver supplies its
-// model, its two kernels, the Layout of its staged block, and to run_batch what stages its arrays and what launches its kernels. run_batch
-// is run_staged with the two launches, the keys and the result record of Sim3 and EPnP; the eight-point solvers' score-slot form of it is
-// run_slots of eight_point_internal.inc; the Sim3 transform optimiser (sim3_opt.hip), a one-launch solver over the same handle, calls
-// run_staged itself. (An .inc, not an .h: bench.py fingerprints every .h of this directory into the committed counters of the extractor and
-// matcher stages, which include none of this.)
+// solve_internal.inc -- what the batch solvers share: the RANSACs of solve/ (sim3_solve.hip, pnp_solve.hip, and through
+// eight_point_internal.inc two_view_solve.hip and essential_solve.hip), the Sim3 transform optimiser (sim3_opt.hip), the pose recovery
+// (two_view_reconstruct.hip), the triangulator (triangulate.hip) and the landmark upkeep (landmark_update.hip). On the device: the
+// counter-based sampler, the hypothesis key, the result record and its invalid form, the cyclic Jacobi rotation (jacobi_math.inc), its
+// sweeps over a matrix in LDS, the wavefront's sum (wave_sum) and Horn's quaternion form of the absolute orientation. DESIGN.md 3.9 rule 2
+// fixes every operation; the units are built with -ffp-contract=off. On the host: batch_handle (one staged block and its page-locked
+// twin, a stream, grow-only records, and for the solvers that have them the mapped result and flags blocks), batch_create, and
+// run_staged: what the solver's plan checked (solve_plan.inc holds every host decision of a call: errors, capacity, layout, staging,
+// read-back), lock, stage, reserve, one upload, launch, synchronise, collect. run_batch is run_staged with the two launches, the keys and
+// the result record of Sim3 and EPnP; the eight-point solvers' score-slot form of it is run_slots of eight_point_internal.inc; the
+// one-launch solvers call run_staged themselves. (An .inc, not an .h: bench.py fingerprints every .h of this directory into the committed
+// counters of the extractor and matcher stages, which include none of this.)
 #pragma once
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <initializer_list>
 #include <memory>
 #include <mutex>
 
@@ -22,10 +23,11 @@
 #include "jacobi_math.inc"
 #include "ovs_common.h"
 #include "owned_internal.inc"
+#include "solve_plan.inc"
 
 namespace {
 
-constexpr int kMaxIter = 1 << 20;   // h takes 20 bits of the sampler's counter
+using splan::kMaxIter;   // h takes 20 bits of the sampler's counter
 
 __device__ __forceinline__ uint64_t mix64(uint64_t z) {   // the splitmix64 finaliser
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -245,37 +247,63 @@ __device__ __forceinline__ void horn_rotation(const double (&M)[3][3], double (&
     R[8] = 1.0 - 2.0 * (x * x + y * y);
 }
 
-// ---- the host side: one handle and one batch call under ovs_sim3_*, ovs_pnp_*, ovs_sim3opt_*, ovs_twoview_* and ovs_essential_*
-struct ransac_handle {
+// ---- the host side: one handle, one create and one batch call under the nine C-ABI families of solve_plan.inc
+struct batch_handle {
     int device = 0;
-    int max_problems = 0, max_total_matches = 0;
+    int max_problems = 0, max_total_matches = 0;   // fixed at create: a plan's check reads them without the lock
     std::mutex mu;
     ovs::Owned res;
     hipStream_t stream = nullptr;
     uint8_t *d_block = nullptr, *h_block = nullptr;   // the staged block (the solver's Layout) and its page-locked twin
-    double* d_wave_models = nullptr;                  // [problem][wave] the model of the wave's best hypothesis; grows with problems x max_num_iter
-    size_t wave_models_cap = 0;                       // in records of model_doubles
-    int model_doubles = 0;
-    // results, page-locked and mapped: the finish kernel writes them, the host reads them after the stream has drained
-    ResultRec *h_result = nullptr, *m_result = nullptr;
+    // device memory in records of record_doubles doubles, grow-only: a wave's best model per (problem, wave), a score slot per (problem slot,
+    // hypothesis), a match's keys; what a call needs of it depends on its arguments
+    double* d_records = nullptr;
+    size_t records_cap = 0;
+    int record_doubles = 0;
+    // results, page-locked and mapped: the finish kernel writes them, the host reads them after the stream has drained. The result block is
+    // the solver's record per problem; a solver whose results come back through the staged block has neither
+    uint8_t *h_result = nullptr, *m_result = nullptr;
     uint8_t *h_flags = nullptr, *m_flags = nullptr;
 
-    // room for `records` models; the stream is idle: every call ends in a synchronise
-    ovs_status reserve_models(size_t records) {
-        if (records <= wave_models_cap) return OVS_OK;
-        wave_models_cap = 0;
-        if (d_wave_models) OVS_HIP_TRY(res.drop(&d_wave_models));
-        OVS_HIP_TRY(res.dev(&d_wave_models, sizeof(double) * model_doubles * records));
-        wave_models_cap = records;
+    // the result block as the solver's record type, on the host and as the kernels address it
+    template <class Rec>
+    Rec* h_rec() { return reinterpret_cast<Rec*>(h_result); }
+    template <class Rec>
+    Rec* m_rec() { return reinterpret_cast<Rec*>(m_result); }
+    // the records as the kernels' element type
+    template <class T>
+    T* records_as() { return reinterpret_cast<T*>(d_records); }
+
+    // room for `records` records; the stream is idle: every call ends in a synchronise
+    ovs_status reserve(size_t records) {
+        if (records <= records_cap) return OVS_OK;
+        records_cap = 0;
+        if (d_records) OVS_HIP_TRY(res.drop(&d_records));
+        OVS_HIP_TRY(res.dev(&d_records, sizeof(double) * record_doubles * records));
+        records_cap = records;
         return OVS_OK;
     }
 };
 
-// H: ovs_sim3, ovs_pnp, ovs_sim3opt, ovs_twoview or ovs_essential. block_bytes: the solver's Layout at full capacity; initial_records: the models that fit without
-// growing; result_bytes: the solver's record per problem in the mapped result block where it is not ResultRec
-template <class H>
-ovs_status ransac_create(int32_t device, int32_t max_problems, int32_t max_total_matches, size_t block_bytes, size_t initial_records,
-                         int model_doubles, H** out, size_t result_bytes = sizeof(ResultRec)) {
+// a handle's limits for its plan's check, read when the check asks for them: after the argument errors that need no handle
+inline auto caps_of(const batch_handle* s) {
+    return [s] { return splan::Caps{s->max_problems, s->max_total_matches, 0, s->device}; };
+}
+
+// page-locked memory the kernels write through `*mapped`
+template <class T>
+ovs_status mapped_block(ovs::Owned& res, T** host, T** mapped, size_t bytes) {
+    OVS_HIP_TRY(res.pinned(host, bytes, hipHostMallocMapped));
+    OVS_HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(mapped), *host, 0));
+    return OVS_OK;
+}
+
+// The one create. H: the solver's handle. block_bytes: its Layout at full capacity; initial_records of record_doubles: the records that fit
+// without growing; result_bytes: its record per problem in the mapped result block, 0 for a solver that reads its results from the staged
+// block (it gets no result and no flags block); extra(handle) acquires what the solver's handle adds, under the same owner.
+template <class H, class Extra>
+ovs_status batch_create(int32_t device, int32_t max_problems, int32_t max_total_matches, size_t block_bytes, size_t initial_records, int record_doubles,
+                        size_t result_bytes, H** out, Extra extra) {
     if (!out || max_problems < 1 || max_total_matches < 1) return OVS_ERR_INVALID;
     *out = nullptr;
     if (max_problems > 65535) return OVS_ERR_INVALID;   // a grid's y extent
@@ -286,44 +314,28 @@ ovs_status ransac_create(int32_t device, int32_t max_problems, int32_t max_total
     s->device = device;
     s->max_problems = max_problems;
     s->max_total_matches = max_total_matches;
-    s->model_doubles = model_doubles;
+    s->record_doubles = record_doubles;
     OVS_HIP_TRY(s->res.stream(&s->stream));
     OVS_HIP_TRY(s->res.dev(&s->d_block, block_bytes));
-    if (s->reserve_models(initial_records) != OVS_OK) return OVS_ERR_HIP;
+    if (s->reserve(initial_records) != OVS_OK) return OVS_ERR_HIP;
     OVS_HIP_TRY(s->res.pinned(&s->h_block, block_bytes));
-    OVS_HIP_TRY(s->res.pinned(&s->h_result, result_bytes * (size_t)max_problems, hipHostMallocMapped));
-    OVS_HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->m_result), s->h_result, 0));
-    OVS_HIP_TRY(s->res.pinned(&s->h_flags, (size_t)max_total_matches, hipHostMallocMapped));
-    OVS_HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->m_flags), s->h_flags, 0));
+    if (result_bytes > 0) {
+        if (mapped_block(s->res, &s->h_result, &s->m_result, result_bytes * (size_t)max_problems) != OVS_OK) return OVS_ERR_HIP;
+        if (mapped_block(s->res, &s->h_flags, &s->m_flags, (size_t)max_total_matches) != OVS_OK) return OVS_ERR_HIP;
+    }
+    const ovs_status added = extra(s);
+    if (added != OVS_OK) return added;
     *out = owner.release();
     return OVS_OK;
 }
+inline ovs_status no_extra(batch_handle*) { return OVS_OK; }
 
 template <class H>
-ovs_status ransac_destroy(H* s) {
+ovs_status batch_destroy(H* s) {
     if (!s) return OVS_ERR_INVALID;
     hipSetDevice(s->device);
     delete s;
     return OVS_OK;
-}
-
-// an ovs_camera as the kernels read it (Rec: a, b, c, d, model, pad): perspective (fx, fy, cx, cy) or equirectangular ((double)cols,
-// (double)rows, -, -); false for an unknown model or intrinsics a kernel cannot use
-template <class Rec>
-bool camera_ok(const ovs_camera& c, Rec* rec) {
-    rec->pad = 0;
-    rec->model = c.model;
-    if (c.model == 0) {
-        if (!std::isfinite(c.fx) || !std::isfinite(c.fy) || !std::isfinite(c.cx) || !std::isfinite(c.cy)) return false;
-        rec->a = c.fx, rec->b = c.fy, rec->c = c.cx, rec->d = c.cy;
-        return true;
-    }
-    if (c.model == 1) {
-        if (c.cols < 1 || c.rows < 1) return false;
-        rec->a = (double)c.cols, rec->b = (double)c.rows, rec->c = 0.0, rec->d = 0.0;
-        return true;
-    }
-    return false;
 }
 
 // where a call's results go: the caller's arrays of the C ABI (scale: nullptr for a solver that has none)
@@ -333,65 +345,35 @@ struct BatchOut {
     uint8_t* flags;
 };
 
-inline bool all_set(std::initializer_list<const void*> pointers) {
-    for (const void* q : pointers)
-        if (!q) return false;
-    return true;
-}
-
-// One batch call of any solver of this file's shape, whatever it launches. `required`: the pointers every call needs; `per_match`: the
-// arrays needed once there is a match, as is the per-match output. stage(h_block, layout, T) copies the solver's arrays into the
-// page-locked block and may refuse them (OVS_ERR_INVALID); reserve() grows what the launch needs while the stream is idle; launch(stream, T) enqueues the solver's kernels
-// behind the block's upload; collect(T) copies the mapped results out after the stream has drained. The order of decisions is the ABI's:
-// argument errors before the lock, OVS_ERR_CAPACITY before anything is staged, and no output is touched on any error.
-template <class Layout, class Stage, class Reserve, class Launch, class Collect>
-ovs_status run_staged(ransac_handle* s, int32_t n_problems, const int32_t* offsets, std::initializer_list<const void*> required,
-                      std::initializer_list<const void*> per_match, const void* per_match_out, Layout (*layout_of)(int, int), Stage stage,
-                      Reserve reserve, Launch launch, Collect collect) {
-    // every argument error is decided here, before the device is touched
-    if (!s || n_problems < 0) return OVS_ERR_INVALID;
-    if (n_problems == 0) return OVS_OK;
-    if (!offsets || !all_set(required)) return OVS_ERR_INVALID;
-    if (offsets[0] != 0) return OVS_ERR_INVALID;
-    for (int32_t p = 0; p < n_problems; ++p)
-        if (offsets[p + 1] < offsets[p]) return OVS_ERR_INVALID;
-    const int32_t T = offsets[n_problems];
-    if (T > 0 && (!per_match_out || !all_set(per_match))) return OVS_ERR_INVALID;
+// One batch call of any solver of this file's shape, whatever it launches. `checked`: what the solver's plan (solve_plan.inc: check) made of
+// the call's arguments, capacity included, before anything is touched; upload_bytes: its Layout's bytes. stage() fills the page-locked block
+// (the plan's stage); reserve() grows what the launch needs while the stream is idle; launch(stream, T) enqueues the solver's kernels
+// behind the block's upload; collect(T) copies the results out after the stream has drained. No output is touched on any error.
+template <class Stage, class Reserve, class Launch, class Collect>
+ovs_status run_staged(batch_handle* s, const splan::Checked& checked, size_t upload_bytes, Stage stage, Reserve reserve, Launch launch, Collect collect) {
+    if (!checked.run) return checked.status;
     std::lock_guard<std::mutex> lock(s->mu);
-    if (n_problems > s->max_problems || T > s->max_total_matches) return OVS_ERR_CAPACITY;   // nothing is truncated
-    const Layout lay = layout_of(n_problems, T);
-    const ovs_status staged = stage(s->h_block, lay, T);
-    if (staged != OVS_OK) return staged;
-    std::memcpy(s->h_block + lay.offsets, offsets, 4 * ((size_t)n_problems + 1));
+    stage();
     OVS_HIP_TRY(hipSetDevice(s->device));
     const ovs_status reserved = reserve();
     if (reserved != OVS_OK) return reserved;
-    OVS_HIP_TRY(hipMemcpyAsync(s->d_block, s->h_block, lay.bytes, hipMemcpyHostToDevice, s->stream));
-    const ovs_status launched = launch(s->stream, T);
+    OVS_HIP_TRY(hipMemcpyAsync(s->d_block, s->h_block, upload_bytes, hipMemcpyHostToDevice, s->stream));
+    const ovs_status launched = launch(s->stream, checked.T);
     if (launched != OVS_OK) return launched;
     OVS_HIP_TRY(hipStreamSynchronize(s->stream));
-    collect(T);
+    collect(checked.T);
     return OVS_OK;
 }
+inline ovs_status nothing_to_reserve() { return OVS_OK; }
 
 // One solve_batch call of a RANSAC solver: run_staged with the two launches, the keys and the result record both solvers have.
 // hypotheses(stream, waves_per_problem, T) and finish(stream, waves_per_problem, T) launch the solver's two kernels.
-template <class Layout, class Stage, class Hypotheses, class Finish>
-ovs_status run_batch(ransac_handle* s, int32_t n_problems, const int32_t* offsets, std::initializer_list<const void*> required,
-                     std::initializer_list<const void*> per_match, int32_t min_num_inliers, int32_t max_num_iter, int hyp_per_wave,
-                     Layout (*layout_of)(int, int), const BatchOut& o, Stage stage, Hypotheses hypotheses, Finish finish) {
-    if (!s || n_problems < 0 || max_num_iter < 1 || max_num_iter > kMaxIter || min_num_inliers < 0) return OVS_ERR_INVALID;
-    if (n_problems > 0 && (!o.valid || !o.best_iter || !o.num_inliers || !o.rot || !o.trans)) return OVS_ERR_INVALID;
-    if (n_problems > 0 && !all_set(required)) return OVS_ERR_INVALID;
-    const int waves = (max_num_iter + hyp_per_wave - 1) / hyp_per_wave;
+template <class Stage, class Hypotheses, class Finish>
+ovs_status run_batch(batch_handle* s, const splan::Checked& checked, size_t upload_bytes, int32_t n_problems, int32_t max_num_iter, int hyp_per_wave,
+                     const BatchOut& o, Stage stage, Hypotheses hypotheses, Finish finish) {
+    const int waves = checked.run ? (max_num_iter + hyp_per_wave - 1) / hyp_per_wave : 0;   // (a refused max_num_iter is not computed with)
     return run_staged(
-        s, n_problems, offsets, required, per_match, o.flags, layout_of,
-        [&](uint8_t* h_block, const Layout& lay, int32_t T) {
-            const ovs_status staged = stage(h_block, lay, T);
-            if (staged == OVS_OK) std::memset(h_block + lay.keys, 0, 8 * (size_t)n_problems);
-            return staged;
-        },
-        [&] { return s->reserve_models((size_t)n_problems * (size_t)waves) != OVS_OK ? OVS_ERR_HIP : OVS_OK; },
+        s, checked, upload_bytes, stage, [&] { return s->reserve((size_t)n_problems * (size_t)waves) != OVS_OK ? OVS_ERR_HIP : OVS_OK; },
         [&](hipStream_t stream, int32_t T) {
             hypotheses(stream, waves, T);
             OVS_HIP_TRY(hipGetLastError());
@@ -401,7 +383,7 @@ ovs_status run_batch(ransac_handle* s, int32_t n_problems, const int32_t* offset
         },
         [&](int32_t T) {
             for (int32_t p = 0; p < n_problems; ++p) {
-                const ResultRec& r = s->h_result[p];
+                const ResultRec& r = s->h_rec<ResultRec>()[p];
                 o.valid[p] = r.valid;
                 o.best_iter[p] = r.best_iter;
                 o.num_inliers[p] = r.num_inliers;

@@ -28,25 +28,10 @@ namespace {
 constexpr int kLanes = 64;
 constexpr int kKeyDoublesPerMatch = rec::kMaxHypotheses / 2;   // a match's eight u32 keys, in the handle's records of doubles
 constexpr int kInitialKeyMatches = 256;                        // the key buffer a handle is created with; it grows with a call's matches
-static_assert(sizeof(rec::Problem) == 112, "rec::Problem is laid out in the staged block by the host");
 
-// The staged block of one call, sections in this order: problems rec::Problem [P], kp_ref f64 [2 T], kp_cur f64 [2 T], b_ref f64 [3 T],
-// b_cur f64 [3 T], offsets i32 [P + 1], inlier u8 [T].
-struct Layout {
-    size_t problems, kp1, kp2, b1, b2, offsets, inlier, bytes;
-};
-__host__ __device__ inline Layout layout_of(int P, int T) {
-    Layout l;
-    l.problems = 0;
-    l.kp1 = l.problems + sizeof(rec::Problem) * (size_t)P;
-    l.kp2 = l.kp1 + 16 * (size_t)T;
-    l.b1 = l.kp2 + 16 * (size_t)T;
-    l.b2 = l.b1 + 24 * (size_t)T;
-    l.offsets = l.b2 + 24 * (size_t)T;
-    l.inlier = l.offsets + 4 * ((size_t)P + 1);
-    l.bytes = l.inlier + (size_t)T;
-    return l;
-}
+// the staged block of one call: solve_plan.inc
+using splan::reconstruct::Layout;
+using splan::reconstruct::layout_of;
 
 // per (problem, hypothesis) between the two kernels; count -1: there is no such hypothesis
 struct HypRec {
@@ -196,31 +181,23 @@ __global__ __launch_bounds__(kLanes) void k_reconstruct_finish(const uint8_t* __
 
 }   // namespace
 
-struct ovs_reconstruct : ransac_handle {
+struct ovs_reconstruct : batch_handle {                   // its records: a match's eight u32 keys
     HypRec* d_hyp = nullptr;                      // [problems][8] between the two kernels
     double *h_pos = nullptr, *m_pos = nullptr;    // the triangulated points, page-locked and mapped like the scaffold's flags
-    ReconRec* h_rec() { return reinterpret_cast<ReconRec*>(h_result); }
-    ReconRec* m_rec() { return reinterpret_cast<ReconRec*>(m_result); }
-    uint32_t* d_keys() { return reinterpret_cast<uint32_t*>(d_wave_models); }
 };
 
 extern "C" {
 
 ovs_status ovs_reconstruct_create(int32_t device, int32_t max_problems, int32_t max_total_matches, ovs_reconstruct** out) {
-    const ovs_status st = ransac_create(device, max_problems, max_total_matches, layout_of(max_problems, max_total_matches).bytes,
-                                        (size_t)(max_total_matches < kInitialKeyMatches ? max_total_matches : kInitialKeyMatches), kKeyDoublesPerMatch,
-                                        out, sizeof(ReconRec));
-    if (st != OVS_OK) return st;
-    std::unique_ptr<ovs_reconstruct> owner(*out);
-    *out = nullptr;
-    OVS_HIP_TRY(owner->res.dev(&owner->d_hyp, sizeof(HypRec) * rec::kMaxHypotheses * (size_t)max_problems));
-    OVS_HIP_TRY(owner->res.pinned(&owner->h_pos, 24 * (size_t)max_total_matches, hipHostMallocMapped));
-    OVS_HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&owner->m_pos), owner->h_pos, 0));
-    *out = owner.release();
-    return OVS_OK;
+    return batch_create(device, max_problems, max_total_matches, layout_of(max_problems, max_total_matches).bytes,
+                        (size_t)(max_total_matches < kInitialKeyMatches ? max_total_matches : kInitialKeyMatches), kKeyDoublesPerMatch, sizeof(ReconRec),
+                        out, [&](ovs_reconstruct* s) {
+                            OVS_HIP_TRY(s->res.dev(&s->d_hyp, sizeof(HypRec) * rec::kMaxHypotheses * (size_t)max_problems));
+                            return mapped_block(s->res, &s->h_pos, &s->m_pos, 24 * (size_t)max_total_matches);
+                        });
 }
 
-ovs_status ovs_reconstruct_destroy(ovs_reconstruct* s) { return ransac_destroy(s); }
+ovs_status ovs_reconstruct_destroy(ovs_reconstruct* s) { return batch_destroy(s); }
 
 ovs_status ovs_reconstruct_batch(ovs_reconstruct* s, int32_t n_problems, const int32_t* offsets, const int32_t* models, const double* mats,
                                  const ovs_camera* cams, const uint8_t* inlier_flags, const double* keypts_ref, const double* keypts_cur,
@@ -228,42 +205,25 @@ ovs_status ovs_reconstruct_batch(ovs_reconstruct* s, int32_t n_problems, const i
                                  int32_t min_num_triangulated, int32_t* out_success, int32_t* out_best, double* out_rot_ref_to_cur,
                                  double* out_trans_ref_to_cur, int32_t* out_counts, float* out_parallax_deg, double* out_triangulated_pts,
                                  uint8_t* out_is_triangulated) {
-    if (!(reproj_err_thr > 0.0f) || !std::isfinite(reproj_err_thr) || !(parallax_deg_thr > 0.0f) || !std::isfinite(parallax_deg_thr)) return OVS_ERR_INVALID;
+    const splan::reconstruct::Call call{s != nullptr, n_problems, offsets, models, mats, cams, inlier_flags, keypts_ref, keypts_cur, bearings_ref,
+                                        bearings_cur, reproj_err_thr, parallax_deg_thr, out_success, out_best, out_rot_ref_to_cur, out_trans_ref_to_cur,
+                                        out_counts, out_parallax_deg, out_triangulated_pts, out_is_triangulated};
+    const splan::Checked checked = splan::reconstruct::check(call, caps_of(s));
+    const Layout lay = layout_of(n_problems, checked.T);
     const float thr_sq = rec::threshold_sq(reproj_err_thr);
-    const auto stage = [&](uint8_t* h_block, const Layout& lay, int32_t T) {
-        rec::Problem* problems = reinterpret_cast<rec::Problem*>(h_block + lay.problems);
-        for (int32_t p = 0; p < n_problems; ++p) {
-            const ovs_camera& c = cams[p];
-            if (models[p] < 1 || models[p] > 2 || c.model != 0) return OVS_ERR_INVALID;
-            if (!std::isfinite(c.fx) || !std::isfinite(c.fy) || !std::isfinite(c.cx) || !std::isfinite(c.cy) || c.fx == 0.0 || c.fy == 0.0) return OVS_ERR_INVALID;
-            rec::Problem& q = problems[p];
-            std::memcpy(q.mat, mats + 9 * (size_t)p, sizeof(q.mat));
-            q.fx = c.fx, q.fy = c.fy, q.cx = c.cx, q.cy = c.cy;
-            q.model = models[p];
-            q.pad = 0;
-        }
-        if (T > 0) {
-            std::memcpy(h_block + lay.kp1, keypts_ref, 16 * (size_t)T);
-            std::memcpy(h_block + lay.kp2, keypts_cur, 16 * (size_t)T);
-            std::memcpy(h_block + lay.b1, bearings_ref, 24 * (size_t)T);
-            std::memcpy(h_block + lay.b2, bearings_cur, 24 * (size_t)T);
-            std::memcpy(h_block + lay.inlier, inlier_flags, (size_t)T);
-        }
-        return OVS_OK;
-    };
-    const auto reserve = [&] { return s->reserve_models((size_t)offsets[n_problems]) != OVS_OK ? OVS_ERR_HIP : OVS_OK; };
+    const auto reserve = [&] { return s->reserve((size_t)checked.T) != OVS_OK ? OVS_ERR_HIP : OVS_OK; };
     const auto launch = [&](hipStream_t st, int32_t T) {
         hipLaunchKernelGGL(k_reconstruct_hypotheses, dim3(rec::kMaxHypotheses, n_problems), dim3(kLanes), 0, st, s->d_block, n_problems, T, thr_sq,
-                           s->d_keys(), s->d_hyp);
+                           s->records_as<uint32_t>(), s->d_hyp);
         OVS_HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_reconstruct_finish, dim3(n_problems), dim3(kLanes), 0, st, s->d_block, n_problems, T, thr_sq, parallax_deg_thr,
-                           min_num_triangulated, s->d_hyp, s->m_rec(), s->m_pos, s->m_flags);
+                           min_num_triangulated, s->d_hyp, s->m_rec<ReconRec>(), s->m_pos, s->m_flags);
         OVS_HIP_TRY(hipGetLastError());
         return OVS_OK;
     };
     const auto collect = [&](int32_t T) {
         for (int32_t p = 0; p < n_problems; ++p) {
-            const ReconRec& r = s->h_rec()[p];
+            const ReconRec& r = s->h_rec<ReconRec>()[p];
             out_success[p] = r.success;
             out_best[p] = r.best;
             std::memcpy(out_rot_ref_to_cur + 9 * (size_t)p, r.rot, sizeof(r.rot));
@@ -276,9 +236,7 @@ ovs_status ovs_reconstruct_batch(ovs_reconstruct* s, int32_t n_problems, const i
             std::memcpy(out_is_triangulated, s->h_flags, (size_t)T);
         }
     };
-    return run_staged(s, n_problems, offsets, {models, mats, cams, out_success, out_best, out_rot_ref_to_cur, out_trans_ref_to_cur, out_counts, out_parallax_deg},
-                      {inlier_flags, keypts_ref, keypts_cur, bearings_ref, bearings_cur, out_triangulated_pts}, out_is_triangulated, layout_of, stage,
-                      reserve, launch, collect);
+    return run_staged(s, checked, lay.bytes, [&] { splan::reconstruct::stage(call, lay, s->h_block); }, reserve, launch, collect);
 }
 
 }   // extern "C"

@@ -33,18 +33,9 @@ constexpr int kSweeps = 8;
 constexpr int kSampleShare = 16;   // the counter share of a hypothesis (solve.two_view_problem_seed: p << 24)
 constexpr double kChiH = 5.991, kChiF = 3.841, kScore = 5.991;
 
-// The staged block of one call, sections in this order: x1 f64 [2 T], x2 f64 [2 T], offsets i32 [P + 1].
-struct Layout {
-    size_t x1, x2, offsets, bytes;
-};
-__host__ __device__ inline Layout layout_of(int P, int T) {
-    Layout l;
-    l.x1 = 0;
-    l.x2 = l.x1 + 16 * (size_t)T;
-    l.offsets = l.x2 + 16 * (size_t)T;
-    l.bytes = l.offsets + 4 * ((size_t)P + 1);
-    return l;
-}
+// the staged block of one call: solve_plan.inc
+using splan::twoview::Layout;
+using splan::twoview::layout_of;
 
 // per problem in the result block: index 0 is H, 1 is F
 struct TwoViewRec {
@@ -385,47 +376,37 @@ __global__ __launch_bounds__(64) void k_twoview_finish(const uint8_t* __restrict
 
 struct ovs_twoview : eight_point_handle {                 // its d_inlier_idx: [2][matches of the call], H's half and F's
     uint8_t *h_flags_f = nullptr, *m_flags_f = nullptr;   // F's flags; the scaffold's h_flags / m_flags hold H's
-    TwoViewRec* h_rec() { return reinterpret_cast<TwoViewRec*>(h_result); }
-    TwoViewRec* m_rec() { return reinterpret_cast<TwoViewRec*>(m_result); }
 };
 
 extern "C" {
 
 ovs_status ovs_twoview_create(int32_t device, int32_t max_problems, int32_t max_total_matches, ovs_twoview** out) {
-    const auto flags_f = [&](ovs_twoview* s) {
-        OVS_HIP_TRY(s->res.pinned(&s->h_flags_f, (size_t)max_total_matches, hipHostMallocMapped));
-        OVS_HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&s->m_flags_f), s->h_flags_f, 0));
-        return OVS_OK;
-    };
+    const auto flags_f = [&](ovs_twoview* s) { return mapped_block(s->res, &s->h_flags_f, &s->m_flags_f, (size_t)max_total_matches); };
     return eight_point_create(device, max_problems, max_total_matches, layout_of(max_problems, max_total_matches).bytes, 2, sizeof(TwoViewRec), out, flags_f);
 }
 
-ovs_status ovs_twoview_destroy(ovs_twoview* s) { return ransac_destroy(s); }
+ovs_status ovs_twoview_destroy(ovs_twoview* s) { return batch_destroy(s); }
 
 ovs_status ovs_twoview_solve_batch(ovs_twoview* s, int32_t n_problems, const int32_t* offsets, const double* x1, const double* x2, double sigma,
                                    int32_t max_num_iter, int32_t recompute, uint64_t seed, int32_t models, double* out_H_21, double* out_F_21,
                                    double* out_scores, int32_t* out_valid, int32_t* out_best_iter, int32_t* out_num_inliers, int32_t* out_selected,
                                    uint8_t* out_inlier_flags_H, uint8_t* out_inlier_flags_F) {
-    if (max_num_iter < 1 || max_num_iter > kMaxIter || models < 1 || models > 3 || !(sigma > 0.0) || !std::isfinite(sigma)) return OVS_ERR_INVALID;
+    const splan::twoview::Call call{s != nullptr, n_problems, offsets, x1, x2, sigma, max_num_iter, models, out_H_21, out_F_21, out_scores, out_valid,
+                                    out_best_iter, out_num_inliers, out_selected, out_inlier_flags_H, out_inlier_flags_F};
+    const splan::Checked checked = splan::twoview::check(call, caps_of(s));
+    const Layout lay = layout_of(n_problems, checked.T);
     const double inv_sigma_sq = 1.0 / (sigma * sigma);
-    const auto stage = [&](uint8_t* h_block, const Layout& lay, int32_t T) {
-        if (T > 0) {
-            std::memcpy(h_block + lay.x1, x1, 16 * (size_t)T);
-            std::memcpy(h_block + lay.x2, x2, 16 * (size_t)T);
-        }
-        return OVS_OK;
-    };
     const auto hypotheses = [&](hipStream_t st, int32_t T) {
         hipLaunchKernelGGL(k_twoview_hypotheses, dim3(max_num_iter, 2, n_problems), dim3(64), 0, st, s->d_block, n_problems, T, max_num_iter, models, seed,
-                           inv_sigma_sq, s->d_wave_models);
+                           inv_sigma_sq, s->d_records);
     };
     const auto finish = [&](hipStream_t st, int32_t T) {
         hipLaunchKernelGGL(k_twoview_finish, dim3(n_problems), dim3(64), 0, st, s->d_block, n_problems, T, max_num_iter, models, recompute ? 1 : 0,
-                           inv_sigma_sq, s->d_wave_models, s->d_inlier_idx, s->m_rec(), s->m_flags, s->m_flags_f);
+                           inv_sigma_sq, s->d_records, s->d_inlier_idx, s->m_rec<TwoViewRec>(), s->m_flags, s->m_flags_f);
     };
     const auto collect = [&](int32_t T) {
         for (int32_t p = 0; p < n_problems; ++p) {
-            const TwoViewRec& r = s->h_rec()[p];
+            const TwoViewRec& r = s->h_rec<TwoViewRec>()[p];
             std::memcpy(out_H_21 + 9 * (size_t)p, r.mat[0], sizeof(r.mat[0]));
             std::memcpy(out_F_21 + 9 * (size_t)p, r.mat[1], sizeof(r.mat[1]));
             for (int m = 0; m < 2; ++m) {
@@ -441,8 +422,7 @@ ovs_status ovs_twoview_solve_batch(ovs_twoview* s, int32_t n_problems, const int
             std::memcpy(out_inlier_flags_F, s->h_flags_f, (size_t)T);
         }
     };
-    return run_slots(s, n_problems, offsets, {out_H_21, out_F_21, out_scores, out_valid, out_best_iter, out_num_inliers, out_selected},
-                     {x1, x2, out_inlier_flags_F}, out_inlier_flags_H, layout_of, 2, max_num_iter, stage, hypotheses, finish, collect);
+    return run_slots(s, checked, lay.bytes, n_problems, 2, max_num_iter, [&] { splan::twoview::stage(call, lay, s->h_block); }, hypotheses, finish, collect);
 }
 
 }   // extern "C"
